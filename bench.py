@@ -19,7 +19,12 @@ measured live: HIP events recorded on the engine's stream around every compariso
 give the launch duration; the wave-instructions per comparison of exactly this kernel instantiation come from the
 committed rocprofv3 counter passes (profiles/pmc_current.json, scripts/profile_round.sh + pmc_summary.py), refused when
 kernel or shape differ.  `hbm` holds the memory side: the north-star's algorithmic bytes, the compulsory bytes and the
-counter-measured fabric traffic.  `cpu_baseline` (rank 0, N=1) times the CPU oracle port on a bounded sample.
+counter-measured fabric traffic.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line.  --full adds what takes work of its
+own: `cpu_baseline` (rank 0, N=1) times the CPU oracle port on a bounded sample, `parity` checks the HIP path against
+it, `result_check` (N=1) re-runs the last timed step and `merge_check` (N>1) checks the merged block; --full also
+turns on the --max-seconds budget by default.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 """
 import argparse
 import json
@@ -61,14 +66,23 @@ def parse_args():
     ap.add_argument("--direct", action="store_true",
                     help="BASELINE config 4: cross-correlation as a sliding window in real space (BIOEM_CC_DIRECT=1; "
                          "images up to 160 pixels, e.g. --pixels 128) instead of the transform path")
-    ap.add_argument("--max-seconds", type=float, default=480.0,
+    ap.add_argument("--max-seconds", type=float, default=None,
                     help="wall-clock budget of the whole run (set-up + warm-up + timed steps + merge): after the first "
                          "warm-up step the warm-up and step counts are trimmed, on every rank alike, so that the run "
-                         "ends inside it; the line reports steps_requested / steps (= run) and warmup_requested / warmup")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "ends inside it; the line reports steps_requested / steps (= run) and warmup_requested / warmup. "
+                         "Default: 480 with --full, none otherwise (--steps is then exactly the number of timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check beyond the headline: CPU baseline and parity against the CPU oracle, "
+                         "untimed re-run check of the last timed step (N = 1), merged-block check (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the per-particle arrays the last timed step computed (rank 0, "
+                         "merged at N > 1) as DIR/<name>.npy in float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline and parity")
     ap.add_argument("--cpu-orientations", type=int, default=64, help="orientations of the CPU-baseline sample")
     ap.add_argument("--cpu-repeats", type=int, default=3)
     args = ap.parse_args()
+    if args.max_seconds is None:
+        args.max_seconds = 480.0 if args.full else 0.0
     cfg = args.config if args.config != "auto" else ("3" if args.gpus == 8 else "2")
     if args.particles is None:
         args.particles = 10000 if cfg == "3" else 1000
@@ -230,6 +244,37 @@ def cpu_baseline(W, n_orient, n_threads, repeats, algo=1):
     return n_orient * W.nCTF * nP / dt, times, pmap, orc.logp_constant(pd), particle_check
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, pmap, cands=None, limit=DUMP_LIMIT_BYTES, seed=20261016):
+    """What one step hands its caller -- the per-particle map entries (PROB_MAP_DTYPE) and, with --write-angles, the
+    K best orientations per particle (CANDIDATE_DTYPE) -- as d/map_<field>.npy and d/angles_<field>.npy, integer and
+    double fields as float64, float fields as float32.  Above `limit` bytes in all, a fixed seeded sample of the
+    particles is written instead, and d/particle_index.npy names them.  Returns the names written."""
+    import numpy as np
+    arrays = {}
+    for src, prefix in ((pmap, "map_"), (cands, "angles_")):
+        if src is None:
+            continue
+        for f in src.dtype.names:
+            if f == "pad":
+                continue
+            a = src[f]
+            arrays[prefix + f] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    n = len(pmap)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        keep = max(1, limit // (total // n + 8))          # + 8 bytes per kept particle for its index
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["particle_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     args = parse_args()
     if args.direct:
@@ -346,7 +391,7 @@ def main():
         return float(t.item())
 
     # time budget (--max-seconds): the first executed step prices a step; warm-up, then timed steps are trimmed to fit
-    tail_s = 90.0 if (world == 1 and not args.no_cpu_baseline) else 10.0
+    tail_s = 90.0 if (world == 1 and args.full and not args.no_cpu_baseline) else 10.0
     warmup_run, steps_run = args.warmup, args.steps
     if args.warmup > 0:
         tp = time.perf_counter()
@@ -367,7 +412,7 @@ def main():
     while done < steps_run:
         last = one_step()
         done += 1
-        if args.warmup == 0 and done == 1 and steps_run > 1:
+        if args.max_seconds > 0 and args.warmup == 0 and done == 1 and steps_run > 1:
             sync()          # no warm-up step priced a step: the first timed one does (one extra barrier in the region)
             _, more = plan_steps(args.steps - 1, 0, rank_max(time.perf_counter() - t0),
                                  rank_max(time.perf_counter() - t_start), args.max_seconds, tail_s)
@@ -381,6 +426,9 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, *(last if K else (last, None)))
 
     # BASELINE.json's metric string (value = the comparisons/s half; the log P half is the `parity` object)
     metric_name = "image-comparisons/sec (orient x CTF x particle) at %d^2" % W.N
@@ -501,8 +549,10 @@ def main():
         rl["counters_source"] = "none: profiles/pmc_current.json missing"
     out["roofline"] = rl
     out["hbm"] = hbm
+    if dumped is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "of": "the last timed step", "arrays": dumped}
 
-    if world == 1:
+    if world == 1 and args.full:
         # the TIMED pass checks itself: its last step's block must be finite, must select the planted orientation
         # (particle p was rendered from orientation (7919 p) mod orientations) for most particles, and one more
         # (untimed) step on the same inputs must reproduce it bit for bit
@@ -516,7 +566,7 @@ def main():
         out["result_check"] = {"of": "the last timed step", "finite": fin, "planted_orientation_recovered": rec,
                                "bitwise_equal_to_untimed_rerun": bit, "ok": bool(fin and bit and rec >= 0.9)}
     out["particle_stack"] = stack_source
-    if world > 1 and rank == 0:
+    if world > 1 and rank == 0 and args.full:
         # the merged block, checked: arg-max orientations are global indices, and the planted truth (particle p was
         # rendered from orientation (7919 p) mod orientations of block 0) is what most particles must select
         merged = last[0] if K else last
@@ -524,7 +574,7 @@ def main():
         out["merge_check"] = {"orient_in_range": bool(((merged["orient"] >= 0) & (merged["orient"] < world * W.nOrient)).all()),
                               "planted_orientation_recovered": float((merged["orient"] == planted).mean()),
                               "finite": bool(np.isfinite(merged["Constoadd"]).all() and (merged["Total"] > 0).all())}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as orc
         # every host core this process may use: affinity mask, cut to the cgroup's CPU quota if there is one; on a box

@@ -7,6 +7,8 @@ import subprocess
 import sys
 import time
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -110,3 +112,100 @@ def test_shared_stack_path_is_per_launch_and_per_shape(monkeypatch):
     assert a != b and a.startswith("/dev/shm/") and "29511" in a
     monkeypatch.setenv("MASTER_PORT", "29512")
     assert bench.shared_stack_path((224, 10000, 4608, 5, 2)) != a
+
+
+def test_plain_run_keeps_its_step_count_and_full_restores_the_budget():
+    """A plain run times exactly --steps steps (no wall-clock budget unless one is asked for); --full turns on the
+    extra measurements and the 480 s budget."""
+    import bench
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse_args()
+        assert (a.steps, a.warmup, a.full, a.max_seconds, a.dump_outputs) == (7, 2, False, 0.0, None)
+        sys.argv = ["bench.py", "--full"]
+        a = bench.parse_args()
+        assert a.full and a.max_seconds == 480.0
+        sys.argv = ["bench.py", "--max-seconds", "60", "--dump-outputs", "out"]
+        a = bench.parse_args()
+        assert (a.full, a.max_seconds, a.dump_outputs) == (False, 60.0, "out")
+    finally:
+        sys.argv = argv
+    # no budget: plan_steps leaves both counts as asked
+    assert bench.plan_steps(7, 1, 100.0, 1000.0, 0.0, 10.0) == (1, 7)
+
+
+def _prob_block(n, seed=5):
+    import numpy as np
+    from bioem_amd.engine import CANDIDATE_DTYPE, PROB_MAP_DTYPE
+    rng = np.random.default_rng(seed)
+    pmap = np.zeros(n, dtype=PROB_MAP_DTYPE)
+    for f in PROB_MAP_DTYPE.names:
+        pmap[f] = rng.integers(-50, 50, size=n) if pmap[f].dtype.kind == "i" else rng.normal(size=n)
+    cands = np.zeros((n, 3), dtype=CANDIDATE_DTYPE)
+    for f in ("forAngles", "ConstAngle", "logp"):
+        cands[f] = rng.normal(size=(n, 3))
+    cands["orient"] = rng.integers(0, 4608, size=(n, 3))
+    return pmap, cands
+
+
+def test_dump_outputs_writes_every_field_as_float(tmp_path):
+    import numpy as np
+    import bench
+    pmap, cands = _prob_block(100)
+    names = bench.dump_outputs(str(tmp_path / "a"), pmap)
+    assert names == sorted("map_" + f for f in pmap.dtype.names)
+    for f in pmap.dtype.names:
+        a = np.load(tmp_path / "a" / ("map_%s.npy" % f))
+        assert a.dtype == (np.float32 if pmap[f].dtype == np.float32 else np.float64)
+        assert np.array_equal(a, pmap[f])                       # exact: int32 and float fields alike
+    names = bench.dump_outputs(str(tmp_path / "b"), pmap, cands)
+    assert "angles_pad" not in names and "angles_orient" in names
+    a = np.load(tmp_path / "b" / "angles_orient.npy")
+    assert a.dtype == np.float64 and a.shape == (100, 3) and np.array_equal(a, cands["orient"])
+
+
+def test_dump_outputs_samples_a_fixed_subset_above_the_limit(tmp_path):
+    import numpy as np
+    import bench
+    pmap, cands = _prob_block(1000)
+    limit = 20000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), pmap, cands, limit=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert sorted(os.listdir(tmp_path / "b")) == files and "particle_index.npy" in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in files) <= limit    # 128 = .npy header
+    idx = np.load(tmp_path / "a" / "particle_index.npy").astype(np.int64)
+    assert 0 < len(idx) < 1000 and np.all(np.diff(idx) > 0)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))      # same sample each time
+    assert np.array_equal(np.load(tmp_path / "a" / "map_Total.npy"), pmap["Total"][idx])
+
+
+def _run_bench(args, timeout):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-4000:]
+    import json
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.gpu
+def test_bench_plain_and_full_runs_on_a_small_workload(tmp_path):
+    """The plain line times exactly --steps steps and carries nothing of --full; the dumped outputs are the same in
+    both runs (same seeded inputs); --full adds the CPU baseline, parity and the re-run check of the timed pass."""
+    import numpy as np
+    shape = ["--gpus", "1", "--particles", "20", "--orientations", "288"]
+    plain = _run_bench(shape + ["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "plain")], 300)
+    assert plain["steps"] == plain["steps_requested"] == 3 and plain["warmup"] == 1
+    assert plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["unit"] == "comparisons/s"
+    assert not {"cpu_baseline", "parity", "result_check"} & set(plain)
+    full = _run_bench(shape + ["--steps", "2", "--warmup", "1", "--full", "--cpu-orientations", "8", "--cpu-repeats",
+                               "1", "--dump-outputs", str(tmp_path / "full")], 300)
+    assert full["result_check"]["ok"] and full["parity"]["argmax_mismatches"] == 0
+    assert full["parity"]["max_rel_dlogp"] <= full["parity"]["tolerance_rel"] and full["cpu_baseline"]["value"] > 0
+    names = plain["outputs"]["arrays"]
+    assert names == full["outputs"]["arrays"] and "map_Total" in names and "map_orient" in names
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / (n + ".npy")), np.load(tmp_path / "full" / (n + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and a.shape == (20,) and np.array_equal(a, b), n
