@@ -38,7 +38,7 @@
 //   window_tiles.hpp     k_phase_shift, k_merge_tiles  wide windows no kernel covers: tiles of a window kernel
 //   kernel_select.hpp    kernel table, k_compare_wide2 rules, plan_kernels: which kernel runs which shape
 //   posterior.hpp        calc_logpro / calProb semantics (bioem_algorithm.h:18-142)
-//   fold_kernels.hpp     k_fold_wave, k_fold_angles (k_fold: serial variant): fold the per-comparison partials into the probability block in the
+//   fold_kernels.hpp     k_fold_wave, k_fold_angles: fold the per-comparison partials into the probability block in the
 //                          reference's (orientation, CTF) order (bioem_algorithm.h:96-123, bioem.cpp:1527-1600)
 //   this file            device context, launch logic, the C ABI
 //   kernels_*.hip        one translation unit per comparison-kernel family (the instantiations of kernel_table.inc),
@@ -249,10 +249,6 @@ struct bioem_hip_ctx
 #include "fold_kernels.hpp"
 #include "window_tiles.hpp"
 
-#ifndef BIOEM_NYQUIST_SPLIT
-#define BIOEM_NYQUIST_SPLIT 1
-#endif
-
 namespace
 {
 
@@ -421,7 +417,7 @@ int launch_compare_fold(bioem_hip_ctx *h, const BatchBuf &bb, int nOC, int orien
   const int ocGroups = (nOC + 3) / 4;
   // few particles: whole groups per XCD (fast_block_pair); the grid is padded to a multiple of 8 groups
   // (measured for 65...200 particles as well: 1-3 % slower than the chunk order there)
-  const bool groupPerXcd = h->nMaps <= 64 && h->fast && !h->wide2 && !getenv("BIOEM_NO_GROUP_XCD");
+  const bool groupPerXcd = h->nMaps <= 64 && h->fast && !h->wide2;
   if (groupPerXcd)
     a.pchunk = -1;
   const dim3 grid((unsigned) ((size_t) (groupPerXcd ? (ocGroups + 7) / 8 * 8 : ocGroups) * h->nMaps));
@@ -528,28 +524,20 @@ int launch_compare_fold(bioem_hip_ctx *h, const BatchBuf &bb, int nOC, int orien
   h->comparisons += (long long) nOC * h->nMaps;
   bioem_hip_prob_map *pmap = reinterpret_cast<bioem_hip_prob_map *>(h->dProb);
   bioem_hip_prob_angle *pang = reinterpret_cast<bioem_hip_prob_angle *>(h->dProb + sizeof(bioem_hip_prob_map) * h->nMaps);
-  static const bool serialFold = getenv("BIOEM_SERIAL_FOLD") != nullptr; // debugging: the one-thread-per-particle fold
-  if (serialFold)
-    hipLaunchKernelGGL(k_fold, dim3((h->nMaps + 127) / 128), dim3(128), 0, h->stream, h->dPartials, h->maxOC, nOC,
-                       h->nMaps, bb.params, h->dSumRef, h->dDisp, h->nd, h->pd, orient0, conv0, convPerOrient, ids,
-                       pmap, pang, h->angO0);
-  else
+  if (h->pd.writeAngles)
   {
-    if (h->pd.writeAngles)
-    {
-      const int nRuns = ids ? nSeg : (nOC + convPerOrient - 1) / convPerOrient;
-      const long long nt = (long long) nRuns * h->nMaps;
-      hipLaunchKernelGGL(k_fold_angles, dim3((unsigned) ((nt + 255) / 256)), dim3(256), 0, h->stream, h->dPartials,
-                         h->maxOC, nOC, h->nMaps, orient0, convPerOrient, segs, nRuns, pang, h->angO0);
-    }
-    if (h->nMaps <= 64 && nOC >= 1024)
-      hipLaunchKernelGGL(k_fold_wave<4>, dim3(h->nMaps), dim3(256), 0, h->stream, h->dPartials, h->maxOC, nOC, h->nMaps,
-                         bb.params, h->dSumRef, h->dDisp, h->nd, h->pd, orient0, conv0, convPerOrient, ids, pmap);
-    else
-      hipLaunchKernelGGL(k_fold_wave<1>, dim3((h->nMaps + 3) / 4), dim3(256), 0, h->stream, h->dPartials, h->maxOC, nOC,
-                         h->nMaps, bb.params, h->dSumRef, h->dDisp, h->nd, h->pd, orient0, conv0, convPerOrient, ids,
-                         pmap);
+    const int nRuns = ids ? nSeg : (nOC + convPerOrient - 1) / convPerOrient;
+    const long long nt = (long long) nRuns * h->nMaps;
+    hipLaunchKernelGGL(k_fold_angles, dim3((unsigned) ((nt + 255) / 256)), dim3(256), 0, h->stream, h->dPartials,
+                       h->maxOC, nOC, h->nMaps, orient0, convPerOrient, segs, nRuns, pang, h->angO0);
   }
+  if (h->nMaps <= 64 && nOC >= 1024)
+    hipLaunchKernelGGL(k_fold_wave<4>, dim3(h->nMaps), dim3(256), 0, h->stream, h->dPartials, h->maxOC, nOC, h->nMaps,
+                       bb.params, h->dSumRef, h->dDisp, h->nd, h->pd, orient0, conv0, convPerOrient, ids, pmap);
+  else
+    hipLaunchKernelGGL(k_fold_wave<1>, dim3((h->nMaps + 3) / 4), dim3(256), 0, h->stream, h->dPartials, h->maxOC, nOC,
+                       h->nMaps, bb.params, h->dSumRef, h->dDisp, h->nd, h->pd, orient0, conv0, convPerOrient, ids,
+                       pmap);
   HIP_CHECK(h, hipGetLastError());
   if (phase_end(h, h->stream)) // comparison = the kernels of the launch and the fold behind them (what compareRefMaps does)
     return 1;
@@ -584,7 +572,7 @@ bool dft_use_mfma(int N)
 {
   int A, B;
   dft_split(N, A, B);
-  return dft_mfma_fits(N, A, B) && !getenv("BIOEM_DFT_VECTOR");
+  return dft_mfma_fits(N, A, B);
 }
 hipError_t dft_allow_lds(int N)
 {
@@ -703,10 +691,10 @@ int project_batch(bioem_hip_ctx *h, const BatchBuf &bb, hipStream_t st, int o0, 
   // pixel is granted to that)
   const bool keepLength = h->quatNormDev * 4.0 * std::max(1.0, reach) < 0.5;
   if (h->dStamp && boxSide >= 1 && (size_t) boxSide * boxSide * sizeof(double) <= 52 * 1024 && N < 32768 &&
-      keepLength && !getenv("BIOEM_PROJECT_BANDS") && !getenv("BIOEM_PROJECT_GLOBAL_ATOMICS"))
+      keepLength)
   {
     // with the fast r2c behind it the kernel stores the box alone and the transform skips everything outside it
-    const int compact = r2c_use_fft(N) && !getenv("BIOEM_PROJECT_FULL_MAP");
+    const int compact = r2c_use_fft(N);
     hipLaunchKernelGGL(k_project_box, dim3(std::min(nO, 3 * h->nCU)), dim3(256), sizeof(double) * boxSide * boxSide, st,
                        h->dPts, h->nPts, h->dAngles, o0, h->isQuat, N, h->pixelSize, h->shiftX, h->shiftY, h->iradMax,
                        h->dStamp, boxLo, boxSide, nO, compact, bb.projReal, bb.tempDen);
@@ -717,7 +705,7 @@ int project_batch(bioem_hip_ctx *h, const BatchBuf &bb, hipStream_t st, int o0, 
   const int TR = 40960 / (8 * N); // rows of one LDS band: three blocks per CU
   // the record of every (orientation, point) borrows the row-pass buffer of the r2c that follows
   const bool coordsFit = (size_t) h->nPts * sizeof(ProjectRecord) <= (size_t) N * h->H * sizeof(double2);
-  if (TR >= 12 && h->iradMax <= 16 && h->dStamp && N < 32768 && coordsFit && !getenv("BIOEM_PROJECT_GLOBAL_ATOMICS"))
+  if (TR >= 12 && h->iradMax <= 16 && h->dStamp && N < 32768 && coordsFit)
   {
     ProjectRecord *coords = reinterpret_cast<ProjectRecord *>(bb.rowSpec);
     hipLaunchKernelGGL(k_project_coords, dim3((h->nPts + 255) / 256, nO), dim3(256), 0, st, h->dPts, h->nPts, h->dAngles,
@@ -931,20 +919,6 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
   HIP_CHECK(h, hipDeviceGetAttribute(&h->nCU, hipDeviceAttributeMultiprocessorCount, device));
   HIP_CHECK(h, dft_allow_lds(N));
   HIP_CHECK(h, conv_allow_lds());
-  if (getenv("BIOEM_PREP_OCCUPANCY"))
-  { // blocks per CU the runtime grants the preparation kernels at this image size
-    int nb = 0;
-    const int TRo = std::max(1, 40960 / (8 * N));
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_project_bands, 256, sizeof(double) * TRo * N);
-    fprintf(stderr, "k_project_bands: %d blocks/CU (dynamic LDS %zu B)\n", nb, sizeof(double) * TRo * N);
-    if (dft_use_mfma(N))
-    {
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_dft_rows_mfma<2>, kDftMfmaThreads, dft_mfma_rows_lds(N));
-      fprintf(stderr, "k_dft_rows_mfma<2>: %d blocks/CU (dynamic LDS %zu B)\n", nb, dft_mfma_rows_lds(N));
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_dft_cols_mfma<2>, kDftMfmaThreads, dft_mfma_cols_lds(N));
-      fprintf(stderr, "k_dft_cols_mfma<2>: %d blocks/CU (dynamic LDS %zu B)\n", nb, dft_mfma_cols_lds(N));
-    }
-  }
   {
     int prLow = 0, prHigh = 0;
     HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
@@ -1000,13 +974,14 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
   // kernel reads one argument more, 54.74 against 54.68 M/s).  64^2 and 128^2 gain nothing, 128^2 loses 1...3 % on
   // few-particle jobs: not padded.  k_compare_wide2 (operands once per comparison) gains nothing: its plans, the tiled
   // ones, odd sizes and the direct kernel keep Hp = H.
-  // (BIOEM_PITCH_PAD: another number of words.  7 / 15 / 23 / 31 / 47 are within 2 % of each other at 256^2 ... 512^2,
+  // (Other numbers of words: 7 / 15 / 23 / 31 / 47 are within 2 % of each other at 256^2 ... 512^2,
   // profiles/r04_padded_pitch_ab.txt.)
+  constexpr int kPitchPadWords = 15;
   h->Hp = h->H;
   const bool directCC = getenv("BIOEM_CC_DIRECT") && atoi(getenv("BIOEM_CC_DIRECT")) != 0; // (its own kernels read conv)
   if (h->fast && !h->wide2 && !h->rowsK && !h->tileT && !directCC && N % 64 == 0 && N >= 192 &&
       !getenv("BIOEM_NO_PITCH_PAD"))
-    h->Hp = h->H + (getenv("BIOEM_PITCH_PAD") ? atoi(getenv("BIOEM_PITCH_PAD")) : 15);
+    h->Hp = h->H + kPitchPadWords;
   h->Mc = (size_t) N * h->Hp;
 
   // batch sizing: conv buffer <= ~96 MiB, partial buffer <= ~128 MiB
@@ -1027,7 +1002,7 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
   int obMax = 64;
   {
     const long long perOrient = (long long) nCTF * nMaps;
-    if (perOrient * 64 < 320000 && !getenv("BIOEM_FIXED_BATCH"))
+    if (perOrient * 64 < 320000)
     {
       obMax = (int) std::min<long long>(2048, ((320000 + perOrient - 1) / perOrient + 63) / 64 * 64);
       ocCap = std::min(partCap, (size_t) (1024u << 20) / (h->Mc * sizeof(float2)));
@@ -1038,10 +1013,6 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
     OB = 1;
   if (OB > obMax)
     OB = obMax;
-  if (getenv("BIOEM_PCHUNK")) // tuning knob: particle chunk of the comparison kernel's block order
-    h->pchunk = atoi(getenv("BIOEM_PCHUNK"));
-  if (getenv("BIOEM_BATCH_ORIENTATIONS")) // tuning knob: orientations per batch (conv buffer = OB*nCTF spectra)
-    OB = std::max(1, std::min(OB, atoi(getenv("BIOEM_BATCH_ORIENTATIONS"))));
   if (OB > angO1 - angO0)
     OB = angO1 - angO0;
   h->OB = OB;
@@ -1113,12 +1084,10 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
     // projection/convolution are filler work with many particles: lowest priority so that comparison blocks win the
     // CUs.  With few particles they are the longer half of the pipeline and waiting behind every comparison block
     // stretches them four- to sixfold: same priority as the comparison then (20 particles: 8.41 -> 8.25 ms per pass;
-    // 1 000 particles: no difference either way).  BIOEM_PREP_PRIORITY=low|high overrides.
+    // 1 000 particles: no difference either way).
     int prLow = 0, prHigh = 0;
     HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
-    bool prepHigh = nMaps <= 64;
-    if (const char *e = getenv("BIOEM_PREP_PRIORITY"))
-      prepHigh = e[0] == 'h';
+    const bool prepHigh = nMaps <= 64;
     HIP_CHECK(h, hipStreamCreateWithPriority(&h->prepStream, hipStreamNonBlocking, prepHigh ? prHigh : prLow));
   }
   HIP_CHECK(h, hipMalloc(&h->dProjReal2, sizeof(double) * (size_t) h->OB * N * N));
@@ -1561,7 +1530,7 @@ int bioem_hip_project_convolve_compare_ctf(bioem_hip_handle h, int iOrientBegin,
   // (round 4, with the preparation 2.5x faster than when 32 768 was chosen: 65 536 pairs per batch at least for small
   // images -- 128^2 x 10 particles x 4 608 orientations 63.7 -> 66.2 M/s, x 1 152: 52.5 -> 57.5; 131 072 the same,
   // 16 384 and less lose; at 224^2 32 768 stays: 10 particles 28.6 against 27.3 M/s with 65 536)
-  const long long minPairs = getenv("BIOEM_MIN_BATCH_PAIRS") ? atoll(getenv("BIOEM_MIN_BATCH_PAIRS")) : (h->N <= 160 ? 65536 : 32768);
+  const long long minPairs = h->N <= 160 ? 65536 : 32768;
   const int perBatch = (int) std::min<long long>(h->OB, (minPairs + (long long) nC * h->nMaps - 1) / ((long long) nC * h->nMaps));
   const int OBc = std::min(h->OB, std::max(std::max(64, perBatch), (iOrientEnd - iOrientBegin + 5) / 6));
   // (Round 4 measured batches that shrink towards the END as well -- a half, a quarter of the regular size, so that
@@ -2150,17 +2119,6 @@ int bioem_hip_reset_kernel_stats(bioem_hip_handle h)
   h->comparisons = 0;
   return 0;
 }
-
-#ifdef BIOEM_W2_STAMPS
-// diagnostic build only: summed shader cycles per phase of k_compare_wide2 (and reset)
-int bioem_hip_debug_w2_stamps(unsigned long long *out8)
-{
-  unsigned long long z[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_w2_stamps), sizeof(z)) != hipSuccess)
-    return 1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_w2_stamps), z, sizeof(z)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 int bioem_hip_uses_fast_path(bioem_hip_handle h) { return h && h->fast ? 1 : 0; }
 

@@ -1,5 +1,6 @@
 // compare_fast.hpp -- fast comparison kernel (output-pruned 2-D transform fused with the posterior) + Nyquist rows
-// Part of libbioem_hip.so; included by bioem_hip.hip only (one translation unit, anonymous namespace).
+// Part of libbioem_hip.so; included by bioem_hip.hip and by every kernels_*.hip unit of a comparison family (its
+// helpers serve them all; anonymous namespace).
 #ifndef BIOEM_COMPARE_FAST_HPP
 #define BIOEM_COMPARE_FAST_HPP
 
@@ -324,29 +325,6 @@ __device__ __forceinline__ void window_accumulate(const float2 *Tl, const float2
     else                                                                                                           \
       fft_inverse_mixed<R>(xr, xi);                                                                                \
   } while (0)
-#ifndef BIOEM_MASK_IDLE_COLUMNS
-#define BIOEM_MASK_IDLE_COLUMNS 1
-#endif
-#ifndef BIOEM_BLOCK_BARRIER
-#define BIOEM_BLOCK_BARRIER 1
-#endif
-#if BIOEM_BLOCK_BARRIER
-#define WAVE_OR_BLOCK_SYNC() __syncthreads()
-#else
-#define WAVE_OR_BLOCK_SYNC()                                                                                       \
-  do                                                                                                               \
-  {                                                                                                                \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                         \
-    __builtin_amdgcn_wave_barrier();                                                                               \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                                         \
-  } while (0)
-#endif
-#ifndef BIOEM_FAST_WAVES_PER_SIMD
-#define BIOEM_FAST_WAVES_PER_SIMD 3
-#endif
-#ifndef BIOEM_FAST_HALVES
-#define BIOEM_FAST_HALVES 0
-#endif
 // NYQ (N/2 a multiple of 64, e.g. 128 and 256): the half spectrum has N/2 + 1 columns, one more than fills the
 // 64-lane column blocks, and a whole extra block pass for that single Nyquist column would cost 1/2 (128) or 1/3
 // (256) of the kernel.  Instead k_nyquist_rows (below) forms the 2*WD+1 column-transform outputs of that column
@@ -357,20 +335,17 @@ __device__ __forceinline__ void window_accumulate(const float2 *Tl, const float2
 // DISPLACE_CENTER grid whose offsets are all multiples of GS reaches +-15*GS pixels with the same 2*WD+1 rows.
 // (27- and 31-row windows: k_compare_fastm, compare_fastm.hpp)
 template <int WD, int R, bool NYQ, int GS>
-__global__ __launch_bounds__(256, BIOEM_FAST_WAVES_PER_SIMD) void k_compare_fast(const CompareArgs a)
+__global__ __launch_bounds__(256, 3) void k_compare_fast(const CompareArgs a)
 {
   static_assert(WD <= 10, "windows of at most 21 rows; 27 / 31 rows: k_compare_fastm");
   constexpr int NW = 2 * WD + 1;
   constexpr int R2 = R / 2;            // rows (k2 pairs) per k1 step
   // depth of the operand ring: must divide R2 so that a ring slot is a compile-time function of the k2 pair
   // (R = 30: a ring of 3, not 5 -- 16 registers the 21-row window of that length needs)
-#ifndef BIOEM_FAST_RING
-#define BIOEM_FAST_RING 0
-#endif
-  constexpr int RD = BIOEM_FAST_RING ? BIOEM_FAST_RING : (R2 % 4 == 0) ? 4 : (R2 == 15) ? 3 : (R2 % 5 == 0) ? 5 : (R2 % 3 == 0) ? 3 : (R2 % 2 == 0) ? 2 : 1;
+  constexpr int RD = (R2 % 4 == 0) ? 4 : (R2 == 15) ? 3 : (R2 % 5 == 0) ? 5 : (R2 % 3 == 0) ? 3 : (R2 % 2 == 0) ? 2 : 1;
   constexpr int NR = (WD <= 5) ? 3 : 7; // accumulators (window rows) per lane
-  // T row stride in float2 (64 or 32 columns + 2 pad: row groups land on different banks)
-  constexpr int TS = BIOEM_FAST_HALVES ? 34 : 66;
+  // T row stride in float2 (64 columns + 2 pad: row groups land on different banks)
+  constexpr int TS = 66;
   extern __shared__ __align__(16) unsigned char smem[];
   const int N = a.N, H = a.H, N1 = a.N1;
   float2 *twl = reinterpret_cast<float2 *>(smem);                            // N+1 (+pad)
@@ -413,18 +388,10 @@ __global__ __launch_bounds__(256, BIOEM_FAST_WAVES_PER_SIMD) void k_compare_fast
   const int Hp = a.Hp; // row-pair pitch in 16-byte words (H, or H + 15: comparison_pitch in bioem_hip.hip)
   const size_t M = (size_t) N * Hp;
   // buffer descriptors built from wave-uniform values only (blockIdx / readfirstlane'd wave id)
-  // timing-only ablation builds (never shipped): a zero-record descriptor drops the loads of one operand while
-  // the instruction stream and waits stay (cdna_hip_programming.md, profiling: pricing one buffer's traffic)
-#ifndef BIOEM_ABLATE_F
-#define BIOEM_ABLATE_F 0
-#endif
-#ifndef BIOEM_ABLATE_C
-#define BIOEM_ABLATE_C 0
-#endif
   const auto rsrcF = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<float2 *>(a.ref + (size_t) p * M)), 0,
-                                                       BIOEM_ABLATE_F ? 0 : (int) (M * sizeof(float2)), 0x00020000);
+                                                       (int) (M * sizeof(float2)), 0x00020000);
   const auto rsrcC = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<float2 *>(a.conv + (size_t) oc * M)), 0,
-                                                       BIOEM_ABLATE_C ? 0 : (int) (M * sizeof(float2)), 0x00020000);
+                                                       (int) (M * sizeof(float2)), 0x00020000);
 
   // window lanes
   const int nd = a.nd;
@@ -501,11 +468,9 @@ __global__ __launch_bounds__(256, BIOEM_FAST_WAVES_PER_SIMD) void k_compare_fast
       Tr[d] = 0.f;
       Ti[d] = 0.f;
     }
-#if BIOEM_MASK_IDLE_COLUMNS
     // lanes beyond the last column of the last block sit out the whole transform (EXEC masked once): their
     // loads would only burn vector-memory cycles, and their T columns stay zero
     if (ky < H)
-#endif
     for (int k1 = 0; k1 < n1; k1++)
     {
       float xr[R], xi[R];
@@ -575,50 +540,15 @@ __global__ __launch_bounds__(256, BIOEM_FAST_WAVES_PER_SIMD) void k_compare_fast
       wgt = 1.f;
     if (ky >= H || (split && hsel))
       wgt = 0.f;
-    // T block of THIS wave only: LDS operations of one wave execute in order, so a wave-level fence (no
-    // s_barrier) is enough; BIOEM_BLOCK_BARRIER=1 restores block barriers (keeps the 4 waves in lock-step)
-#if BIOEM_FAST_HALVES
-    for (int hx = 0; hx < 2; hx++)
+    // T block of THIS wave only, written and read between block barriers (they keep the 4 waves in lock-step)
     {
-      const int npairs = min(16, ((H - blk * 64 + 1) >> 1) - 16 * hx);
-      if (npairs <= 0)
-        break;
-      WAVE_OR_BLOCK_SYNC(); // previous window reads are done
-      if (hsel == hx)
-      {
-#pragma unroll
-        for (int d = 0; d < NW; d++)
-          Tl[d * TS + (lane & 31)] = make_float2(Tr[d] * wgt, Ti[d] * wgt);
-      }
-      WAVE_OR_BLOCK_SYNC();
-      const int idx0 = (int) (((long long) (blk * 64 + 32 * hx) * step) % N);
-      if (is_static)
-      {
-        const int rowoff[NR] = {rowbase};
-        window_accumulate<NR, true, 16, TS>(Tl, twl, N, step, idx0, rowoff, nr, acc, npairs);
-      }
-      else
-      {
-        int rowoff[NR];
-#pragma unroll
-        for (int r = 0; r < NR; r++)
-          rowoff[r] = row_of(r);
-        window_accumulate<NR, false, 16, TS>(Tl, twl, N, step, idx0, rowoff, nr, acc, npairs);
-      }
-    }
-#else
-    {
-      WAVE_OR_BLOCK_SYNC(); // previous window reads are done
+      __syncthreads(); // previous window reads are done
 #pragma unroll
       for (int d = 0; d < NW; d++)
         Tl[d * TS + lane] = make_float2(Tr[d] * wgt, Ti[d] * wgt);
-      WAVE_OR_BLOCK_SYNC();
+      __syncthreads();
       const int idx0 = (int) (((long long) (blk * 64) * step) % N);
-#if BIOEM_MASK_IDLE_COLUMNS
       const int npairs = min(32, (H - blk * 64 + 1) >> 1); // columns of this block that exist, in pairs
-#else
-      const int npairs = 32;
-#endif
       if (is_static)
       {
         const int rowoff[NR] = {rowbase};
@@ -633,7 +563,6 @@ __global__ __launch_bounds__(256, BIOEM_FAST_WAVES_PER_SIMD) void k_compare_fast
         window_accumulate<NR, false, 32, TS>(Tl, twl, N, step, idx0, rowoff, nr, acc, npairs);
       }
     }
-#endif
   }
   if (NYQ)
   {

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fastm(const CompareArgs a)
 #pragma unroll
     for (int hh = 0; hh < 2; hh++)
     {
-      WAVE_OR_BLOCK_SYNC(); // the matrix pass of the previous half has read its operands
+      __syncthreads(); // the matrix pass of the previous half has read its operands
       if ((lane >> 5) == hh)
       {
 #pragma unroll
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fastm(const CompareArgs a)
           Pl[PLANE + d * PS + (lane & 31)] = -(Ti[d] * wgt);
         }
       }
-      WAVE_OR_BLOCK_SYNC();
+      __syncthreads();
       const int ky0 = blk * 64 + hh * 32;
       if (ky0 < (NYQ ? H - 1 : H))
       {

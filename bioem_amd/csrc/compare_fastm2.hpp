@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fastm2(const CompareArgs a)
 #pragma unroll
         for (int ct = 0; ct < 3; ct++)
           bq[q][ct] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrcB, (unsigned) lane * 4u, soff0 + (unsigned) (q * 3 + ct) * 256u, 0));
-      WAVE_OR_BLOCK_SYNC(); // D is out of LDS
+      __syncthreads(); // D is out of LDS
 #pragma unroll
       for (int d = 0; d < NACC; d++)
       {
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fastm2(const CompareArgs a)
           }
         }
       }
-      WAVE_OR_BLOCK_SYNC();
+      __syncthreads();
 #pragma unroll
       for (int k4 = 0; k4 < 16; k4 += PF)
       {
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fastm2(const CompareArgs a)
         }
       }
     }
-    WAVE_OR_BLOCK_SYNC(); // the planes are read: their space takes the accumulators until the next matrix pass
+    __syncthreads(); // the planes are read: their space takes the accumulators until the next matrix pass
 #pragma unroll
     for (int rt = 0; rt < 3; rt++)
 #pragma unroll

@@ -152,11 +152,11 @@ __global__ __launch_bounds__(256, (WD <= 10 ? 3 : 2)) void k_compare_rows(const 
       wgt = 1.f;
     if (ky >= H)
       wgt = 0.f;
-    WAVE_OR_BLOCK_SYNC(); // previous window reads are done
+    __syncthreads(); // previous window reads are done
 #pragma unroll
     for (int d = 0; d < NW; d++)
       Tl[d * TS + lane] = make_float2(Tr[d] * wgt, Ti[d] * wgt);
-    WAVE_OR_BLOCK_SYNC();
+    __syncthreads();
     const int idx0 = (int) (((long long) blk * 64 * step) % N);
     const int npairs = min(32, (H - blk * 64 + 1) >> 1); // columns of this block that exist, in pairs
     if (is_static)
@@ -369,11 +369,11 @@ __global__ __launch_bounds__(256, (WD <= 10 ? 3 : 2)) void k_compare_oddfft(cons
       wgt = 1.f;
     if (ky >= H)
       wgt = 0.f;
-    WAVE_OR_BLOCK_SYNC(); // previous window reads are done
+    __syncthreads(); // previous window reads are done
 #pragma unroll
     for (int d = 0; d < NW; d++)
       Tl[d * TS + lane] = make_float2(Tr[d] * wgt, Ti[d] * wgt);
-    WAVE_OR_BLOCK_SYNC();
+    __syncthreads();
     const int idx0 = (int) (((long long) blk * 64 * step) % N);
     const int npairs = min(32, (H - blk * 64 + 1) >> 1); // columns of this block that exist, in pairs
     if (is_static)

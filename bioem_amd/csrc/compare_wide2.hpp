@@ -1,5 +1,5 @@
 // compare_wide2.hpp -- wide translation windows (more than 31 offsets per axis) with a row FFT: one comparison per block
-// Part of libbioem_hip.so; included by bioem_hip.hip only (one translation unit, anonymous namespace).
+// Part of libbioem_hip.so; included by bioem_hip.hip and the kernels_wide2_*.hip units (anonymous namespace).
 #ifndef BIOEM_COMPARE_WIDE2_HPP
 #define BIOEM_COMPARE_WIDE2_HPP
 
@@ -32,47 +32,18 @@ namespace
 // reference's order (bioem_algorithm.h:156-197 / bioem.cpp:1477-1485).
 // LDS: tables + max(4 R 512 B, rows2 TS 8 B): 76 KiB at 224^2 +-40 px -> two blocks per CU.
 // ------------------------------------------------------------------------------------------------
-// diagnostic build only (-DBIOEM_W2_STAMPS, never shipped): shader-clock cycles per phase of wave 0, summed over blocks
-#ifdef BIOEM_W2_STAMPS
-__device__ unsigned long long g_w2_stamps[16];
-#define W2_STAMP(k)                                                                                                \
-  do                                                                                                               \
-  {                                                                                                                \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                                  \
-    if (threadIdx.x == 0)                                                                                          \
-      atomicAdd(&g_w2_stamps[k], now_ - stamp_);                                                                   \
-    stamp_ = now_;                                                                                                 \
-  } while (0)
-#else
-#define W2_STAMP(k)
-#endif
-
 // HALVES = 2: the T block goes through LDS in two halves of the window rows (row pass + posterior per half), for the
 // sizes whose whole T block would leave one block per CU (240^2 ... 256^2 at +-35 ... +-42 px)
 // NW = 8: eight waves per comparison (512-thread blocks) -- half the window rows per wave, so that the 16-point
 // instantiation with 11 rows per wave (110 registers) covers windows of up to 88 rows at FOUR waves per SIMD with two
 // blocks per CU, and larger images / windows keep a register-sized share per wave
-#ifndef BIOEM_W2_HALVES_WAVES
-#define BIOEM_W2_HALVES_WAVES 2 // (experiment builds: 3 = the halves kernels under the three-wave register bound)
-#endif
 template <int R, int NRW, int NBLK, bool NYQ, int HALVES = 1, int NW = 4>
 // waves per SIMD the registers must allow: the T block in halves means its LDS footprint holds a CU to two blocks anyway
 __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ? 4 : 2)
-                                      : HALVES == 2 ? BIOEM_W2_HALVES_WAVES
+                                      : HALVES == 2 ? 2
                                                     : ((NRW * NBLK <= 42 && R <= 16) ? 3 : 2)) void k_compare_wide2(const CompareArgs a)
 {
   constexpr int R2 = R / 2;
-  // depth of the operand ring (divides R2): the first RD row pairs of a wave's next step are issued before the
-  // round's barriers.  With only two waves per SIMD the ring is what hides the L2 latency: as deep as registers allow
-#ifndef BIOEM_W2_RING
-#define BIOEM_W2_RING 4
-#endif
-  constexpr int RD = (R2 % BIOEM_W2_RING == 0) ? BIOEM_W2_RING
-                     : (R2 % 4 == 0)           ? 4
-                     : (R2 % 5 == 0)           ? 5
-                     : (R2 % 3 == 0)           ? 3
-                     : (R2 % 2 == 0)           ? 2
-                                               : 1;
   struct PostConst
   {
     double t2, prior;
@@ -132,19 +103,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
     }
   }
   const size_t M = (size_t) N * H;
-  // timing-only ablation builds (never shipped): zero-record descriptors drop the operand traffic, the instruction
-  // stream and waits stay
-#ifndef BIOEM_W2_ABLATE
-#define BIOEM_W2_ABLATE 0
-#endif
   const auto rsrcF = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<float2 *>(a.ref + (size_t) p * M)), 0,
-                                                       BIOEM_W2_ABLATE ? 0 : (int) (M * sizeof(float2)), 0x00020000);
+                                                       (int) (M * sizeof(float2)), 0x00020000);
   const auto rsrcC = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<float2 *>(a.conv + (size_t) oc * M)), 0,
-                                                       BIOEM_W2_ABLATE ? 0 : (int) (M * sizeof(float2)), 0x00020000);
+                                                       (int) (M * sizeof(float2)), 0x00020000);
 
-#ifdef BIOEM_W2_STAMPS
-  unsigned long long stamp_ = __builtin_amdgcn_s_memtime();
-#endif
   // ---------------- column pass ----------------
   const int nblk = NYQ ? (H - 1) / 64 : (H + 63) / 64;
   const int rpw = (nd + NW - 1) / NW; // window rows per wave
@@ -179,10 +142,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
   // LDS position of window row d's residue row inside a slot: lane addresses held in registers over the column pass,
   // except in the 8-point instantiations, which form the wave-uniform part on the scalar side where it is used
   // (measured: registers +1 % for R >= 16, scalar +8 % for R = 8 at 120^2 +-25 px)
-  #ifndef BIOEM_W2_YOFF
-#define BIOEM_W2_YOFF 1
-#endif
-  constexpr bool YOFF_REGS = BIOEM_W2_YOFF && R > 8 && !(HALVES == 2 && NBLK >= 3) && !(HALVES == 2 && NRW > 21);
+  constexpr bool YOFF_REGS = R > 8 && !(HALVES == 2 && NBLK >= 3) && !(HALVES == 2 && NRW > 21);
   const int dx0 = (r0 - mD) * gs;
   const int res0 = ((dx0 % R) + R) % R; // residue of the wave's first row; row d: (res0 + d gs) mod R
   int yoff[YOFF_REGS ? NRW : 1];
@@ -192,17 +152,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
     for (int d = 0; d < NRW; d++)
       yoff[YOFF_REGS ? d : 0] = ((res0 + d * gs) % R) * 64 + lane;
   }
-  // particle row pairs of this wave's NEXT step may be requested as soon as the current step's outputs are parked
-  // (BIOEM_W2_FNEXT; measured: -1.6 %, and the kernel without ANY operand traffic -- zero-record descriptors -- is only
-  // 3 % faster: operand delivery is not what the time goes to, so the registers are spent elsewhere)
-#ifndef BIOEM_W2_FNEXT
-#define BIOEM_W2_FNEXT 0
-#endif
   // particle row pairs requested at once: all R/2, or a ring of 8 where three column blocks of accumulators leave
   // no room for 16 (k_compare_wide2<32, 21, 3>)
   constexpr int RF = (NBLK >= 3 && R2 == 16) ? 8 : R2;
+  // conv row pairs in flight: a ring whose depth divides R/2 (with two waves per SIMD the rings are what hides the L2
+  // latency)
+  constexpr int RC = (R2 % 4 == 0) ? 4 : (R2 % 5 == 0) ? 5 : (R2 % 3 == 0) ? 3 : (R2 % 2 == 0) ? 2 : 1;
   u32x4 fx[RF];
-  bool fready = false;
+  // (requesting the NEXT step's particle rows here, before the fold, was measured and not kept: DESIGN.md 2.4)
   auto request_f = [&](int k1n, unsigned laneoffn) {
 #pragma unroll
     for (int t = 0; t < RF; t++)
@@ -215,8 +172,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
     {
       const int ky = blk * 64 + lane;
       const unsigned laneoff = (unsigned) (ky < H ? ky : H - 1) * 16u;
-      const int kyn = ky + 64;
-      const unsigned laneoff_next = (unsigned) (kyn < H ? kyn : H - 1) * 16u;
       for (int base = 0; base < N1; base += NW)
       {
         const int k1 = base + wave;
@@ -226,13 +181,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
           // operands of the step: ALL R/2 particle row pairs are requested at once -- they land in the registers the
           // FFT inputs take over (a row pair of F is consumed exactly when its two products are formed), the conv
           // row pairs follow through a ring
-#ifndef BIOEM_W2_CRING
-#define BIOEM_W2_CRING 4
-#endif
-          constexpr int RC = (R2 % BIOEM_W2_CRING == 0) ? BIOEM_W2_CRING : RD;
           u32x4 rc[RC];
-          if (!fready)
-            request_f(k1, laneoff);
+          request_f(k1, laneoff);
 #pragma unroll
           for (int t = 0; t < RC; t++)
             rc[t] = __builtin_amdgcn_raw_buffer_load_b128(rsrcC, laneoff, (unsigned) (k1 * R2 + t) * rowbytes, 0);
@@ -254,52 +204,27 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
                                                                   (unsigned) (k1 * R2 + k2p + RC) * rowbytes, 0);
             __builtin_amdgcn_sched_barrier(0);
           }
-          W2_STAMP(8);
           FFT_RUN(xr, xi);
-          W2_STAMP(9);
           float2 *slot = U + (size_t) wave * R * 64 + lane;
 #pragma unroll
           for (int n = 0; n < R; n++)
             slot[n * 64] = make_float2(xr[FFT_OUT(n)], xi[FFT_OUT(n)]);
-          // next step of this wave: same block four k1 further, or the first one of the next column block
-          fready = false;
-          if (BIOEM_W2_FNEXT && k1 + NW < N1)
-          {
-            request_f(k1 + NW, laneoff);
-            fready = true;
-          }
-          else if (BIOEM_W2_FNEXT && blk + 1 < nblk && wave < N1)
-          {
-            request_f(wave, laneoff_next);
-            fready = true;
-          }
-          W2_STAMP(10);
         }
-#ifndef BIOEM_W2_TIMING_NOBARRIER
         __syncthreads();
-#endif
-        W2_STAMP(5);
         // fold the round's slots into this wave's rows:  T[dx] += w_N^(dx k1) * y_k1[dx mod R]
         // (all NRW accumulators; rows beyond this wave's share fold zeros and are never stored)
 #pragma unroll
         for (int s = 0; s < NW; s++)
         {
           const int k1s = base + s;
-#ifdef BIOEM_W2_TIMING_NOFOLD
-          if (k1s < N1 && a.nd > 1000)
-#else
           if (k1s < N1)
-#endif
           {
             // this wave's NRW twiddles of step k1s are contiguous: a few wide scalar loads
             const const_float2_ptr twk = as_constant(a.twk) + ((size_t) k1s * NW + wave) * NRW;
             const float2 *ys = U + (size_t) s * R * 64;
-#ifndef BIOEM_W2_FOLD_CHUNK
-#define BIOEM_W2_FOLD_CHUNK 7
-#endif
             // rows in chunks: a chunk's LDS reads are issued together, then its FMAs (the chunk size bounds the
             // registers the reads occupy)
-            constexpr int FC = BIOEM_W2_FOLD_CHUNK;
+            constexpr int FC = 7;
 #pragma unroll
             for (int d0 = 0; d0 < NRW; d0 += FC)
             {
@@ -308,16 +233,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
               for (int e = 0; e < FC; e++)
               {
                 const int d = d0 + e < NRW ? d0 + e : NRW - 1;
-#ifdef BIOEM_W2_TIMING_ONETW
-                w[e] = make_float2(twk[0].x, twk[0].y); // timing only: one scalar load per slot instead of NRW
-#else
                 w[e] = make_float2(twk[d].x, twk[d].y);
-#endif
-#ifdef BIOEM_W2_TIMING_ONEY
-                y[e] = ys[yoff[0]];                     // timing only: one LDS read per slot
-#else
                 y[e] = YOFF_REGS ? ys[yoff[YOFF_REGS ? d : 0]] : ys[((res0 + d * gs) % R) * 64 + lane];
-#endif
               }
 #pragma unroll
               for (int e = 0; e < FC; e++)
@@ -337,14 +254,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
             }
           }
         }
-#ifndef BIOEM_W2_TIMING_NOBARRIER
         __syncthreads();
-#endif
-        W2_STAMP(6);
       }
     }
   }
-  W2_STAMP(0);
   const PostW pw = post_consts(a.pd.Ntotpi, N, cst->q, cst->sumref, cst->sumsqref, cst->t2, cst->prior);
   LseF L;
   L.m = -INFINITY;
@@ -382,7 +295,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
       Tl[(size_t) (nd - h0) * TS + c] = make_float2(0.f, 0.f);
   __syncthreads();
 
-  W2_STAMP(1);
   // ---------------- row pass: pairs of rows, private to a wave ----------------
   const int npairs = (h1 - h0) >> 1;
   const int ppw = (npairs + NW - 1) / NW;
@@ -431,7 +343,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  W2_STAMP(2);
 
   // ---------------- recombination over k1 + posterior: lanes = dy ----------------
   for (int c0 = 0; c0 < nd; c0 += 64)
@@ -448,16 +359,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
     // two row pairs per step: their recombination sums and the four log posteriors are independent chains that
     // overlap each other's LDS and double-precision latencies (two waves per SIMD hide little of them)
     // (measured: +4 % at +-40 px for the two-wave instantiations, -2..-4 % for the three-wave ones, which keep one pair)
-#ifndef BIOEM_W2_PPS
-#define BIOEM_W2_PPS 0
-#endif
-    constexpr int PPS = BIOEM_W2_PPS ? BIOEM_W2_PPS : (NRW * NBLK <= 26 && R <= 16) ? 1 : 2;
+    constexpr int PPS = (NRW * NBLK <= 26 && R <= 16) ? 1 : 2;
     // the lane's N1 - 1 recombination twiddles depend on dy only: for N1 <= 8 they are fetched once per chunk and
     // stay in registers over all row pairs (entries beyond N1 are zero and multiply a clamped, finite y)
-#ifndef BIOEM_W2_K1H
-#define BIOEM_W2_K1H 8
-#endif
-    constexpr int K1H = BIOEM_W2_K1H;
+    constexpr int K1H = 8;
     const bool hoist = N1 <= K1H;
     float2 wk[K1H];
     if (hoist)
@@ -528,7 +433,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
           }
         }
       }
-      W2_STAMP(11);
       float accv[2 * PPS];
       int idv[2 * PPS];
       bool okv[2 * PPS];
@@ -541,18 +445,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((NRW * NBLK <= 26 && R <= 16) ?
         idv[v] = dinv[min(m, nd - 1)] * nd + iyr;
       }
       posterior_batch<2 * PPS>(L, accv, idv, okv, pw, ltab, a.algo);
-      W2_STAMP(12);
     }
   }
     if (hf + 1 < HALVES)
       __syncthreads(); // every wave is done with this half's rows before the next half overwrites them
   }
-  W2_STAMP(3);
   lsef_wave_reduce(L);
   if (lane == 0)
     lsew[wave] = L;
   __syncthreads();
-  W2_STAMP(4);
   if (threadIdx.x == 0)
   {
     LseF Z = lsew[0];

@@ -7,62 +7,10 @@ namespace
 {
 
 // ------------------------------------------------------------------------------------------------
-// fold: one thread per particle walks its partials in (orientation, CTF) order.
-// bioem_algorithm.h:94-141 / bioem.cpp:1527-1600.
-// ------------------------------------------------------------------------------------------------
-__global__ void k_fold(const Partial *__restrict__ partials, int ldPart, int nOC, int nMaps,
-                       const bioem_hip_param5 *__restrict__ params, const float *__restrict__ sumRef,
-                       const int *__restrict__ disp, int nd, PD pd, int orient0, int conv0, int convPerOrient,
-                       const int2 *__restrict__ ids, bioem_hip_prob_map *__restrict__ pmap,
-                       bioem_hip_prob_angle *__restrict__ pang, int angO0)
-{
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= nMaps)
-    return;
-  bioem_hip_prob_map pm = pmap[p];
-  const float sumref = sumRef[p];
-  const Partial *P = partials + (size_t) p * ldPart;
-  for (int oc = 0; oc < nOC; oc++)
-  {
-    const Partial r = P[oc];
-    const int iOrient = ids ? ids[oc].x : orient0 + oc / convPerOrient;
-    const int iConv = ids ? ids[oc].y : conv0 + oc % convPerOrient;
-    const double lp = (double) r.best;
-    if (pm.Constoadd < lp)
-    {
-      pm.Total *= exp(-lp + pm.Constoadd);
-      pm.Constoadd = lp;
-      const int ix = r.id / nd, iy = r.id - ix * nd;
-      pm.max_prob_cent_x = -disp[ix];
-      pm.max_prob_cent_y = -disp[iy];
-      pm.max_prob_orient = iOrient;
-      pm.max_prob_conv = iConv;
-      const bioem_hip_param5 q = params[oc];
-      const float value = r.value;
-      pm.max_prob_norm = -(-q.sumC * sumref + pd.Ntotpi * value) / (q.sumC * q.sumC - q.sumsquareC * pd.Ntotpi);
-      pm.max_prob_mu = -(-q.sumC * value + q.sumsquareC * sumref) / (q.sumC * q.sumC - q.sumsquareC * pd.Ntotpi);
-    }
-    pm.Total += r.sumExp * exp(lp - pm.Constoadd);
-    if (pd.writeAngles)
-    {
-      bioem_hip_prob_angle pa = pang[(size_t) (iOrient - angO0) * nMaps + p];
-      if (pa.ConstAngle < lp)
-      {
-        pa.forAngles *= exp(-lp + pa.ConstAngle);
-        pa.ConstAngle = lp;
-      }
-      pa.forAngles += r.sumExp * exp(lp - pa.ConstAngle);
-      pang[(size_t) (iOrient - angO0) * nMaps + p] = pa;
-    }
-  }
-  pmap[p] = pm;
-}
-
-// ------------------------------------------------------------------------------------------------
 // WRITE_PROB_ANGLES table: one thread per (particle, orientation of this launch) folds that orientation's CTF
-// partials into its angle entry, in CTF order -- the same arithmetic sequence per entry as k_fold
-// (bioem_algorithm.h:130-141), but nMaps * nOrient threads instead of nMaps.  The particle entries are then
-// folded by k_fold_wave.  Rows of orientation j: [j*convPerOrient, (j+1)*convPerOrient) (native path, segs == null)
+// partials into its angle entry, in CTF order -- the same arithmetic sequence per entry as the reference
+// (bioem_algorithm.h:130-141).  The particle entries are then folded by k_fold_wave.  Rows of orientation j:
+// [j*convPerOrient, (j+1)*convPerOrient) (native path, segs == null)
 // or the run segs[j] = {first row, end row, orientation} (compat ring: every orientation of a launch is ONE run).
 // ------------------------------------------------------------------------------------------------
 __global__ void k_fold_angles(const Partial *__restrict__ partials, int ldPart, int nOC, int nMaps, int orient0,
@@ -102,7 +50,8 @@ __global__ void k_fold_angles(const Partial *__restrict__ partials, int ldPart, 
 // wave-parallel fold of the particle entries: one wave per particle; lane l folds a contiguous chunk of
 // (orientation, CTF) partials in order, the 64 chunk results are merged by a shuffle reduction that keeps
 // the FIRST maximum (lowest index), then combined with the running state exactly like the sequential fold.
-// The log-sum-exp merge is associative, so the result equals k_fold's up to double rounding (1e-16).
+// The log-sum-exp merge is associative, so the result equals the sequential fold's (bioem_algorithm.h:94-141 /
+// bioem.cpp:1527-1600) up to double rounding (1e-16).
 // ------------------------------------------------------------------------------------------------
 // WPP = 4 (few particles: one wave per particle left the chip to ten waves walking 48 partials each, 40 us per launch):
 // the four waves of a block share one particle, wave w the w-th quarter of its partials; their results are merged in

@@ -1,5 +1,5 @@
 // kernel_select.hpp -- which comparison kernel runs a given (image size, displacement set): ONE place
-// Part of libbioem_hip.so; included by bioem_hip.hip only (one translation unit, anonymous namespace).
+// Part of libbioem_hip.so; included by bioem_hip.hip (the kernel tables it searches live in the kernels_*.hip units).
 //
 //   kernel_table.inc   the instantiations that exist (one line each; scripts/make_kernel_table.py writes it from a
 //                      selection snapshot, scripts/check_kernel_coverage.py holds it against what the GPU tests ran)
@@ -9,30 +9,21 @@
 //   plan_kernels       pure function (no HIP call): displacement list -> KernelPlan; bioem_hip_plan exposes it, so the
 //                      selection is testable without a GPU (tests/test_selection_table.py)
 //
-// Environment knobs of the selection (experiments; none is needed for production runs):
-//   BIOEM_NO_WIDE2        wide windows on tiles of the 21/27/31-row kernels instead of k_compare_wide2
-//   BIOEM_FORCE_WIDE2     k_compare_wide2 from 21 rows on (tests: every instantiation on small shapes)
-//   BIOEM_W2_R=<len>      register-FFT length of k_compare_wide2 where it divides N
-//   BIOEM_NO_TILES        no window tiles: what does not fit a kernel runs k_compare_generic
-//   BIOEM_TILE_ROWS=<t>   tile size of the tiled path (21, 27, 31)
-//   BIOEM_NO_FASTM2       33..47-row windows on k_compare_wide2 (k_compare_fastm2 off)
-//   BIOEM_NO_FASTM        27/31-row windows on tiles of the 21-row kernel (k_compare_fastm off)
-//   BIOEM_NO_ROWS_KERNEL  odd sizes on k_compare_generic
-//   BIOEM_NO_ODD_FFT      odd sizes on k_compare_rows (direct column sums) even where an odd register FFT divides N
-//   BIOEM_POW2_FFT        power-of-two register FFTs only
-//   BIOEM_LONGEST_FFT     k_compare_fast with the longest register FFT at every size (round 3's rule)
-//   BIOEM_FAST_R=<len>    k_compare_fast with this register-FFT length only (sweeps)
-//   BIOEM_KEEP_WD5        11-row windows keep the 11-row template at every size
-// (run-time knobs outside the selection: BIOEM_PCHUNK, BIOEM_BATCH_ORIENTATIONS, BIOEM_FIXED_BATCH, BIOEM_NO_GROUP_XCD,
-//  BIOEM_COMPAT_RING, BIOEM_SERIAL_FOLD, BIOEM_SIGNATURE_LOG, BIOEM_HIP_LIBRARY (Python loader), BIOEM_NO_SPLIT_LAST (no
-//  half-wave split of a narrow last column block), BIOEM_NO_PITCH_PAD / BIOEM_PITCH_PAD=<words> (row-pair pitch of the
-//  comparison layout), BIOEM_MIN_BATCH_PAIRS, BIOEM_CONVOLVE_FUSED)
+// Environment knobs of libbioem_hip.so, the complete list (tests/test_abi_and_host.py pins it).  None is needed for
+// production runs.  Each is read where it acts, every time, so that a test can set it per case:
+//   BIOEM_FORCE_WIDE2           k_compare_wide2 from 21 rows on (test_gpu_parity.py: all wide2 instantiations)
+//   BIOEM_NO_SPLIT_LAST         no half-wave split of a narrow last column block (test_gpu_parity.py: split = unsplit)
+//   BIOEM_NO_PITCH_PAD          comparison layout at pitch H (test_gpu_parity.py: padded = unpadded)
+//   BIOEM_CC_DIRECT=1           cross-correlation as a real-space sliding window (BASELINE config 4, test_gpu_parity.py)
+//   BIOEM_R2C=dft               exact-DFT r2c kernels instead of the fast transform (test_gpu_parity.py: the two agree)
+//   BIOEM_CONVOLVE_FUSED=0/1    two-kernel / fused convolution whatever the particle count (test_gpu_parity.py: bit-equal)
+//   BIOEM_COMPAT_RING=<rows>    rows per half of bioem_hip_compare's staging ring (test_gpu_parity.py: odd ring sizes)
+//   BIOEM_SIGNATURE_LOG=<file>  one line per handle with its kernel instantiations (tests/conftest.py for
+//                               scripts/check_kernel_coverage.py)
+// Outside the library: BIOEM_HIP_LIBRARY (Python loader, bioem_amd/engine.py: an experiment build) and the options of
+// the host layer (bioem_amd/host: the reference's environment, devices and merge).
 #ifndef BIOEM_KERNEL_SELECT_HPP
 #define BIOEM_KERNEL_SELECT_HPP
-
-#ifndef BIOEM_NYQUIST_SPLIT
-#define BIOEM_NYQUIST_SPLIT 1
-#endif
 
 namespace
 {
@@ -105,12 +96,9 @@ size_t compare_lds_bytes(int N, int H, int NW, int waves, int rows = 0)
   const size_t dispBytes = ((size_t) NW * 4 + 255) & ~(size_t) 255;
   return (size_t) ((N + 2) & ~1) * 8 + dispBytes + (size_t) waves * (rows ? rows : NW) * Hs * 8;
 }
-#ifndef BIOEM_FAST_HALVES
-#define BIOEM_FAST_HALVES 0
-#endif
-size_t fast_lds_bytes(int N, int NW, int waves, bool half)
-{ // fast / rows kernels: twiddles + displacement list + log table + per-wave T block [NW][66] ([NW][34] half exchange)
-  return (size_t) ((N + 2) & ~1) * 8 + 256 + 1024 + (size_t) waves * NW * (half ? 34 : 66) * 8;
+size_t fast_lds_bytes(int N, int NW, int waves)
+{ // fast / rows kernels: twiddles + displacement list + log table + per-wave T block [NW][66]
+  return (size_t) ((N + 2) & ~1) * 8 + 256 + 1024 + (size_t) waves * NW * 66 * 8;
 }
 size_t fastm_lds_bytes(int N)
 { // cos / sin planes of the twiddle table (padded), window ranks, log table, per wave two 32 x 33 float planes and the
@@ -227,14 +215,13 @@ const Wide2Rule kWide2Rules[] = {
 bool plan_wide2(KernelPlan &P, int N, int H, int mD)
 {
   const int nd = P.nd;
-  const bool nyq = BIOEM_NYQUIST_SPLIT && (N / 2) % 64 == 0;
+  const bool nyq = (N / 2) % 64 == 0;
   const int nblk = nyq ? (H - 1) / 64 : (H + 63) / 64;
   const int rows2 = 2 * ((nd + 1) / 2), hrows = (rows2 / 2 + 1) & ~1;
   int ts = H; // row stride = 4 mod 16 float2: the (row pair, k1) lanes of the row pass spread over the banks
   while (ts % 16 != 4)
     ts++;
   const bool force = getenv("BIOEM_FORCE_WIDE2") != nullptr;
-  const int forcedR = getenv("BIOEM_W2_R") ? atoi(getenv("BIOEM_W2_R")) : 0;
   if (nd > 128 || (nyq && mD > 42))
     return false;
   for (const Wide2Rule &r : kWide2Rules)
@@ -272,7 +259,7 @@ bool plan_wide2(KernelPlan &P, int N, int H, int mD)
       else
       { // the two-wave kernels run faster on the longest mixed length where the power-of-two part is 8 or less
         // (200^2 +-30 px 11.2 -> 15.3 M/s with 20 points), else on the power-of-two part
-        if (!nyq && !getenv("BIOEM_POW2_FFT"))
+        if (!nyq)
           for (int l : {30, 20, 18, 12, 10})
             if (N % l == 0 && N % 16 != 0)
               lens.push_back(l);
@@ -282,16 +269,10 @@ bool plan_wide2(KernelPlan &P, int N, int H, int mD)
             lens.push_back(l);
             break;
           }
-        if (!nyq && !getenv("BIOEM_POW2_FFT") && N % 6 == 0 && N % 4 != 0)
+        if (!nyq && N % 6 == 0 && N % 4 != 0)
           lens.insert(lens.begin(), 6);
       }
       break;
-    }
-    if (forcedR)
-    {
-      lens.clear();
-      if (N % forcedR == 0)
-        lens.push_back(forcedR);
     }
     for (int R : lens)
     {
@@ -336,22 +317,18 @@ bool plan_wide2(KernelPlan &P, int N, int H, int mD)
 // base kernel of a window of at most 2 winD + 1 rows (also the tile kernel of the tiled path)
 bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
 {
-  const bool nyq = BIOEM_NYQUIST_SPLIT && N % 2 == 0 && (N / 2) % 64 == 0;
+  const bool nyq = N % 2 == 0 && (N / 2) % 64 == 0;
   if (N % 2 == 0 && N >= 8)
   {
     if (winD > 10)
     { // 27 / 31 rows: k_compare_fastm, register FFT of at most 16 points (three waves per SIMD); Nyquist split: 16
-      if (getenv("BIOEM_NO_FASTM"))
-        return false;
       std::vector<int> lens;
       if (nyq)
         lens.push_back(16);
       else
-        fft_lengths(N, 16, P.gs == 1 && !getenv("BIOEM_POW2_FFT"), lens);
+        fft_lengths(N, 16, P.gs == 1, lens);
       for (int R : lens)
       {
-        if (getenv("BIOEM_FAST_R") && R != atoi(getenv("BIOEM_FAST_R")))
-          continue;
         if (const fast_kernel_t fn = find_kernel(KF_FASTM, winD, R, nyq, P.gs))
         {
           P.family = KF_FASTM;
@@ -372,23 +349,22 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
     // 62.3 -> 63.8 M/s, +-5 px 72.4 -> 77.2.  The 32-point Nyquist kernels have no registers left for the split: 16
     // points (21 rows) / 8 points (11 rows) only, which pays at 320^2 with 21 rows still (25.5 -> 26.7 M/s) and no longer
     // with 11 rows (-3 %) or at 448^2 (-3 / -30 %).
-    const bool nyq32 = BIOEM_NYQUIST_SPLIT && !nyq && (N / 2) % 64 == 32 && (N <= 256 || (N == 320 && winD == 10)) &&
+    const bool nyq32 = !nyq && (N / 2) % 64 == 32 && (N <= 256 || (N == 320 && winD == 10)) &&
                        !getenv("BIOEM_NO_SPLIT_LAST");
     if (nyq32)
     {
       const int R = winD == 5 ? 8 : 16;
-      if (!(getenv("BIOEM_FAST_R") && R != atoi(getenv("BIOEM_FAST_R"))))
-        if (const fast_kernel_t fn = find_kernel(KF_FAST, winD, R, true, P.gs))
-        {
-          P.family = KF_FAST;
-          P.fn = fn;
-          P.fast = R / 2;
-          P.N1 = N / R;
-          P.nyq = true;
-          P.winD = winD;
-          P.ldsBytes = fast_lds_bytes(N, 2 * winD + 1, 4, false);
-          return true;
-        }
+      if (const fast_kernel_t fn = find_kernel(KF_FAST, winD, R, true, P.gs))
+      {
+        P.family = KF_FAST;
+        P.fn = fn;
+        P.fast = R / 2;
+        P.N1 = N / R;
+        P.nyq = true;
+        P.winD = winD;
+        P.ldsBytes = fast_lds_bytes(N, 2 * winD + 1, 4);
+        return true;
+      }
     }
     std::vector<int> lens;
     if (nyq)
@@ -401,14 +377,14 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
         lens.push_back(8);
     }
     else
-      fft_lengths(N, 32, P.gs == 1 && !getenv("BIOEM_POW2_FFT"), lens);
+      fft_lengths(N, 32, P.gs == 1, lens);
     {
       // up to 256 pixels the longest length is not the fastest (round 4, sweep of every length in the table over 64...240
       // pixels, 1 000 particles): 21-row windows 16 > 12 > 20 > 18 > 10 > 32 > 30 > 8 (224^2: 51.0 / 50.0 / 47.5 M/s
       // with 16 / 32 / 8 points, 180^2: 61.0 with 12 against 59.5 with 30), 11-row windows 8 first up to 160 pixels
       // (64^2: 271 / 259 / 228 M/s with 8 / 16 / 32), 16 first above (224^2: 57.1 / 55.8 / 55.7); from 288 pixels on
       // 32 and 16 points are level and the order stays
-      if (N <= 256 && !getenv("BIOEM_LONGEST_FFT"))
+      if (N <= 256)
       {
         static const int pref21[] = {16, 12, 20, 18, 10, 32, 30, 8, 6, 4, 2};
         static const int pref11s[] = {8, 16, 12, 10, 18, 20, 32, 30, 6, 4, 2};
@@ -425,13 +401,11 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
     }
     for (int R : lens)
     {
-      if (getenv("BIOEM_FAST_R") && R != atoi(getenv("BIOEM_FAST_R"))) // timing experiments: another register-FFT length
-        continue;
       int wd = winD;
       // 11-row windows: with four column blocks and a length <= 16 (or 40+ column steps) the 21-row template is the
       // faster one (+-5 px: 432^2 11.0 -> 13.0 M/s, 360^2 16.7 -> 19.2, 400^2 13.5 -> 14.7)
       const int nblkF = nyq ? (H - 1) / 64 : (H + 63) / 64;
-      if (wd == 5 && untiled && ((nblkF >= 4 && R <= 16) || N / R >= 40) && !getenv("BIOEM_KEEP_WD5") &&
+      if (wd == 5 && untiled && ((nblkF >= 4 && R <= 16) || N / R >= 40) &&
           find_kernel(KF_FAST, 10, R, nyq, P.gs))
         wd = 10;
       if (const fast_kernel_t fn = find_kernel(KF_FAST, wd, R, nyq, P.gs))
@@ -442,15 +416,15 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
         P.N1 = N / R;
         P.nyq = nyq;
         P.winD = wd;
-        P.ldsBytes = fast_lds_bytes(N, 2 * wd + 1, 4, BIOEM_FAST_HALVES);
+        P.ldsBytes = fast_lds_bytes(N, 2 * wd + 1, 4);
         return true;
       }
     }
     return false;
   }
-  if (N >= 8 && !getenv("BIOEM_NO_ROWS_KERNEL"))
+  if (N >= 8)
   { // odd N: register FFT of odd length over the reference layout where 25 / 15 / 9 / 5 / 3 divides N, else direct sums
-    if (P.gs == 1 && !getenv("BIOEM_NO_ODD_FFT"))
+    if (P.gs == 1)
       for (int r : {25, 15, 9, 5, 3})
         if (N % r == 0)
           if (const fast_kernel_t fn = find_kernel(KF_ODDFFT, winD, r))
@@ -461,7 +435,7 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
             P.N1 = N / r;
             P.fn = fn;
             P.winD = winD;
-            P.ldsBytes = fast_lds_bytes(N, 2 * winD + 1, 4, false);
+            P.ldsBytes = fast_lds_bytes(N, 2 * winD + 1, 4);
             return true;
           }
     if (const fast_kernel_t fn = find_kernel(KF_ROWS, winD, P.gs))
@@ -470,7 +444,7 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
       P.rowsK = true;
       P.fn = fn;
       P.winD = winD;
-      P.ldsBytes = fast_lds_bytes(N, 2 * winD + 1, 4, false);
+      P.ldsBytes = fast_lds_bytes(N, 2 * winD + 1, 4);
       return true;
     }
   }
@@ -528,10 +502,9 @@ KernelPlan plan_kernels(int N, int maxD, int grid, int algo)
   //     longest length that divides N: the recombination costs 8 fused multiply-adds per accumulator and step whatever
   //     the length, so fewer, longer steps win (per column and unit of N: 14 / 16 / 18 / 19 instructions at 16 / 12 / 10 / 8)
   //     Row strides 2..4 (a coarse DISPLACE_CENTER grid) with the 16-point kernel: rows 4 / 8 / 2 apart pair up.
-  if (N >= 64 && symmetric && P.nd >= 33 && P.nd <= 2 * kFm2WD + 1 && !getenv("BIOEM_NO_FASTM2") &&
-      !getenv("BIOEM_FORCE_WIDE2"))
+  if (N >= 64 && symmetric && P.nd >= 33 && P.nd <= 2 * kFm2WD + 1 && !getenv("BIOEM_FORCE_WIDE2"))
   {
-    const bool nyq = BIOEM_NYQUIST_SPLIT && (N / 2) % 64 == 0;
+    const bool nyq = (N / 2) % 64 == 0;
     for (int R : {16, 12, 10, 8})
     {
       if (N % R != 0)
@@ -554,13 +527,13 @@ KernelPlan plan_kernels(int N, int maxD, int grid, int algo)
   }
   // 2. wide symmetric windows on even sizes: k_compare_wide2
   if (N % 2 == 0 && N >= 8 && symmetric && (P.nd > 31 || (getenv("BIOEM_FORCE_WIDE2") && P.nd >= 21)) &&
-      !getenv("BIOEM_NO_WIDE2") && plan_wide2(P, N, H, mD))
+      plan_wide2(P, N, H, mD))
     return P;
   // 3. tiles of a window kernel on phase-shifted conv spectra (window_tiles.hpp): launches^2 x the measured cost of one
   //    launch of the 21- / 27- / 31-row kernel (ms at 224^2: k_compare_fast 6.05, k_compare_fastm 6.5 / 6.7)
   //    (also a window that fits one kernel whose instantiation is not in the table -- 31 rows at stride 4: it must not
   //    drop to the generic kernel)
-  if (N >= 8 && symmetric && P.nd > 11 && !getenv("BIOEM_NO_TILES"))
+  if (N >= 8 && symmetric && P.nd > 11)
   {
     static const int tileRows[3] = {21, 27, 31};
     static const double tileCost[3] = {6.05, 6.5, 6.7};
@@ -571,9 +544,7 @@ KernelPlan plan_kernels(int N, int maxD, int grid, int algo)
     });
     for (int k : order)
     {
-      int t = tileRows[k];
-      if (getenv("BIOEM_TILE_ROWS"))
-        t = atoi(getenv("BIOEM_TILE_ROWS")) == 31 ? 31 : atoi(getenv("BIOEM_TILE_ROWS")) == 27 ? 27 : 21;
+      const int t = tileRows[k];
       KernelPlan Q = P;
       if (!plan_window_kernel(Q, N, H, (t - 1) / 2, false))
         continue;

@@ -971,24 +971,13 @@ k_convolve_sums(const float2 *__restrict__ proj, const float2 *__restrict__ ctf,
   // formed (two operand sets: what 128 registers hold for 3 orientations x 6 CTFs or 4 x 4), so that a tile costs them
   // their ~550 vector instructions and not a round trip to memory on top.  The two roles are two loops with the same
   // number of barriers (in one loop the operand sets would stay live across the adding wave's ring of terms).
-#ifdef BIOEM_CONV_TIMING // timing-only build: the adding wave's cycles in additions / in total come back as sumC / sumsquareC
-  long long cyAdd = 0, cy0 = clock64();
-#endif
   if (wave == 0)
   {
     __builtin_amdgcn_s_setprio(3); // the adding wave is the critical path: it issues ahead of the producers of its SIMD
     lds_barrier();                 // tile 0 is there
     for (int t = 0; t < nt; t++)
     {
-#ifdef BIOEM_CONV_TIMING
-      asm volatile("" : "+v"(ss));
-      const long long c0 = clock64();
-#endif
       add_tile(t);
-#ifdef BIOEM_CONV_TIMING
-      asm volatile("" : "+v"(ss));
-      cyAdd += clock64() - c0;
-#endif
       lds_barrier();
     }
   }
@@ -1021,13 +1010,6 @@ k_convolve_sums(const float2 *__restrict__ proj, const float2 *__restrict__ ctf,
       lds_barrier();
     }
   }
-#ifdef BIOEM_CONV_TIMING
-  if (wave == 0 && lane < nJ * nCb)
-  {
-    sC[lane] = (float) cyAdd;
-    ss = (float) (clock64() - cy0) * (float) (N * N);
-  }
-#endif
   if (wave == 0 && lane < nJ * nCb)
   {
     const int o = lane / nCb, cl = lane - o * nCb;

@@ -40,6 +40,44 @@ def test_struct_sizes_match_reference_layout():
     assert L.bioem_hip_prob_size(10, 7, 3) == 400 + 10 * 7 * 16
 
 
+# every environment variable the native code reads; a new knob has to be added here on purpose
+KEPT_ENVIRONMENT = {
+    # options of the reference
+    "BIOEM_ALGO", "BIOEM_DEBUG_OUTPUT", "BIOEM_DEBUG_BREAK", "BIOEM_DEBUG_NMAPS", "GPUDEVICE", "GPU",
+    # the reference's performance knobs: read and reported, no effect (driver.cpp)
+    "GPUWORKLOAD", "GPUASYNC", "GPUDUALSTREAM", "BIOEM_CUDA_THREAD_COUNT", "BIOEM_PROJ_CONV_AT_ONCE", "OMP_NUM_THREADS",
+    # devices and the merge of their results
+    "BIOEM_GPUS", "BIOEM_SHARDS", "BIOEM_HOST_MERGE", "BIOEM_FORCE_RCCL",
+    # libbioem_hip.so (the list with what each does: bioem_amd/csrc/kernel_select.hpp)
+    "BIOEM_CC_DIRECT", "BIOEM_COMPAT_RING", "BIOEM_R2C", "BIOEM_CONVOLVE_FUSED", "BIOEM_SIGNATURE_LOG",
+    "BIOEM_FORCE_WIDE2", "BIOEM_NO_SPLIT_LAST", "BIOEM_NO_PITCH_PAD",
+}
+
+
+def test_environment_surface_is_pinned():
+    """The names passed to getenv in the engine and the host layer are the kept list: a stray variable in a user's
+    environment cannot change which kernel runs unless it is one of these."""
+    names, other = set(), set()
+    for sub in ("csrc", "host"):
+        d = os.path.join(ROOT, "bioem_amd", sub)
+        for fn in sorted(os.listdir(d)):
+            if not fn.endswith((".hip", ".hpp", ".inc", ".cpp", ".h")):
+                continue
+            with open(os.path.join(d, fn)) as f:
+                src = f.read()
+            for arg in re.findall(r"\bgetenv\(([^()]*)\)", src):
+                m = re.fullmatch(r'\s*"(\w+)"\s*', arg)
+                if m:
+                    names.add(m.group(1))
+                else:
+                    other.add((fn, arg.strip()))
+            # the reference's knobs are a table walked with getenv(k)
+            for tab in re.findall(r"\bknobs\[\]\s*=\s*\{([^}]*)\}", src):
+                names.update(re.findall(r'"(\w+)"', tab))
+    assert other == {("driver.cpp", "k")}
+    assert sorted(names) == sorted(KEPT_ENVIRONMENT)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from bioem_amd import engine
     monkeypatch.setattr(engine, "_lib", None)

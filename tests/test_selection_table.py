@@ -18,7 +18,7 @@ def plan(L, N, d, g, algo):
     return buf.value.decode() if rc == 0 else "rejected"
 
 
-def test_selection_matches_the_committed_snapshot():
+def check_snapshot():
     import bioem_amd.engine as eng
     L = eng.load_library()
     bad = []
@@ -32,6 +32,21 @@ def test_selection_matches_the_committed_snapshot():
                 bad.append((N, d, g, algo, sig, got))
     assert n > 16000
     assert not bad, "%d shapes changed kernel, e.g. %s" % (len(bad), bad[:5])
+
+
+def test_selection_matches_the_committed_snapshot():
+    check_snapshot()
+
+
+def test_removed_selection_variables_change_nothing(monkeypatch):
+    """The experiment switches of earlier rounds are gone from the library: set to values that used to change the plan,
+    they leave every shape of the snapshot on its kernel."""
+    for var, val in [("BIOEM_NO_FASTM", "1"), ("BIOEM_NO_FASTM2", "1"), ("BIOEM_NO_WIDE2", "1"), ("BIOEM_NO_TILES", "1"),
+                     ("BIOEM_NO_ROWS_KERNEL", "1"), ("BIOEM_NO_ODD_FFT", "1"), ("BIOEM_POW2_FFT", "1"),
+                     ("BIOEM_LONGEST_FFT", "1"), ("BIOEM_KEEP_WD5", "1"), ("BIOEM_FAST_R", "8"), ("BIOEM_W2_R", "16"),
+                     ("BIOEM_TILE_ROWS", "27")]:
+        monkeypatch.setenv(var, val)
+    check_snapshot()
 
 
 def test_every_table_entry_is_selected_by_some_shape_of_the_snapshot():
