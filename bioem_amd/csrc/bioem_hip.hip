@@ -57,6 +57,7 @@
 #include <dlfcn.h>
 
 #include <map>
+#include <memory>
 #include <mutex>
 #include <queue>
 #include <string>
@@ -88,6 +89,22 @@ struct HipErr
 
 } // namespace
 
+#include "prep_kernels.hpp"
+#include "dft_mfma.hpp"
+#include "posterior.hpp"
+#include "fft_registers.hpp"
+#include "compare_args.hpp"
+#include "compare_fast.hpp"
+#include "compare_wide2.hpp"
+#include "compare_fastm.hpp"
+#include "compare_fastm2.hpp"
+#include "compare_generic.hpp"
+#include "compare_rows.hpp"
+#include "compare_direct.hpp"
+#include "kernel_select.hpp"
+#include "fold_kernels.hpp"
+#include "window_tiles.hpp"
+
 struct bioem_hip_ctx
 {
   int device = 0;
@@ -97,35 +114,14 @@ struct bioem_hip_ctx
   int N = 0, H = 0, M = 0;
   int Hp = 0;    // row-pair pitch of the comparison layout in 16-byte words (H, or H + 15: comparison_pitch)
   size_t Mc = 0; // float2 per image of the comparison layout, N * Hp
-  int fast = 0, N1 = 0, winD = 0; // winD = template window half width used by the fast kernel
+  KernelPlan plan; // which comparison kernel runs this shape and how (kernel_select.hpp)
   int pchunk = 128;               // particle chunk of the fast kernel's block order (0 = all particles); measured:
                                   // 1 000 particles 6.73 -> 6.56 ms, 10 000 particles (2 GB, beyond the Infinity
                                   // Cache) 78.5 -> 63.2 ms per launch
-  int gs = 1;                     // pixels per window row of the fast kernel (gcd of the displacement offsets)
-  // wide windows (more than 31 offsets per axis): tilesPerAxis^2 launches of a tileT-row window (window_tiles.hpp)
-  int genericWaves = 4; // waves per block of the generic kernel
-  int genericRows = 0;  // ... and its window rows per pass through the LDS (0 = all)
-  bool rowsK = false;   // k_compare_rows / k_compare_oddfft (odd N) instead of the generic kernel
-  int oddR = 0;         // k_compare_oddfft: register-FFT length (3, 5, 9, 15, 25) dividing an odd N; 0 = direct sums
-  int tileT = 0, tilesPerAxis = 1;
-  std::vector<int> tileCenter, tileValid; // per axis tile: centre (in window rows) and number of rows inside the window
   int *dDispLocal = nullptr, *dTileCenter = nullptr, *dTileValid = nullptr, *dRankOfRow = nullptr;
-  const void *fn = nullptr; // the comparison kernel of this handle (fast_kernel_t, kernel_select.hpp)
-  size_t ldsBytes = 0;      // its dynamic LDS per block
-  int family = 0;           // KernelFamily
-  // k_compare_wide2 (compare_wide2.hpp): wide window in ONE launch per batch -- column transforms shared by the four
-  // waves of a comparison, row FFT
-  bool wide2 = false;
-  bool fastm = false; // 23..31-row windows: k_compare_fastm (window pass on the matrix cores)
-  bool fastm2 = false; // 33..47-row windows: k_compare_fastm2 (rows split over the half-waves, 3 x 3 matrix tiles)
-  int w2NRW = 0, w2NBLK = 0, w2TS = 0, w2Rows2 = 0, nyqWD = 0, w2Halves = 1, w2NW = 4;
   float *dBtab = nullptr;  // k_compare_fastm2: tabulated B operand of the matrix pass
-  float2 *dTwk2 = nullptr; // [N1][nd] recombination twiddles exp(2 pi i dx k1 / N), rows in sorted order
   float2 *dConvShift = nullptr;
   Partial *dPartTiles = nullptr;
-  bool nyq = false;               // Nyquist column handled outside the 64-column blocks (N/2 a multiple of 64)
-  int nd = 0;                     // displacements per axis
-  std::vector<int> disp;
   int OB = 0;     // orientations per batch of the native path
   int maxOC = 0;  // capacity of conv/param/partial buffers in (orientation*CTF) units
   int chunkB = 0; // images per DFT chunk
@@ -153,18 +149,9 @@ struct bioem_hip_ctx
   double2 *dTwD = nullptr; // N entries, double
   int *dDisp = nullptr;
   double2 *dLtab = nullptr;
-  float2 *dTwk = nullptr;
-  float2 *dTwNyq = nullptr; // [N/2 row pairs][2*winD+1][2] twiddles of the Nyquist pre-kernel (nyq only)
-  float *dTnyq = nullptr; // [nMaps][maxOC][2*winD+1] Nyquist-column rows of the current launch (nyq only)
-
-  double *dProjReal = nullptr; // [chunkB][N*N]
-  double *dTempDen = nullptr;  // [chunkB]
-  double2 *dRowSpec = nullptr; // [chunkB][N][H]
-  float2 *dSpecRef = nullptr;  // [chunkB][M] reference layout
-  float *dScratch = nullptr;   // [maxOC][M] ordered |X|^2 terms for sumsquareC
-  float2 *dConv = nullptr;     // [maxOC][M] comparison layout
-  bioem_hip_param5 *dParams = nullptr;
-  double2 *dPostC = nullptr;    // [maxOC] {t2, prior} of the log posterior per (orientation, CTF) row (k_posterior_consts)
+  float2 *dTwk = nullptr;   // recombination twiddles exp(2 pi i dx k1 / N) of the comparison kernel, laid out per family
+  float2 *dTwNyq = nullptr; // [N/2 row pairs][2*nyqWD+1][2] twiddles of the Nyquist pre-kernel (nyq only)
+  float *dTnyq = nullptr; // [nMaps][maxOC][2*nyqWD+1] Nyquist-column rows of the current launch (nyq only)
   Partial *dPartials = nullptr; // [nMaps][maxOC]
   unsigned char *dProb = nullptr;
   size_t probBytes = 0;    // bytes start_run / finish_run move (shard handles: the map entries only)
@@ -177,27 +164,31 @@ struct bioem_hip_ctx
   size_t sendBytes = 0, recvBytes = 0;
   bioem_hip_prob_map *dMerged = nullptr;
 
-  // second buffer set + stream: projection/convolution of batch k+1 overlap the comparison of batch k
+  // two pipeline slots + a second stream: projection/convolution of batch k+1 (prepStream) overlap the comparison of
+  // batch k.  Slot 0's projection buffers also stage the particle uploads and the debug hooks.
+  struct Slot
+  {
+    double *projReal = nullptr; // [images][N*N]
+    double *tempDen = nullptr;  // [images]
+    double2 *rowSpec = nullptr; // [images][N][H]
+    float2 *specRef = nullptr;  // [images][M] reference layout
+    float *scratch = nullptr;   // [maxOC][M] ordered |X|^2 terms for sumsquareC
+    float2 *conv = nullptr;     // [maxOC][M] comparison layout
+    bioem_hip_param5 *params = nullptr;
+    double2 *postc = nullptr; // [maxOC] {t2, prior} of the log posterior per (orientation, CTF) row (k_posterior_consts)
+    // staged device entries (bioem_hip_project / _convolve / _compare_device): what the slot holds
+    int stageO0 = 0, stageNO = 0, stageC0 = 0, stageNC = 0;
+    hipEvent_t prepDone = nullptr, cmpDone = nullptr;
+    bool cmpPending = false;
+  };
+  Slot slot[2];
   hipStream_t prepStream = nullptr;
-  double *dProjReal2 = nullptr;
-  double *dTempDen2 = nullptr;
-  double2 *dRowSpec2 = nullptr;
-  float2 *dSpecRef2 = nullptr;
-  float *dScratch2 = nullptr;
-  float2 *dConv2 = nullptr;
-  bioem_hip_param5 *dParams2 = nullptr;
-  double2 *dPostC2 = nullptr;
-  // staged device entries (bioem_hip_project / _convolve / _compare_device): what each pipeline slot holds
-  int stageO0[2] = {0, 0}, stageNO[2] = {0, 0}, stageC0[2] = {0, 0}, stageNC[2] = {0, 0};
-  hipEvent_t prepDone[2] = {nullptr, nullptr};
-  hipEvent_t cmpDone[2] = {nullptr, nullptr};
-  bool cmpPending[2] = {false, false};
 
   // reference-compatible entry (bioem_hip_compare): the caller hands over a few conv spectra per call (ONE per call
   // in the reference's default ALGO-1 loop, bioem.cpp:534,811-853).  They are staged into a two-half ring -- pinned
   // host rows, H2D copies on their own stream -- and compared with ONE kernel launch per filled half (flush at
-  // finish_run), folding in call order through a per-row (orientation, CTF) table.  Half k uses buffer set k of
-  // the native pipeline (conv, params, cmpDone[k]).
+  // finish_run), folding in call order through a per-row (orientation, CTF) table.  Half k uses pipeline slot k
+  // (conv, params, cmpDone).
   struct CompatHalf
   {
     float2 *hConv = nullptr;          // pinned [ringCap][M], reference layout
@@ -213,6 +204,14 @@ struct bioem_hip_ctx
   int ringCap = 0, ringHalf = 0, ringCount = 0;
   std::vector<int> ringOrients; // orientations with rows in the current half, in first-appearance order
   hipStream_t copyStream = nullptr;
+
+  // every device and pinned-host allocation of the handle (dev_alloc, host_alloc): bioem_hip_destroy frees them
+  struct Alloc
+  {
+    void *p;
+    bool pinned;
+  };
+  std::vector<Alloc> allocs;
 
   // timing
   // per-batch phase records (bioem_hip_set_phase_timing): the reference's BIOEM_DEBUG_OUTPUT report (timer.cpp:138-165,
@@ -232,22 +231,6 @@ struct bioem_hip_ctx
 
   std::string err;
 };
-
-#include "prep_kernels.hpp"
-#include "dft_mfma.hpp"
-#include "posterior.hpp"
-#include "fft_registers.hpp"
-#include "compare_args.hpp"
-#include "compare_fast.hpp"
-#include "compare_wide2.hpp"
-#include "compare_fastm.hpp"
-#include "compare_fastm2.hpp"
-#include "compare_generic.hpp"
-#include "compare_rows.hpp"
-#include "compare_direct.hpp"
-#include "kernel_select.hpp"
-#include "fold_kernels.hpp"
-#include "window_tiles.hpp"
 
 namespace
 {
@@ -322,27 +305,63 @@ void drain_phases(bioem_hip_ctx *h)
   h->phasePending.clear();
 }
 
-struct BatchBuf
+// allocations recorded on the handle (freed by bioem_hip_destroy)
+template <class T>
+int dev_alloc(bioem_hip_ctx *h, T *&p, size_t n)
 {
-  double *projReal;
-  double *tempDen;
-  double2 *rowSpec;
-  float2 *specRef;
-  float *scratch;
-  float2 *conv;
-  bioem_hip_param5 *params;
-  double2 *postc;
-};
-
-BatchBuf batch_buf(bioem_hip_ctx *h, int which)
-{
-  BatchBuf b;
-  if (which == 0)
-    b = {h->dProjReal, h->dTempDen, h->dRowSpec, h->dSpecRef, h->dScratch, h->dConv, h->dParams, h->dPostC};
-  else
-    b = {h->dProjReal2, h->dTempDen2, h->dRowSpec2, h->dSpecRef2, h->dScratch2, h->dConv2, h->dParams2, h->dPostC2};
-  return b;
+  HIP_CHECK(h, hipMalloc(&p, sizeof(T) * n));
+  if (p)
+    h->allocs.push_back({p, false});
+  return 0;
 }
+template <class T>
+int host_alloc(bioem_hip_ctx *h, T *&p, size_t n)
+{
+  HIP_CHECK(h, hipHostMalloc(&p, sizeof(T) * n, hipHostMallocDefault));
+  if (p)
+    h->allocs.push_back({p, true});
+  return 0;
+}
+// a device buffer that is replaced: freed now and dropped from the record
+template <class T>
+void dev_release(bioem_hip_ctx *h, T *&p)
+{
+  if (!p)
+    return;
+  for (size_t i = 0; i < h->allocs.size(); i++)
+    if (h->allocs[i].p == p)
+    {
+      h->allocs.erase(h->allocs.begin() + i);
+      break;
+    }
+  hipFree(p);
+  p = nullptr;
+}
+// n host values into a new device buffer
+template <class T>
+int upload(bioem_hip_ctx *h, T *&p, const T *src, size_t n)
+{
+  if (dev_alloc(h, p, n))
+    return 1;
+  HIP_CHECK(h, hipMemcpy(p, src, sizeof(T) * n, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// exp(2 pi i ((a b) mod N) / N) for ab = a b: the one expression every twiddle table is built from
+double2 twiddle_d(long long ab, int N)
+{
+  const double ang = 2.0 * M_PI * (double) ((ab % N + N) % N) / (double) N;
+  return make_double2(cos(ang), sin(ang));
+}
+float2 twiddle(long long ab, int N)
+{
+  const double2 w = twiddle_d(ab, N);
+  return make_float2((float) w.x, (float) w.y);
+}
+
+// the slot's buffers are written by something other than the staged entries: nothing is staged in it any more, and
+// bioem_hip_convolve / bioem_hip_compare_device on it return 2 until bioem_hip_project fills it again
+void void_slot(bioem_hip_ctx::Slot &s) { s.stageNO = s.stageNC = 0; }
 
 // ids == nullptr: row oc of the launch is (orient0 + oc / convPerOrient, conv0 + oc % convPerOrient) (native path);
 // otherwise ids[oc] = {orientation, CTF} and segs[0..nSeg) = runs of equal orientation (compat ring)
@@ -371,9 +390,11 @@ void launch_nyquist(bioem_hip_ctx *h, const CompareArgs &aw, int WD, int nOC)
     launch_nyquist_rows<1>(h, aw, WD, nOC);
 }
 
-int launch_compare_fold(bioem_hip_ctx *h, const BatchBuf &bb, int nOC, int orient0, int conv0, int convPerOrient,
-                        const int2 *ids = nullptr, const int4 *segs = nullptr, int nSeg = 0)
+int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC, int orient0, int conv0,
+                        int convPerOrient, const int2 *ids = nullptr, const int4 *segs = nullptr, int nSeg = 0)
 {
+  const KernelPlan &P = h->plan;
+  const int fam = P.family;
   CompareArgs a;
   a.ref = h->dRef;
   a.conv = bb.conv;
@@ -393,34 +414,54 @@ int launch_compare_fold(bioem_hip_ctx *h, const BatchBuf &bb, int nOC, int orien
   a.N = h->N;
   a.H = h->H;
   a.Hp = h->Hp;
-  a.N1 = h->N1;
-  a.nd = h->nd;
+  a.N1 = P.N1;
+  a.nd = P.nd;
   a.maxD = h->pd.maxDisplaceCenter;
   a.nOC = nOC;
   a.nMaps = h->nMaps;
   a.algo = h->algo;
   a.pd = h->pd;
-  a.gs = h->gs;
-  a.ndx = a.ndy = h->nd;
+  a.gs = P.gs;
+  a.ndx = a.ndy = P.nd;
+  a.nyqWD = P.nyqWD;
   {
     // k_compare_fast / k_compare_fastm: a last column block of at most 32 columns is shared by the half-waves
     // (with the Nyquist split the blocks hold the H - 1 columns below N / 2: whole ones, or -- 192^2, 320^2, 448^2, which
     // were planned that way -- a last one of 32, and then the split is not optional)
-    const int cols = h->nyq ? h->H - 1 : h->H;
+    const int cols = P.nyq ? h->H - 1 : h->H;
     const int nblkF = (cols + 63) / 64, rem = cols - (nblkF - 1) * 64;
-    a.split = h->fast && !h->fastm2 && !h->wide2 && !h->rowsK && rem <= 32 && h->N1 >= 2 &&
-              (h->nyq || !getenv("BIOEM_NO_SPLIT_LAST"));
+    a.split = (fam == KF_FAST || fam == KF_FASTM) && rem <= 32 && P.N1 >= 2 &&
+              (P.nyq || !getenv("BIOEM_NO_SPLIT_LAST"));
   }
   a.pchunk = h->pchunk > 0 ? std::min(h->pchunk, h->nMaps) : h->nMaps;
   if (a.pchunk >= 8) // a multiple of 8: a particle then stays on one XCD (65 particles: chunks of 64 + 1, 43.6 -> 45.3 M/s)
     a.pchunk &= ~7;
   const int ocGroups = (nOC + 3) / 4;
-  // few particles: whole groups per XCD (fast_block_pair); the grid is padded to a multiple of 8 groups
-  // (measured for 65...200 particles as well: 1-3 % slower than the chunk order there)
-  const bool groupPerXcd = h->nMaps <= 64 && h->fast && !h->wide2;
+  // few particles, k_compare_fast / _fastm / _fastm2: whole groups per XCD (fast_block_pair); the grid is padded to a
+  // multiple of 8 groups (measured for 65...200 particles as well: 1-3 % slower than the chunk order there)
+  const bool groupPerXcd = h->nMaps <= 64 && (fam == KF_FAST || fam == KF_FASTM || fam == KF_FASTM2);
   if (groupPerXcd)
     a.pchunk = -1;
-  const dim3 grid((unsigned) ((size_t) (groupPerXcd ? (ocGroups + 7) / 8 * 8 : ocGroups) * h->nMaps));
+  // launch geometry by family: four comparisons per 256-thread block, except k_compare_wide2 (one block of w2NW waves
+  // per comparison) and k_compare_generic (genericWaves comparisons per block)
+  dim3 grid((unsigned) ((size_t) (groupPerXcd ? (ocGroups + 7) / 8 * 8 : ocGroups) * h->nMaps)), block(256);
+  if (fam == KF_WIDE2)
+  {
+    a.ts = P.w2TS;
+    grid = dim3((unsigned) ((size_t) nOC * h->nMaps));
+    block = dim3(64 * P.w2NW);
+  }
+  else if (fam == KF_GENERIC)
+  {
+    a.ts = P.genericRows;
+    grid = dim3((unsigned) ((size_t) ((nOC + P.genericWaves - 1) / P.genericWaves) * h->nMaps));
+    block = dim3(64 * P.genericWaves);
+  }
+  auto launch = [&](const CompareArgs &aw) {
+    if (P.nyq)
+      launch_nyquist(h, aw, P.nyqWD, nOC);
+    hipLaunchKernelGGL(P.fn, grid, block, P.ldsBytes, h->stream, aw);
+  };
   hipEvent_t e0 = get_event(h), e1 = get_event(h);
   if (!e0 || !e1)
   {
@@ -443,79 +484,45 @@ int launch_compare_fold(bioem_hip_ctx *h, const BatchBuf &bb, int nOC, int orien
     ad.gs = h->pd.GridSpaceCenter;
     ad.maxD = h->pd.maxDisplaceCenter;
     hipLaunchKernelGGL(k_c2r_cols, dim3(h->H, nOC), dim3(128), sizeof(double2) * h->N, h->stream, bb.conv, h->N, h->H,
-                       h->fast, h->N1, h->dTwD, h->dDirectZ);
+                       P.halfR, P.N1, h->dTwD, h->dDirectZ);
     hipLaunchKernelGGL(k_c2r_rows, dim3(h->N, nOC), dim3(128), sizeof(double2) * h->H, h->stream, h->dDirectZ, h->N,
                        h->H, h->dTwD, h->dConvReal);
     const dim3 gridd((unsigned) ((size_t) nOC * ((h->nMaps + 31) / 32)));
     hipLaunchKernelGGL((k_compare_direct<3, 8>), gridd, dim3(512), direct_lds_bytes(h->N), h->stream, ad, h->dConvReal,
                        h->dMapsReal);
   }
-  else if (h->wide2)
-  {
-    CompareArgs aw = a;
-    aw.twk = h->dTwk2;
-    aw.ts = h->w2TS;
-    aw.nyqWD = h->nyqWD;
-    if (h->nyq)
-      launch_nyquist(h, aw, h->nyqWD == 20 || h->nyqWD == 31 ? h->nyqWD : 42, nOC);
-    hipLaunchKernelGGL(reinterpret_cast<fast_kernel_t>(const_cast<void *>(h->fn)), dim3((unsigned) ((size_t) nOC * h->nMaps)), dim3(64 * h->w2NW), h->ldsBytes, h->stream, aw);
-  }
-  else if (h->fastm2)
-  {
-    CompareArgs aw = a;
-    aw.twk = h->dTwk2;
-    aw.nyqWD = h->nyqWD;
-    if (h->nyq)
-      launch_nyquist(h, aw, h->nyqWD == 20 ? 20 : 31, nOC);
-    hipLaunchKernelGGL(reinterpret_cast<fast_kernel_t>(const_cast<void *>(h->fn)), grid, dim3(256), h->ldsBytes, h->stream, aw);
-  }
-  else if (h->fast || h->rowsK)
-  {
-    auto launch_window = [&](const CompareArgs &aw) {
-      if (h->nyq)
-        launch_nyquist(h, aw, h->winD == 5 || h->winD == 10 || h->winD == 13 ? h->winD : 15, nOC);
-      hipLaunchKernelGGL(reinterpret_cast<fast_kernel_t>(const_cast<void *>(h->fn)), grid, dim3(256), h->ldsBytes, h->stream, aw);
-    };
-    if (!h->tileT)
-      launch_window(a);
-    else
-    { // wide window: one launch per tile on the phase-shifted conv spectra, then merge (window_tiles.hpp)
-      const int nT = h->tilesPerAxis;
-      const size_t tileStride = (size_t) h->nMaps * h->maxOC;
-      const size_t total = (size_t) nOC * h->M;
-      CompareArgs at = a;
-      at.disp = h->dDispLocal;
-      at.nd = h->tileT;
-      at.maxD = h->winD * h->gs;
-      for (int tx = 0; tx < nT; tx++)
-        for (int ty = 0; ty < nT; ty++)
-        {
-          const int sx = h->gs * h->tileCenter[tx], sy = h->gs * h->tileCenter[ty];
-          if (sx == 0 && sy == 0)
-            at.conv = bb.conv;
-          else
-          {
-            hipLaunchKernelGGL(k_phase_shift, dim3(2048), dim3(256), 0, h->stream, bb.conv, h->dConvShift, total, h->N,
-                               h->H, h->fast, h->N1, sx, sy, h->dTw);
-            at.conv = h->dConvShift;
-          }
-          at.ndx = h->tileValid[tx];
-          at.ndy = h->tileValid[ty];
-          at.partials = h->dPartTiles + (size_t) (tx * nT + ty) * tileStride;
-          launch_window(at);
-        }
-      const long long nt = (long long) nOC * h->nMaps;
-      hipLaunchKernelGGL(k_merge_tiles, dim3((unsigned) ((nt + 255) / 256)), dim3(256), 0, h->stream, h->dPartTiles,
-                         nT * nT, tileStride, h->maxOC, nOC, h->nMaps, h->tileT, nT, h->dTileCenter,
-                         h->pd.maxDisplaceCenter / h->gs, h->nd, h->dRankOfRow, h->dPartials);
-    }
-  }
+  else if (!P.tileT)
+    launch(a);
   else
-  {
-    const int gw = h->genericWaves;
-    a.ts = h->genericRows;
-    const dim3 gridg((unsigned) ((size_t) ((nOC + gw - 1) / gw) * h->nMaps));
-    hipLaunchKernelGGL(reinterpret_cast<fast_kernel_t>(const_cast<void *>(h->fn)), gridg, dim3(64 * gw), h->ldsBytes, h->stream, a);
+  { // wide window: one launch per tile on the phase-shifted conv spectra, then merge (window_tiles.hpp)
+    const int nT = P.tilesPerAxis;
+    const size_t tileStride = (size_t) h->nMaps * h->maxOC;
+    const size_t total = (size_t) nOC * h->M;
+    CompareArgs at = a;
+    at.disp = h->dDispLocal;
+    at.nd = P.tileT;
+    at.maxD = P.winD * P.gs;
+    for (int tx = 0; tx < nT; tx++)
+      for (int ty = 0; ty < nT; ty++)
+      {
+        const int sx = P.gs * P.tileCenter[tx], sy = P.gs * P.tileCenter[ty];
+        if (sx == 0 && sy == 0)
+          at.conv = bb.conv;
+        else
+        {
+          hipLaunchKernelGGL(k_phase_shift, dim3(2048), dim3(256), 0, h->stream, bb.conv, h->dConvShift, total, h->N,
+                             h->H, P.halfR, P.N1, sx, sy, h->dTw);
+          at.conv = h->dConvShift;
+        }
+        at.ndx = P.tileValid[tx];
+        at.ndy = P.tileValid[ty];
+        at.partials = h->dPartTiles + (size_t) (tx * nT + ty) * tileStride;
+        launch(at);
+      }
+    const long long nt = (long long) nOC * h->nMaps;
+    hipLaunchKernelGGL(k_merge_tiles, dim3((unsigned) ((nt + 255) / 256)), dim3(256), 0, h->stream, h->dPartTiles,
+                       nT * nT, tileStride, h->maxOC, nOC, h->nMaps, P.tileT, nT, h->dTileCenter,
+                       h->pd.maxDisplaceCenter / P.gs, P.nd, h->dRankOfRow, h->dPartials);
   }
   HIP_CHECK(h, hipGetLastError());
   HIP_CHECK(h, hipEventRecord(e1, h->stream));
@@ -533,10 +540,10 @@ int launch_compare_fold(bioem_hip_ctx *h, const BatchBuf &bb, int nOC, int orien
   }
   if (h->nMaps <= 64 && nOC >= 1024)
     hipLaunchKernelGGL(k_fold_wave<4>, dim3(h->nMaps), dim3(256), 0, h->stream, h->dPartials, h->maxOC, nOC, h->nMaps,
-                       bb.params, h->dSumRef, h->dDisp, h->nd, h->pd, orient0, conv0, convPerOrient, ids, pmap);
+                       bb.params, h->dSumRef, h->dDisp, P.nd, h->pd, orient0, conv0, convPerOrient, ids, pmap);
   else
     hipLaunchKernelGGL(k_fold_wave<1>, dim3((h->nMaps + 3) / 4), dim3(256), 0, h->stream, h->dPartials, h->maxOC, nOC,
-                       h->nMaps, bb.params, h->dSumRef, h->dDisp, h->nd, h->pd, orient0, conv0, convPerOrient, ids,
+                       h->nMaps, bb.params, h->dSumRef, h->dDisp, P.nd, h->pd, orient0, conv0, convPerOrient, ids,
                        pmap);
   HIP_CHECK(h, hipGetLastError());
   if (phase_end(h, h->stream)) // comparison = the kernels of the launch and the fold behind them (what compareRefMaps does)
@@ -670,7 +677,7 @@ hipError_t launch_r2c(hipStream_t st, int nCU, const double *srcD, const float *
   return hipGetLastError();
 }
 
-int run_r2c(bioem_hip_ctx *h, const BatchBuf &bb, hipStream_t st, const double *srcD, const float *srcF, int nImg,
+int run_r2c(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, const double *srcD, const float *srcF, int nImg,
             int lo = 0, int side = 0)
 {
   HIP_CHECK(h, launch_r2c(st, h->nCU, srcD, srcF, bb.tempDen, h->NormDen, h->N, nImg, h->dTwD, bb.rowSpec, bb.specRef, lo,
@@ -678,7 +685,7 @@ int run_r2c(bioem_hip_ctx *h, const BatchBuf &bb, hipStream_t st, const double *
   return 0;
 }
 
-int project_batch(bioem_hip_ctx *h, const BatchBuf &bb, hipStream_t st, int o0, int nO)
+int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, int o0, int nO)
 {
   const int N = h->N;
   // the pixels a point of the model can reach in any orientation, with its footprint: a box around the map centre
@@ -737,13 +744,10 @@ int compat_alloc(bioem_hip_ctx *h)
   for (int k = 0; k < 2; k++)
   {
     bioem_hip_ctx::CompatHalf &r = h->ring[k];
-    HIP_CHECK(h, hipHostMalloc(&r.hConv, sizeof(float2) * M * cap, hipHostMallocDefault));
-    HIP_CHECK(h, hipHostMalloc(&r.hPar, sizeof(bioem_hip_param5) * cap, hipHostMallocDefault));
-    HIP_CHECK(h, hipHostMalloc(&r.hIds, sizeof(int2) * cap, hipHostMallocDefault));
-    HIP_CHECK(h, hipHostMalloc(&r.hSeg, sizeof(int4) * cap, hipHostMallocDefault));
-    HIP_CHECK(h, hipMalloc(&r.dStage, sizeof(float2) * M * cap));
-    HIP_CHECK(h, hipMalloc(&r.dIds, sizeof(int2) * cap));
-    HIP_CHECK(h, hipMalloc(&r.dSeg, sizeof(int4) * cap));
+    if (host_alloc(h, r.hConv, M * cap) || host_alloc(h, r.hPar, cap) || host_alloc(h, r.hIds, cap) ||
+        host_alloc(h, r.hSeg, cap) || dev_alloc(h, r.dStage, M * cap) || dev_alloc(h, r.dIds, cap) ||
+        dev_alloc(h, r.dSeg, cap))
+      return 1;
     HIP_CHECK(h, hipEventCreateWithFlags(&r.staged, hipEventDisableTiming));
   }
   HIP_CHECK(h, hipStreamCreateWithFlags(&h->copyStream, hipStreamNonBlocking));
@@ -751,35 +755,6 @@ int compat_alloc(bioem_hip_ctx *h)
   h->ringHalf = 0;
   h->ringCount = 0;
   return 0;
-}
-
-void compat_free(bioem_hip_ctx *h)
-{
-  for (int k = 0; k < 2; k++)
-  {
-    bioem_hip_ctx::CompatHalf &r = h->ring[k];
-    if (r.hConv)
-      hipHostFree(r.hConv);
-    if (r.hPar)
-      hipHostFree(r.hPar);
-    if (r.hIds)
-      hipHostFree(r.hIds);
-    if (r.hSeg)
-      hipHostFree(r.hSeg);
-    if (r.dStage)
-      hipFree(r.dStage);
-    if (r.dIds)
-      hipFree(r.dIds);
-    if (r.dSeg)
-      hipFree(r.dSeg);
-    if (r.staged)
-      hipEventDestroy(r.staged);
-    r = bioem_hip_ctx::CompatHalf();
-  }
-  if (h->copyStream)
-    hipStreamDestroy(h->copyStream);
-  h->copyStream = nullptr;
-  h->ringCap = h->ringCount = 0;
 }
 
 // launch the comparison of the rows staged in the current half, then switch halves
@@ -790,7 +765,8 @@ int compat_flush(bioem_hip_ctx *h)
     return 0;
   const int half = h->ringHalf;
   bioem_hip_ctx::CompatHalf &r = h->ring[half];
-  const BatchBuf bb = batch_buf(h, half);
+  bioem_hip_ctx::Slot &bb = h->slot[half];
+  void_slot(bb);
   // runs of equal orientation (rows arrive in call order; an orientation never returns within a half, see compare)
   int nSeg = 0;
   for (int i = 0; i < n; i++)
@@ -806,12 +782,12 @@ int compat_flush(bioem_hip_ctx *h)
   HIP_CHECK(h, hipMemcpyAsync(r.dIds, r.hIds, sizeof(int2) * n, hipMemcpyHostToDevice, h->stream));
   HIP_CHECK(h, hipMemcpyAsync(r.dSeg, r.hSeg, sizeof(int4) * nSeg, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_reorder, dim3(std::min(2048, 8 * n)), dim3(256), 0, h->stream, r.dStage, bb.conv, n, h->N, h->H,
-                     h->fast, h->N1, h->Hp);
+                     h->plan.halfR, h->plan.N1, h->Hp);
   HIP_CHECK(h, hipGetLastError());
   if (launch_compare_fold(h, bb, n, 0, 0, 1, r.dIds, r.dSeg, nSeg))
     return 1;
-  HIP_CHECK(h, hipEventRecord(h->cmpDone[half], h->stream));
-  h->cmpPending[half] = true;
+  HIP_CHECK(h, hipEventRecord(bb.cmpDone, h->stream));
+  bb.cmpPending = true;
   h->ringHalf ^= 1;
   h->ringCount = 0;
   h->ringOrients.clear();
@@ -819,7 +795,7 @@ int compat_flush(bioem_hip_ctx *h)
 }
 
 // conv spectra of CTFs [c0, c0 + nC) of the nO projected orientations, row ob * nC + (c - c0)
-int convolve_batch(bioem_hip_ctx *h, const BatchBuf &bb, hipStream_t st, int nO, int c0, int nC)
+int convolve_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, int nO, int c0, int nC)
 {
   // few particles: the preparation is the longer half of the pipeline and the fused kernel shortens it; many particles:
   // it hides behind the comparison either way, and the one-wave blocks of k_parseval_ordered take less from the
@@ -833,19 +809,19 @@ int convolve_batch(bioem_hip_ctx *h, const BatchBuf &bb, hipStream_t st, int nO,
     // longer than the 960 additions)
     if (nC <= 4)
       hipLaunchKernelGGL((k_convolve_sums<4, 4>), dim3(1, (nO + 3) / 4), dim3(kConvThreads), conv_lanes_lds(4 * nC), st,
-                         bb.specRef, h->dCTF, h->dCtfParam, h->N, h->H, h->fast, h->N1, c0, nC, nO, 4 * nC, bb.conv, bb.params, h->Hp);
+                         bb.specRef, h->dCTF, h->dCtfParam, h->N, h->H, h->plan.halfR, h->plan.N1, c0, nC, nO, 4 * nC, bb.conv, bb.params, h->Hp);
     else if (nC == 5)
       hipLaunchKernelGGL((k_convolve_sums<3, 5>), dim3(1, (nO + 2) / 3), dim3(kConvThreads), conv_lanes_lds(15), st, bb.specRef,
-                         h->dCTF, h->dCtfParam, h->N, h->H, h->fast, h->N1, c0, nC, nO, 15, bb.conv, bb.params, h->Hp);
+                         h->dCTF, h->dCtfParam, h->N, h->H, h->plan.halfR, h->plan.N1, c0, nC, nO, 15, bb.conv, bb.params, h->Hp);
     else
       hipLaunchKernelGGL((k_convolve_sums<3, 6>), dim3((nC + 5) / 6, (nO + 2) / 3), dim3(kConvThreads), conv_lanes_lds(18), st,
-                         bb.specRef, h->dCTF, h->dCtfParam, h->N, h->H, h->fast, h->N1, c0, nC, nO, 18, bb.conv, bb.params, h->Hp);
+                         bb.specRef, h->dCTF, h->dCtfParam, h->N, h->H, h->plan.halfR, h->plan.N1, c0, nC, nO, 18, bb.conv, bb.params, h->Hp);
     HIP_CHECK(h, hipGetLastError());
     return 0;
   }
   const int M4 = (int) ((h->M + 3) & ~(size_t) 3);
   hipLaunchKernelGGL(k_convolve, dim3(nC, nO), dim3(256), 0, st, bb.specRef, h->dCTF, h->dCtfParam, h->N, h->H,
-                     h->fast, h->N1, c0, bb.conv, bb.scratch, M4, bb.params, h->Hp);
+                     h->plan.halfR, h->plan.N1, c0, bb.conv, bb.scratch, M4, bb.params, h->Hp);
   HIP_CHECK(h, hipGetLastError());
   // the ordered Parseval sums of all nC x nO spectra side by side: four sequential chains per wave
   hipLaunchKernelGGL(k_parseval_ordered, dim3((nC * nO + 3) / 4), dim3(64), 0, st, bb.scratch, (int) h->M, M4, nC * nO,
@@ -923,49 +899,37 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
     int prLow = 0, prHigh = 0;
     HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
     HIP_CHECK(h, hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prHigh));
+    // projection/convolution are filler work with many particles: lowest priority so that comparison blocks win the
+    // CUs.  With few particles they are the longer half of the pipeline and waiting behind every comparison block
+    // stretches them four- to sixfold: same priority as the comparison then (20 particles: 8.41 -> 8.25 ms per pass;
+    // 1 000 particles: no difference either way).
+    HIP_CHECK(h, hipStreamCreateWithPriority(&h->prepStream, hipStreamNonBlocking, nMaps <= 64 ? prHigh : prLow));
   }
 
   // which kernel runs this shape: kernel_select.hpp (pure function of N and the displacement set)
   const int maxD = pd->maxDisplaceCenter;
+  h->plan = plan_kernels(N, maxD, pd->GridSpaceCenter, algo);
+  const KernelPlan &P = h->plan;
+  if (P.err || !P.fn)
   {
-    KernelPlan P = plan_kernels(N, maxD, pd->GridSpaceCenter, algo);
-    if (P.err || !P.fn)
+    h->err = P.err ? P.err : "no comparison kernel for this configuration";
+    return 2;
+  }
+  HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(P.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int) P.ldsBytes));
+  const int mD = maxD / P.gs;
+  const char *directEnv = getenv("BIOEM_CC_DIRECT");
+  h->direct = directEnv && atoi(directEnv) != 0;
+  if (h->direct)
+  { // compare_direct.hpp: the sliding-window evaluation of the same cross-correlation values
+    const int gsd = pd->GridSpaceCenter;
+    if (N > kDirectMaxN || gsd < 1 || maxD % gsd != 0 || 2 * (maxD / gsd) + 1 > 24 || P.tileT)
     {
-      h->err = P.err ? P.err : "no comparison kernel for this configuration";
+      h->err = "BIOEM_CC_DIRECT: the direct cross-correlation takes images up to 160 pixels and regular windows of at "
+               "most 24 offsets per axis";
       return 2;
     }
-    h->disp = P.disp;
-    h->nd = P.nd;
-    h->gs = P.gs;
-    h->winD = P.winD;
-    h->family = P.family;
-    h->fast = P.fast;
-    h->N1 = P.N1;
-    h->oddR = P.oddR;
-    h->nyq = P.nyq;
-    h->fastm = P.fastm;
-    h->fastm2 = P.fastm2;
-    h->rowsK = P.rowsK;
-    h->wide2 = P.wide2;
-    h->tileT = P.tileT;
-    h->tilesPerAxis = P.tilesPerAxis;
-    h->tileCenter = P.tileCenter;
-    h->tileValid = P.tileValid;
-    h->w2NRW = P.w2NRW;
-    h->w2NBLK = P.w2NBLK;
-    h->w2TS = P.w2TS;
-    h->w2Rows2 = P.w2Rows2;
-    h->nyqWD = P.nyqWD;
-    h->w2Halves = P.w2Halves;
-    h->w2NW = P.w2NW;
-    h->genericWaves = P.genericWaves;
-    h->genericRows = P.genericRows;
-    h->fn = reinterpret_cast<const void *>(P.fn);
-    h->ldsBytes = P.ldsBytes;
-    HIP_CHECK(h, hipFuncSetAttribute(h->fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int) h->ldsBytes));
   }
-  const int mD = maxD / h->gs;
   // Pitch of the comparison layout.  A lane block of the fast kernels keeps eight rows of one 64-column block in flight;
   // with N a multiple of 64 a row pair is 16 B more than a multiple of 512 B (4 112 B at 512^2, 2 064 B at 256^2) and all
   // of them start in the same few L2 channels.  Fifteen more words make the pitch an odd number of 256-byte lines
@@ -977,18 +941,16 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
   // (Other numbers of words: 7 / 15 / 23 / 31 / 47 are within 2 % of each other at 256^2 ... 512^2,
   // profiles/r04_padded_pitch_ab.txt.)
   constexpr int kPitchPadWords = 15;
-  h->Hp = h->H;
-  const bool directCC = getenv("BIOEM_CC_DIRECT") && atoi(getenv("BIOEM_CC_DIRECT")) != 0; // (its own kernels read conv)
-  if (h->fast && !h->wide2 && !h->rowsK && !h->tileT && !directCC && N % 64 == 0 && N >= 192 &&
-      !getenv("BIOEM_NO_PITCH_PAD"))
-    h->Hp = h->H + kPitchPadWords;
+  const bool padPitch = (P.family == KF_FAST || P.family == KF_FASTM || P.family == KF_FASTM2) && !P.tileT &&
+                        !h->direct && N % 64 == 0 && N >= 192 && !getenv("BIOEM_NO_PITCH_PAD");
+  h->Hp = padPitch ? h->H + kPitchPadWords : h->H;
   h->Mc = (size_t) N * h->Hp;
 
   // batch sizing: conv buffer <= ~96 MiB, partial buffer <= ~128 MiB
   const size_t M = (size_t) h->M;
   size_t ocCap = (96u << 20) / (h->Mc * sizeof(float2));
   // (tiled wide windows keep one partial per tile and comparison besides the merged one)
-  const size_t partBuffers = 1 + (h->tileT ? (size_t) h->tilesPerAxis * h->tilesPerAxis : 0);
+  const size_t partBuffers = 1 + (P.tileT ? (size_t) P.tilesPerAxis * P.tilesPerAxis : 0);
   size_t partCap = (128u << 20) / ((size_t) nMaps * sizeof(Partial));
   if (partBuffers > 1)
     partCap = std::max<size_t>((size_t) nCTF, (1024u << 20) / ((size_t) nMaps * sizeof(Partial) * partBuffers));
@@ -1019,210 +981,150 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
   h->maxOC = OB * nCTF;
   h->chunkB = OB > 32 ? OB : 32;
 
-  HIP_CHECK(h, hipMalloc(&h->dRef, sizeof(float2) * h->Mc * nMaps));
-  HIP_CHECK(h, hipMalloc(&h->dSumRef, sizeof(float) * nMaps));
-  HIP_CHECK(h, hipMalloc(&h->dSumsqRef, sizeof(float) * nMaps));
-  HIP_CHECK(h, hipMalloc(&h->dCTF, sizeof(float2) * M * nCTF));
-  HIP_CHECK(h, hipMalloc(&h->dCtfParam, sizeof(float) * 3 * nCTF));
-  HIP_CHECK(h, hipMalloc(&h->dAngles, sizeof(float4) * nAngles));
-  HIP_CHECK(h, hipMalloc(&h->dTw, sizeof(float2) * (N + 1)));
-  HIP_CHECK(h, hipMalloc(&h->dTwD, sizeof(double2) * N));
-  HIP_CHECK(h, hipMalloc(&h->dDisp, sizeof(int) * h->nd));
-  HIP_CHECK(h, hipMalloc(&h->dLtab, sizeof(double2) * 64));
-  HIP_CHECK(h, hipMalloc(&h->dProjReal, sizeof(double) * (size_t) h->chunkB * N * N));
-  HIP_CHECK(h, hipMalloc(&h->dTempDen, sizeof(double) * h->chunkB));
-  HIP_CHECK(h, hipMalloc(&h->dRowSpec, sizeof(double2) * (size_t) h->chunkB * M));
-  HIP_CHECK(h, hipMalloc(&h->dSpecRef, sizeof(float2) * (size_t) h->chunkB * M));
-  HIP_CHECK(h, hipMalloc(&h->dScratch, sizeof(float) * (size_t) ((h->maxOC + 31) & ~31) * ((M + 3) & ~(size_t) 3)));
-  HIP_CHECK(h, hipMalloc(&h->dConv, sizeof(float2) * (size_t) h->maxOC * h->Mc));
-  HIP_CHECK(h, hipMalloc(&h->dParams, sizeof(bioem_hip_param5) * h->maxOC));
-  HIP_CHECK(h, hipMalloc(&h->dPostC, sizeof(double2) * h->maxOC));
-  HIP_CHECK(h, hipMalloc(&h->dPartials, sizeof(Partial) * (size_t) nMaps * h->maxOC));
-  if (const char *de = getenv("BIOEM_CC_DIRECT"))
-    h->direct = atoi(de) != 0;
+  if (dev_alloc(h, h->dRef, h->Mc * nMaps) || dev_alloc(h, h->dSumRef, nMaps) || dev_alloc(h, h->dSumsqRef, nMaps) ||
+      dev_alloc(h, h->dCTF, M * nCTF) || dev_alloc(h, h->dCtfParam, 3 * nCTF) || dev_alloc(h, h->dAngles, nAngles) ||
+      dev_alloc(h, h->dPartials, (size_t) nMaps * h->maxOC))
+    return 1;
+  // the two pipeline slots; slot 0's projection buffers hold chunkB (>= 32) images for the particle uploads
+  const size_t scratchFloats = (size_t) ((h->maxOC + 31) & ~31) * ((M + 3) & ~(size_t) 3);
+  for (int k = 0; k < 2; k++)
+  {
+    bioem_hip_ctx::Slot &sl = h->slot[k];
+    const size_t nImg = k == 0 ? h->chunkB : h->OB;
+    if (dev_alloc(h, sl.projReal, nImg * N * N) || dev_alloc(h, sl.tempDen, nImg) || dev_alloc(h, sl.rowSpec, nImg * M) ||
+        dev_alloc(h, sl.specRef, nImg * M) || dev_alloc(h, sl.scratch, scratchFloats) ||
+        dev_alloc(h, sl.conv, (size_t) h->maxOC * h->Mc) || dev_alloc(h, sl.params, h->maxOC) ||
+        dev_alloc(h, sl.postc, h->maxOC))
+      return 1;
+    HIP_CHECK(h, hipEventCreateWithFlags(&sl.prepDone, hipEventDisableTiming));
+    HIP_CHECK(h, hipEventCreateWithFlags(&sl.cmpDone, hipEventDisableTiming));
+  }
   if (h->direct)
-  { // compare_direct.hpp: the sliding-window evaluation of the same cross-correlation values
-    const int gsd = pd->GridSpaceCenter;
-    if (N > kDirectMaxN || gsd < 1 || maxD % gsd != 0 || 2 * (maxD / gsd) + 1 > 24 || h->tileT)
-    {
-      h->err = "BIOEM_CC_DIRECT: the direct cross-correlation takes images up to 160 pixels and regular windows of at "
-               "most 24 offsets per axis";
-      return 2;
-    }
-    HIP_CHECK(h, hipMalloc(&h->dMapsReal, sizeof(float) * (size_t) nMaps * N * N));
+  {
+    if (dev_alloc(h, h->dMapsReal, (size_t) nMaps * N * N) || dev_alloc(h, h->dConvReal, (size_t) h->maxOC * N * N) ||
+        dev_alloc(h, h->dDirectZ, (size_t) h->maxOC * M))
+      return 1;
     HIP_CHECK(h, hipMemset(h->dMapsReal, 0, sizeof(float) * (size_t) nMaps * N * N));
-    HIP_CHECK(h, hipMalloc(&h->dConvReal, sizeof(float) * (size_t) h->maxOC * N * N));
-    HIP_CHECK(h, hipMalloc(&h->dDirectZ, sizeof(double2) * (size_t) h->maxOC * M));
     HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_compare_direct<3, 8>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int) direct_lds_bytes(N)));
   }
-  if (h->nyq)
-    HIP_CHECK(h, hipMalloc(&h->dTnyq, sizeof(float) * (size_t) nMaps * h->maxOC * (2 * h->winD + 1)));
-  if (h->tileT)
+  if (P.nyq && dev_alloc(h, h->dTnyq, (size_t) nMaps * h->maxOC * (2 * P.nyqWD + 1)))
+    return 1;
+  if (P.tileT)
   {
-    const int nT = h->tilesPerAxis;
-    HIP_CHECK(h, hipMalloc(&h->dPartTiles, sizeof(Partial) * (size_t) nT * nT * nMaps * h->maxOC));
-    HIP_CHECK(h, hipMalloc(&h->dConvShift, sizeof(float2) * (size_t) h->maxOC * M));
-    std::vector<int> local(h->tileT), rank(2 * mD + 1, 0);
-    for (int j = 0; j < h->tileT; j++)
-      local[j] = h->gs * (j - h->winD); // sorted local list: the kernel's rows and lanes in the same order
-    for (int v = 0; v < h->nd; v++)
-      rank[h->disp[v] / h->gs + mD] = v; // visiting rank of window row m in the reference's order
-    HIP_CHECK(h, hipMalloc(&h->dDispLocal, sizeof(int) * local.size()));
-    HIP_CHECK(h, hipMemcpy(h->dDispLocal, local.data(), sizeof(int) * local.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(h, hipMalloc(&h->dRankOfRow, sizeof(int) * rank.size()));
-    HIP_CHECK(h, hipMemcpy(h->dRankOfRow, rank.data(), sizeof(int) * rank.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(h, hipMalloc(&h->dTileCenter, sizeof(int) * nT));
-    HIP_CHECK(h, hipMemcpy(h->dTileCenter, h->tileCenter.data(), sizeof(int) * nT, hipMemcpyHostToDevice));
-    HIP_CHECK(h, hipMalloc(&h->dTileValid, sizeof(int) * nT));
-    HIP_CHECK(h, hipMemcpy(h->dTileValid, h->tileValid.data(), sizeof(int) * nT, hipMemcpyHostToDevice));
+    const int nT = P.tilesPerAxis;
+    std::vector<int> local(P.tileT), rank(2 * mD + 1, 0);
+    for (int j = 0; j < P.tileT; j++)
+      local[j] = P.gs * (j - P.winD); // sorted local list: the kernel's rows and lanes in the same order
+    for (int v = 0; v < P.nd; v++)
+      rank[P.disp[v] / P.gs + mD] = v; // visiting rank of window row m in the reference's order
+    if (dev_alloc(h, h->dPartTiles, (size_t) nT * nT * nMaps * h->maxOC) || dev_alloc(h, h->dConvShift, (size_t) h->maxOC * M) ||
+        upload(h, h->dDispLocal, local.data(), local.size()) || upload(h, h->dRankOfRow, rank.data(), rank.size()) ||
+        upload(h, h->dTileCenter, P.tileCenter.data(), nT) || upload(h, h->dTileValid, P.tileValid.data(), nT))
+      return 1;
   }
   h->devProbBytes = bioem_hip_prob_size(nMaps, angO1 - angO0, pd->writeAngles);
   h->probBytes = shard ? bioem_hip_prob_size(nMaps, 0, 0) : h->devProbBytes;
-  HIP_CHECK(h, hipMalloc(&h->dProb, h->devProbBytes));
-  {
-    // projection/convolution are filler work with many particles: lowest priority so that comparison blocks win the
-    // CUs.  With few particles they are the longer half of the pipeline and waiting behind every comparison block
-    // stretches them four- to sixfold: same priority as the comparison then (20 particles: 8.41 -> 8.25 ms per pass;
-    // 1 000 particles: no difference either way).
-    int prLow = 0, prHigh = 0;
-    HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
-    const bool prepHigh = nMaps <= 64;
-    HIP_CHECK(h, hipStreamCreateWithPriority(&h->prepStream, hipStreamNonBlocking, prepHigh ? prHigh : prLow));
-  }
-  HIP_CHECK(h, hipMalloc(&h->dProjReal2, sizeof(double) * (size_t) h->OB * N * N));
-  HIP_CHECK(h, hipMalloc(&h->dTempDen2, sizeof(double) * h->OB));
-  HIP_CHECK(h, hipMalloc(&h->dRowSpec2, sizeof(double2) * (size_t) h->OB * M));
-  HIP_CHECK(h, hipMalloc(&h->dSpecRef2, sizeof(float2) * (size_t) h->OB * M));
-  HIP_CHECK(h, hipMalloc(&h->dScratch2, sizeof(float) * (size_t) ((h->maxOC + 31) & ~31) * ((M + 3) & ~(size_t) 3)));
-  HIP_CHECK(h, hipMalloc(&h->dConv2, sizeof(float2) * (size_t) h->maxOC * h->Mc));
-  HIP_CHECK(h, hipMalloc(&h->dParams2, sizeof(bioem_hip_param5) * h->maxOC));
-  HIP_CHECK(h, hipMalloc(&h->dPostC2, sizeof(double2) * h->maxOC));
-  for (int i = 0; i < 2; i++)
-  {
-    HIP_CHECK(h, hipEventCreateWithFlags(&h->prepDone[i], hipEventDisableTiming));
-    HIP_CHECK(h, hipEventCreateWithFlags(&h->cmpDone[i], hipEventDisableTiming));
-  }
+  if (dev_alloc(h, h->dProb, h->devProbBytes))
+    return 1;
 
-  if (h->wide2)
-  { // recombination twiddles exp(2 pi i dx k1 / N), dx = (m - mD) gs, laid out per (k1, wave): the NRW window rows a
+  std::vector<float2> twk; // recombination twiddles of the comparison kernel
+  if (P.family == KF_WIDE2)
+  { // exp(2 pi i dx k1 / N), dx = (m - mD) gs, laid out per (k1, wave): the NRW window rows a
     // wave folds are contiguous (rows beyond the window: zero)
-    const int NRW = h->w2NRW, NWV = h->w2NW, rpw = (h->nd + NWV - 1) / NWV;
-    std::vector<float2> t2((size_t) h->N1 * NWV * NRW, make_float2(0.f, 0.f));
-    for (int k1 = 0; k1 < h->N1; k1++)
+    const int NRW = P.w2NRW, NWV = P.w2NW, rpw = (P.nd + NWV - 1) / NWV;
+    twk.assign((size_t) P.N1 * NWV * NRW, make_float2(0.f, 0.f));
+    for (int k1 = 0; k1 < P.N1; k1++)
       for (int w = 0; w < NWV; w++)
         for (int d = 0; d < NRW; d++)
         {
           const int m = w * rpw + d;
-          if (m >= h->nd)
-            continue;
-          const long long dx = (long long) (m - mD) * h->gs;
-          const double ang = 2.0 * M_PI * (double) (((dx * k1) % N + N) % N) / (double) N;
-          t2[((size_t) k1 * NWV + w) * NRW + d] = make_float2((float) cos(ang), (float) sin(ang));
+          if (m < P.nd)
+            twk[((size_t) k1 * NWV + w) * NRW + d] = twiddle((long long) (m - mD) * P.gs * k1, N);
         }
-    HIP_CHECK(h, hipMalloc(&h->dTwk2, sizeof(float2) * t2.size()));
-    HIP_CHECK(h, hipMemcpy(h->dTwk2, t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice));
   }
-  if (h->fastm2)
-  { // recombination twiddles of k_compare_fastm2<R, NYQ, GS>: [k1 pair s][accumulator a = OFF g + j] = {w^(dx 2s), w^(dx (2s+1))}
+  if (P.family == KF_FASTM2)
+  { // k_compare_fastm2<R, NYQ, GS>: [k1 pair s][accumulator a = OFF g + j] = {w^(dx 2s), w^(dx (2s+1))} (two float2)
     // for the LOW-half row dx = (2 OFF g + j - 23) GS (the high half folds the rows OFF further with the same numbers); zero
     // for a k1 beyond N1 - 1 (rows outside the displacement list are masked by their rank in the kernel)
-    const int Rl = 2 * h->fast, off = fastm2_off(Rl, h->gs), nAcc = fastm2_acc(Rl, h->gs);
-    const int nS = (h->N1 + 1) / 2;
-    std::vector<float4> t4((size_t) nS * nAcc, make_float4(0.f, 0.f, 0.f, 0.f));
+    const int Rl = 2 * P.halfR, off = fastm2_off(Rl, P.gs), nAcc = fastm2_acc(Rl, P.gs);
+    const int nS = (P.N1 + 1) / 2;
+    twk.assign((size_t) nS * nAcc * 2, make_float2(0.f, 0.f));
     for (int s2 = 0; s2 < nS; s2++)
       for (int ac = 0; ac < nAcc; ac++)
       {
-        const long long dx = (long long) (2 * off * (ac / off) + (ac % off) - kFm2WD) * h->gs;
-        float w[4] = {0.f, 0.f, 0.f, 0.f};
+        const long long dx = (long long) (2 * off * (ac / off) + (ac % off) - kFm2WD) * P.gs;
         for (int e = 0; e < 2; e++)
-        {
-          const int k1 = 2 * s2 + e;
-          if (k1 >= h->N1)
-            continue;
-          const double ang = 2.0 * M_PI * (double) (((dx * k1) % N + N) % N) / (double) N;
-          w[2 * e] = (float) cos(ang);
-          w[2 * e + 1] = (float) sin(ang);
-        }
-        t4[(size_t) s2 * nAcc + ac] = make_float4(w[0], w[1], w[2], w[3]);
+          if (2 * s2 + e < P.N1)
+            twk[((size_t) s2 * nAcc + ac) * 2 + e] = twiddle(dx * (2 * s2 + e), N);
       }
-    HIP_CHECK(h, hipMalloc(&h->dTwk2, sizeof(float4) * t4.size()));
-    HIP_CHECK(h, hipMemcpy(h->dTwk2, t4.data(), sizeof(float4) * t4.size(), hipMemcpyHostToDevice));
     // B operand of the matrix pass: lane l of k-step K, column tile ct supplies (l / 16 odd ? sin : cos)(2 pi ky dy / N),
     // ky = 2 K + l / 32, dy = (16 ct + l % 16 - 23) GS -- the float twiddles exp(2 pi i k / N) every kernel uses
-    std::vector<float> bt(fastm2_btab_floats(h->H, h->nyq));
+    std::vector<float> bt(fastm2_btab_floats(h->H, P.nyq));
     for (size_t K = 0; K < bt.size() / 192; K++)
       for (int ct = 0; ct < 3; ct++)
         for (int l = 0; l < 64; l++)
         {
-          const long long ky = 2 * (long long) K + (l >> 5), dy = (long long) (16 * ct + (l & 15) - kFm2WD) * h->gs;
-          const double ang = 2.0 * M_PI * (double) (((ky * dy) % N + N) % N) / (double) N;
-          bt[(K * 3 + ct) * 64 + l] = ((l >> 4) & 1) ? (float) sin(ang) : (float) cos(ang);
+          const long long ky = 2 * (long long) K + (l >> 5), dy = (long long) (16 * ct + (l & 15) - kFm2WD) * P.gs;
+          const float2 w = twiddle(ky * dy, N);
+          bt[(K * 3 + ct) * 64 + l] = ((l >> 4) & 1) ? w.y : w.x;
         }
-    HIP_CHECK(h, hipMalloc(&h->dBtab, sizeof(float) * bt.size()));
-    HIP_CHECK(h, hipMemcpy(h->dBtab, bt.data(), sizeof(float) * bt.size(), hipMemcpyHostToDevice));
+    if (upload(h, h->dBtab, bt.data(), bt.size()))
+      return 1;
+  }
+  if (P.family == KF_FAST || P.family == KF_FASTM || P.family == KF_ROWS || P.family == KF_ODDFFT)
+  { // the window kernels
+    const int NW = 2 * P.winD + 1;
+    // [N1][2 winD + 1], d = -winD..winD; k_compare_rows: a "register FFT" of length 1, one table row per kx;
+    // k_compare_oddfft: N1 = N / oddR
+    const int nK1 = P.family == KF_ROWS ? N : P.N1;
+    twk.resize((size_t) nK1 * NW);
+    for (int k1 = 0; k1 < nK1; k1++)
+      for (int d = -P.winD; d <= P.winD; d++)
+        twk[(size_t) k1 * NW + d + P.winD] = twiddle((long long) d * P.gs * k1, N);
+  }
+  if (!twk.empty() && upload(h, h->dTwk, twk.data(), twk.size()))
+    return 1;
+  if (P.nyq)
+  { // Nyquist pre-kernel (every family with the split): per (k1, k2 pair) the 2*nyqWD+1 twiddle pairs w^(kx0 m gs),
+    // w^(kx1 m gs), contiguous
+    const int NW = 2 * P.nyqWD + 1, R2 = P.halfR;
+    std::vector<float2> twn((size_t) (N / 2) * NW * 2);
+    for (int k1 = 0; k1 < P.N1; k1++)
+      for (int k2p = 0; k2p < R2; k2p++)
+        for (int m = -P.nyqWD; m <= P.nyqWD; m++)
+          for (int e = 0; e < 2; e++)
+          {
+            const long long kx = (long long) P.N1 * (2 * k2p + e) + k1;
+            twn[(((size_t) (k1 * R2 + k2p) * NW) + (m + P.nyqWD)) * 2 + e] = twiddle(kx * m * P.gs, N);
+          }
+    if (upload(h, h->dTwNyq, twn.data(), twn.size()))
+      return 1;
   }
   std::vector<float2> tw(N + 1);
   std::vector<double2> twd(N);
   for (int k = 0; k <= N; k++)
+    tw[k] = twiddle(k, N);
+  for (int k = 0; k < N; k++)
+    twd[k] = twiddle_d(k, N);
+  // log table: bin i of the mantissa interval [1,2): c = 1/centre, entry {c, -log(c)}
+  std::vector<double2> lt(64);
+  for (int i = 0; i < 64; i++)
   {
-    const double ang = 2.0 * M_PI * (double) (k % N) / (double) N;
-    tw[k] = make_float2((float) cos(ang), (float) sin(ang));
-    if (k < N)
-      twd[k] = make_double2(cos(ang), sin(ang));
+    const double c = 1.0 / (1.0 + ((double) i + 0.5) / 64.0);
+    lt[i] = make_double2(c, -log(c));
   }
-  HIP_CHECK(h, hipMemcpy(h->dTw, tw.data(), sizeof(float2) * (N + 1), hipMemcpyHostToDevice));
-  HIP_CHECK(h, hipMemcpy(h->dTwD, twd.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
-  HIP_CHECK(h, hipMemcpy(h->dDisp, h->disp.data(), sizeof(int) * h->nd, hipMemcpyHostToDevice));
-  {
-    // log table: bin i of the mantissa interval [1,2): c = 1/centre, entry {c, -log(c)}
-    std::vector<double2> lt(64);
-    for (int i = 0; i < 64; i++)
-    {
-      const double c = 1.0 / (1.0 + ((double) i + 0.5) / 64.0);
-      lt[i] = make_double2(c, -log(c));
-    }
-    HIP_CHECK(h, hipMemcpy(h->dLtab, lt.data(), sizeof(double2) * 64, hipMemcpyHostToDevice));
-  }
-  if (h->fast || h->rowsK)
-  {
-    const int NW = 2 * h->winD + 1;
-    // k_compare_rows: a "register FFT" of length 1, one table row per kx; k_compare_oddfft: N1 = N / oddR
-    const int nK1 = (h->rowsK && !h->oddR) ? N : h->N1;
-    std::vector<float2> twk((size_t) nK1 * NW);
-    for (int k1 = 0; k1 < nK1; k1++)
-      for (int d = -h->winD; d <= h->winD; d++)
-      {
-        const double ang = 2.0 * M_PI * (double) ((((long long) d * h->gs * k1) % N + N) % N) / (double) N;
-        twk[(size_t) k1 * NW + d + h->winD] = make_float2((float) cos(ang), (float) sin(ang));
-      }
-    HIP_CHECK(h, hipMalloc(&h->dTwk, sizeof(float2) * twk.size()));
-    HIP_CHECK(h, hipMemcpy(h->dTwk, twk.data(), sizeof(float2) * twk.size(), hipMemcpyHostToDevice));
-    if (h->nyq)
-    { // Nyquist pre-kernel: per (k1, k2 pair) the 2*winD+1 twiddle pairs w^(kx0 m gs), w^(kx1 m gs), contiguous
-      const int R2 = h->fast;
-      std::vector<float2> twn((size_t) (N / 2) * NW * 2);
-      for (int k1 = 0; k1 < h->N1; k1++)
-        for (int k2p = 0; k2p < R2; k2p++)
-          for (int m = -h->winD; m <= h->winD; m++)
-            for (int e = 0; e < 2; e++)
-            {
-              const long long kx = (long long) h->N1 * (2 * k2p + e) + k1;
-              const int idx = (int) (((kx * m * h->gs) % N + N) % N);
-              twn[(((size_t) (k1 * R2 + k2p) * NW) + (m + h->winD)) * 2 + e] = tw[idx];
-            }
-      HIP_CHECK(h, hipMalloc(&h->dTwNyq, sizeof(float2) * twn.size()));
-      HIP_CHECK(h, hipMemcpy(h->dTwNyq, twn.data(), sizeof(float2) * twn.size(), hipMemcpyHostToDevice));
-    }
-  }
+  if (upload(h, h->dTw, tw.data(), tw.size()) || upload(h, h->dTwD, twd.data(), twd.size()) ||
+      upload(h, h->dDisp, P.disp.data(), P.disp.size()) || upload(h, h->dLtab, lt.data(), lt.size()))
+    return 1;
   // BIOEM_SIGNATURE_LOG=<file>: one line per handle with the comparison-kernel instantiations its launches will use
   // (scripts/check_kernel_coverage.py holds the lines of a test run against the kernels in the code object)
   if (const char *lg = getenv("BIOEM_SIGNATURE_LOG"))
     if (FILE *f = fopen(lg, "a"))
     {
       fprintf(f, "%s\n", bioem_hip_kernel_signature(h));
-      if (h->nyq)
-        fprintf(f, "k_nyquist_rows<%d, %d>\n", (h->wide2 || h->fastm2) ? h->nyqWD : h->winD, h->nMaps <= 64 ? 4 : 1);
+      if (P.nyq)
+        fprintf(f, "k_nyquist_rows<%d, %d>\n", P.nyqWD, h->nMaps <= 64 ? 4 : 1);
       fclose(f);
     }
   return 0;
@@ -1251,29 +1153,21 @@ int bioem_hip_destroy(bioem_hip_handle h)
   drain_phases(h);
   for (hipEvent_t e : h->evPool)
     hipEventDestroy(e);
-  void *ptrs[] = {h->dRef,     h->dSumRef,  h->dSumsqRef, h->dCTF,     h->dCtfParam, h->dPts,   h->dAngles,
-                  h->dTw,      h->dTwD,     h->dDisp,     h->dLtab,    h->dTwk,     h->dProjReal, h->dTempDen,  h->dRowSpec, h->dSpecRef,
-                  h->dScratch, h->dConv,    h->dParams,   h->dPartials, h->dProb,
-                  h->dProjReal2, h->dTempDen2, h->dRowSpec2, h->dSpecRef2, h->dScratch2, h->dConv2, h->dParams2,
-                  h->dTnyq, h->dTwNyq, h->dPartTiles, h->dConvShift, h->dDispLocal, h->dRankOfRow, h->dTileCenter, h->dTileValid,
-                  h->dCand, h->dSend, h->dRecv, h->dMerged, h->dTwk2, h->dBtab, h->dPostC, h->dPostC2,
-                  h->dMapsReal, h->dConvReal, h->dDirectZ, h->dStamp};
-  for (void *p : ptrs)
-    if (p)
-      hipFree(p);
-  compat_free(h);
-  for (int i = 0; i < 2; i++)
-  {
-    if (h->prepDone[i])
-      hipEventDestroy(h->prepDone[i]);
-    if (h->cmpDone[i])
-      hipEventDestroy(h->cmpDone[i]);
-  }
   if (h->prepStream)
-  {
     hipStreamSynchronize(h->prepStream);
+  for (const bioem_hip_ctx::Alloc &al : h->allocs)
+    if (al.pinned)
+      hipHostFree(al.p);
+    else
+      hipFree(al.p);
+  for (int k = 0; k < 2; k++)
+    for (hipEvent_t e : {h->slot[k].prepDone, h->slot[k].cmpDone, h->ring[k].staged})
+      if (e)
+        hipEventDestroy(e);
+  if (h->copyStream)
+    hipStreamDestroy(h->copyStream);
+  if (h->prepStream)
     hipStreamDestroy(h->prepStream);
-  }
   if (h->stream)
     hipStreamDestroy(h->stream);
   delete h;
@@ -1289,15 +1183,17 @@ int bioem_hip_upload_particles(bioem_hip_handle h, const float *refFFT, const fl
     return 2;
   }
   const size_t M = (size_t) h->M;
+  bioem_hip_ctx::Slot &s0 = h->slot[0]; // the images pass through slot 0
+  void_slot(s0);
   HIP_CHECK(h, hipMemcpyAsync(h->dSumRef, sum, sizeof(float) * h->nMaps, hipMemcpyHostToDevice, h->stream));
   HIP_CHECK(h, hipMemcpyAsync(h->dSumsqRef, sumsq, sizeof(float) * h->nMaps, hipMemcpyHostToDevice, h->stream));
   for (int b = 0; b < h->nMaps; b += h->chunkB)
   {
     const int n = std::min(h->chunkB, h->nMaps - b);
-    HIP_CHECK(h, hipMemcpyAsync(h->dSpecRef, refFFT + 2 * M * (size_t) b, sizeof(float2) * M * n,
+    HIP_CHECK(h, hipMemcpyAsync(s0.specRef, refFFT + 2 * M * (size_t) b, sizeof(float2) * M * n,
                                 hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_reorder, dim3(1024), dim3(256), 0, h->stream, h->dSpecRef, h->dRef + h->Mc * (size_t) b, n, h->N,
-                       h->H, h->fast, h->N1, h->Hp);
+    hipLaunchKernelGGL(k_reorder, dim3(1024), dim3(256), 0, h->stream, s0.specRef, h->dRef + h->Mc * (size_t) b, n, h->N,
+                       h->H, h->plan.halfR, h->plan.N1, h->Hp);
     HIP_CHECK(h, hipGetLastError());
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
@@ -1307,10 +1203,12 @@ int bioem_hip_upload_particles(bioem_hip_handle h, const float *refFFT, const fl
 int bioem_hip_upload_particle_maps(bioem_hip_handle h, const float *maps)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
-  const size_t M = (size_t) h->M;
   const int N = h->N;
+  bioem_hip_ctx::Slot &s0 = h->slot[0]; // the transforms pass through slot 0
+  void_slot(s0);
   float *dMaps = nullptr;
   HIP_CHECK(h, hipMalloc(&dMaps, sizeof(float) * (size_t) h->chunkB * N * N));
+  std::unique_ptr<float, hipError_t (*)(void *)> freeMaps(dMaps, hipFree); // scratch: freed on every return
   for (int b = 0; b < h->nMaps; b += h->chunkB)
   {
     const int n = std::min(h->chunkB, h->nMaps - b);
@@ -1321,17 +1219,13 @@ int bioem_hip_upload_particle_maps(bioem_hip_handle h, const float *maps)
     if (h->direct)
       HIP_CHECK(h, hipMemcpyAsync(h->dMapsReal + (size_t) b * N * N, dMaps, sizeof(float) * (size_t) n * N * N,
                                   hipMemcpyDeviceToDevice, h->stream));
-    if (run_r2c(h, batch_buf(h, 0), h->stream, nullptr, dMaps, n))
-    {
-      hipFree(dMaps);
+    if (run_r2c(h, s0, h->stream, nullptr, dMaps, n))
       return 1;
-    }
-    hipLaunchKernelGGL(k_reorder, dim3(1024), dim3(256), 0, h->stream, h->dSpecRef, h->dRef + h->Mc * (size_t) b, n, N,
-                       h->H, h->fast, h->N1, h->Hp);
+    hipLaunchKernelGGL(k_reorder, dim3(1024), dim3(256), 0, h->stream, s0.specRef, h->dRef + h->Mc * (size_t) b, n, N,
+                       h->H, h->plan.halfR, h->plan.N1, h->Hp);
     HIP_CHECK(h, hipGetLastError());
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
-  hipFree(dMaps);
   return 0;
 }
 
@@ -1347,11 +1241,9 @@ int bioem_hip_upload_model(bioem_hip_handle h, const bioem_hip_model_point *pts,
                            float pixelSize, int shiftX, int shiftY)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
-  if (h->dPts)
-    hipFree(h->dPts);
-  h->dPts = nullptr;
-  HIP_CHECK(h, hipMalloc(&h->dPts, sizeof(bioem_hip_model_point) * (size_t) nPts));
-  HIP_CHECK(h, hipMemcpy(h->dPts, pts, sizeof(bioem_hip_model_point) * (size_t) nPts, hipMemcpyHostToDevice));
+  dev_release(h, h->dPts);
+  if (upload(h, h->dPts, pts, (size_t) nPts))
+    return 1;
   h->nPts = nPts;
   h->NormDen = NormDen;
   h->pixelSize = pixelSize;
@@ -1365,13 +1257,12 @@ int bioem_hip_upload_model(bioem_hip_handle h, const bioem_hip_model_point *pts,
   for (int n = 0; n < nPts; n++)
     h->modelRadius = std::max(h->modelRadius, std::sqrt((double) pts[n].pos[0] * pts[n].pos[0] + (double) pts[n].pos[1] * pts[n].pos[1] +
                                                         (double) pts[n].pos[2] * pts[n].pos[2]));
-  if (h->dStamp)
-    hipFree(h->dStamp);
-  h->dStamp = nullptr;
+  dev_release(h, h->dStamp);
   const size_t cells = (size_t) nPts * (2 * h->iradMax + 1) * (2 * h->iradMax + 1);
   if (h->iradMax <= 16 && nPts > 0 && cells <= ((size_t) 1 << 27)) // at most 1 GiB of footprints, else k_project
   {
-    HIP_CHECK(h, hipMalloc(&h->dStamp, sizeof(double) * cells));
+    if (dev_alloc(h, h->dStamp, cells))
+      return 1;
     hipLaunchKernelGGL(k_project_stamps, dim3((unsigned) ((cells + 255) / 256)), dim3(256), 0, h->stream, h->dPts, nPts,
                        h->iradMax, pixelSize, h->dStamp);
     HIP_CHECK(h, hipGetLastError());
@@ -1462,10 +1353,11 @@ int bioem_hip_compare(bioem_hip_handle h, int iPipeline, int iOrient, int iConvS
       return 1;
     const int half = h->ringHalf;
     bioem_hip_ctx::CompatHalf &r = h->ring[half];
-    if (h->ringCount == 0 && h->cmpPending[half])
+    bioem_hip_ctx::Slot &sl = h->slot[half];
+    if (h->ringCount == 0 && sl.cmpPending)
     { // the launch that last used this half (two flushes ago) must have consumed its staged rows
-      HIP_CHECK(h, hipEventSynchronize(h->cmpDone[half]));
-      h->cmpPending[half] = false;
+      HIP_CHECK(h, hipEventSynchronize(sl.cmpDone));
+      sl.cmpPending = false;
     }
     const int row0 = h->ringCount;
     const int n = std::min(maxParallelConv - done, h->ringCap - row0);
@@ -1488,8 +1380,8 @@ int bioem_hip_compare(bioem_hip_handle h, int iPipeline, int iOrient, int iConvS
   bool launch = h->ringCount == h->ringCap;
   if (!launch && h->ringCount >= 32)
   {
-    const int other = h->ringHalf ^ 1;
-    launch = !h->cmpPending[other] || hipEventQuery(h->cmpDone[other]) == hipSuccess;
+    const bioem_hip_ctx::Slot &other = h->slot[h->ringHalf ^ 1];
+    launch = !other.cmpPending || hipEventQuery(other.cmpDone) == hipSuccess;
   }
   if (launch && compat_flush(h))
     return 1;
@@ -1542,14 +1434,14 @@ int bioem_hip_project_convolve_compare_ctf(bioem_hip_handle h, int iOrientBegin,
   first.push_back(iOrientEnd);
   const int nb = (int) first.size() - 1;
   auto prep = [&](int b) -> int {
-    const int slot = b & 1;
+    bioem_hip_ctx::Slot &bb = h->slot[b & 1];
     const int o0 = first[b];
     const int nO = first[b + 1] - o0;
-    const BatchBuf bb = batch_buf(h, slot);
-    if (h->cmpPending[slot])
+    void_slot(bb);
+    if (bb.cmpPending)
     {
-      HIP_CHECK(h, hipStreamWaitEvent(h->prepStream, h->cmpDone[slot], 0));
-      h->cmpPending[slot] = false;
+      HIP_CHECK(h, hipStreamWaitEvent(h->prepStream, bb.cmpDone, 0));
+      bb.cmpPending = false;
     }
     if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_PROJECTION, o0, o0 + nO, 0, 0) || project_batch(h, bb, h->prepStream, o0, nO) ||
         phase_end(h, h->prepStream))
@@ -1557,27 +1449,29 @@ int bioem_hip_project_convolve_compare_ctf(bioem_hip_handle h, int iOrientBegin,
     if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_CONVOLUTION, o0, o0 + nO, iConvBegin, iConvBegin + nC) ||
         convolve_batch(h, bb, h->prepStream, nO, iConvBegin, nC) || phase_end(h, h->prepStream))
       return 1;
-    HIP_CHECK(h, hipEventRecord(h->prepDone[slot], h->prepStream));
+    HIP_CHECK(h, hipEventRecord(bb.prepDone, h->prepStream));
     return 0;
   };
   // anything still queued on the main stream that uses slot 0/1 buffers (debug hooks, compat entry) goes first
-  HIP_CHECK(h, hipEventRecord(h->cmpDone[0], h->stream));
-  HIP_CHECK(h, hipEventRecord(h->cmpDone[1], h->stream));
-  h->cmpPending[0] = h->cmpPending[1] = true;
+  for (bioem_hip_ctx::Slot &sl : h->slot)
+  {
+    HIP_CHECK(h, hipEventRecord(sl.cmpDone, h->stream));
+    sl.cmpPending = true;
+  }
   if (nb > 0 && prep(0))
     return 1;
   for (int b = 0; b < nb; b++)
   {
-    const int slot = b & 1;
+    bioem_hip_ctx::Slot &bb = h->slot[b & 1];
     const int o0 = first[b];
     const int nO = first[b + 1] - o0;
     if (b + 1 < nb && prep(b + 1))
       return 1;
-    HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->prepDone[slot], 0));
-    if (launch_compare_fold(h, batch_buf(h, slot), nO * nC, o0, iConvBegin, nC))
+    HIP_CHECK(h, hipStreamWaitEvent(h->stream, bb.prepDone, 0));
+    if (launch_compare_fold(h, bb, nO * nC, o0, iConvBegin, nC))
       return 1;
-    HIP_CHECK(h, hipEventRecord(h->cmpDone[slot], h->stream));
-    h->cmpPending[slot] = true;
+    HIP_CHECK(h, hipEventRecord(bb.cmpDone, h->stream));
+    bb.cmpPending = true;
   }
   // later main-stream work (finish_run, debug hooks) must also see prepStream drained: it is, through prepDone
   return 0;
@@ -1587,7 +1481,7 @@ int bioem_hip_project_convolve_compare_ctf(bioem_hip_handle h, int iOrientBegin,
 int bioem_hip_project(bioem_hip_handle h, int iPipeline, int iOrientBegin, int iOrientEnd)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
-  const int slot = iPipeline & 1, nO = iOrientEnd - iOrientBegin;
+  const int nO = iOrientEnd - iOrientBegin;
   if (!h->dPts || iOrientBegin < 0 || iOrientEnd > h->nAnglesUp || nO < 1)
   {
     h->err = "bioem_hip_project: model/orientations not uploaded or range invalid";
@@ -1609,23 +1503,25 @@ int bioem_hip_project(bioem_hip_handle h, int iPipeline, int iOrientBegin, int i
     return 1;
   // the comparison that last read this buffer set goes first (NOT the other set's: that one is what this call overlaps);
   // with none queued, whatever the main stream holds so far (start_run, debug hooks, the compat entry)
-  if (!h->cmpPending[slot])
-    HIP_CHECK(h, hipEventRecord(h->cmpDone[slot], h->stream));
-  HIP_CHECK(h, hipStreamWaitEvent(h->prepStream, h->cmpDone[slot], 0));
-  h->cmpPending[slot] = false;
-  h->stageNO[slot] = h->stageNC[slot] = 0;
+  bioem_hip_ctx::Slot &sl = h->slot[iPipeline & 1];
+  if (!sl.cmpPending)
+    HIP_CHECK(h, hipEventRecord(sl.cmpDone, h->stream));
+  HIP_CHECK(h, hipStreamWaitEvent(h->prepStream, sl.cmpDone, 0));
+  sl.cmpPending = false;
+  void_slot(sl);
   if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_PROJECTION, iOrientBegin, iOrientEnd, 0, 0) ||
-      project_batch(h, batch_buf(h, slot), h->prepStream, iOrientBegin, nO) || phase_end(h, h->prepStream))
+      project_batch(h, sl, h->prepStream, iOrientBegin, nO) || phase_end(h, h->prepStream))
     return 1;
-  h->stageO0[slot] = iOrientBegin;
-  h->stageNO[slot] = nO;
+  sl.stageO0 = iOrientBegin;
+  sl.stageNO = nO;
   return 0;
 }
 
 int bioem_hip_convolve(bioem_hip_handle h, int iPipeline, int iConvBegin, int iConvEnd)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
-  const int slot = iPipeline & 1, nC = iConvEnd - iConvBegin, nO = h->stageNO[slot];
+  bioem_hip_ctx::Slot &sl = h->slot[iPipeline & 1];
+  const int nC = iConvEnd - iConvBegin, nO = sl.stageNO;
   if (nO < 1)
   {
     h->err = "bioem_hip_convolve: no projections in this pipeline slot (call bioem_hip_project first)";
@@ -1638,34 +1534,35 @@ int bioem_hip_convolve(bioem_hip_handle h, int iPipeline, int iConvBegin, int iC
     h->err = buf;
     return 2;
   }
-  if (h->cmpPending[slot])
+  if (sl.cmpPending)
   { // a comparison of this slot's previous conv rows is still queued: it reads what this call overwrites
-    HIP_CHECK(h, hipStreamWaitEvent(h->prepStream, h->cmpDone[slot], 0));
-    h->cmpPending[slot] = false;
+    HIP_CHECK(h, hipStreamWaitEvent(h->prepStream, sl.cmpDone, 0));
+    sl.cmpPending = false;
   }
-  if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_CONVOLUTION, h->stageO0[slot], h->stageO0[slot] + nO, iConvBegin, iConvEnd) ||
-      convolve_batch(h, batch_buf(h, slot), h->prepStream, nO, iConvBegin, nC) || phase_end(h, h->prepStream))
+  if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_CONVOLUTION, sl.stageO0, sl.stageO0 + nO, iConvBegin, iConvEnd) ||
+      convolve_batch(h, sl, h->prepStream, nO, iConvBegin, nC) || phase_end(h, h->prepStream))
     return 1;
-  HIP_CHECK(h, hipEventRecord(h->prepDone[slot], h->prepStream));
-  h->stageC0[slot] = iConvBegin;
-  h->stageNC[slot] = nC;
+  HIP_CHECK(h, hipEventRecord(sl.prepDone, h->prepStream));
+  sl.stageC0 = iConvBegin;
+  sl.stageNC = nC;
   return 0;
 }
 
 int bioem_hip_compare_device(bioem_hip_handle h, int iPipeline)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
-  const int slot = iPipeline & 1, nO = h->stageNO[slot], nC = h->stageNC[slot];
+  bioem_hip_ctx::Slot &sl = h->slot[iPipeline & 1];
+  const int nO = sl.stageNO, nC = sl.stageNC;
   if (nO < 1 || nC < 1)
   {
     h->err = "bioem_hip_compare_device: no conv spectra in this pipeline slot (call bioem_hip_project and bioem_hip_convolve first)";
     return 2;
   }
-  HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->prepDone[slot], 0));
-  if (launch_compare_fold(h, batch_buf(h, slot), nO * nC, h->stageO0[slot], h->stageC0[slot], nC))
+  HIP_CHECK(h, hipStreamWaitEvent(h->stream, sl.prepDone, 0));
+  if (launch_compare_fold(h, sl, nO * nC, sl.stageO0, sl.stageC0, nC))
     return 1;
-  HIP_CHECK(h, hipEventRecord(h->cmpDone[slot], h->stream));
-  h->cmpPending[slot] = true;
+  HIP_CHECK(h, hipEventRecord(sl.cmpDone, h->stream));
+  sl.cmpPending = true;
   return 0;
 }
 
@@ -1791,11 +1688,10 @@ static int topk_device(bioem_hip_ctx *h, int K, double numconst)
   }
   if (h->candK != K)
   {
-    if (h->dCand)
-      hipFree(h->dCand);
-    h->dCand = nullptr;
+    dev_release(h, h->dCand);
     h->candK = 0;
-    HIP_CHECK(h, hipMalloc(&h->dCand, sizeof(bioem_hip_angle_candidate) * (size_t) h->nMaps * K));
+    if (dev_alloc(h, h->dCand, (size_t) h->nMaps * K))
+      return 1;
     h->candK = K;
   }
   const bioem_hip_prob_angle *pang =
@@ -1975,20 +1871,18 @@ int bioem_hip_merge(bioem_hip_handle *handles, int n, void *pProbMaps_host, int 
       return 1;
     if (h->sendBytes < payload)
     {
-      if (h->dSend)
-        hipFree(h->dSend);
-      h->dSend = nullptr;
+      dev_release(h, h->dSend);
       h->sendBytes = 0;
-      HIP_CHECK(h, hipMalloc(&h->dSend, payload));
+      if (dev_alloc(h, h->dSend, payload))
+        return 1;
       h->sendBytes = payload;
     }
     if (h->recvBytes < payload * n)
     {
-      if (h->dRecv)
-        hipFree(h->dRecv);
-      h->dRecv = nullptr;
+      dev_release(h, h->dRecv);
       h->recvBytes = 0;
-      HIP_CHECK(h, hipMalloc(&h->dRecv, payload * n));
+      if (dev_alloc(h, h->dRecv, payload * n))
+        return 1;
       h->recvBytes = payload * n;
     }
     HIP_CHECK(h, hipMemcpyAsync(h->dSend, h->dProb, mapBytes, hipMemcpyDeviceToDevice, h->stream));
@@ -2010,8 +1904,8 @@ int bioem_hip_merge(bioem_hip_handle *handles, int n, void *pProbMaps_host, int 
   RCCL_CHECK(h0, g_rccl.GroupEnd());
   // fold on the first device, result to the host
   HIP_CHECK(h0, hipSetDevice(h0->device));
-  if (!h0->dMerged)
-    HIP_CHECK(h0, hipMalloc(&h0->dMerged, mapBytes));
+  if (!h0->dMerged && dev_alloc(h0, h0->dMerged, nMaps))
+    return 1;
   hipLaunchKernelGGL(k_merge_shards, dim3((nMaps + 127) / 128), dim3(128), 0, h0->stream, h0->dRecv, n, payload, nMaps,
                      h0->dMerged);
   HIP_CHECK(h0, hipGetLastError());
@@ -2045,9 +1939,11 @@ int bioem_hip_merge(bioem_hip_handle *handles, int n, void *pProbMaps_host, int 
 int bioem_hip_debug_projection(bioem_hip_handle h, int iOrient, float *spec_out)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
-  if (project_batch(h, batch_buf(h, 0), h->stream, iOrient, 1))
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  if (project_batch(h, s0, h->stream, iOrient, 1))
     return 1;
-  HIP_CHECK(h, hipMemcpyAsync(spec_out, h->dSpecRef, sizeof(float2) * (size_t) h->M, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipMemcpyAsync(spec_out, s0.specRef, sizeof(float2) * (size_t) h->M, hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(h, hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -2056,18 +1952,20 @@ int bioem_hip_debug_convolution(bioem_hip_handle h, int iOrient, int iConv, floa
                                 float *sumsquareC)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
-  if (project_batch(h, batch_buf(h, 0), h->stream, iOrient, 1))
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  if (project_batch(h, s0, h->stream, iOrient, 1))
     return 1;
-  if (convolve_batch(h, batch_buf(h, 0), h->stream, 1, 0, h->nCTF))
+  if (convolve_batch(h, s0, h->stream, 1, 0, h->nCTF))
     return 1;
   const size_t M = (size_t) h->M;
-  float2 *tmp = h->dSpecRef + M; // chunkB >= 32 slots; slot 0 holds the projection spectrum
-  hipLaunchKernelGGL(k_unreorder, dim3(256), dim3(256), 0, h->stream, h->dConv + h->Mc * (size_t) iConv, tmp, 1, h->N,
-                     h->H, h->fast, h->N1, h->Hp);
+  float2 *tmp = s0.specRef + M; // chunkB >= 32 images; the first holds the projection spectrum
+  hipLaunchKernelGGL(k_unreorder, dim3(256), dim3(256), 0, h->stream, s0.conv + h->Mc * (size_t) iConv, tmp, 1, h->N,
+                     h->H, h->plan.halfR, h->plan.N1, h->Hp);
   HIP_CHECK(h, hipGetLastError());
   HIP_CHECK(h, hipMemcpyAsync(spec_out, tmp, sizeof(float2) * M, hipMemcpyDeviceToHost, h->stream));
   bioem_hip_param5 q;
-  HIP_CHECK(h, hipMemcpyAsync(&q, h->dParams + iConv, sizeof(q), hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipMemcpyAsync(&q, s0.params + iConv, sizeof(q), hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(h, hipStreamSynchronize(h->stream));
   *sumC = q.sumC;
   *sumsquareC = q.sumsquareC;
@@ -2078,13 +1976,15 @@ int bioem_hip_debug_particles(bioem_hip_handle h, float *refFFT_out, float *sum_
 {
   HIP_CHECK(h, hipSetDevice(h->device));
   const size_t M = (size_t) h->M;
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
   for (int b = 0; b < h->nMaps; b += h->chunkB)
   {
     const int n = std::min(h->chunkB, h->nMaps - b);
-    hipLaunchKernelGGL(k_unreorder, dim3(1024), dim3(256), 0, h->stream, h->dRef + h->Mc * (size_t) b, h->dSpecRef, n, h->N,
-                       h->H, h->fast, h->N1, h->Hp);
+    hipLaunchKernelGGL(k_unreorder, dim3(1024), dim3(256), 0, h->stream, h->dRef + h->Mc * (size_t) b, s0.specRef, n, h->N,
+                       h->H, h->plan.halfR, h->plan.N1, h->Hp);
     HIP_CHECK(h, hipGetLastError());
-    HIP_CHECK(h, hipMemcpyAsync(refFFT_out + 2 * M * (size_t) b, h->dSpecRef, sizeof(float2) * M * n,
+    HIP_CHECK(h, hipMemcpyAsync(refFFT_out + 2 * M * (size_t) b, s0.specRef, sizeof(float2) * M * n,
                                 hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
@@ -2120,7 +2020,11 @@ int bioem_hip_reset_kernel_stats(bioem_hip_handle h)
   return 0;
 }
 
-int bioem_hip_uses_fast_path(bioem_hip_handle h) { return h && h->fast ? 1 : 0; }
+int bioem_hip_uses_fast_path(bioem_hip_handle h)
+{ // the families with a register FFT
+  const int f = h ? h->plan.family : KF_GENERIC;
+  return f == KF_FAST || f == KF_FASTM || f == KF_FASTM2 || f == KF_WIDE2 ? 1 : 0;
+}
 
 int bioem_hip_plan(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo, char *signature, int cap)
 {
@@ -2145,15 +2049,16 @@ const char *bioem_hip_kernel_name(bioem_hip_handle h)
     return "";
   if (h->direct)
     return "k_compare_direct";
-  if (h->wide2)
-    return "k_compare_wide2";
-  if (h->fastm2)
-    return "k_compare_fastm2";
-  if (h->fastm)
-    return "k_compare_fastm";
-  if (h->fast)
-    return "k_compare_fast";
-  return h->rowsK ? (h->oddR ? "k_compare_oddfft" : "k_compare_rows") : "k_compare_generic";
+  switch (h->plan.family)
+  {
+  case KF_FAST: return "k_compare_fast";
+  case KF_FASTM: return "k_compare_fastm";
+  case KF_FASTM2: return "k_compare_fastm2";
+  case KF_WIDE2: return "k_compare_wide2";
+  case KF_ODDFFT: return "k_compare_oddfft";
+  case KF_ROWS: return "k_compare_rows";
+  default: return "k_compare_generic";
+  }
 }
 
 const char *bioem_hip_kernel_signature(bioem_hip_handle h)
@@ -2161,28 +2066,10 @@ const char *bioem_hip_kernel_signature(bioem_hip_handle h)
   if (!h)
     return "";
   static thread_local char buf[96];
-  const char *nq = h->nyq ? "true" : "false";
   if (h->direct)
     snprintf(buf, sizeof(buf), "k_compare_direct<3, 8>");
-  else if (h->wide2)
-    if (h->w2Halves == 2)
-      snprintf(buf, sizeof(buf), h->w2NW == 8 ? "k_compare_wide2<%d, %d, %d, %s, 2, 8>" : "k_compare_wide2<%d, %d, %d, %s, 2>",
-               2 * h->fast, h->w2NRW, h->w2NBLK, nq);
-    else
-      snprintf(buf, sizeof(buf), h->w2NW == 8 ? "k_compare_wide2<%d, %d, %d, %s, 1, 8>" : "k_compare_wide2<%d, %d, %d, %s>",
-               2 * h->fast, h->w2NRW, h->w2NBLK, nq);
-  else if (h->fastm2)
-    snprintf(buf, sizeof(buf), "k_compare_fastm2<%d, %s, %d>", 2 * h->fast, nq, h->gs);
-  else if (h->fastm)
-    snprintf(buf, sizeof(buf), "k_compare_fastm<%d, %d, %s, %d>", h->winD, 2 * h->fast, nq, h->gs);
-  else if (h->fast)
-    snprintf(buf, sizeof(buf), "k_compare_fast<%d, %d, %s, %d>", h->winD, 2 * h->fast, nq, h->gs);
-  else if (h->rowsK && h->oddR)
-    snprintf(buf, sizeof(buf), "k_compare_oddfft<%d, %d>", h->winD, h->oddR);
-  else if (h->rowsK)
-    snprintf(buf, sizeof(buf), "k_compare_rows<%d, %d>", h->winD, h->gs);
   else
-    snprintf(buf, sizeof(buf), "k_compare_generic");
+    plan_signature(h->plan, buf, sizeof(buf));
   return buf;
 }
 
@@ -2196,10 +2083,7 @@ int bioem_hip_r2c(int device, int N, int nImg, const float *in, float *out)
   hipDeviceGetAttribute(&nCU, hipDeviceAttributeMultiprocessorCount, device);
   std::vector<double2> twd(N);
   for (int k = 0; k < N; k++)
-  {
-    const double ang = 2.0 * M_PI * (double) k / (double) N;
-    twd[k] = make_double2(cos(ang), sin(ang));
-  }
+    twd[k] = twiddle_d(k, N);
   double2 *dTw = nullptr, *dRow = nullptr;
   float *dIn = nullptr;
   float2 *dOut = nullptr;

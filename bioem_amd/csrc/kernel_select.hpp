@@ -125,11 +125,15 @@ struct KernelPlan
   std::vector<int> disp; // displacement list per axis in the reference's visiting order
   int nd = 0, gs = 1, winD = 0;
   int family = KF_GENERIC;
-  int fast = 0, N1 = 0, oddR = 0; // fast = register-FFT length / 2 (0: no register FFT)
-  bool nyq = false, fastm = false, fastm2 = false, rowsK = false, wide2 = false;
+  int halfR = 0, N1 = 0; // register-FFT length / 2 (0: no register FFT) and N / length
+  int oddR = 0;          // k_compare_oddfft: register-FFT length (3, 5, 9, 15, 25) dividing an odd N
+  bool nyq = false;      // Nyquist column handled outside the 64-column blocks (N / 2 a multiple of 64)
+  int nyqWD = 0;         // window half width of the k_nyquist_rows instantiation that fills it
+  // wide windows no kernel covers: tilesPerAxis^2 launches of a tileT-row window (window_tiles.hpp); per axis tile its
+  // centre (in window rows) and its number of rows inside the window
   int tileT = 0, tilesPerAxis = 1;
   std::vector<int> tileCenter, tileValid;
-  int w2NRW = 0, w2NBLK = 0, w2TS = 0, w2Rows2 = 0, nyqWD = 0, w2Halves = 1, w2NW = 4;
+  int w2NRW = 0, w2NBLK = 0, w2TS = 0, w2Rows2 = 0, w2Halves = 1, w2NW = 4;
   int genericWaves = 4;
   int genericRows = 0; // k_compare_generic: window rows per pass through the LDS (0 = all)
   size_t ldsBytes = 0;
@@ -292,10 +296,9 @@ bool plan_wide2(KernelPlan &P, int N, int H, int mD)
       const fast_kernel_t fn = find_kernel(KF_WIDE2, R, r.nrw, nblk, nyq, halves, r.nw);
       if (!fn)
         continue;
-      P.wide2 = true;
       P.family = KF_WIDE2;
       P.fn = fn;
-      P.fast = R / 2;
+      P.halfR = R / 2;
       P.N1 = N / R;
       P.nyq = nyq;
       P.w2NBLK = nblk;
@@ -305,13 +308,26 @@ bool plan_wide2(KernelPlan &P, int N, int H, int mD)
       P.w2TS = ts;
       P.w2Rows2 = halves == 2 ? hrows : rows2;
       P.nyqWD = mD <= 20 ? 20 : mD <= 31 ? 31 : 42;
-      if (nyq)
-        P.winD = P.nyqWD; // sizes the Nyquist pre-kernel's tables
       P.ldsBytes = wide2_lds_bytes(N, R, P.w2Rows2, ts, r.nw);
       return true;
     }
   }
   return false;
+}
+
+// k_compare_fast / k_compare_fastm with R-point register FFTs over a window of 2 wd + 1 rows; the Nyquist pre-kernel
+// of a split plan runs the same window
+bool take_window(KernelPlan &P, int family, fast_kernel_t fn, int N, int R, bool nyq, int wd, size_t ldsBytes)
+{
+  P.family = family;
+  P.fn = fn;
+  P.halfR = R / 2;
+  P.N1 = N / R;
+  P.nyq = nyq;
+  P.nyqWD = nyq ? wd : 0;
+  P.winD = wd;
+  P.ldsBytes = ldsBytes;
+  return true;
 }
 
 // base kernel of a window of at most 2 winD + 1 rows (also the tile kernel of the tiled path)
@@ -330,17 +346,7 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
       for (int R : lens)
       {
         if (const fast_kernel_t fn = find_kernel(KF_FASTM, winD, R, nyq, P.gs))
-        {
-          P.family = KF_FASTM;
-          P.fastm = true;
-          P.fn = fn;
-          P.fast = R / 2;
-          P.N1 = N / R;
-          P.nyq = nyq;
-          P.winD = winD;
-          P.ldsBytes = fastm_lds_bytes(N);
-          return true;
-        }
+          return take_window(P, KF_FASTM, fn, N, R, nyq, winD, fastm_lds_bytes(N));
       }
       return false;
     }
@@ -355,16 +361,7 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
     {
       const int R = winD == 5 ? 8 : 16;
       if (const fast_kernel_t fn = find_kernel(KF_FAST, winD, R, true, P.gs))
-      {
-        P.family = KF_FAST;
-        P.fn = fn;
-        P.fast = R / 2;
-        P.N1 = N / R;
-        P.nyq = true;
-        P.winD = winD;
-        P.ldsBytes = fast_lds_bytes(N, 2 * winD + 1, 4);
-        return true;
-      }
+        return take_window(P, KF_FAST, fn, N, R, true, winD, fast_lds_bytes(N, 2 * winD + 1, 4));
     }
     std::vector<int> lens;
     if (nyq)
@@ -409,16 +406,7 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
           find_kernel(KF_FAST, 10, R, nyq, P.gs))
         wd = 10;
       if (const fast_kernel_t fn = find_kernel(KF_FAST, wd, R, nyq, P.gs))
-      {
-        P.family = KF_FAST;
-        P.fn = fn;
-        P.fast = R / 2;
-        P.N1 = N / R;
-        P.nyq = nyq;
-        P.winD = wd;
-        P.ldsBytes = fast_lds_bytes(N, 2 * wd + 1, 4);
-        return true;
-      }
+        return take_window(P, KF_FAST, fn, N, R, nyq, wd, fast_lds_bytes(N, 2 * wd + 1, 4));
     }
     return false;
   }
@@ -430,7 +418,6 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
           if (const fast_kernel_t fn = find_kernel(KF_ODDFFT, winD, r))
           {
             P.family = KF_ODDFFT;
-            P.rowsK = true;
             P.oddR = r;
             P.N1 = N / r;
             P.fn = fn;
@@ -441,7 +428,6 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
     if (const fast_kernel_t fn = find_kernel(KF_ROWS, winD, P.gs))
     {
       P.family = KF_ROWS;
-      P.rowsK = true;
       P.fn = fn;
       P.winD = winD;
       P.ldsBytes = fast_lds_bytes(N, 2 * winD + 1, 4);
@@ -513,14 +499,11 @@ KernelPlan plan_kernels(int N, int maxD, int grid, int algo)
       if (!fn)
         continue;
       P.family = KF_FASTM2;
-      P.fastm2 = true;
       P.fn = fn;
-      P.fast = R / 2;
+      P.halfR = R / 2;
       P.N1 = N / R;
       P.nyq = nyq;
       P.nyqWD = mD <= 20 ? 20 : 31;
-      if (nyq)
-        P.winD = P.nyqWD; // sizes the Nyquist pre-kernel's tables
       P.ldsBytes = fastm2_lds_bytes();
       return P;
     }
@@ -561,7 +544,7 @@ KernelPlan plan_kernels(int N, int maxD, int grid, int algo)
   // 4. the direct pruned DFT for what is left (irregular displacement sets beyond 31 rows, N < 8)
   P.family = KF_GENERIC;
   P.fn = find_kernel(KF_GENERIC);
-  P.fast = 0;
+  P.halfR = 0;
   P.N1 = 0;
   P.nyq = false;
   // the window rows pass through the LDS in groups of whole register chunks (16 rows) where they do not fit at once --
@@ -592,14 +575,14 @@ void plan_signature(const KernelPlan &P, char *buf, size_t cap)
   case KF_WIDE2:
     if (P.w2Halves == 2)
       snprintf(buf, cap, P.w2NW == 8 ? "k_compare_wide2<%d, %d, %d, %s, 2, 8>" : "k_compare_wide2<%d, %d, %d, %s, 2>",
-               2 * P.fast, P.w2NRW, P.w2NBLK, nq);
+               2 * P.halfR, P.w2NRW, P.w2NBLK, nq);
     else
       snprintf(buf, cap, P.w2NW == 8 ? "k_compare_wide2<%d, %d, %d, %s, 1, 8>" : "k_compare_wide2<%d, %d, %d, %s>",
-               2 * P.fast, P.w2NRW, P.w2NBLK, nq);
+               2 * P.halfR, P.w2NRW, P.w2NBLK, nq);
     break;
-  case KF_FASTM: snprintf(buf, cap, "k_compare_fastm<%d, %d, %s, %d>", P.winD, 2 * P.fast, nq, P.gs); break;
-  case KF_FASTM2: snprintf(buf, cap, "k_compare_fastm2<%d, %s, %d>", 2 * P.fast, nq, P.gs); break;
-  case KF_FAST: snprintf(buf, cap, "k_compare_fast<%d, %d, %s, %d>", P.winD, 2 * P.fast, nq, P.gs); break;
+  case KF_FASTM: snprintf(buf, cap, "k_compare_fastm<%d, %d, %s, %d>", P.winD, 2 * P.halfR, nq, P.gs); break;
+  case KF_FASTM2: snprintf(buf, cap, "k_compare_fastm2<%d, %s, %d>", 2 * P.halfR, nq, P.gs); break;
+  case KF_FAST: snprintf(buf, cap, "k_compare_fast<%d, %d, %s, %d>", P.winD, 2 * P.halfR, nq, P.gs); break;
   case KF_ODDFFT: snprintf(buf, cap, "k_compare_oddfft<%d, %d>", P.winD, P.oddR); break;
   case KF_ROWS: snprintf(buf, cap, "k_compare_rows<%d, %d>", P.winD, P.gs); break;
   default: snprintf(buf, cap, "k_compare_generic"); break;

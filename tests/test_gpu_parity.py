@@ -164,6 +164,14 @@ def test_staged_device_entries_equal_the_fused_entry(name, split_ctf):
         E2.compare_device(1)
     with pytest.raises(RuntimeError, match="range invalid"):
         E2.project(0, 0, S.nAngles + 1)
+    # the fused entry overwrites both buffer sets: what was staged before it is gone
+    raw_2, _, _ = eng.new_prob_block(S.nMaps, S.nAngles, S.pd.writeAngles)
+    E2.start_run(raw_2)
+    E2.project(0, 0, min(3, S.nAngles))
+    E2.convolve(0, 0, S.nCTF)
+    E2.project_convolve_compare(0, S.nAngles)
+    with pytest.raises(RuntimeError, match="bioem_hip_project and bioem_hip_convolve first"):
+        E2.compare_device(0)
     E2.close()
     E.close()
 
