@@ -40,6 +40,8 @@
 //   posterior.hpp        calc_logpro / calProb semantics (bioem_algorithm.h:18-142)
 //   fold_kernels.hpp     k_fold_wave, k_fold_angles: fold the per-comparison partials into the probability block in the
 //                          reference's (orientation, CTF) order (bioem_algorithm.h:96-123, bioem.cpp:1527-1600)
+//                        k_fold_own, k_fold_own_angles: the same for the own-list pass (one orientation list per particle,
+//                          bioem_hip_compare_own_orientations: the comparison kernels as they are, one launch per particle)
 //   this file            device context, launch logic, the C ABI
 //   kernels_*.hip        one translation unit per comparison-kernel family (the instantiations of kernel_table.inc),
 //                          linked into the same library: kernels_fast, kernels_fastm, kernels_wide2_{short,16,long},
@@ -145,6 +147,14 @@ struct bioem_hip_ctx
   int nCU = 256;   // compute units of the device: size of the resident grids of the preparation kernels
   float4 *dAngles = nullptr;
   int nAnglesUp = 0, isQuat = 1;
+  // one orientation list per particle (bioem_hip_upload_particle_orientations, bioem_hip_compare_own_orientations):
+  // [nMaps][ownK] entries; the all-to-all entries never read this state
+  float4 *dOwnAngles = nullptr;
+  int ownK = 0, ownIsQuat = 1;
+  double ownQuatNormDev = 0.;
+  int ownOB = 0;                       // slots (particle, list entry) per batch of the own-list pass
+  size_t slotImages[2] = {0, 0};       // images the projection buffers of a pipeline slot hold
+  size_t slotRows = 0, partRows = 0;   // rows the conv / params / postc buffers of a slot and dPartials (dTnyq) hold
   float2 *dTw = nullptr;   // N+1 entries exp(+2 pi i k/N), float
   double2 *dTwD = nullptr; // N entries, double
   int *dDisp = nullptr;
@@ -371,7 +381,7 @@ template <int Q>
 void launch_nyquist_rows(bioem_hip_ctx *h, const CompareArgs &aw, int WD, int nOC)
 {
   const int PB = 16 / Q;
-  const dim3 gridq((unsigned) (((size_t) (h->nMaps + PB - 1) / PB) * ((nOC + 15) / 16)));
+  const dim3 gridq((unsigned) (((size_t) (aw.nMaps + PB - 1) / PB) * ((nOC + 15) / 16)));
   switch (WD)
   {
 #define X(W)                                                                                                            \
@@ -384,14 +394,15 @@ void launch_nyquist_rows(bioem_hip_ctx *h, const CompareArgs &aw, int WD, int nO
 }
 void launch_nyquist(bioem_hip_ctx *h, const CompareArgs &aw, int WD, int nOC)
 {
-  if (h->nMaps <= 64)
+  if (aw.nMaps <= 64)
     launch_nyquist_rows<4>(h, aw, WD, nOC);
   else
     launch_nyquist_rows<1>(h, aw, WD, nOC);
 }
 
-int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC, int orient0, int conv0,
-                        int convPerOrient, const int2 *ids = nullptr, const int4 *segs = nullptr, int nSeg = 0)
+// argument block, grid and block of a comparison launch: the nOC conv rows of a slot against nMaps particles (the
+// handle's, or ONE in the own-list pass, whose launches point ref / sumRef / sumsqRef at that particle)
+CompareArgs compare_args(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC, int nMaps, dim3 &grid, dim3 &block)
 {
   const KernelPlan &P = h->plan;
   const int fam = P.family;
@@ -418,7 +429,7 @@ int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC
   a.nd = P.nd;
   a.maxD = h->pd.maxDisplaceCenter;
   a.nOC = nOC;
-  a.nMaps = h->nMaps;
+  a.nMaps = nMaps;
   a.algo = h->algo;
   a.pd = h->pd;
   a.gs = P.gs;
@@ -433,30 +444,40 @@ int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC
     a.split = (fam == KF_FAST || fam == KF_FASTM) && rem <= 32 && P.N1 >= 2 &&
               (P.nyq || !getenv("BIOEM_NO_SPLIT_LAST"));
   }
-  a.pchunk = h->pchunk > 0 ? std::min(h->pchunk, h->nMaps) : h->nMaps;
+  a.pchunk = h->pchunk > 0 ? std::min(h->pchunk, nMaps) : nMaps;
   if (a.pchunk >= 8) // a multiple of 8: a particle then stays on one XCD (65 particles: chunks of 64 + 1, 43.6 -> 45.3 M/s)
     a.pchunk &= ~7;
   const int ocGroups = (nOC + 3) / 4;
   // few particles, k_compare_fast / _fastm / _fastm2: whole groups per XCD (fast_block_pair); the grid is padded to a
   // multiple of 8 groups (measured for 65...200 particles as well: 1-3 % slower than the chunk order there)
-  const bool groupPerXcd = h->nMaps <= 64 && (fam == KF_FAST || fam == KF_FASTM || fam == KF_FASTM2);
+  const bool groupPerXcd = nMaps <= 64 && (fam == KF_FAST || fam == KF_FASTM || fam == KF_FASTM2);
   if (groupPerXcd)
     a.pchunk = -1;
   // launch geometry by family: four comparisons per 256-thread block, except k_compare_wide2 (one block of w2NW waves
   // per comparison) and k_compare_generic (genericWaves comparisons per block)
-  dim3 grid((unsigned) ((size_t) (groupPerXcd ? (ocGroups + 7) / 8 * 8 : ocGroups) * h->nMaps)), block(256);
+  grid = dim3((unsigned) ((size_t) (groupPerXcd ? (ocGroups + 7) / 8 * 8 : ocGroups) * nMaps));
+  block = dim3(256);
   if (fam == KF_WIDE2)
   {
     a.ts = P.w2TS;
-    grid = dim3((unsigned) ((size_t) nOC * h->nMaps));
+    grid = dim3((unsigned) ((size_t) nOC * nMaps));
     block = dim3(64 * P.w2NW);
   }
   else if (fam == KF_GENERIC)
   {
     a.ts = P.genericRows;
-    grid = dim3((unsigned) ((size_t) ((nOC + P.genericWaves - 1) / P.genericWaves) * h->nMaps));
+    grid = dim3((unsigned) ((size_t) ((nOC + P.genericWaves - 1) / P.genericWaves) * nMaps));
     block = dim3(64 * P.genericWaves);
   }
+  return a;
+}
+
+int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC, int orient0, int conv0,
+                        int convPerOrient, const int2 *ids = nullptr, const int4 *segs = nullptr, int nSeg = 0)
+{
+  const KernelPlan &P = h->plan;
+  dim3 grid, block;
+  const CompareArgs a = compare_args(h, bb, nOC, h->nMaps, grid, block);
   auto launch = [&](const CompareArgs &aw) {
     if (P.nyq)
       launch_nyquist(h, aw, P.nyqWD, nOC);
@@ -547,6 +568,72 @@ int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC
                        pmap);
   HIP_CHECK(h, hipGetLastError());
   if (phase_end(h, h->stream)) // comparison = the kernels of the launch and the fold behind them (what compareRefMaps does)
+    return 1;
+  if (h->evPending.size() > 512)
+    drain_events(h);
+  return 0;
+}
+
+// Own-list pass: the nOC conv rows of the slot are rows [slot0 nC, ...) of the flat [particle][list entry][CTF] order;
+// every row is compared with its own particle and each particle's rows are folded into its entry.  The comparison
+// kernels are launched as they are, once per particle with rows in the slot: a launch over that particle's run of
+// rows with nMaps = 1, ref / sumRef / sumsqRef pointed at the particle and conv / params / postc / partials / tnyq at the
+// run -- exactly the launch a handle that holds that particle alone makes (its block order, its k_nyquist_rows).  Row oc
+// of the slot leaves its result in partials[oc].
+int launch_compare_own(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC, int slot0, int nC)
+{
+  const KernelPlan &P = h->plan;
+  const int R = h->ownK * nC, row0 = slot0 * nC;
+  hipEvent_t e0 = get_event(h), e1 = get_event(h);
+  if (!e0 || !e1)
+  {
+    if (e0)
+      h->evPool.push_back(e0);
+    if (e1)
+      h->evPool.push_back(e1);
+    h->err = "hipEventCreate failed";
+    return 1;
+  }
+  const int nSlots = nOC / nC;
+  hipLaunchKernelGGL(k_posterior_consts, dim3((nOC + 63) / 64), dim3(64), 0, h->stream, bb.params, h->pd, bb.postc, nOC);
+  HIP_CHECK(h, hipEventRecord(e0, h->stream));
+  if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, slot0, slot0 + nSlots, 0, nC))
+    return 1;
+  const int pFirst = slot0 / h->ownK, pEnd = (slot0 + nSlots + h->ownK - 1) / h->ownK;
+  for (int p = pFirst; p < pEnd; p++)
+  {
+    const long long g0 = (long long) p * R;
+    const int rb = (int) (std::max<long long>(g0, row0) - row0), n = (int) (std::min<long long>(g0 + R, row0 + nOC) - row0) - rb;
+    dim3 grid, block;
+    CompareArgs a = compare_args(h, bb, n, 1, grid, block);
+    a.ref += (size_t) p * h->Mc;
+    a.sumRef += p;
+    a.sumsqRef += p;
+    a.conv += (size_t) rb * h->Mc;
+    a.params += rb;
+    a.postc += rb;
+    a.partials += rb;
+    if (P.nyq)
+    {
+      a.tnyq += (size_t) rb * (2 * P.nyqWD + 1);
+      launch_nyquist(h, a, P.nyqWD, n);
+    }
+    hipLaunchKernelGGL(P.fn, grid, block, P.ldsBytes, h->stream, a);
+  }
+  HIP_CHECK(h, hipGetLastError());
+  HIP_CHECK(h, hipEventRecord(e1, h->stream));
+  h->evPending.push_back({e0, e1});
+  h->launches++;
+  h->comparisons += nOC;
+  bioem_hip_prob_map *pmap = reinterpret_cast<bioem_hip_prob_map *>(h->dProb);
+  bioem_hip_prob_angle *pang = reinterpret_cast<bioem_hip_prob_angle *>(h->dProb + sizeof(bioem_hip_prob_map) * h->nMaps);
+  if (h->pd.writeAngles)
+    hipLaunchKernelGGL(k_fold_own_angles, dim3((nSlots + 255) / 256), dim3(256), 0, h->stream, h->dPartials, nSlots, slot0,
+                       h->ownK, nC, h->nMaps, pang);
+  hipLaunchKernelGGL(k_fold_own, dim3((pEnd - pFirst + 3) / 4), dim3(256), 0, h->stream, h->dPartials, nOC, row0, R,
+                     nC, pFirst, pEnd, bb.params, h->dSumRef, h->dDisp, P.nd, h->pd, pmap);
+  HIP_CHECK(h, hipGetLastError());
+  if (phase_end(h, h->stream))
     return 1;
   if (h->evPending.size() > 512)
     drain_events(h);
@@ -685,7 +772,17 @@ int run_r2c(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, con
   return 0;
 }
 
-int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, int o0, int nO)
+// the orientation list a projection reads: the shared one, or the per-particle lists as one flat list of slots
+struct OrientList
+{
+  const float4 *d;
+  int isQuat;
+  double quatNormDev;
+};
+OrientList shared_list(const bioem_hip_ctx *h) { return {h->dAngles, h->isQuat, h->quatNormDev}; }
+OrientList own_list(const bioem_hip_ctx *h) { return {h->dOwnAngles, h->ownIsQuat, h->ownQuatNormDev}; }
+
+int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, const OrientList &L, int o0, int nO)
 {
   const int N = h->N;
   // the pixels a point of the model can reach in any orientation, with its footprint: a box around the map centre
@@ -696,14 +793,14 @@ int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t s
   // (orientations that stretch the model -- quaternions that are not of unit length -- take the band kernel: the box
   // has one pixel of margin; the matrix entries of a quaternion with |q|^2 = 1 + e are off by at most ~3 e, and half a
   // pixel is granted to that)
-  const bool keepLength = h->quatNormDev * 4.0 * std::max(1.0, reach) < 0.5;
+  const bool keepLength = L.quatNormDev * 4.0 * std::max(1.0, reach) < 0.5;
   if (h->dStamp && boxSide >= 1 && (size_t) boxSide * boxSide * sizeof(double) <= 52 * 1024 && N < 32768 &&
       keepLength)
   {
     // with the fast r2c behind it the kernel stores the box alone and the transform skips everything outside it
     const int compact = r2c_use_fft(N);
     hipLaunchKernelGGL(k_project_box, dim3(std::min(nO, 3 * h->nCU)), dim3(256), sizeof(double) * boxSide * boxSide, st,
-                       h->dPts, h->nPts, h->dAngles, o0, h->isQuat, N, h->pixelSize, h->shiftX, h->shiftY, h->iradMax,
+                       h->dPts, h->nPts, L.d, o0, L.isQuat, N, h->pixelSize, h->shiftX, h->shiftY, h->iradMax,
                        h->dStamp, boxLo, boxSide, nO, compact, bb.projReal, bb.tempDen);
     HIP_CHECK(h, hipGetLastError());
     return compact ? run_r2c(h, bb, st, bb.projReal, nullptr, nO, boxLo, boxSide) : run_r2c(h, bb, st, bb.projReal, nullptr, nO);
@@ -715,8 +812,8 @@ int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t s
   if (TR >= 12 && h->iradMax <= 16 && h->dStamp && N < 32768 && coordsFit)
   {
     ProjectRecord *coords = reinterpret_cast<ProjectRecord *>(bb.rowSpec);
-    hipLaunchKernelGGL(k_project_coords, dim3((h->nPts + 255) / 256, nO), dim3(256), 0, st, h->dPts, h->nPts, h->dAngles,
-                       o0, h->isQuat, N, h->pixelSize, h->shiftX, h->shiftY, coords);
+    hipLaunchKernelGGL(k_project_coords, dim3((h->nPts + 255) / 256, nO), dim3(256), 0, st, h->dPts, h->nPts, L.d,
+                       o0, L.isQuat, N, h->pixelSize, h->shiftX, h->shiftY, coords);
     const int units = ((N + TR - 1) / TR) * nO;
     hipLaunchKernelGGL(k_project_bands, dim3(std::min(units, 3 * h->nCU)), dim3(256), sizeof(double) * TR * N, st, coords,
                        h->nPts, nO, N, TR, h->iradMax, h->dStamp, bb.projReal, bb.tempDen);
@@ -724,8 +821,8 @@ int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t s
   else
   {
     HIP_CHECK(h, hipMemsetAsync(bb.projReal, 0, sizeof(double) * (size_t) nO * N * N, st));
-    hipLaunchKernelGGL(k_project, dim3((h->nPts + 255) / 256, nO), dim3(256), 0, st, h->dPts, h->nPts, h->dAngles, o0,
-                       h->isQuat, N, h->pixelSize, h->shiftX, h->shiftY, bb.projReal, bb.tempDen);
+    hipLaunchKernelGGL(k_project, dim3((h->nPts + 255) / 256, nO), dim3(256), 0, st, h->dPts, h->nPts, L.d, o0,
+                       L.isQuat, N, h->pixelSize, h->shiftX, h->shiftY, bb.projReal, bb.tempDen);
   }
   HIP_CHECK(h, hipGetLastError());
   return run_r2c(h, bb, st, bb.projReal, nullptr, nO);
@@ -795,14 +892,16 @@ int compat_flush(bioem_hip_ctx *h)
 }
 
 // conv spectra of CTFs [c0, c0 + nC) of the nO projected orientations, row ob * nC + (c - c0)
-int convolve_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, int nO, int c0, int nC)
+int convolve_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, int nO, int c0, int nC, bool own = false)
 {
   // few particles: the preparation is the longer half of the pipeline and the fused kernel shortens it; many particles:
   // it hides behind the comparison either way, and the one-wave blocks of k_parseval_ordered take less from the
   // comparison kernel than the 16-wave blocks of k_convolve_sums (round 4, the fused kernel with 3-4 orientations per
   // block: 65...200 particles +1...3 %, 400 particles equal, 1 000 particles 52.5 against 53.4 M comparisons/s)
   const char *fe = getenv("BIOEM_CONVOLVE_FUSED");
-  if (fe ? atoi(fe) != 0 : h->nMaps <= 256)
+  // (the own-list pass: a conv spectrum meets one particle, the preparation is the long pole whatever nMaps is, and its
+  // batches hold no buffer for the ordered sums of the two-kernel path -- always fused)
+  if (own || (fe ? atoi(fe) != 0 : h->nMaps <= 256))
   {
     // chains on the lanes of the adding wave: 4 orientations x up to 4 CTFs, 3 x 5, or 3 x 6 per block (16, 15, 18
     // products per producing thread and tile: more, and the producers -- ~25 vector instructions per product -- take
@@ -827,6 +926,57 @@ int convolve_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t 
   hipLaunchKernelGGL(k_parseval_ordered, dim3((nC * nO + 3) / 4), dim3(64), 0, st, bb.scratch, (int) h->M, M4, nC * nO,
                      (float) (h->N * h->N), bb.params);
   HIP_CHECK(h, hipGetLastError());
+  return 0;
+}
+
+// the two-slot pipeline of the fused entries: projection + convolution of batch b + 1 run on prepStream while batch b is
+// compared.  first = first orientation of every batch, and the end; own: the orientations are slots (particle, list
+// entry) of the per-particle lists and every conv row meets its own particle only (launch_compare_own).
+int run_pipeline(bioem_hip_ctx *h, const std::vector<int> &first, int iConvBegin, int nC, bool own)
+{
+  const OrientList L = own ? own_list(h) : shared_list(h);
+  const int nb = (int) first.size() - 1;
+  auto prep = [&](int b) -> int {
+    bioem_hip_ctx::Slot &bb = h->slot[b & 1];
+    const int o0 = first[b];
+    const int nO = first[b + 1] - o0;
+    void_slot(bb);
+    if (bb.cmpPending)
+    {
+      HIP_CHECK(h, hipStreamWaitEvent(h->prepStream, bb.cmpDone, 0));
+      bb.cmpPending = false;
+    }
+    if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_PROJECTION, o0, o0 + nO, 0, 0) ||
+        project_batch(h, bb, h->prepStream, L, o0, nO) || phase_end(h, h->prepStream))
+      return 1;
+    if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_CONVOLUTION, o0, o0 + nO, iConvBegin, iConvBegin + nC) ||
+        convolve_batch(h, bb, h->prepStream, nO, iConvBegin, nC, own) || phase_end(h, h->prepStream))
+      return 1;
+    HIP_CHECK(h, hipEventRecord(bb.prepDone, h->prepStream));
+    return 0;
+  };
+  // anything still queued on the main stream that uses slot 0/1 buffers (debug hooks, compat entry) goes first
+  for (bioem_hip_ctx::Slot &sl : h->slot)
+  {
+    HIP_CHECK(h, hipEventRecord(sl.cmpDone, h->stream));
+    sl.cmpPending = true;
+  }
+  if (nb > 0 && prep(0))
+    return 1;
+  for (int b = 0; b < nb; b++)
+  {
+    bioem_hip_ctx::Slot &bb = h->slot[b & 1];
+    const int o0 = first[b];
+    const int nO = first[b + 1] - o0;
+    if (b + 1 < nb && prep(b + 1))
+      return 1;
+    HIP_CHECK(h, hipStreamWaitEvent(h->stream, bb.prepDone, 0));
+    if (own ? launch_compare_own(h, bb, nO * nC, o0, nC) : launch_compare_fold(h, bb, nO * nC, o0, iConvBegin, nC))
+      return 1;
+    HIP_CHECK(h, hipEventRecord(bb.cmpDone, h->stream));
+    bb.cmpPending = true;
+  }
+  // later main-stream work (finish_run, debug hooks) must also see prepStream drained: it is, through prepDone
   return 0;
 }
 
@@ -998,7 +1148,10 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
       return 1;
     HIP_CHECK(h, hipEventCreateWithFlags(&sl.prepDone, hipEventDisableTiming));
     HIP_CHECK(h, hipEventCreateWithFlags(&sl.cmpDone, hipEventDisableTiming));
+    h->slotImages[k] = nImg;
   }
+  h->slotRows = (size_t) h->maxOC;
+  h->partRows = (size_t) nMaps * h->maxOC;
   if (h->direct)
   {
     if (dev_alloc(h, h->dMapsReal, (size_t) nMaps * N * N) || dev_alloc(h, h->dConvReal, (size_t) h->maxOC * N * N) ||
@@ -1297,6 +1450,165 @@ int bioem_hip_upload_orientations(bioem_hip_handle h, const float *angles4, int 
   return 0;
 }
 
+int bioem_hip_upload_particle_orientations(bioem_hip_handle h, const float *angles4, int K, int isQuat)
+{
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const KernelPlan &P = h->plan;
+  if (P.tileT || h->direct || h->shard)
+  {
+    h->err = P.tileT    ? "upload_particle_orientations: the own-list pass does not take tiled wide windows"
+             : h->direct ? "upload_particle_orientations: the own-list pass does not take BIOEM_CC_DIRECT handles"
+                         : "upload_particle_orientations: the own-list pass does not take shard handles";
+    return 2;
+  }
+  if (!angles4 || K < 1 || K > h->nAngles)
+  {
+    h->err = "upload_particle_orientations: need 1 <= K <= nAngles of the handle";
+    return 2;
+  }
+  const long long nSlots = (long long) h->nMaps * K;
+  if (nSlots * h->nCTF > 0x7fffffffLL)
+  {
+    h->err = "upload_particle_orientations: more than 2^31 (particle, list entry, CTF) rows";
+    return 2;
+  }
+  // slots per batch: the preparation is the long pole of this pass (a conv spectrum meets ONE particle), so a batch
+  // holds up to 1 024 slots (conv buffer <= 1 GiB per pipeline slot) whatever the all-to-all batch of the handle is
+  const long long convCap = (long long) ((size_t) (1024u << 20) / (h->Mc * sizeof(float2))) / h->nCTF;
+  const int ownOB = (int) std::min<long long>(nSlots, std::max<long long>(h->OB, std::min<long long>(1024, convCap)));
+  const size_t rows = (size_t) ownOB * h->nCTF, M = (size_t) h->M, N = (size_t) h->N;
+  // nothing queued may still use the buffers that are replaced
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  // grow what is too small: every new buffer first, the old ones go when all of them exist -- a failed allocation
+  // (return 1) leaves the handle as it was
+  {
+    struct Grown
+    {
+      double *projReal = nullptr, *tempDen = nullptr;
+      double2 *rowSpec = nullptr, *postc = nullptr;
+      float2 *specRef = nullptr, *conv = nullptr;
+      bioem_hip_param5 *params = nullptr;
+    } g[2];
+    Partial *partials = nullptr;
+    float *tnyq = nullptr;
+    const bool growRows = h->slotRows < rows, growPart = h->partRows < rows;
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; k++)
+    {
+      if (h->slotImages[k] < (size_t) ownOB)
+        ok = !dev_alloc(h, g[k].projReal, (size_t) ownOB * N * N) && !dev_alloc(h, g[k].tempDen, (size_t) ownOB) &&
+             !dev_alloc(h, g[k].rowSpec, (size_t) ownOB * M) && !dev_alloc(h, g[k].specRef, (size_t) ownOB * M);
+      if (ok && growRows)
+        ok = !dev_alloc(h, g[k].conv, rows * h->Mc) && !dev_alloc(h, g[k].params, rows) && !dev_alloc(h, g[k].postc, rows);
+    }
+    if (ok && growPart)
+      ok = !dev_alloc(h, partials, rows) && (!P.nyq || !dev_alloc(h, tnyq, rows * (size_t) (2 * P.nyqWD + 1)));
+    if (!ok)
+    {
+      for (Grown &x : g)
+      {
+        dev_release(h, x.projReal);
+        dev_release(h, x.tempDen);
+        dev_release(h, x.rowSpec);
+        dev_release(h, x.specRef);
+        dev_release(h, x.conv);
+        dev_release(h, x.params);
+        dev_release(h, x.postc);
+      }
+      dev_release(h, partials);
+      dev_release(h, tnyq);
+      return 1;
+    }
+    for (int k = 0; k < 2; k++)
+    {
+      bioem_hip_ctx::Slot &sl = h->slot[k];
+      if (g[k].projReal)
+      {
+        void_slot(sl);
+        dev_release(h, sl.projReal);
+        dev_release(h, sl.tempDen);
+        dev_release(h, sl.rowSpec);
+        dev_release(h, sl.specRef);
+        sl.projReal = g[k].projReal;
+        sl.tempDen = g[k].tempDen;
+        sl.rowSpec = g[k].rowSpec;
+        sl.specRef = g[k].specRef;
+        h->slotImages[k] = (size_t) ownOB;
+      }
+      if (g[k].conv)
+      {
+        void_slot(sl);
+        dev_release(h, sl.conv);
+        dev_release(h, sl.params);
+        dev_release(h, sl.postc);
+        sl.conv = g[k].conv;
+        sl.params = g[k].params;
+        sl.postc = g[k].postc;
+      }
+    }
+    if (growRows)
+      h->slotRows = rows;
+    if (growPart)
+    { // (one partial, one set of Nyquist rows per conv row in this pass)
+      dev_release(h, h->dPartials);
+      dev_release(h, h->dTnyq);
+      h->dPartials = partials;
+      h->dTnyq = tnyq;
+      h->partRows = rows;
+    }
+  }
+  if (h->ownK != K)
+  {
+    float4 *lists = nullptr;
+    if (dev_alloc(h, lists, (size_t) nSlots))
+      return 1;
+    dev_release(h, h->dOwnAngles);
+    h->dOwnAngles = lists;
+    h->ownK = 0;
+  }
+  HIP_CHECK(h, hipMemcpy(h->dOwnAngles, angles4, sizeof(float4) * (size_t) nSlots, hipMemcpyHostToDevice));
+  h->ownK = K;
+  h->ownOB = ownOB;
+  h->ownIsQuat = isQuat;
+  h->ownQuatNormDev = 0.; // (see bioem_hip_upload_orientations)
+  if (isQuat)
+    for (long long k = 0; k < nSlots; k++)
+    {
+      const float *q = angles4 + 4 * (size_t) k;
+      const double n2 = (double) q[0] * q[0] + (double) q[1] * q[1] + (double) q[2] * q[2] + (double) q[3] * q[3];
+      const double dev = std::fabs(n2 - 1.0);
+      h->ownQuatNormDev = dev == dev ? std::max(h->ownQuatNormDev, dev) : 1e30;
+    }
+  return 0;
+}
+
+int bioem_hip_compare_own_orientations(bioem_hip_handle h, int iMapBegin, int iMapEnd)
+{
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (!h->dOwnAngles || h->ownK < 1)
+  {
+    h->err = "compare_own_orientations: no per-particle orientation lists (bioem_hip_upload_particle_orientations)";
+    return 2;
+  }
+  if (!h->dPts || iMapBegin < 0 || iMapEnd > h->nMaps || iMapBegin > iMapEnd)
+  {
+    h->err = "compare_own_orientations: model not uploaded or particle range invalid";
+    return 2;
+  }
+  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
+    return 1;
+  // batches of slots (particle, list entry): at most ownOB, at least six per call where that leaves 64 or more per
+  // batch (the first batch's preparation hides behind nothing), of equal size
+  const long long s0 = (long long) iMapBegin * h->ownK, s1 = (long long) iMapEnd * h->ownK;
+  const int per = (int) std::min<long long>(h->ownOB, std::max<long long>(64, (s1 - s0 + 5) / 6));
+  std::vector<int> first;
+  for (long long s = s0; s < s1; s += per)
+    first.push_back((int) s);
+  first.push_back((int) s1);
+  return run_pipeline(h, first, 0, h->nCTF, true);
+}
+
 void *bioem_hip_host_alloc(size_t size)
 {
   void *p = nullptr;
@@ -1432,49 +1744,7 @@ int bioem_hip_project_convolve_compare_ctf(bioem_hip_handle h, int iOrientBegin,
   for (int o = iOrientBegin; o < iOrientEnd; o += OBc)
     first.push_back(o);
   first.push_back(iOrientEnd);
-  const int nb = (int) first.size() - 1;
-  auto prep = [&](int b) -> int {
-    bioem_hip_ctx::Slot &bb = h->slot[b & 1];
-    const int o0 = first[b];
-    const int nO = first[b + 1] - o0;
-    void_slot(bb);
-    if (bb.cmpPending)
-    {
-      HIP_CHECK(h, hipStreamWaitEvent(h->prepStream, bb.cmpDone, 0));
-      bb.cmpPending = false;
-    }
-    if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_PROJECTION, o0, o0 + nO, 0, 0) || project_batch(h, bb, h->prepStream, o0, nO) ||
-        phase_end(h, h->prepStream))
-      return 1;
-    if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_CONVOLUTION, o0, o0 + nO, iConvBegin, iConvBegin + nC) ||
-        convolve_batch(h, bb, h->prepStream, nO, iConvBegin, nC) || phase_end(h, h->prepStream))
-      return 1;
-    HIP_CHECK(h, hipEventRecord(bb.prepDone, h->prepStream));
-    return 0;
-  };
-  // anything still queued on the main stream that uses slot 0/1 buffers (debug hooks, compat entry) goes first
-  for (bioem_hip_ctx::Slot &sl : h->slot)
-  {
-    HIP_CHECK(h, hipEventRecord(sl.cmpDone, h->stream));
-    sl.cmpPending = true;
-  }
-  if (nb > 0 && prep(0))
-    return 1;
-  for (int b = 0; b < nb; b++)
-  {
-    bioem_hip_ctx::Slot &bb = h->slot[b & 1];
-    const int o0 = first[b];
-    const int nO = first[b + 1] - o0;
-    if (b + 1 < nb && prep(b + 1))
-      return 1;
-    HIP_CHECK(h, hipStreamWaitEvent(h->stream, bb.prepDone, 0));
-    if (launch_compare_fold(h, bb, nO * nC, o0, iConvBegin, nC))
-      return 1;
-    HIP_CHECK(h, hipEventRecord(bb.cmpDone, h->stream));
-    bb.cmpPending = true;
-  }
-  // later main-stream work (finish_run, debug hooks) must also see prepStream drained: it is, through prepDone
-  return 0;
+  return run_pipeline(h, first, iConvBegin, nC, false);
 }
 
 // ---- the three stages of the loop body as separate, asynchronous, batched entries (device-resident hand-over) ----
@@ -1510,7 +1780,7 @@ int bioem_hip_project(bioem_hip_handle h, int iPipeline, int iOrientBegin, int i
   sl.cmpPending = false;
   void_slot(sl);
   if (phase_begin(h, h->prepStream, BIOEM_HIP_PHASE_PROJECTION, iOrientBegin, iOrientEnd, 0, 0) ||
-      project_batch(h, sl, h->prepStream, iOrientBegin, nO) || phase_end(h, h->prepStream))
+      project_batch(h, sl, h->prepStream, shared_list(h), iOrientBegin, nO) || phase_end(h, h->prepStream))
     return 1;
   sl.stageO0 = iOrientBegin;
   sl.stageNO = nO;
@@ -1941,7 +2211,7 @@ int bioem_hip_debug_projection(bioem_hip_handle h, int iOrient, float *spec_out)
   HIP_CHECK(h, hipSetDevice(h->device));
   bioem_hip_ctx::Slot &s0 = h->slot[0];
   void_slot(s0);
-  if (project_batch(h, s0, h->stream, iOrient, 1))
+  if (project_batch(h, s0, h->stream, shared_list(h), iOrient, 1))
     return 1;
   HIP_CHECK(h, hipMemcpyAsync(spec_out, s0.specRef, sizeof(float2) * (size_t) h->M, hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(h, hipStreamSynchronize(h->stream));
@@ -1954,7 +2224,7 @@ int bioem_hip_debug_convolution(bioem_hip_handle h, int iOrient, int iConv, floa
   HIP_CHECK(h, hipSetDevice(h->device));
   bioem_hip_ctx::Slot &s0 = h->slot[0];
   void_slot(s0);
-  if (project_batch(h, s0, h->stream, iOrient, 1))
+  if (project_batch(h, s0, h->stream, shared_list(h), iOrient, 1))
     return 1;
   if (convolve_batch(h, s0, h->stream, 1, 0, h->nCTF))
     return 1;

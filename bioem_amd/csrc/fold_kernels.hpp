@@ -153,6 +153,105 @@ __global__ __launch_bounds__(256) void k_fold_wave(const Partial *__restrict__ p
 }
 
 // ------------------------------------------------------------------------------------------------
+// own-list pass (bioem_hip_compare_own_orientations): row oc of a launch is row row0 + oc of the flat
+// [particle][list entry k][CTF] order (R = K * nCTF rows per particle) and was compared with its own particle only;
+// partials[oc] is its result.  One wave per particle with rows in the launch folds exactly those rows, by the rules of
+// k_fold_wave (first maximum = lowest row, log-sum-exp in double, norm / mu from the best row); max_prob_orient is the
+// index in that particle's list.  A list that straddles two launches is folded in two steps, like two batches of the
+// all-to-all pass.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fold_own(const Partial *__restrict__ partials, int nOC, int row0, int R, int nCTF,
+                                                  int pFirst, int pEnd, const bioem_hip_param5 *__restrict__ params,
+                                                  const float *__restrict__ sumRef, const int *__restrict__ disp, int nd,
+                                                  PD pd, bioem_hip_prob_map *__restrict__ pmap)
+{
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int p = pFirst + blockIdx.x * 4 + wave;
+  if (p >= pEnd)
+    return;
+  const long long g0 = (long long) p * R; // first row of the particle in the flat order
+  const int rb = (int) (max(g0, (long long) row0) - row0), re = (int) (min(g0 + R, (long long) row0 + nOC) - row0);
+  const int chunk = (re - rb + 63) / 64;
+  const int b = min(re, rb + lane * chunk), e = min(re, b + chunk);
+  double m = -INFINITY, sacc = 0.;
+  int idx = 0x7fffffff;
+#pragma unroll 4
+  for (int oc = b; oc < e; oc++)
+  {
+    const Partial r = partials[oc];
+    const double lp = (double) r.best;
+    if (m < lp)
+    {
+      sacc = (m == -INFINITY) ? 0. : sacc * exp(m - lp);
+      m = lp;
+      idx = oc;
+    }
+    sacc += r.sumExp * exp(lp - m);
+  }
+  for (int off = 32; off > 0; off >>= 1)
+  {
+    const double m2 = __shfl_xor(m, off);
+    const double s2 = __shfl_xor(sacc, off);
+    const int i2 = __shfl_xor(idx, off);
+    if (m2 > m || (m2 == m && i2 < idx))
+    {
+      sacc = ((m == -INFINITY) ? 0. : sacc * exp(m - m2)) + s2;
+      m = m2;
+      idx = i2;
+    }
+    else
+      sacc += (m2 == -INFINITY) ? 0. : s2 * exp(m2 - m);
+  }
+  if (lane == 0 && idx != 0x7fffffff)
+  {
+    bioem_hip_prob_map pm = pmap[p];
+    if (pm.Constoadd < m)
+    {
+      pm.Total *= exp(-m + pm.Constoadd);
+      pm.Constoadd = m;
+      const Partial r = partials[idx];
+      const int ix = r.id / nd, iy = r.id - ix * nd;
+      const int local = (int) ((long long) row0 + idx - g0); // k * nCTF + CTF
+      pm.max_prob_cent_x = -disp[ix];
+      pm.max_prob_cent_y = -disp[iy];
+      pm.max_prob_orient = local / nCTF;
+      pm.max_prob_conv = local % nCTF;
+      const bioem_hip_param5 q = params[idx];
+      const float sumref = sumRef[p];
+      const float value = r.value;
+      pm.max_prob_norm = -(-q.sumC * sumref + pd.Ntotpi * value) / (q.sumC * q.sumC - q.sumsquareC * pd.Ntotpi);
+      pm.max_prob_mu = -(-q.sumC * value + q.sumsquareC * sumref) / (q.sumC * q.sumC - q.sumsquareC * pd.Ntotpi);
+    }
+    pm.Total += sacc * exp(m - pm.Constoadd);
+    pmap[p] = pm;
+  }
+}
+
+// WRITE_PROB_ANGLES of the own-list pass: one thread per slot (particle p, list entry k) of the launch folds the slot's
+// CTF rows, in CTF order, into entry (k, p) of the [nAngles][nMaps] table -- the arithmetic of k_fold_angles.
+__global__ void k_fold_own_angles(const Partial *__restrict__ partials, int nSlots, int slot0, int K, int nCTF, int nMaps,
+                                  bioem_hip_prob_angle *__restrict__ pang)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nSlots)
+    return;
+  const int s = slot0 + t, p = s / K, k = s - p * K;
+  bioem_hip_prob_angle pa = pang[(size_t) k * nMaps + p];
+  for (int oc = t * nCTF; oc < (t + 1) * nCTF; oc++)
+  {
+    const Partial r = partials[oc];
+    const double lp = (double) r.best;
+    if (pa.ConstAngle < lp)
+    {
+      pa.forAngles *= exp(-lp + pa.ConstAngle);
+      pa.ConstAngle = lp;
+    }
+    pa.forAngles += r.sumExp * exp(lp - pa.ConstAngle);
+  }
+  pang[(size_t) k * nMaps + p] = pa;
+}
+
+// ------------------------------------------------------------------------------------------------
 // shard handles: the angle table never leaves the device
 // ------------------------------------------------------------------------------------------------
 __global__ void k_init_angles(bioem_hip_prob_angle *__restrict__ pang, size_t n)

@@ -61,6 +61,11 @@ def load_library():
     L.bioem_hip_upload_ctf.argtypes = [vp, vp, vp]
     L.bioem_hip_upload_model.argtypes = [vp, vp, ci, cf, cf, ci, ci]
     L.bioem_hip_upload_orientations.argtypes = [vp, vp, ci, ci]
+    # (a build from before these two entries, loaded through BIOEM_HIP_LIBRARY as the other side of an A/B run, still
+    # serves every other entry; the Engine methods that need them raise AttributeError on it)
+    if hasattr(L, "bioem_hip_upload_particle_orientations"):
+        L.bioem_hip_upload_particle_orientations.argtypes = [vp, vp, ci, ci]
+        L.bioem_hip_compare_own_orientations.argtypes = [vp, ci, ci]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -109,7 +114,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_kernel_stats", "bioem_hip_reset_kernel_stats", "bioem_hip_uses_fast_path",
            "bioem_hip_kernel_name", "bioem_hip_kernel_signature", "bioem_hip_plan",
            "bioem_hip_synchronize", "bioem_hip_r2c", "bioem_hip_project", "bioem_hip_convolve",
-           "bioem_hip_compare_device", "bioem_hip_max_batch", "bioem_hip_set_phase_timing", "bioem_hip_phase_records"]
+           "bioem_hip_compare_device", "bioem_hip_max_batch", "bioem_hip_set_phase_timing", "bioem_hip_phase_records",
+           "bioem_hip_upload_particle_orientations", "bioem_hip_compare_own_orientations"]
 
 
 def _p(a):
@@ -212,6 +218,13 @@ class Engine:
         self._chk(self.L.bioem_hip_upload_orientations(self.h, _p(angles), len(angles), int(bool(isQuat))),
                   "upload_orientations")
 
+    def upload_particle_orientations(self, angles, isQuat):
+        """one orientation list per particle, angles[nMaps, K, 4] (K <= nAngles): round 2 of the manual's refinement"""
+        angles = np.ascontiguousarray(angles, dtype=np.float32)
+        assert angles.ndim == 3 and angles.shape[0] == self.nMaps and angles.shape[2] == 4
+        self._chk(self.L.bioem_hip_upload_particle_orientations(self.h, _p(angles), angles.shape[1], int(bool(isQuat))),
+                  "upload_particle_orientations")
+
     def prob_bytes(self):
         """bytes start_run / finish_run move: the whole block, or only the map entries for a shard handle"""
         if self.shard is not None:
@@ -234,6 +247,11 @@ class Engine:
 
     def project_convolve_compare_ctf(self, o0, o1, c0, c1):
         self._chk(self.L.bioem_hip_project_convolve_compare_ctf(self.h, o0, o1, c0, c1), "project_convolve_compare_ctf")
+
+    def compare_own_orientations(self, p0, p1):
+        """particles [p0, p1), each against its own list (upload_particle_orientations) x all CTFs, asynchronous;
+        pmap["orient"] is the index in the particle's list"""
+        self._chk(self.L.bioem_hip_compare_own_orientations(self.h, p0, p1), "compare_own_orientations")
 
     def project(self, iPipeline, o0, o1):
         """== bioem::createProjection for [o0, o1), asynchronous; the spectra stay in buffer set iPipeline & 1"""

@@ -64,6 +64,8 @@ struct InputParams
 int ctf_kernels(int N, float pixelSize, bool usepsf, float startAmp, float endAmp, int nAmp, float startPhase,
                 float endPhase, int nPhase, float startEnv, float endEnv, int nEnv, float *refCTF, float *ctfParam,
                 float *steps, void (*r2c)(void *, int, const float *, float *), void *ctx);
+// a quaternion list in the format --ReadOrientation reads (header line with the count, four 12-character columns)
+std::vector<float> read_quaternion_list(const char *file);
 float volume_element(float voluang, int gridSpaceCenter, int maxDisplaceCenter, float pixelSize, int nAmp,
                      float gridEnvelop, float gridPhase, float sigB, float sigDef, float sigAmp);
 
@@ -112,6 +114,8 @@ public:
   Model model;
   ParticleStack particles;
   std::string outfileName = "Output_Probabilities";
+  std::string refineFile;        // --RefineOrientations: the small grid of round 2 (empty: one round)
+  std::vector<float> refineGrid; // its quaternions [G][4], read with the options
   std::vector<unsigned char> prob;              // merged map entries [nMaps]
   std::vector<bioem_hip_angle_candidate> cand;  // merged K best orientations [nMaps][K] (WRITE_PROB_ANGLES)
 
@@ -134,6 +138,10 @@ private:
   };
   int readOptions(int argc, char **argv);
   void writeOutput();
+  // Output_Probabilities text of a probability block; orientation(i, o) = the four numbers of orientation o of map i
+  void writeProbabilities(const std::string &file, const bioem_hip_prob_map *pmap, const bioem_hip_param_device &pd,
+                          const float *angles, size_t anglesPerMap, bool angProb);
+  void runRound2(); // --RefineOrientations: every particle against best (x) grid, OutputFile_Round2
   std::vector<Shard> shards;
 };
 

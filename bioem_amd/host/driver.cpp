@@ -69,6 +69,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"Inputfile", required_argument, 0, 0},
                                        {"PrintBestCalMap", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
+                                       {"RefineOrientations", required_argument, 0, 0},
                                        {"ReadPDB", no_argument, 0, 0},
                                        {"ReadModelMRC", no_argument, 0, 0},
                                        {"ReadMRC", no_argument, 0, 0},
@@ -87,6 +88,8 @@ int Driver::readOptions(int ac, char **av)
     printf("  --Particlesfile arg    (Mandatory) Name of particle-image file\n");
     printf("  --Inputfile arg        (Mandatory) Name of input parameter file\n");
     printf("  --ReadOrientation arg  (Optional) Read file name containing orientations\n");
+    printf("  --RefineOrientations arg (Optional) Second round: file with a small list of quaternions; every particle\n");
+    printf("                         is evaluated again on its best orientation x that list (OutputFile_Round2)\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
     printf("  --ReadMRC              (Optional) If reading particle file in MRC format\n");
@@ -150,6 +153,11 @@ int Driver::readOptions(int ac, char **av)
       anglefile = optarg;
       param.notuniformangles = true;
     }
+    else if (name == "RefineOrientations")
+    {
+      std::cout << "Refining orientations (second round) with the list: " << optarg << "\n";
+      refineFile = optarg;
+    }
     else if (name == "OutputFile")
     {
       std::cout << "Writing OUTPUT to: " << optarg << "\n";
@@ -181,6 +189,16 @@ int Driver::readOptions(int ac, char **av)
   if (particles.readMultMRC && !particles.readMRC)
     fatal("For multiple MRCs command --ReadMRC is necessary too");
   param.readParameters(infile.c_str());
+  if (!refineFile.empty())
+  { // round 2 multiplies quaternions and evaluates lists of its own: no prior per orientation, no ANG_PROB (yet)
+    if (!param.doquater)
+      fatal("--RefineOrientations needs quaternions (USE_QUATERNIONS): the second round multiplies them");
+    if (param.yespriorAngles)
+      fatal("--RefineOrientations is not valid with prior for orientations (PRIOR_ANGLES)");
+    if (param.pd.writeAngles)
+      fatal("--RefineOrientations is not valid with WRITE_PROB_ANGLES");
+    refineGrid = read_quaternion_list(refineFile.c_str()); // now: a bad list must not end a run after its first round
+  }
   particles.readRefMaps(param, mapfile.c_str());
   model.readModel(param, modelfile.c_str());
   param.calculateGridsParam(anglefile.c_str());
@@ -486,7 +504,69 @@ int Driver::run()
     }
   }
   writeOutput();
+  if (!refineFile.empty())
+    runRound2();
   return 0;
+}
+
+// Round 2 of the manual's model comparison (doc/index.rst, "modcom") in the same run: particle p is evaluated again on
+// the list best_p (x) grid -- the Hamilton product in (x, y, z, w) storage, the model rotated by best_p first and the
+// small rotation applied to the rotated model (bioem_amd/refine.py states and tests the convention) -- through the
+// own-list pass of the engine on the first selected device.  The numbers of particle p are those of a run on that
+// particle alone with its list through --ReadOrientation: volu of a list of G orientations (param.cpp:1131,1324).
+void Driver::runRound2()
+{
+  const std::vector<float> &grid = refineGrid;
+  const int G = (int) (grid.size() / 4), nMaps = particles.ntot, nC = param.nTotCTFs;
+  std::cout << "Second round: " << G << " orientations per particle\n";
+  const bioem_hip_prob_map *r1 = (const bioem_hip_prob_map *) prob.data();
+  std::vector<float> lists((size_t) nMaps * G * 4);
+  for (int i = 0; i < nMaps; i++)
+  {
+    const float *b = param.angles.data() + 4 * (size_t) r1[i].max_prob_orient;
+    const double bx = b[0], by = b[1], bz = b[2], bw = b[3];
+    for (int k = 0; k < G; k++)
+    {
+      const float *g = grid.data() + 4 * (size_t) k;
+      float *o = lists.data() + ((size_t) i * G + k) * 4;
+      if (g[0] == 0.f && g[1] == 0.f && g[2] == 0.f && g[3] == 1.f)
+      { // the identity: the round-1 orientation itself, bit for bit
+        memcpy(o, b, 4 * sizeof(float));
+        continue;
+      }
+      const double gx = g[0], gy = g[1], gz = g[2], gw = g[3];
+      const double q[4] = {bw * gx + bx * gw + by * gz - bz * gy, bw * gy - bx * gz + by * gw + bz * gx,
+                           bw * gz + bx * gy - by * gx + bz * gw, bw * gw - bx * gx - by * gy - bz * gz};
+      const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      for (int c = 0; c < 4; c++)
+        o[c] = (float) (q[c] / nrm);
+    }
+  }
+  bioem_hip_param_device pd2 = param.pd;
+  pd2.writeAngles = 0;
+  pd2.volu = volume_element((float) (1. / (float) G * param.priorMod), pd2.GridSpaceCenter, pd2.maxDisplaceCenter,
+                            param.pixelSize, param.numberGridPointsCTF_amp, param.gridEnvelop, param.gridCTF_phase,
+                            pd2.sigmaPriorbctf, pd2.sigmaPriordefo, pd2.sigmaPrioramp);
+  bioem_hip_handle h = nullptr;
+  check(h, bioem_hip_create(&h, firstDev, &pd2, nMaps, G, nC, algo), "bioem_hip_create (second round)");
+  check(h, bioem_hip_upload_particle_maps(h, particles.maps.data()), "upload particles");
+  check(h, bioem_hip_upload_ctf(h, param.refCTF.data(), param.ctfParam.data()), "upload CTF");
+  check(h, bioem_hip_upload_model(h, model.points.data(), (int) model.points.size(), model.NormDen, param.pixelSize,
+                                  param.shiftX, param.shiftY),
+        "upload model");
+  check(h, bioem_hip_upload_particle_orientations(h, lists.data(), G, 1), "upload particle orientations");
+  std::vector<bioem_hip_prob_map> pm(nMaps);
+  for (int i = 0; i < nMaps; i++) // bioem.cpp:681-699
+  {
+    memset(&pm[i], 0, sizeof(pm[i]));
+    pm[i].Total = 0.0;
+    pm[i].Constoadd = -999999.;
+  }
+  check(h, bioem_hip_start_run(h, pm.data()), "start run (second round)");
+  check(h, bioem_hip_compare_own_orientations(h, 0, nMaps), "compare own orientations");
+  check(h, bioem_hip_finish_run(h, pm.data()), "finish run (second round)");
+  bioem_hip_destroy(h);
+  writeProbabilities(outfileName + "_Round2", pm.data(), pd2, lists.data(), (size_t) G, false);
 }
 
 void Driver::cleanup()
@@ -503,18 +583,24 @@ void Driver::cleanup()
 // Output_Probabilities and ANG_PROB, text layout of bioem.cpp:1047-1374 (fixed, 4 decimals).
 void Driver::writeOutput()
 {
+  writeProbabilities(outfileName, (const bioem_hip_prob_map *) prob.data(), param.pd, param.angles.data(), 0, true);
+}
+
+// angles: the list max_prob_orient indexes -- one for all maps (anglesPerMap = 0) or anglesPerMap entries per map (the
+// second round); angProb: ANG_PROB is written beside it when pd.writeAngles asks for it
+void Driver::writeProbabilities(const std::string &file, const bioem_hip_prob_map *pmap, const bioem_hip_param_device &pd,
+                                const float *angles, size_t anglesPerMap, bool angProb)
+{
   const int nMaps = particles.ntot;
-  const bioem_hip_prob_map *pmap = (const bioem_hip_prob_map *) prob.data();
-  const bioem_hip_param_device &pd = param.pd;
+  const bool writeAng = angProb && pd.writeAngles;
   const double numconst = 0.5 * log(M_PI) + (1 - pd.Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(pd.volu);
   const char *bar = "************************* HEADER:: NOTATION *******************************************\n";
-  const float *A = param.angles.data();
   const float *K = param.ctfParam.data();
 
   std::ofstream ang;
   ang.precision(4);
   ang.setf(std::ios::fixed);
-  if (pd.writeAngles)
+  if (writeAng)
   {
     ang.open("ANG_PROB");
     ang << bar;
@@ -530,7 +616,7 @@ void Driver::writeOutput()
   std::ofstream out;
   out.precision(4);
   out.setf(std::ios::fixed);
-  out.open(outfileName.c_str());
+  out.open(file.c_str());
   out << bar;
   out << "Notation= RefMap:  MapNumber ; LogProb natural logarithm of posterior Probability ; Constant: Numerical "
          "Const. for adding Probabilities \n";
@@ -566,6 +652,7 @@ void Driver::writeOutput()
       out << "Warning - RefMap: " << i << "Check that constant is finite: " << pm.Constoadd << "\n";
       out << "Warning - RefMap: i) check model, ii) check refmap , iii) check GPU on/off command inconsitency\n";
     }
+    const float *A = angles + 4 * anglesPerMap * (size_t) i; // this map's list
     const float *a = A + 4 * (size_t) pm.max_prob_orient;
     const float *k = K + 3 * (size_t) pm.max_prob_conv;
     out << a[0] << " [] " << a[1] << " [] " << a[2] << " [] ";
@@ -584,7 +671,7 @@ void Driver::writeOutput()
       out << "RefMap: " << i << " CTFMaxParam: " << 2 * M_PI * k[1] / denomi / param.elecwavel * 0.0001
           << " [micro-m] " << 4 * M_PI * M_PI * k[2] / denomi << " [A²] \n";
     }
-    if (pd.writeAngles)
+    if (writeAng)
     {
       // the K best orientations (selected by the reference's min-heap rule, bioem.cpp:1251-1286 -- on the device for
       // orientation-block shards, see Driver::run), best first
@@ -609,7 +696,7 @@ void Driver::writeOutput()
       }
     }
   }
-  if (pd.writeAngles)
+  if (writeAng)
     ang.close();
   out.close();
 }

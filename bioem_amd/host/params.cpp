@@ -402,6 +402,38 @@ float column12(const std::string &line, int col)
 }
 } // namespace
 
+std::vector<float> read_quaternion_list(const char *file)
+{
+  std::ifstream input(file);
+  if (!input.good())
+    fatal("Quaterion list file %s", file);
+  std::string line;
+  std::getline(input, line);
+  int n = 0;
+  if (sscanf(line.substr(0, 12).c_str(), "%d", &n) != 1)
+    fatal("line parsed by sscanf has wrong argument");
+  if (n < 1)
+    fatal("Invalid number of quaternions %d", n);
+  std::vector<float> q;
+  int cnt = 0;
+  while (std::getline(input, line))
+  {
+    for (int c = 0; c < 4; c++)
+    {
+      const float v = column12(line, c);
+      if (v < -1 || v > 1)
+        fatal("Reading quaterions from list. Value out of range %lf row %d", (double) v, cnt);
+      q.push_back(v);
+    }
+    cnt++;
+    if (n < cnt)
+      fatal("More quaternions than expected in header %d instead of %d", cnt, n);
+  }
+  if (n > cnt)
+    fatal("Less quaternions than expected in header %d instead of %d", cnt, n);
+  return q;
+}
+
 void InputParams::calculateGridsParam(const char *anglefile)
 {
   angles.clear();

@@ -123,6 +123,13 @@ int bioem_hip_upload_model(bioem_hip_handle h, const bioem_hip_model_point *pts,
                            float pixelSize, int shiftX, int shiftY);
 /* bioem_param::angles [n] as {pos0,pos1,pos2,quat4} (defs.h:105-110); isQuat = param.doquater. */
 int bioem_hip_upload_orientations(bioem_hip_handle h, const float *angles4, int n, int isQuat);
+/* One orientation list per particle: angles4 = [nMaps][K] x {pos0,pos1,pos2,quat4}; K <= nAngles of the handle.
+ * No reference counterpart as an interface: it is round 2 of doc/index.rst "modcom", where the reference runs one
+ * process per particle with --ReadOrientation <that particle's list>.  Returns 2 (bioem_hip_last_error says why) for
+ * K < 1 or K > nAngles and for handles the own-list pass does not take: tiled wide windows, BIOEM_CC_DIRECT=1, shards.
+ * The pipeline buffers of the handle grow to the batches of that pass (up to 1 024 list entries each: several GB at
+ * large images) and stay that size; when that memory is not there the call returns 1 and the handle is as it was. */
+int bioem_hip_upload_particle_orientations(bioem_hip_handle h, const float *angles4, int K, int isQuat);
 
 /* bioem::malloc_device_host / free_device_host (bioem.h:56-57; bioem_cuda.cu:1037-1053): pinned host memory
  * for the probability block. */
@@ -151,6 +158,15 @@ int bioem_hip_project_convolve_compare(bioem_hip_handle h, int iOrientBegin, int
  * orientations than GPUs the CTF grid is split as well (north_star: "orientations x CTF-envelope grid shard"). */
 int bioem_hip_project_convolve_compare_ctf(bioem_hip_handle h, int iOrientBegin, int iOrientEnd, int iConvBegin,
                                            int iConvEnd);
+
+/* project -> convolve -> compare, on the device, of list entries [0, K) x all CTFs of particles [iMapBegin, iMapEnd),
+ * each particle against its own list only (bioem_hip_upload_particle_orientations).  Per particle the result equals what
+ * bioem_hip_project_convolve_compare gives on a handle that holds that particle alone and its list as the shared list:
+ * max_prob_orient is the index in THAT particle's list, and with WRITE_PROB_ANGLES entry (k, p) of the
+ * [nAngles][nMaps] table receives list entry k of particle p.  Entries of particles outside the range are not touched.
+ * Asynchronous like the fused entry; start_run / finish_run as usual.  Phase records of this pass carry the range of
+ * slots p * K + k of a batch in iOrientBegin / iOrientEnd. */
+int bioem_hip_compare_own_orientations(bioem_hip_handle h, int iMapBegin, int iMapEnd);
 
 /* The same three stages as separate entries, for an integrator who keeps the reference's loop (bioem.cpp:763-891) and
  * replaces its body piece by piece: every call is asynchronous and batched, and what one stage produces stays on the
