@@ -41,7 +41,9 @@
 //   fold_kernels.hpp     k_fold_wave, k_fold_angles: fold the per-comparison partials into the probability block in the
 //                          reference's (orientation, CTF) order (bioem_algorithm.h:96-123, bioem.cpp:1527-1600)
 //                        k_fold_own, k_fold_own_angles: the same for the own-list pass (one orientation list per particle,
-//                          bioem_hip_compare_own_orientations: the comparison kernels as they are, one launch per particle)
+//                          of any length: bioem_hip_compare_own_orientations)
+//   compare_fast_own.hpp k_compare_fast_own, k_nyquist_rows_own (kernels_fast_own.hip): k_compare_fast with a block table,
+//                          one launch per batch of the own-list pass; the other families: one launch per particle
 //   this file            device context, launch logic, the C ABI
 //   kernels_*.hip        one translation unit per comparison-kernel family (the instantiations of kernel_table.inc),
 //                          linked into the same library: kernels_fast, kernels_fastm, kernels_wide2_{short,16,long},
@@ -147,12 +149,27 @@ struct bioem_hip_ctx
   int nCU = 256;   // compute units of the device: size of the resident grids of the preparation kernels
   float4 *dAngles = nullptr;
   int nAnglesUp = 0, isQuat = 1;
-  // one orientation list per particle (bioem_hip_upload_particle_orientations, bioem_hip_compare_own_orientations):
-  // [nMaps][ownK] entries; the all-to-all entries never read this state
-  float4 *dOwnAngles = nullptr;
-  int ownK = 0, ownIsQuat = 1;
+  // one orientation list per particle (bioem_hip_upload_particle_orientation_lists, bioem_hip_compare_own_orientations):
+  // particle p owns the flat slots ownOff[p] ... ownOff[p + 1]; the all-to-all entries never read this state
+  float4 *dOwnAngles = nullptr;        // [slots]
+  int *dOwnOff = nullptr;              // [nMaps + 1], ownOff on the device
+  int *dSlotParticle = nullptr;        // [slots] particle of a slot
+  size_t ownSlotCap = 0;               // slots dOwnAngles / dSlotParticle hold
+  std::vector<int> ownOff;             // empty: no lists
+  int ownK = 0, ownIsQuat = 1;         // ownK: the longest list
   double ownQuatNormDev = 0.;
   int ownOB = 0;                       // slots (particle, list entry) per batch of the own-list pass
+  // the comparison of a batch as ONE launch (k_compare_fast_own: plans of k_compare_fast, where bioem_hip_set_own_launch
+  // asked for it; ownFnPlan: the plan's own kernel, ownFn: the one in use or null), else one launch of the plan's kernel
+  // per particle, the default.  Block table of the batches of particles [ownTabP0, ownTabP1):
+  // batch b begins at slot ownTabSlot[b] and owns entries ownTabFirst[b] ... ownTabFirst[b + 1] of dOwnBlocks
+  own_kernel_t ownFn = nullptr, ownFnPlan = nullptr;
+  nyq_own_kernel_t ownNyqFn = nullptr;
+  bool ownXcdOrder = true;
+  int4 *dOwnBlocks = nullptr;
+  size_t ownBlockCap = 0;
+  int ownTabP0 = -1, ownTabP1 = -1;
+  std::vector<int> ownTabSlot, ownTabFirst;
   size_t slotImages[2] = {0, 0};       // images the projection buffers of a pipeline slot hold
   size_t slotRows = 0, partRows = 0;   // rows the conv / params / postc buffers of a slot and dPartials (dTnyq) hold
   float2 *dTw = nullptr;   // N+1 entries exp(+2 pi i k/N), float
@@ -575,15 +592,20 @@ int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC
 }
 
 // Own-list pass: the nOC conv rows of the slot are rows [slot0 nC, ...) of the flat [particle][list entry][CTF] order;
-// every row is compared with its own particle and each particle's rows are folded into its entry.  The comparison
-// kernels are launched as they are, once per particle with rows in the slot: a launch over that particle's run of
-// rows with nMaps = 1, ref / sumRef / sumsqRef pointed at the particle and conv / params / postc / partials / tnyq at the
-// run -- exactly the launch a handle that holds that particle alone makes (its block order, its k_nyquist_rows).  Row oc
-// of the slot leaves its result in partials[oc].
+// every row is compared with its own particle and each particle's rows are folded into its entry.  Row oc of the slot
+// leaves its result in partials[oc].
+//   k_compare_fast plans after bioem_hip_set_own_launch(BIOEM_HIP_OWN_LAUNCH_BATCH): ONE launch of k_compare_fast_own over
+//     the batch, its blocks mapped to (particle, four rows) by the block table of the batch (own_block_table); the
+//     Nyquist rows by k_nyquist_rows_own.
+//   every other family, and the default of all (BIOEM_HIP_OWN_LAUNCH_PARTICLE): the comparison kernels as they are, once
+//     per particle with rows in the slot: a launch over that particle's run of rows with nMaps = 1, ref / sumRef /
+//     sumsqRef pointed at the particle and conv / params / postc / partials / tnyq at the run -- exactly the launch a
+//     handle that holds that particle alone makes (its block order, its k_nyquist_rows).
+// The two give the same partials bit for bit: a wave computes one (particle, row) pair by the same instructions in both.
 int launch_compare_own(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC, int slot0, int nC)
 {
   const KernelPlan &P = h->plan;
-  const int R = h->ownK * nC, row0 = slot0 * nC;
+  const int row0 = slot0 * nC;
   hipEvent_t e0 = get_event(h), e1 = get_event(h);
   if (!e0 || !e1)
   {
@@ -599,27 +621,50 @@ int launch_compare_own(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC,
   HIP_CHECK(h, hipEventRecord(e0, h->stream));
   if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, slot0, slot0 + nSlots, 0, nC))
     return 1;
-  const int pFirst = slot0 / h->ownK, pEnd = (slot0 + nSlots + h->ownK - 1) / h->ownK;
-  for (int p = pFirst; p < pEnd; p++)
+  // particles with slots in the batch: off[pFirst] <= slot0 < off[pFirst + 1], off[pEnd] >= the batch's end (particles
+  // with an empty list between them have no rows)
+  const std::vector<int> &off = h->ownOff;
+  const int pFirst = (int) (std::upper_bound(off.begin(), off.end(), slot0) - off.begin()) - 1;
+  const int pEnd = (int) (std::lower_bound(off.begin(), off.end(), slot0 + nSlots) - off.begin());
+  if (h->ownFn)
   {
-    const long long g0 = (long long) p * R;
-    const int rb = (int) (std::max<long long>(g0, row0) - row0), n = (int) (std::min<long long>(g0 + R, row0 + nOC) - row0) - rb;
-    dim3 grid, block;
-    CompareArgs a = compare_args(h, bb, n, 1, grid, block);
-    a.ref += (size_t) p * h->Mc;
-    a.sumRef += p;
-    a.sumsqRef += p;
-    a.conv += (size_t) rb * h->Mc;
-    a.params += rb;
-    a.postc += rb;
-    a.partials += rb;
-    if (P.nyq)
+    const auto it = std::lower_bound(h->ownTabSlot.begin(), h->ownTabSlot.end(), slot0);
+    if (it == h->ownTabSlot.end() || *it != slot0)
     {
-      a.tnyq += (size_t) rb * (2 * P.nyqWD + 1);
-      launch_nyquist(h, a, P.nyqWD, n);
+      h->err = "compare_own_orientations: no block table for this batch";
+      return 1;
     }
-    hipLaunchKernelGGL(P.fn, grid, block, P.ldsBytes, h->stream, a);
+    const size_t b = (size_t) (it - h->ownTabSlot.begin());
+    const int first = h->ownTabFirst[b], nBlocks = h->ownTabFirst[b + 1] - first;
+    dim3 grid, block;
+    const CompareArgs a = compare_args(h, bb, nOC, h->nMaps, grid, block);
+    if (P.nyq)
+      hipLaunchKernelGGL(h->ownNyqFn, dim3((nOC + 63) / 64), dim3(256), 0, h->stream, a, h->dSlotParticle, row0, nC);
+    hipLaunchKernelGGL(h->ownFn, dim3(nBlocks), dim3(256), P.ldsBytes, h->stream, a, h->dOwnBlocks + first);
   }
+  else
+    for (int p = pFirst; p < pEnd; p++)
+    {
+      const long long g0 = (long long) off[p] * nC, g1 = (long long) off[p + 1] * nC;
+      const int rb = (int) (std::max<long long>(g0, row0) - row0), n = (int) (std::min<long long>(g1, row0 + nOC) - row0) - rb;
+      if (n <= 0)
+        continue;
+      dim3 grid, block;
+      CompareArgs a = compare_args(h, bb, n, 1, grid, block);
+      a.ref += (size_t) p * h->Mc;
+      a.sumRef += p;
+      a.sumsqRef += p;
+      a.conv += (size_t) rb * h->Mc;
+      a.params += rb;
+      a.postc += rb;
+      a.partials += rb;
+      if (P.nyq)
+      {
+        a.tnyq += (size_t) rb * (2 * P.nyqWD + 1);
+        launch_nyquist(h, a, P.nyqWD, n);
+      }
+      hipLaunchKernelGGL(P.fn, grid, block, P.ldsBytes, h->stream, a);
+    }
   HIP_CHECK(h, hipGetLastError());
   HIP_CHECK(h, hipEventRecord(e1, h->stream));
   h->evPending.push_back({e0, e1});
@@ -629,14 +674,93 @@ int launch_compare_own(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC,
   bioem_hip_prob_angle *pang = reinterpret_cast<bioem_hip_prob_angle *>(h->dProb + sizeof(bioem_hip_prob_map) * h->nMaps);
   if (h->pd.writeAngles)
     hipLaunchKernelGGL(k_fold_own_angles, dim3((nSlots + 255) / 256), dim3(256), 0, h->stream, h->dPartials, nSlots, slot0,
-                       h->ownK, nC, h->nMaps, pang);
-  hipLaunchKernelGGL(k_fold_own, dim3((pEnd - pFirst + 3) / 4), dim3(256), 0, h->stream, h->dPartials, nOC, row0, R,
-                     nC, pFirst, pEnd, bb.params, h->dSumRef, h->dDisp, P.nd, h->pd, pmap);
+                       h->dOwnOff, h->dSlotParticle, nC, h->nMaps, pang);
+  hipLaunchKernelGGL(k_fold_own, dim3((pEnd - pFirst + 3) / 4), dim3(256), 0, h->stream, h->dPartials, nOC, row0,
+                     h->dOwnOff, nC, pFirst, pEnd, bb.params, h->dSumRef, h->dDisp, P.nd, h->pd, pmap);
   HIP_CHECK(h, hipGetLastError());
   if (phase_end(h, h->stream))
     return 1;
   if (h->evPending.size() > 512)
     drain_events(h);
+  return 0;
+}
+
+// batches of the own-list pass over particles [p0, p1): slots (particle, list entry), at most ownOB per batch, at least
+// six per call where that leaves 64 or more per batch (the first batch's preparation hides behind nothing), of equal
+// size.  Returns the first slot of every batch, and the end.
+std::vector<int> own_batches(const bioem_hip_ctx *h, int p0, int p1)
+{
+  const long long s0 = h->ownOff[p0], s1 = h->ownOff[p1];
+  const int per = (int) std::min<long long>(h->ownOB, std::max<long long>(64, (s1 - s0 + 5) / 6));
+  std::vector<int> first;
+  for (long long s = s0; s < s1; s += per)
+    first.push_back((int) s);
+  first.push_back((int) s1);
+  return first;
+}
+
+// Block table of k_compare_fast_own for the batches of particles [p0, p1): one entry {particle, first row, end row, 0}
+// per block, rows counted from the batch's first row, at most four consecutive rows of ONE particle's run in the batch
+// (the groups of four begin at the run's first row, as the per-particle launch forms them).  It depends on the offsets,
+// nCTF and the batch cuts only.  Order inside a batch (the order does not change results; DESIGN 2.9 has the
+// measurement): plain row order, or -- workgroups go round-robin over the 8 XCDs, each with its own L2 -- a particle's
+// blocks at indices congruent mod 8: its spectrum, the only operand several blocks share, then stays in ONE L2.  The runs
+// of a batch go to the XCD with the fewest blocks so far; where the eight queues run out unevenly the tail closes up.
+int own_block_table(bioem_hip_ctx *h, int p0, int p1)
+{
+  const std::vector<int> first = own_batches(h, p0, p1);
+  const int nb = (int) first.size() - 1, nC = h->nCTF;
+  const std::vector<int> &off = h->ownOff;
+  std::vector<int4> tab;
+  std::vector<int> tabSlot, tabFirst;
+  for (int b = 0; b < nb; b++)
+  {
+    const long long row0 = (long long) first[b] * nC, rowEnd = (long long) first[b + 1] * nC;
+    tabSlot.push_back(first[b]);
+    tabFirst.push_back((int) tab.size());
+    const int pFirst = (int) (std::upper_bound(off.begin(), off.end(), first[b]) - off.begin()) - 1;
+    std::vector<int4> q[8];
+    for (int p = pFirst; p < h->nMaps && (long long) off[p] * nC < rowEnd; p++)
+    {
+      const int rb = (int) (std::max<long long>((long long) off[p] * nC, row0) - row0);
+      const int re = (int) (std::min<long long>((long long) off[p + 1] * nC, rowEnd) - row0);
+      if (re <= rb)
+        continue;
+      int x = 0;
+      if (h->ownXcdOrder)
+        for (int k = 1; k < 8; k++)
+          if (q[k].size() < q[x].size())
+            x = k;
+      for (int g = rb; g < re; g += 4)
+        q[x].push_back(make_int4(p, g, std::min(g + 4, re), 0));
+    }
+    size_t longest = 0;
+    for (const auto &v : q)
+      longest = std::max(longest, v.size());
+    for (size_t i = 0; i < longest; i++)
+      for (const auto &v : q)
+        if (i < v.size())
+          tab.push_back(v[i]);
+  }
+  tabFirst.push_back((int) tab.size());
+  // nothing queued may still read the table that is replaced
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  if (tab.size() > h->ownBlockCap)
+  {
+    int4 *t = nullptr;
+    if (dev_alloc(h, t, tab.size()))
+      return 1;
+    dev_release(h, h->dOwnBlocks);
+    h->dOwnBlocks = t;
+    h->ownBlockCap = tab.size();
+  }
+  h->ownTabP0 = h->ownTabP1 = -1;
+  if (!tab.empty())
+    HIP_CHECK(h, hipMemcpy(h->dOwnBlocks, tab.data(), sizeof(int4) * tab.size(), hipMemcpyHostToDevice));
+  h->ownTabSlot.swap(tabSlot);
+  h->ownTabFirst.swap(tabFirst);
+  h->ownTabP0 = p0;
+  h->ownTabP1 = p1;
   return 0;
 }
 
@@ -1080,6 +1204,19 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
       return 2;
     }
   }
+  // own-list pass: one launch per particle unless bioem_hip_set_own_launch asks for one launch per batch, which the
+  // handle can do where the plan's kernel has an own variant (the single launch has no same-box measurement against the
+  // per-particle launches yet, DESIGN 2.9: it is not the default of any shape)
+  {
+    h->ownFnPlan = h->direct ? nullptr : plan_own_kernel(P);
+    h->ownFn = nullptr;
+    if (h->ownFnPlan)
+    {
+      h->ownNyqFn = P.nyq ? reinterpret_cast<nyq_own_kernel_t>(const_cast<void *>(bioem_nyquist_rows_own(P.nyqWD))) : nullptr;
+      HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(h->ownFnPlan), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int) P.ldsBytes));
+    }
+  }
   // Pitch of the comparison layout.  A lane block of the fast kernels keeps eight rows of one 64-column block in flight;
   // with N a multiple of 64 a row pair is 16 B more than a multiple of 512 B (4 112 B at 512^2, 2 064 B at 256^2) and all
   // of them start in the same few L2 channels.  Fifteen more words make the pitch an odd number of 256-byte lines
@@ -1450,28 +1587,37 @@ int bioem_hip_upload_orientations(bioem_hip_handle h, const float *angles4, int 
   return 0;
 }
 
-int bioem_hip_upload_particle_orientations(bioem_hip_handle h, const float *angles4, int K, int isQuat)
+// the common path of the two uploads: `what` names the entry in messages
+static int upload_own_lists(bioem_hip_handle h, const float *angles4, const long long *offsets, int isQuat, const char *what)
 {
-  HIP_CHECK(h, hipSetDevice(h->device));
   const KernelPlan &P = h->plan;
+  auto refuse = [&](const char *why) {
+    h->err = std::string(what) + ": " + why;
+    return 2;
+  };
   if (P.tileT || h->direct || h->shard)
+    return refuse(P.tileT    ? "the own-list pass does not take tiled wide windows"
+                  : h->direct ? "the own-list pass does not take BIOEM_CC_DIRECT handles"
+                              : "the own-list pass does not take shard handles");
+  if (!angles4 || !offsets)
+    return refuse("null argument");
+  if (offsets[0] != 0)
+    return refuse("offsets[0] must be 0");
+  int K = 0;
+  for (int p = 0; p < h->nMaps; p++)
   {
-    h->err = P.tileT    ? "upload_particle_orientations: the own-list pass does not take tiled wide windows"
-             : h->direct ? "upload_particle_orientations: the own-list pass does not take BIOEM_CC_DIRECT handles"
-                         : "upload_particle_orientations: the own-list pass does not take shard handles";
-    return 2;
+    const long long len = offsets[p + 1] - offsets[p];
+    if (len < 0)
+      return refuse("offsets must not decrease");
+    if (len > h->nAngles)
+      return refuse("a list is longer than nAngles of the handle");
+    K = std::max(K, (int) len);
   }
-  if (!angles4 || K < 1 || K > h->nAngles)
-  {
-    h->err = "upload_particle_orientations: need 1 <= K <= nAngles of the handle";
-    return 2;
-  }
-  const long long nSlots = (long long) h->nMaps * K;
+  const long long nSlots = offsets[h->nMaps];
+  if (nSlots < 1)
+    return refuse("the lists are all empty");
   if (nSlots * h->nCTF > 0x7fffffffLL)
-  {
-    h->err = "upload_particle_orientations: more than 2^31 (particle, list entry, CTF) rows";
-    return 2;
-  }
+    return refuse("more than 2^31 (particle, list entry, CTF) rows");
   // slots per batch: the preparation is the long pole of this pass (a conv spectrum meets ONE particle), so a batch
   // holds up to 1 024 slots (conv buffer <= 1 GiB per pipeline slot) whatever the all-to-all batch of the handle is
   const long long convCap = (long long) ((size_t) (1024u << 20) / (h->Mc * sizeof(float2))) / h->nCTF;
@@ -1558,16 +1704,38 @@ int bioem_hip_upload_particle_orientations(bioem_hip_handle h, const float *angl
       h->partRows = rows;
     }
   }
-  if (h->ownK != K)
+  if ((size_t) nSlots > h->ownSlotCap || !h->dOwnOff)
   {
     float4 *lists = nullptr;
-    if (dev_alloc(h, lists, (size_t) nSlots))
+    int *slotP = nullptr, *doff = nullptr;
+    if (dev_alloc(h, lists, (size_t) nSlots) || dev_alloc(h, slotP, (size_t) nSlots) ||
+        (!h->dOwnOff && dev_alloc(h, doff, (size_t) h->nMaps + 1)))
+    {
+      dev_release(h, lists);
+      dev_release(h, slotP);
+      dev_release(h, doff);
       return 1;
+    }
     dev_release(h, h->dOwnAngles);
+    dev_release(h, h->dSlotParticle);
     h->dOwnAngles = lists;
-    h->ownK = 0;
+    h->dSlotParticle = slotP;
+    if (doff)
+      h->dOwnOff = doff;
+    h->ownSlotCap = (size_t) nSlots;
+    h->ownOff.clear();
   }
+  std::vector<int> off(h->nMaps + 1), slotP((size_t) nSlots);
+  for (int p = 0; p <= h->nMaps; p++)
+    off[p] = (int) offsets[p];
+  for (int p = 0; p < h->nMaps; p++)
+    for (int s = off[p]; s < off[p + 1]; s++)
+      slotP[s] = p;
+  h->ownOff.clear(); // (no lists until every piece is in place)
   HIP_CHECK(h, hipMemcpy(h->dOwnAngles, angles4, sizeof(float4) * (size_t) nSlots, hipMemcpyHostToDevice));
+  HIP_CHECK(h, hipMemcpy(h->dOwnOff, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice));
+  HIP_CHECK(h, hipMemcpy(h->dSlotParticle, slotP.data(), sizeof(int) * slotP.size(), hipMemcpyHostToDevice));
+  h->ownOff.swap(off);
   h->ownK = K;
   h->ownOB = ownOB;
   h->ownIsQuat = isQuat;
@@ -1580,13 +1748,67 @@ int bioem_hip_upload_particle_orientations(bioem_hip_handle h, const float *angl
       const double dev = std::fabs(n2 - 1.0);
       h->ownQuatNormDev = dev == dev ? std::max(h->ownQuatNormDev, dev) : 1e30;
     }
+  // the block table of a pass over all particles (another range builds its own at the call)
+  h->ownTabP0 = h->ownTabP1 = -1;
+  if (h->ownFn && own_block_table(h, 0, h->nMaps))
+  {
+    h->ownOff.clear();
+    return 1;
+  }
+  // BIOEM_SIGNATURE_LOG: the kernels of the single launch, where the pass of this handle will use them
+  if (h->ownFn)
+    if (const char *lg = getenv("BIOEM_SIGNATURE_LOG"))
+      if (FILE *f = fopen(lg, "a"))
+      {
+        fprintf(f, "%s\n", bioem_hip_own_kernel_signature(h));
+        if (P.nyq)
+          fprintf(f, "k_nyquist_rows_own<%d>\n", P.nyqWD);
+        fclose(f);
+      }
+  return 0;
+}
+
+int bioem_hip_upload_particle_orientation_lists(bioem_hip_handle h, const float *angles4, const long long *offsets, int isQuat)
+{
+  HIP_CHECK(h, hipSetDevice(h->device));
+  return upload_own_lists(h, angles4, offsets, isQuat, "upload_particle_orientation_lists");
+}
+
+// lists of one length K: offsets[p] = p K of the same path
+int bioem_hip_upload_particle_orientations(bioem_hip_handle h, const float *angles4, int K, int isQuat)
+{
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const KernelPlan &P = h->plan;
+  if (!(P.tileT || h->direct || h->shard) && (!angles4 || K < 1 || K > h->nAngles))
+  {
+    h->err = "upload_particle_orientations: need 1 <= K <= nAngles of the handle";
+    return 2;
+  }
+  std::vector<long long> offsets((size_t) h->nMaps + 1);
+  for (int p = 0; p <= h->nMaps; p++)
+    offsets[p] = (long long) p * K;
+  return upload_own_lists(h, angles4, offsets.data(), isQuat, "upload_particle_orientations");
+}
+
+int bioem_hip_set_own_launch(bioem_hip_handle h, int mode)
+{
+  if (!h)
+    return 2;
+  if (mode != BIOEM_HIP_OWN_LAUNCH_BATCH && mode != BIOEM_HIP_OWN_LAUNCH_PARTICLE && mode != BIOEM_HIP_OWN_LAUNCH_BATCH_ROWS)
+  {
+    h->err = "set_own_launch: unknown mode";
+    return 2;
+  }
+  h->ownFn = mode == BIOEM_HIP_OWN_LAUNCH_PARTICLE ? nullptr : h->ownFnPlan;
+  h->ownXcdOrder = mode != BIOEM_HIP_OWN_LAUNCH_BATCH_ROWS;
+  h->ownTabP0 = h->ownTabP1 = -1; // the block table follows at the next pass
   return 0;
 }
 
 int bioem_hip_compare_own_orientations(bioem_hip_handle h, int iMapBegin, int iMapEnd)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
-  if (!h->dOwnAngles || h->ownK < 1)
+  if (!h->dOwnAngles || h->ownOff.empty())
   {
     h->err = "compare_own_orientations: no per-particle orientation lists (bioem_hip_upload_particle_orientations)";
     return 2;
@@ -1598,15 +1820,11 @@ int bioem_hip_compare_own_orientations(bioem_hip_handle h, int iMapBegin, int iM
   }
   if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
     return 1;
-  // batches of slots (particle, list entry): at most ownOB, at least six per call where that leaves 64 or more per
-  // batch (the first batch's preparation hides behind nothing), of equal size
-  const long long s0 = (long long) iMapBegin * h->ownK, s1 = (long long) iMapEnd * h->ownK;
-  const int per = (int) std::min<long long>(h->ownOB, std::max<long long>(64, (s1 - s0 + 5) / 6));
-  std::vector<int> first;
-  for (long long s = s0; s < s1; s += per)
-    first.push_back((int) s);
-  first.push_back((int) s1);
-  return run_pipeline(h, first, 0, h->nCTF, true);
+  if (h->ownOff[iMapBegin] == h->ownOff[iMapEnd]) // (no particle, or empty lists only)
+    return 0;
+  if (h->ownFn && (h->ownTabP0 != iMapBegin || h->ownTabP1 != iMapEnd) && own_block_table(h, iMapBegin, iMapEnd))
+    return 1;
+  return run_pipeline(h, own_batches(h, iMapBegin, iMapEnd), 0, h->nCTF, true);
 }
 
 void *bioem_hip_host_alloc(size_t size)
@@ -2311,6 +2529,35 @@ int bioem_hip_plan(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter,
     snprintf(signature + n, (size_t) cap - n, " x %d^2 tiles of %d rows", P.tilesPerAxis, P.tileT);
   }
   return 0;
+}
+
+int bioem_hip_plan_own(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo, char *signature, int cap)
+{
+  if (numberPixels < 2 || numberPixels > kMaxPixels || maxDisplaceCenter < 0 || gridSpaceCenter < 1 ||
+      maxDisplaceCenter >= numberPixels / 2 || !signature || cap < 1)
+    return 2;
+  const KernelPlan P = plan_kernels(numberPixels, maxDisplaceCenter, gridSpaceCenter, algo);
+  if (P.err || !P.fn)
+    return 1;
+  plan_own_signature(P, plan_own_kernel(P) != nullptr, signature, (size_t) cap);
+  if (P.tileT)
+  {
+    const size_t n = strlen(signature);
+    snprintf(signature + n, (size_t) cap - n, " x %d^2 tiles of %d rows", P.tilesPerAxis, P.tileT);
+  }
+  return 0;
+}
+
+const char *bioem_hip_own_kernel_signature(bioem_hip_handle h)
+{
+  if (!h)
+    return "";
+  static thread_local char buf[128];
+  if (h->direct)
+    snprintf(buf, sizeof(buf), "per particle: k_compare_direct<3, 8>");
+  else
+    plan_own_signature(h->plan, h->ownFn != nullptr, buf, sizeof(buf));
+  return buf;
 }
 
 const char *bioem_hip_kernel_name(bioem_hip_handle h)

@@ -154,14 +154,15 @@ __global__ __launch_bounds__(256) void k_fold_wave(const Partial *__restrict__ p
 
 // ------------------------------------------------------------------------------------------------
 // own-list pass (bioem_hip_compare_own_orientations): row oc of a launch is row row0 + oc of the flat
-// [particle][list entry k][CTF] order (R = K * nCTF rows per particle) and was compared with its own particle only;
-// partials[oc] is its result.  One wave per particle with rows in the launch folds exactly those rows, by the rules of
-// k_fold_wave (first maximum = lowest row, log-sum-exp in double, norm / mu from the best row); max_prob_orient is the
-// index in that particle's list.  A list that straddles two launches is folded in two steps, like two batches of the
-// all-to-all pass.
+// [particle][list entry k][CTF] order -- particle p owns slots off[p] ... off[p + 1], nCTF rows each, the lists may differ
+// in length -- and was compared with its own particle only; partials[oc] is its result.  One wave per particle with rows
+// in the launch folds exactly those rows, by the rules of k_fold_wave (first maximum = lowest row, log-sum-exp in double,
+// norm / mu from the best row); max_prob_orient is the index in that particle's list.  A list that straddles two launches
+// is folded in two steps, like two batches of the all-to-all pass; a particle without rows in the launch is not touched.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_fold_own(const Partial *__restrict__ partials, int nOC, int row0, int R, int nCTF,
-                                                  int pFirst, int pEnd, const bioem_hip_param5 *__restrict__ params,
+__global__ __launch_bounds__(256) void k_fold_own(const Partial *__restrict__ partials, int nOC, int row0,
+                                                  const int *__restrict__ off, int nCTF, int pFirst, int pEnd,
+                                                  const bioem_hip_param5 *__restrict__ params,
                                                   const float *__restrict__ sumRef, const int *__restrict__ disp, int nd,
                                                   PD pd, bioem_hip_prob_map *__restrict__ pmap)
 {
@@ -169,8 +170,10 @@ __global__ __launch_bounds__(256) void k_fold_own(const Partial *__restrict__ pa
   const int p = pFirst + blockIdx.x * 4 + wave;
   if (p >= pEnd)
     return;
-  const long long g0 = (long long) p * R; // first row of the particle in the flat order
-  const int rb = (int) (max(g0, (long long) row0) - row0), re = (int) (min(g0 + R, (long long) row0 + nOC) - row0);
+  const long long g0 = (long long) off[p] * nCTF, g1 = (long long) off[p + 1] * nCTF; // the particle's rows in the flat order
+  const int rb = (int) (max(g0, (long long) row0) - row0), re = (int) (min(g1, (long long) row0 + nOC) - row0);
+  if (re <= rb)
+    return;
   const int chunk = (re - rb + 63) / 64;
   const int b = min(re, rb + lane * chunk), e = min(re, b + chunk);
   double m = -INFINITY, sacc = 0.;
@@ -188,11 +191,11 @@ __global__ __launch_bounds__(256) void k_fold_own(const Partial *__restrict__ pa
     }
     sacc += r.sumExp * exp(lp - m);
   }
-  for (int off = 32; off > 0; off >>= 1)
+  for (int o = 32; o > 0; o >>= 1)
   {
-    const double m2 = __shfl_xor(m, off);
-    const double s2 = __shfl_xor(sacc, off);
-    const int i2 = __shfl_xor(idx, off);
+    const double m2 = __shfl_xor(m, o);
+    const double s2 = __shfl_xor(sacc, o);
+    const int i2 = __shfl_xor(idx, o);
     if (m2 > m || (m2 == m && i2 < idx))
     {
       sacc = ((m == -INFINITY) ? 0. : sacc * exp(m - m2)) + s2;
@@ -227,15 +230,17 @@ __global__ __launch_bounds__(256) void k_fold_own(const Partial *__restrict__ pa
   }
 }
 
-// WRITE_PROB_ANGLES of the own-list pass: one thread per slot (particle p, list entry k) of the launch folds the slot's
-// CTF rows, in CTF order, into entry (k, p) of the [nAngles][nMaps] table -- the arithmetic of k_fold_angles.
-__global__ void k_fold_own_angles(const Partial *__restrict__ partials, int nSlots, int slot0, int K, int nCTF, int nMaps,
+// WRITE_PROB_ANGLES of the own-list pass: one thread per slot of the launch -- flat slot s belongs to particle
+// slotParticle[s], list entry k = s - off[p] -- folds the slot's CTF rows, in CTF order, into entry (k, p) of the
+// [nAngles][nMaps] table: the arithmetic of k_fold_angles.  Entries (k, p) beyond the particle's list are never addressed.
+__global__ void k_fold_own_angles(const Partial *__restrict__ partials, int nSlots, int slot0,
+                                  const int *__restrict__ off, const int *__restrict__ slotParticle, int nCTF, int nMaps,
                                   bioem_hip_prob_angle *__restrict__ pang)
 {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nSlots)
     return;
-  const int s = slot0 + t, p = s / K, k = s - p * K;
+  const int s = slot0 + t, p = slotParticle[s], k = s - off[p];
   bioem_hip_prob_angle pa = pang[(size_t) k * nMaps + p];
   for (int oc = t * nCTF; oc < (t + 1) * nCTF; oc++)
   {

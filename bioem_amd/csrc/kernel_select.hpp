@@ -20,6 +20,7 @@
 //   BIOEM_COMPAT_RING=<rows>    rows per half of bioem_hip_compare's staging ring (test_gpu_parity.py: odd ring sizes)
 //   BIOEM_SIGNATURE_LOG=<file>  one line per handle with its kernel instantiations (tests/conftest.py for
 //                               scripts/check_kernel_coverage.py)
+// (The launch mode of the own-list pass is no environment knob: bioem_hip_set_own_launch, include/bioem_hip.h.)
 // Outside the library: BIOEM_HIP_LIBRARY (Python loader, bioem_amd/engine.py: an experiment build) and the options of
 // the host layer (bioem_amd/host: the reference's environment, devices and merge).
 #ifndef BIOEM_KERNEL_SELECT_HPP
@@ -85,6 +86,30 @@ fast_kernel_t find_kernel(int family, int a0 = 0, int a1 = 0, int a2 = 0, int a3
         return reinterpret_cast<fast_kernel_t>(const_cast<void *>(e.fn));
     }
   return nullptr;
+}
+
+// the own-list pass: k_compare_fast_own (kernels_fast_own.hip) under the arguments of the plan's k_compare_fast, or null --
+// another family, a tiled plan, an instantiation that was left out: such a shape keeps one launch per particle
+typedef void (*own_kernel_t)(const CompareArgs, const int4 *);
+typedef void (*nyq_own_kernel_t)(const CompareArgs, const int *, int, int);
+
+own_kernel_t find_own_kernel(int family, int wd, int R, bool nyq, int gs)
+{
+#ifdef BIOEM_SLIM
+  return nullptr;
+#else
+  if (family != KF_FAST || (nyq && !bioem_nyquist_rows_own(wd)))
+    return nullptr;
+  int n = 0;
+  const KernelEntry *tab = bioem_kernels_fast_own(&n);
+  for (int i = 0; i < n; i++)
+  {
+    const KernelEntry &e = tab[i];
+    if (e.fn && e.family == KF_FAST && e.a[0] == wd && e.a[1] == R && e.a[2] == (int) nyq && e.a[3] == gs)
+      return reinterpret_cast<own_kernel_t>(const_cast<void *>(e.fn));
+  }
+  return nullptr;
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -565,6 +590,27 @@ KernelPlan plan_kernels(int N, int maxD, int grid, int algo)
   if (P.ldsBytes > kLdsCU)
     P.err = "configuration exceeds the 160 KiB LDS budget of the comparison kernel";
   return P;
+}
+
+// single launch of the own-list pass for this plan (null: one launch per particle)
+own_kernel_t plan_own_kernel(const KernelPlan &P)
+{
+  return P.tileT ? nullptr : find_own_kernel(P.family, P.winD, 2 * P.halfR, P.nyq, P.gs);
+}
+
+void plan_signature(const KernelPlan &P, char *buf, size_t cap);
+
+// what the own-list pass launches: "k_compare_fast_own<...>" (one launch per batch), or the plan's kernel once per particle
+void plan_own_signature(const KernelPlan &P, bool single, char *buf, size_t cap)
+{
+  if (single)
+  {
+    snprintf(buf, cap, "k_compare_fast_own<%d, %d, %s, %d>", P.winD, 2 * P.halfR, P.nyq ? "true" : "false", P.gs);
+    return;
+  }
+  const int n = snprintf(buf, cap, "per particle: ");
+  if (n >= 0 && (size_t) n < cap)
+    plan_signature(P, buf + n, cap - (size_t) n);
 }
 
 void plan_signature(const KernelPlan &P, char *buf, size_t cap)

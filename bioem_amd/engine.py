@@ -66,6 +66,12 @@ def load_library():
     if hasattr(L, "bioem_hip_upload_particle_orientations"):
         L.bioem_hip_upload_particle_orientations.argtypes = [vp, vp, ci, ci]
         L.bioem_hip_compare_own_orientations.argtypes = [vp, ci, ci]
+    if hasattr(L, "bioem_hip_upload_particle_orientation_lists"):
+        L.bioem_hip_upload_particle_orientation_lists.argtypes = [vp, vp, vp, ci]
+        L.bioem_hip_plan_own.argtypes = [ci, ci, ci, ci, C.c_char_p, ci]
+        L.bioem_hip_own_kernel_signature.argtypes = [vp]
+        L.bioem_hip_own_kernel_signature.restype = C.c_char_p
+        L.bioem_hip_set_own_launch.argtypes = [vp, ci]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -115,7 +121,9 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_kernel_name", "bioem_hip_kernel_signature", "bioem_hip_plan",
            "bioem_hip_synchronize", "bioem_hip_r2c", "bioem_hip_project", "bioem_hip_convolve",
            "bioem_hip_compare_device", "bioem_hip_max_batch", "bioem_hip_set_phase_timing", "bioem_hip_phase_records",
-           "bioem_hip_upload_particle_orientations", "bioem_hip_compare_own_orientations"]
+           "bioem_hip_upload_particle_orientations", "bioem_hip_compare_own_orientations",
+           "bioem_hip_upload_particle_orientation_lists", "bioem_hip_plan_own", "bioem_hip_own_kernel_signature",
+           "bioem_hip_set_own_launch"]
 
 
 def _p(a):
@@ -188,6 +196,18 @@ class Engine:
     def kernel_signature(self):
         return self.L.bioem_hip_kernel_signature(self.h).decode()
 
+    @property
+    def own_kernel_signature(self):
+        """what compare_own_orientations launches: "k_compare_fast_own<...>" (one launch per batch) or
+        "per particle: <kernel_signature>"""
+        return self.L.bioem_hip_own_kernel_signature(self.h).decode()
+
+    def set_own_launch(self, mode):
+        """how compare_own_orientations launches its comparison: "particle" (one launch per particle, the default),
+        "batch" (one launch per batch where the shape has the kernel, bioem_hip_plan_own) or "rows" (the same with the
+        block table in plain row order); results do not depend on it"""
+        self._chk(self.L.bioem_hip_set_own_launch(self.h, {"particle": 0, "batch": 1, "rows": 2}[mode]), "set_own_launch")
+
     def upload_particles(self, refFFT, sumRef, sumsqRef):
         refFFT = np.ascontiguousarray(refFFT, dtype=np.float32)
         assert refFFT.shape == (self.nMaps, self.N, self.H, 2)
@@ -224,6 +244,26 @@ class Engine:
         assert angles.ndim == 3 and angles.shape[0] == self.nMaps and angles.shape[2] == 4
         self._chk(self.L.bioem_hip_upload_particle_orientations(self.h, _p(angles), angles.shape[1], int(bool(isQuat))),
                   "upload_particle_orientations")
+
+    def upload_particle_orientation_lists(self, lists, isQuat=True):
+        """one orientation list per particle, of any length up to nAngles (an empty list leaves the particle out of the
+        pass): a sequence of nMaps arrays [K_p, 4], or the tuple (flat [n, 4], offsets [nMaps + 1]), offsets of an integer
+        type.  (The two cannot be confused: nMaps + 1 integers are a list of one particle of two only if nMaps is 2, and
+        three numbers are no list of quaternions.)"""
+        second = np.asarray(lists[1]) if isinstance(lists, tuple) and len(lists) == 2 else None
+        if second is not None and second.ndim == 1 and second.dtype.kind in "iu" and len(second) == self.nMaps + 1:
+            flat = np.ascontiguousarray(lists[0], dtype=np.float32).reshape(-1, 4)
+            offsets = np.ascontiguousarray(lists[1], dtype=np.int64)
+        else:
+            parts = [np.asarray(a, dtype=np.float32).reshape(-1, 4) for a in lists]
+            offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+            offsets[1:] = np.cumsum([len(a) for a in parts])
+            flat = np.ascontiguousarray(np.concatenate(parts, axis=0)) if parts else np.zeros((0, 4), dtype=np.float32)
+        assert len(offsets) == self.nMaps + 1 and (len(offsets) == 0 or offsets[-1] <= len(flat))
+        if len(flat) == 0:
+            flat = np.zeros((1, 4), dtype=np.float32)  # (a valid pointer; the library refuses the empty total)
+        self._chk(self.L.bioem_hip_upload_particle_orientation_lists(self.h, _p(flat), _p(offsets), int(bool(isQuat))),
+                  "upload_particle_orientation_lists")
 
     def prob_bytes(self):
         """bytes start_run / finish_run move: the whole block, or only the map entries for a shard handle"""

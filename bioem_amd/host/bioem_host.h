@@ -116,6 +116,10 @@ public:
   std::string outfileName = "Output_Probabilities";
   std::string refineFile;        // --RefineOrientations: the small grid of round 2 (empty: one round)
   std::vector<float> refineGrid; // its quaternions [G][4], read with the options
+  // --RefineSeeds M / --RefineLogWindow W: round 2 around up to M orientations per particle, the best of round 1 and
+  // those within W of its log posterior (lists of different lengths); M = 1: the best alone, today's run
+  int refineSeeds = 1;
+  double refineLogWindow = -1.; // < 0: unlimited
   std::vector<unsigned char> prob;              // merged map entries [nMaps]
   std::vector<bioem_hip_angle_candidate> cand;  // merged K best orientations [nMaps][K] (WRITE_PROB_ANGLES)
 
@@ -139,9 +143,13 @@ private:
   int readOptions(int argc, char **argv);
   void writeOutput();
   // Output_Probabilities text of a probability block; orientation(i, o) = the four numbers of orientation o of map i
+  // (angleOffsets: map i's list begins at entry angleOffsets[i] instead of anglesPerMap * i; voluPerMap: map i's own
+  // volume element in the constant of its log posterior -- the lists of round 2 differ in length)
   void writeProbabilities(const std::string &file, const bioem_hip_prob_map *pmap, const bioem_hip_param_device &pd,
-                          const float *angles, size_t anglesPerMap, bool angProb);
+                          const float *angles, size_t anglesPerMap, bool angProb, const long long *angleOffsets = nullptr,
+                          const float *voluPerMap = nullptr);
   void runRound2(); // --RefineOrientations: every particle against best (x) grid, OutputFile_Round2
+  void runRound2Seeds(); // the same around several seeds per particle (--RefineSeeds >= 2)
   std::vector<Shard> shards;
 };
 

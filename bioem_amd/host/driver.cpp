@@ -70,6 +70,8 @@ int Driver::readOptions(int ac, char **av)
                                        {"PrintBestCalMap", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
+                                       {"RefineSeeds", required_argument, 0, 0},
+                                       {"RefineLogWindow", required_argument, 0, 0},
                                        {"ReadPDB", no_argument, 0, 0},
                                        {"ReadModelMRC", no_argument, 0, 0},
                                        {"ReadMRC", no_argument, 0, 0},
@@ -90,6 +92,9 @@ int Driver::readOptions(int ac, char **av)
     printf("  --ReadOrientation arg  (Optional) Read file name containing orientations\n");
     printf("  --RefineOrientations arg (Optional) Second round: file with a small list of quaternions; every particle\n");
     printf("                         is evaluated again on its best orientation x that list (OutputFile_Round2)\n");
+    printf("  --RefineSeeds arg      (Optional) Second round around up to arg orientations per particle: the best of the\n");
+    printf("                         first round and the next ones in its ranking (default 1)\n");
+    printf("  --RefineLogWindow arg  (Optional) ... of which only those within arg of the best log posterior\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
     printf("  --ReadMRC              (Optional) If reading particle file in MRC format\n");
@@ -158,6 +163,20 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Refining orientations (second round) with the list: " << optarg << "\n";
       refineFile = optarg;
     }
+    else if (name == "RefineSeeds")
+    {
+      refineSeeds = atoi(optarg);
+      if (refineSeeds < 1)
+        fatal("--RefineSeeds needs a positive number");
+      std::cout << "Second round around up to " << refineSeeds << " orientations per particle\n";
+    }
+    else if (name == "RefineLogWindow")
+    {
+      refineLogWindow = atof(optarg);
+      if (!(refineLogWindow >= 0.))
+        fatal("--RefineLogWindow needs a non-negative number");
+      std::cout << "Second round: seeds within " << refineLogWindow << " of the best log posterior\n";
+    }
     else if (name == "OutputFile")
     {
       std::cout << "Writing OUTPUT to: " << optarg << "\n";
@@ -189,6 +208,8 @@ int Driver::readOptions(int ac, char **av)
   if (particles.readMultMRC && !particles.readMRC)
     fatal("For multiple MRCs command --ReadMRC is necessary too");
   param.readParameters(infile.c_str());
+  if (refineFile.empty() && (refineSeeds != 1 || refineLogWindow >= 0.))
+    fatal("--RefineSeeds / --RefineLogWindow go with --RefineOrientations");
   if (!refineFile.empty())
   { // round 2 multiplies quaternions and evaluates lists of its own: no prior per orientation, no ANG_PROB (yet)
     if (!param.doquater)
@@ -202,6 +223,10 @@ int Driver::readOptions(int ac, char **av)
   particles.readRefMaps(param, mapfile.c_str());
   model.readModel(param, modelfile.c_str());
   param.calculateGridsParam(anglefile.c_str());
+  // several seeds per particle: round 1 keeps its angle table on the device, for the seed selection only (ANG_PROB is
+  // not written, OutputFile is what it is without the option)
+  if (refineSeeds >= 2)
+    param.pd.writeAngles = std::min(refineSeeds, param.nTotGridAngles);
   return 0;
 }
 
@@ -505,7 +530,12 @@ int Driver::run()
   }
   writeOutput();
   if (!refineFile.empty())
-    runRound2();
+  {
+    if (refineSeeds >= 2)
+      runRound2Seeds();
+    else
+      runRound2();
+  }
   return 0;
 }
 
@@ -569,6 +599,93 @@ void Driver::runRound2()
   writeProbabilities(outfileName + "_Round2", pm.data(), pd2, lists.data(), (size_t) G, false);
 }
 
+// best (x) grid: the Hamilton product in (x, y, z, w) storage, normalised; the identity of the grid gives `best` bit for bit
+static void compose_list(const float *b, const std::vector<float> &grid, float *out)
+{
+  const int G = (int) (grid.size() / 4);
+  const double bx = b[0], by = b[1], bz = b[2], bw = b[3];
+  for (int k = 0; k < G; k++)
+  {
+    const float *g = grid.data() + 4 * (size_t) k;
+    float *o = out + 4 * (size_t) k;
+    if (g[0] == 0.f && g[1] == 0.f && g[2] == 0.f && g[3] == 1.f)
+    {
+      memcpy(o, b, 4 * sizeof(float));
+      continue;
+    }
+    const double gx = g[0], gy = g[1], gz = g[2], gw = g[3];
+    const double q[4] = {bw * gx + bx * gw + by * gz - bz * gy, bw * gy - bx * gz + by * gw + bz * gx,
+                         bw * gz + bx * gy - by * gx + bz * gw, bw * gw - bx * gx - by * gy - bz * gz};
+    const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int c = 0; c < 4; c++)
+      o[c] = (float) (q[c] / nrm);
+  }
+}
+
+// Round 2 around SEVERAL orientations per particle (--RefineSeeds M >= 2, --RefineLogWindow W): the seeds of particle p
+// are the first of its M best orientations of round 1 (the ANG_PROB ranking: bioem_hip_topk_angles, or the merged top-K
+// over shards) and those of the others whose log posterior lies within W of the first's, in that order; its list is the
+// concatenation of seed (x) grid over its seeds, no duplicates removed (bioem_amd/refine.py: seed_lists).  The lists
+// differ in length, and the line of particle p carries ITS constant: volu of a list of K_p orientations, what a run on
+// that particle alone with its list through --ReadOrientation prints.
+void Driver::runRound2Seeds()
+{
+  const std::vector<float> &grid = refineGrid;
+  const int G = (int) (grid.size() / 4), nMaps = particles.ntot, nC = param.nTotCTFs, K = param.pd.writeAngles;
+  std::vector<long long> offsets(1, 0);
+  std::vector<float> lists;
+  std::vector<float> volu(nMaps);
+  int longest = 0;
+  for (int i = 0; i < nMaps; i++)
+  {
+    int nSeeds = 0;
+    double first = 0.;
+    for (int r = 0; r < K && nSeeds < refineSeeds; r++)
+    {
+      const bioem_hip_angle_candidate &c = cand[(size_t) i * K + r];
+      if (c.orient < 0)
+        continue;
+      if (nSeeds == 0)
+        first = c.logp;
+      else if (refineLogWindow >= 0. && !(c.logp >= first - refineLogWindow))
+        continue;
+      lists.resize(lists.size() + 4 * (size_t) G);
+      compose_list(param.angles.data() + 4 * (size_t) c.orient, grid, lists.data() + lists.size() - 4 * (size_t) G);
+      nSeeds++;
+    }
+    const int Kp = nSeeds * G;
+    offsets.push_back(offsets.back() + Kp);
+    longest = std::max(longest, Kp);
+    volu[i] = volume_element((float) (1. / (float) std::max(1, Kp) * param.priorMod), param.pd.GridSpaceCenter,
+                             param.pd.maxDisplaceCenter, param.pixelSize, param.numberGridPointsCTF_amp, param.gridEnvelop,
+                             param.gridCTF_phase, param.pd.sigmaPriorbctf, param.pd.sigmaPriordefo, param.pd.sigmaPrioramp);
+  }
+  std::cout << "Second round: " << offsets.back() << " orientations for " << nMaps << " particles, " << G
+            << " per seed, at most " << longest << " per particle\n";
+  bioem_hip_param_device pd2 = param.pd;
+  pd2.writeAngles = 0;
+  bioem_hip_handle h = nullptr;
+  check(h, bioem_hip_create(&h, firstDev, &pd2, nMaps, std::max(1, longest), nC, algo), "bioem_hip_create (second round)");
+  check(h, bioem_hip_upload_particle_maps(h, particles.maps.data()), "upload particles");
+  check(h, bioem_hip_upload_ctf(h, param.refCTF.data(), param.ctfParam.data()), "upload CTF");
+  check(h, bioem_hip_upload_model(h, model.points.data(), (int) model.points.size(), model.NormDen, param.pixelSize,
+                                  param.shiftX, param.shiftY),
+        "upload model");
+  check(h, bioem_hip_upload_particle_orientation_lists(h, lists.data(), offsets.data(), 1), "upload particle orientation lists");
+  std::vector<bioem_hip_prob_map> pm(nMaps);
+  for (int i = 0; i < nMaps; i++) // bioem.cpp:681-699
+  {
+    memset(&pm[i], 0, sizeof(pm[i]));
+    pm[i].Total = 0.0;
+    pm[i].Constoadd = -999999.;
+  }
+  check(h, bioem_hip_start_run(h, pm.data()), "start run (second round)");
+  check(h, bioem_hip_compare_own_orientations(h, 0, nMaps), "compare own orientations");
+  check(h, bioem_hip_finish_run(h, pm.data()), "finish run (second round)");
+  bioem_hip_destroy(h);
+  writeProbabilities(outfileName + "_Round2", pm.data(), pd2, lists.data(), 0, false, offsets.data(), volu.data());
+}
+
 void Driver::cleanup()
 {
   for (Shard &sh : shards)
@@ -583,13 +700,16 @@ void Driver::cleanup()
 // Output_Probabilities and ANG_PROB, text layout of bioem.cpp:1047-1374 (fixed, 4 decimals).
 void Driver::writeOutput()
 {
-  writeProbabilities(outfileName, (const bioem_hip_prob_map *) prob.data(), param.pd, param.angles.data(), 0, true);
+  // (--RefineSeeds >= 2 set writeAngles for the seed selection: no ANG_PROB then)
+  writeProbabilities(outfileName, (const bioem_hip_prob_map *) prob.data(), param.pd, param.angles.data(), 0,
+                     refineSeeds < 2);
 }
 
 // angles: the list max_prob_orient indexes -- one for all maps (anglesPerMap = 0) or anglesPerMap entries per map (the
 // second round); angProb: ANG_PROB is written beside it when pd.writeAngles asks for it
 void Driver::writeProbabilities(const std::string &file, const bioem_hip_prob_map *pmap, const bioem_hip_param_device &pd,
-                                const float *angles, size_t anglesPerMap, bool angProb)
+                                const float *angles, size_t anglesPerMap, bool angProb, const long long *angleOffsets,
+                                const float *voluPerMap)
 {
   const int nMaps = particles.ntot;
   const bool writeAng = angProb && pd.writeAngles;
@@ -642,7 +762,7 @@ void Driver::writeProbabilities(const std::string &file, const bioem_hip_prob_ma
     if (pm.Total > 1.e-38)
     {
       const double lp = log(pm.Total) + pm.Constoadd + 0.5 * log(M_PI) +
-                        (1 - pd.Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(pd.volu);
+                        (1 - pd.Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(voluPerMap ? voluPerMap[i] : pd.volu);
       out << "RefMap: " << i << " LogProb:  " << lp << " Constant: " << pm.Constoadd << "\n";
       out << "RefMap: " << i << " Maximizing Param: " << lp << " ";
     }
@@ -652,7 +772,7 @@ void Driver::writeProbabilities(const std::string &file, const bioem_hip_prob_ma
       out << "Warning - RefMap: " << i << "Check that constant is finite: " << pm.Constoadd << "\n";
       out << "Warning - RefMap: i) check model, ii) check refmap , iii) check GPU on/off command inconsitency\n";
     }
-    const float *A = angles + 4 * anglesPerMap * (size_t) i; // this map's list
+    const float *A = angles + 4 * (angleOffsets ? (size_t) angleOffsets[i] : anglesPerMap * (size_t) i); // this map's list
     const float *a = A + 4 * (size_t) pm.max_prob_orient;
     const float *k = K + 3 * (size_t) pm.max_prob_conv;
     out << a[0] << " [] " << a[1] << " [] " << a[2] << " [] ";

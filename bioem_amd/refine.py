@@ -1,6 +1,7 @@
 """Orientation lists of a second, local round ("round 2" of the manual's model-comparison example, doc/index.rst
 section modcom): every particle's best orientation of round 1 multiplied with a small grid of rotations.  numpy only,
-no device; the lists go to Engine.upload_particle_orientations / compare_own_orientations.
+no device; the lists go to Engine.upload_particle_orientations (one length) or upload_particle_orientation_lists (seed_lists:
+as many seeds per particle as carry its round-1 posterior) and compare_own_orientations.
 
 Quaternions are stored as the reference stores them, (x, y, z, w) with w = quat4 (bioem.cpp:1630-1646)."""
 import numpy as np
@@ -58,3 +59,39 @@ def refine_lists(angles, pmap, grid):
     pmap its probability block (pmap["orient"][p] = best orientation of particle p)."""
     angles = np.asarray(angles)
     return compose(angles[np.asarray(pmap["orient"], dtype=np.int64)], grid)
+
+
+def seed_lists(angles, cands, grid, max_seeds=1, log_window=np.inf):
+    """Round-2 lists around SEVERAL round-1 orientations per particle: a sharp particle needs one seed, an ambiguous one
+    the few that carry its posterior.
+
+    angles[nAngles, 4]: the round-1 quaternion list; cands[nMaps][K]: the candidates of Engine.topk_angles (fields
+    "orient", "logp"), best first, orient = -1 beyond the owned count.  Particle p keeps at most max_seeds seeds in
+    candidate order: always the first, then those with logp >= logp_first - log_window.  Its list is the concatenation
+    of compose(seed, grid) over its seeds (no duplicate removal), so entry 0 of every seed's block is the seed itself
+    where the grid's first entry is the identity.  Returns (flat float32 [n, 4], offsets int64 [nMaps + 1])."""
+    angles = np.asarray(angles)
+    grid = np.asarray(grid)
+    assert max_seeds >= 1 and log_window >= 0
+    G = len(grid)
+    parts, offsets = [], [0]
+    for row in cands:
+        orient = np.asarray(row["orient"], dtype=np.int64)
+        logp = np.asarray(row["logp"], dtype=np.float64)
+        seeds = []
+        first = None
+        for o, l in zip(orient, logp):
+            if o < 0:
+                continue
+            if first is None:
+                first = l
+            elif not l >= first - log_window:
+                continue
+            seeds.append(int(o))
+            if len(seeds) == max_seeds:
+                break
+        if seeds:
+            parts.append(compose(angles[seeds], grid).reshape(len(seeds) * G, 4))
+        offsets.append(offsets[-1] + len(seeds) * G)
+    flat = np.concatenate(parts, axis=0) if parts else np.zeros((0, 4), dtype=np.float32)
+    return np.ascontiguousarray(flat, dtype=np.float32), np.asarray(offsets, dtype=np.int64)

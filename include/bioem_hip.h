@@ -130,6 +130,14 @@ int bioem_hip_upload_orientations(bioem_hip_handle h, const float *angles4, int 
  * The pipeline buffers of the handle grow to the batches of that pass (up to 1 024 list entries each: several GB at
  * large images) and stay that size; when that memory is not there the call returns 1 and the handle is as it was. */
 int bioem_hip_upload_particle_orientations(bioem_hip_handle h, const float *angles4, int K, int isQuat);
+/* The same with lists of any length: particle p owns entries offsets[p] ... offsets[p + 1] of angles4 (offsets[nMaps + 1],
+ * offsets[0] = 0, non-decreasing, every length <= nAngles of the handle).  A particle with an empty list takes no part in
+ * the pass: its entries of the probability block stay as bioem_hip_start_run left them.  Returns 2 with a message for
+ * offsets[0] != 0, decreasing offsets, a list longer than nAngles, an empty total and the handle kinds refused above; the
+ * handle stays usable (and keeps the lists it had).  bioem_hip_upload_particle_orientations is the offsets[p] = p K case
+ * of this entry. */
+int bioem_hip_upload_particle_orientation_lists(bioem_hip_handle h, const float *angles4, const long long *offsets,
+                                                int isQuat);
 
 /* bioem::malloc_device_host / free_device_host (bioem.h:56-57; bioem_cuda.cu:1037-1053): pinned host memory
  * for the probability block. */
@@ -165,8 +173,19 @@ int bioem_hip_project_convolve_compare_ctf(bioem_hip_handle h, int iOrientBegin,
  * max_prob_orient is the index in THAT particle's list, and with WRITE_PROB_ANGLES entry (k, p) of the
  * [nAngles][nMaps] table receives list entry k of particle p.  Entries of particles outside the range are not touched.
  * Asynchronous like the fused entry; start_run / finish_run as usual.  Phase records of this pass carry the range of
- * slots p * K + k of a batch in iOrientBegin / iOrientEnd. */
+ * flat slots offsets[p] + k of a batch in iOrientBegin / iOrientEnd.  A batch is compared by one launch per particle, or,
+ * after bioem_hip_set_own_launch, by ONE launch of k_compare_fast_own where the shape runs k_compare_fast
+ * (bioem_hip_own_kernel_signature says which); the two give the same bits. */
 int bioem_hip_compare_own_orientations(bioem_hip_handle h, int iMapBegin, int iMapEnd);
+/* How that pass launches its comparison, from the next call on: one launch per particle (the default of every handle),
+ * or one launch per batch where the shape has the kernel for it (bioem_hip_plan_own; its block table with a particle's
+ * blocks on one XCD, or in plain row order; elsewhere the call changes nothing).  Results do not depend on it, bit for
+ * bit.  The single launch is opt-in: it has not been measured against the per-particle launches on one device yet.
+ * Returns 2 for an unknown mode. */
+#define BIOEM_HIP_OWN_LAUNCH_PARTICLE 0
+#define BIOEM_HIP_OWN_LAUNCH_BATCH 1
+#define BIOEM_HIP_OWN_LAUNCH_BATCH_ROWS 2
+int bioem_hip_set_own_launch(bioem_hip_handle h, int mode);
 
 /* The same three stages as separate entries, for an integrator who keeps the reference's loop (bioem.cpp:763-891) and
  * replaces its body piece by piece: every call is asynchronous and batched, and what one stage produces stays on the
@@ -265,6 +284,12 @@ const char *bioem_hip_kernel_signature(bioem_hip_handle h);
  * instantiation -- and " x T^2 tiles of R rows" for a tiled wide window -- into signature[cap]; 0 on success, 1 when no
  * kernel fits, 2 on invalid arguments. */
 int bioem_hip_plan(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo, char *signature, int cap);
+/* What bioem_hip_compare_own_orientations launches for a configuration once bioem_hip_set_own_launch has asked for one
+ * launch per batch, without a device: "k_compare_fast_own<...>" where the shape has that kernel, else the signature of
+ * bioem_hip_plan prefixed "per particle: " (such a shape keeps per-particle launches in every mode).  Same return codes. */
+int bioem_hip_plan_own(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo, char *signature, int cap);
+/* what a handle launches in the mode it is in: "per particle: ..." until bioem_hip_set_own_launch says otherwise */
+const char *bioem_hip_own_kernel_signature(bioem_hip_handle h);
 int bioem_hip_synchronize(bioem_hip_handle h);
 
 #ifdef __cplusplus
