@@ -1395,6 +1395,16 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
   std::vector<double2> twd(N);
   for (int k = 0; k <= N; k++)
     tw[k] = twiddle(k, N);
+  if (P.family == KF_FAST && sym_window_ok(P.winD, 2 * P.halfR, P.nyq, P.gs))
+  { // window pass over |dy| (compare_args.hpp): cos | sin (2 pi ky j gs / N) per column pair, j = 0..10, behind the
+    // twiddles; whole column blocks (the columns beyond H meet zeros of T, entry 11 is never used: zeros)
+    const size_t nPairs = (size_t) ((h->H + 63) / 64) * 32;
+    tw.resize(sym_table_offset(N) + nPairs * kSymEntries * 2, make_float2(0.f, 0.f));
+    for (size_t kp = 0; kp < nPairs; kp++)
+      for (int j = 0; j <= 10; j++)
+        for (int e = 0; e < 2; e++)
+          tw[sym_table_offset(N) + (kp * kSymEntries + j) * 2 + e] = twiddle((long long) (2 * kp + e) * j * P.gs, N);
+  }
   for (int k = 0; k < N; k++)
     twd[k] = twiddle_d(k, N);
   // log table: bin i of the mantissa interval [1,2): c = 1/centre, entry {c, -log(c)}

@@ -37,6 +37,27 @@ struct CompareArgs
   PD pd;
 };
 
+// k_compare_fast, static 21-row window: the window pass over |dy| (window_accumulate_sym, compare_fast.hpp) reads
+//   symtab[column pair kp][j] = {cos, sin (2 pi (2 kp) j gs / N), cos, sin (2 pi (2 kp + 1) j gs / N)},  j = |dy| / gs
+// kSymEntries float4 per column pair (|dy| = 0..10 and one entry of zeros: the third lane group reads four entries as the
+// others do), for the pairs of whole 64-column blocks.  The table lies BEHIND the N + 1 twiddles in CompareArgs::tw (the
+// argument block stays as it is); a block keeps the slice of its current column block in the LDS.
+constexpr int kSymEntries = 12;
+constexpr int kSymSliceFloat2 = 32 * kSymEntries * 2; // float2 per column block
+constexpr int kSymSliceBytes = kSymSliceFloat2 * 8;
+// which instantiations k_compare_fast<WD, R, NYQ, GS> take that pass (the others keep window_accumulate): the 21-row
+// kernels, except the register FFTs of 20, 30 and 32 points -- at the 168-register bound of three waves per SIMD already,
+// they spill 1, 5 and 12...17 registers with the eighth accumulator and the table prefetch
+constexpr bool sym_window_ok(int WD, int R, bool NYQ, int GS) { return WD == 10 && R <= 18; }
+// first float2 of the table in CompareArgs::tw
+__host__ __device__ constexpr int sym_table_offset(int N) { return (N + 2) & ~1; }
+// head of the fast kernels' LDS: the twiddles, or -- a launch of the static window reads none -- the table slice
+__host__ __device__ constexpr size_t fast_head_bytes(int N, bool sym)
+{
+  const size_t twBytes = (size_t) ((N + 2) & ~1) * 8;
+  return sym && twBytes < (size_t) kSymSliceBytes ? (size_t) kSymSliceBytes : twBytes;
+}
+
 } // namespace
 
 #endif

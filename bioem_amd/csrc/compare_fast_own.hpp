@@ -30,21 +30,29 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast_own(const CompareArgs a
   constexpr int NR = (WD <= 5) ? 3 : 7; // accumulators (window rows) per lane
   // T row stride in float2 (64 columns + 2 pad: row groups land on different banks)
   constexpr int TS = 66;
+  // the static 21-row window runs the pass over |dy| (window_accumulate_sym): 8 accumulators per lane, and the head of
+  // the LDS holds the slice of the cos | sin table for the current column block instead of the twiddles
+  constexpr bool SYM = sym_window_ok(WD, R, NYQ, GS);
+  constexpr int NA = SYM ? 8 : NR;
   extern __shared__ __align__(16) unsigned char smem[];
   const int N = a.N, H = a.H, N1 = a.N1;
-  float2 *twl = reinterpret_cast<float2 *>(smem);                            // N+1 (+pad)
-  int *displ = reinterpret_cast<int *>(smem + (size_t) ((N + 2) & ~1) * 8); // nd ints (256 B reserved)
-  double2 *ltab = reinterpret_cast<double2 *>(smem + (size_t) ((N + 2) & ~1) * 8 + 256); // 64 entries
-  float2 *Tall = reinterpret_cast<float2 *>(smem + (size_t) ((N + 2) & ~1) * 8 + 256 + 1024);
+  const size_t headBytes = fast_head_bytes(N, SYM);
+  float2 *twl = reinterpret_cast<float2 *>(smem);                 // N+1 (+pad), or the table slice
+  int *displ = reinterpret_cast<int *>(smem + headBytes);         // nd ints (256 B reserved)
+  double2 *ltab = reinterpret_cast<double2 *>(smem + headBytes + 256); // 64 entries
+  float2 *Tall = reinterpret_cast<float2 *>(smem + headBytes + 256 + 1024);
   // wave index made provably uniform (SGPR) so that per-wave base pointers use scalar addressing
   const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   float2 *Tl = Tall + (size_t) wave * NW * TS;
 
-  for (int t = threadIdx.x; t <= N; t += blockDim.x)
-    twl[t] = a.tw[t];
   int *dinv = displ + 32; // visiting rank of window row m (displacement m*GS), index m + mD
   const int mD = a.maxD / GS;
+  // (the rows -WD..WD, all of them: what is_static below says of a 21-row window)
+  const bool symw = SYM && a.nd == NW && mD == WD;
+  if (!symw)
+    for (int t = threadIdx.x; t <= N; t += blockDim.x)
+      twl[t] = a.tw[t];
   for (int t = threadIdx.x; t < a.nd; t += blockDim.x)
   {
     const int dv = a.disp[t];
@@ -84,10 +92,15 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast_own(const CompareArgs a
   // NR CONSECUTIVE rows of it in sorted order, whatever the visiting order of the algorithm (ALGO 1 visits
   // 0..maxD, -maxD..-1); dinv[] translates back to visiting ranks for the arg-max bookkeeping
   const bool is_static = (nr == NR) && (nd == G * NR) && (nd == 2 * mD + 1);
-  float acc[NR];
+  float acc[NA];
 #pragma unroll
-  for (int r = 0; r < NR; r++)
+  for (int r = 0; r < NA; r++)
     acc[r] = 0.f;
+  // window_accumulate_sym: lane = 3 * row + group (lane 63 reads row 20 and is dropped later)
+  const int srow = min(lane / 3, NW - 1), sgrp = lane % 3;
+  const float2 *Trow = Tl + srow * TS;
+  const float4 *stab = reinterpret_cast<const float4 *>(smem) + sgrp * 4;
+  const float2 *symsrc = a.tw + sym_table_offset(N) + threadIdx.x;
   // T row (in float2 units) of accumulator r of this lane; idle lanes (grp >= G) read rows 0.. and are dropped
   // later.  Only the first is kept live across the column loop: the static window uses base + r*TS, the general
   // one re-reads its rows from the displacement list per block.
@@ -146,6 +159,14 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast_own(const CompareArgs a
     {
       Tr[d] = 0.f;
       Ti[d] = 0.f;
+    }
+    // table slice of this column block: 24 bytes per thread, requested now and put into the LDS with the T block
+    float2 tabv[3] = {};
+    if (symw)
+    {
+#pragma unroll
+      for (int u = 0; u < 3; u++)
+        tabv[u] = symsrc[blk * kSymSliceFloat2 + u * 256];
     }
     // lanes beyond the last column of the last block sit out the whole transform (EXEC masked once): their
     // loads would only burn vector-memory cycles, and their T columns stay zero
@@ -225,10 +246,21 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast_own(const CompareArgs a
 #pragma unroll
       for (int d = 0; d < NW; d++)
         Tl[d * TS + lane] = make_float2(Tr[d] * wgt, Ti[d] * wgt);
+      if (symw)
+      {
+#pragma unroll
+        for (int u = 0; u < 3; u++)
+          twl[u * 256 + threadIdx.x] = tabv[u];
+      }
       __syncthreads();
       const int idx0 = (int) (((long long) (blk * 64) * step) % N);
       const int npairs = min(32, (H - blk * 64 + 1) >> 1); // columns of this block that exist, in pairs
-      if (is_static)
+      if (symw)
+      {
+        if constexpr (SYM)
+          window_accumulate_sym<TS>(Trow, stab, acc, npairs);
+      }
+      else if (!SYM && is_static)
       {
         const int rowoff[NR] = {rowbase};
         window_accumulate<NR, true, 32, TS>(Tl, twl, N, step, idx0, rowoff, nr, acc, npairs);
@@ -247,9 +279,21 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast_own(const CompareArgs a
   {
     const float *tq = a.tnyq + (size_t) oc * NW; // OWN: one set of Nyquist rows per row of the launch
     const float sg = (dy & 1) ? -1.f : 1.f;
+    if (symw)
+    { // the column's term is real: it enters A only, with the sign of (-1)^|dy|
+      if constexpr (SYM)
+      {
 #pragma unroll
-    for (int r = 0; r < NR; r++)
-      acc[r] = fmaf(sg, tq[is_static ? rowbase / TS + r : row_of(r) / TS], acc[r]);
+        for (int j = 0; j < 4; j++)
+          acc[j] = fmaf((((sgrp * 4 + j) * GS) & 1) ? -1.f : 1.f, tq[srow], acc[j]);
+      }
+    }
+    else
+    {
+#pragma unroll
+      for (int r = 0; r < NR; r++)
+        acc[r] = fmaf(sg, tq[is_static ? rowbase / TS + r : row_of(r) / TS], acc[r]);
+    }
   }
 
   const double2 pc = a.postc[oc];
@@ -262,22 +306,41 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast_own(const CompareArgs a
   {
     // the NR displacements of this lane as one batch (posterior_batch: exact division by N^2 in three instructions,
     // the log-table reads issued together, one log-sum-exp rescale)
-    constexpr int PB = NR > 8 ? 8 : NR;
+    constexpr int PB = NA > 8 ? 8 : NA;
 #pragma unroll
-    for (int r0 = 0; r0 < NR; r0 += PB)
+    for (int r0 = 0; r0 < NA; r0 += PB)
     {
       float accv[PB];
       int idv[PB];
       bool okv[PB];
+      if (symw)
+      { // slot 2 q: dy = +(4 g + q) rows, A - B; slot 2 q + 1: dy = -(4 g + q) rows, A + B (dy = 0 once; 4 g + q <= WD)
+        if constexpr (SYM)
+        {
+          const int ixv = dinv[srow];
 #pragma unroll
-      for (int j = 0; j < PB; j++)
+          for (int j = 0; j < 8; j++)
+          {
+            const int q = j >> 1, m = sgrp * 4 + q;
+            const int iyv = dinv[min(max((j & 1) ? mD - m : mD + m, 0), 31)];
+            okv[j] = lane < 3 * NW && m <= WD && !((j & 1) && m == 0) && srow < a.ndx && iyv < a.ndy;
+            accv[j] = (j & 1) ? acc[q] + acc[4 + q] : acc[q] - acc[4 + q];
+            idv[j] = ixv * nd + iyv;
+          }
+        }
+      }
+      else
       {
-        const int r = r0 + j < NR ? r0 + j : NR - 1;
-        const int ixs = grp * nr + r; // position in the lane-group order; ix = visiting rank of that displacement
-        okv[j] = r0 + j < NR && r < nr && wactive && ixs < a.ndx && iy < a.ndy;
-        const int ix = is_static ? dinv[min(ixs, 31)] : ixs;
-        accv[j] = acc[r];
-        idv[j] = ix * nd + iy;
+#pragma unroll
+        for (int j = 0; j < PB; j++)
+        {
+          const int r = r0 + j < NR ? r0 + j : NR - 1;
+          const int ixs = grp * nr + r; // position in the lane-group order; ix = visiting rank of that displacement
+          okv[j] = r0 + j < NR && r < nr && wactive && ixs < a.ndx && iy < a.ndy;
+          const int ix = is_static ? dinv[min(ixs, 31)] : ixs;
+          accv[j] = acc[r];
+          idv[j] = ix * nd + iy;
+        }
       }
       posterior_batch<PB>(L, accv, idv, okv, pw, ltab, a.algo);
     }

@@ -121,9 +121,10 @@ size_t compare_lds_bytes(int N, int H, int NW, int waves, int rows = 0)
   const size_t dispBytes = ((size_t) NW * 4 + 255) & ~(size_t) 255;
   return (size_t) ((N + 2) & ~1) * 8 + dispBytes + (size_t) waves * (rows ? rows : NW) * Hs * 8;
 }
-size_t fast_lds_bytes(int N, int NW, int waves)
-{ // fast / rows kernels: twiddles + displacement list + log table + per-wave T block [NW][66]
-  return (size_t) ((N + 2) & ~1) * 8 + 256 + 1024 + (size_t) waves * NW * 66 * 8;
+size_t fast_lds_bytes(int N, int NW, int waves, bool sym = false)
+{ // fast / rows kernels: twiddles (sym, k_compare_fast with the window pass over |dy|: or the table slice of a column
+  // block, compare_args.hpp) + displacement list + log table + per-wave T block [NW][66]
+  return fast_head_bytes(N, sym) + 256 + 1024 + (size_t) waves * NW * 66 * 8;
 }
 size_t fastm_lds_bytes(int N)
 { // cos / sin planes of the twiddle table (padded), window ranks, log table, per wave two 32 x 33 float planes and the
@@ -386,7 +387,8 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
     {
       const int R = winD == 5 ? 8 : 16;
       if (const fast_kernel_t fn = find_kernel(KF_FAST, winD, R, true, P.gs))
-        return take_window(P, KF_FAST, fn, N, R, true, winD, fast_lds_bytes(N, 2 * winD + 1, 4));
+        return take_window(P, KF_FAST, fn, N, R, true, winD,
+                           fast_lds_bytes(N, 2 * winD + 1, 4, sym_window_ok(winD, R, true, P.gs)));
     }
     std::vector<int> lens;
     if (nyq)
@@ -431,7 +433,7 @@ bool plan_window_kernel(KernelPlan &P, int N, int H, int winD, bool untiled)
           find_kernel(KF_FAST, 10, R, nyq, P.gs))
         wd = 10;
       if (const fast_kernel_t fn = find_kernel(KF_FAST, wd, R, nyq, P.gs))
-        return take_window(P, KF_FAST, fn, N, R, nyq, wd, fast_lds_bytes(N, 2 * wd + 1, 4));
+        return take_window(P, KF_FAST, fn, N, R, nyq, wd, fast_lds_bytes(N, 2 * wd + 1, 4, sym_window_ok(wd, R, nyq, P.gs)));
     }
     return false;
   }
