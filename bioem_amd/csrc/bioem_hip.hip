@@ -44,6 +44,8 @@
 //                          of any length: bioem_hip_compare_own_orientations)
 //   compare_fast_own.hpp k_compare_fast_own, k_nyquist_rows_own (kernels_fast_own.hip): k_compare_fast with a block table,
 //                          one launch per batch of the own-list pass; the other families: one launch per particle
+//   render_kernels.hpp   k_render_gather, k_render_cols, k_render_rows  bioem_hip_render_best_maps: the calculated image of
+//                          every particle's best-match record (bioem.cpp:1925-2085), the full c2r by exact DFT in double
 //   this file            device context, launch logic, the C ABI
 //   kernels_*.hip        one translation unit per comparison-kernel family (the instantiations of kernel_table.inc),
 //                          linked into the same library: kernels_fast, kernels_fastm, kernels_wide2_{short,16,long},
@@ -108,6 +110,7 @@ struct HipErr
 #include "kernel_select.hpp"
 #include "fold_kernels.hpp"
 #include "window_tiles.hpp"
+#include "render_kernels.hpp"
 
 struct bioem_hip_ctx
 {
@@ -190,6 +193,11 @@ struct bioem_hip_ctx
   unsigned char *dSend = nullptr, *dRecv = nullptr; // RCCL merge buffers
   size_t sendBytes = 0, recvBytes = 0;
   bioem_hip_prob_map *dMerged = nullptr;
+  // bioem_hip_render_best_maps: the records, gathered orientations and maps of one batch (allocated at the first call)
+  RenderRecord *dRenderRec = nullptr;
+  float4 *dRenderAngles = nullptr;
+  float *dRenderOut = nullptr;
+  bool ctfUp = false; // bioem_hip_upload_ctf has run
 
   // two pipeline slots + a second stream: projection/convolution of batch k+1 (prepStream) overlap the comparison of
   // batch k.  Slot 0's projection buffers also stage the particle uploads and the debug hooks.
@@ -1534,6 +1542,7 @@ int bioem_hip_upload_ctf(bioem_hip_handle h, const float *refCTF, const float *c
   HIP_CHECK(h, hipSetDevice(h->device));
   HIP_CHECK(h, hipMemcpy(h->dCTF, refCTF, sizeof(float2) * (size_t) h->M * h->nCTF, hipMemcpyHostToDevice));
   HIP_CHECK(h, hipMemcpy(h->dCtfParam, ctfParam3, sizeof(float) * 3 * h->nCTF, hipMemcpyHostToDevice));
+  h->ctfUp = true;
   return 0;
 }
 
@@ -2431,6 +2440,110 @@ int bioem_hip_merge(bioem_hip_handle *handles, int n, void *pProbMaps_host, int 
       ptrs[s] = gathered[s].data();
     return bioem_hip_merge_topk_host(n, nMaps, K, ptrs.data(), cand_host);
   }
+  return 0;
+}
+
+// ---- the calculated image of the best-match records (bioem::printModel, bioem.cpp:624-657, 1925-2085) ----
+int bioem_hip_render_best_maps(bioem_hip_handle h, const bioem_hip_prob_map *records, int ownLists, int iMapBegin,
+                               int iMapEnd, float *maps_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[256];
+  auto refuse = [&](const char *why) {
+    h->err = std::string("render_best_maps: ") + why;
+    return 2;
+  };
+  if (!records || !maps_out)
+    return refuse("null argument");
+  if (iMapBegin < 0 || iMapEnd > h->nMaps || iMapBegin >= iMapEnd)
+    return refuse("particle range empty, reversed or outside [0, nMaps)");
+  if (!h->dPts || h->nPts < 1)
+    return refuse("model not uploaded");
+  if (!h->ctfUp)
+    return refuse("CTF kernels not uploaded");
+  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
+    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
+                           : "orientations not uploaded");
+  const int N = h->N, H = h->H;
+  std::vector<RenderRecord> recs((size_t) (iMapEnd - iMapBegin));
+  for (int p = iMapBegin; p < iMapEnd; p++)
+  {
+    const bioem_hip_prob_map &r = records[p];
+    const int first = ownLists ? h->ownOff[p] : 0, len = ownLists ? h->ownOff[p + 1] - h->ownOff[p] : h->nAnglesUp;
+    const char *why = nullptr;
+    if (r.max_prob_orient < 0 || r.max_prob_orient >= len)
+      why = "max_prob_orient outside its orientation list";
+    else if (r.max_prob_conv < 0 || r.max_prob_conv >= h->nCTF)
+      why = "max_prob_conv outside [0, nCTF)";
+    else if (r.max_prob_cent_x <= -N || r.max_prob_cent_x >= N || r.max_prob_cent_y <= -N || r.max_prob_cent_y >= N)
+      why = "displacement of N pixels or more";
+    if (why)
+    {
+      snprintf(buf, sizeof(buf), "particle %d: %s (orient %d of %d, conv %d, cent %d %d)", p, why, r.max_prob_orient, len,
+               r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y);
+      return refuse(buf);
+    }
+    recs[(size_t) (p - iMapBegin)] = {first + r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y,
+                                      r.max_prob_norm, r.max_prob_mu};
+  }
+  const int OB = h->OB; // maxOrientations of bioem_hip_max_batch; slot 0 holds at least that many images
+  const size_t NN = (size_t) N * N, lds = sizeof(double2) * 2 * (size_t) N;
+  if (!h->dRenderOut)
+  { // a failed allocation (return 1) leaves the handle as it was
+    RenderRecord *rec = nullptr;
+    float4 *ang = nullptr;
+    float *out = nullptr;
+    if (dev_alloc(h, rec, (size_t) OB) || dev_alloc(h, ang, (size_t) OB) || dev_alloc(h, out, (size_t) OB * NN))
+    {
+      dev_release(h, rec);
+      dev_release(h, ang);
+      dev_release(h, out);
+      (void) hipGetLastError();
+      return 1;
+    }
+    h->dRenderRec = rec;
+    h->dRenderAngles = ang;
+    h->dRenderOut = out;
+  }
+  // (the attribute belongs to the kernel, not the handle: images beyond 2 048 pixels need more than 64 KiB)
+  HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_cols), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+  HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  const OrientList src = ownLists ? own_list(h) : shared_list(h);
+  const OrientList L = {h->dRenderAngles, src.isQuat, src.quatNormDev};
+  int A, B;
+  dft_split(N, A, B);
+  for (size_t b0 = 0; b0 < recs.size(); b0 += (size_t) OB)
+  {
+    const int n = (int) std::min<size_t>((size_t) OB, recs.size() - b0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dRenderRec, recs.data() + b0, sizeof(RenderRecord) * n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_render_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, src.d, h->dRenderRec, n, h->dRenderAngles);
+    HIP_CHECK(h, hipGetLastError());
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, (int) b0, (int) b0 + n, 0, 0) ||
+        project_batch(h, s0, h->stream, L, 0, n) || phase_end(h, h->stream))
+      return 1;
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, (int) b0, (int) b0 + n, 0, 0))
+      return 1;
+    hipLaunchKernelGGL(k_render_cols, dim3(H, n), dim3(256), lds, h->stream, s0.specRef, h->dCTF, h->dRenderRec, N, H, A, B,
+                       h->dTwD, s0.rowSpec);
+    HIP_CHECK(h, hipGetLastError());
+    if (phase_end(h, h->stream) || phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, (int) b0, (int) b0 + n, 0, 0))
+      return 1;
+    hipLaunchKernelGGL(k_render_rows, dim3(N, n), dim3(256), lds, h->stream, s0.rowSpec, h->dRenderRec, N, H, A, B, h->dTwD,
+                       h->dRenderOut);
+    HIP_CHECK(h, hipGetLastError());
+    if (phase_end(h, h->stream))
+      return 1;
+    HIP_CHECK(h, hipMemcpyAsync(maps_out + b0 * NN, h->dRenderOut, sizeof(float) * NN * n, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  drain_phases(h);
   return 0;
 }
 

@@ -72,6 +72,8 @@ def load_library():
         L.bioem_hip_own_kernel_signature.argtypes = [vp]
         L.bioem_hip_own_kernel_signature.restype = C.c_char_p
         L.bioem_hip_set_own_launch.argtypes = [vp, ci]
+    if hasattr(L, "bioem_hip_render_best_maps"):
+        L.bioem_hip_render_best_maps.argtypes = [vp, vp, ci, ci, ci, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -123,7 +125,7 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_compare_device", "bioem_hip_max_batch", "bioem_hip_set_phase_timing", "bioem_hip_phase_records",
            "bioem_hip_upload_particle_orientations", "bioem_hip_compare_own_orientations",
            "bioem_hip_upload_particle_orientation_lists", "bioem_hip_plan_own", "bioem_hip_own_kernel_signature",
-           "bioem_hip_set_own_launch"]
+           "bioem_hip_set_own_launch", "bioem_hip_render_best_maps"]
 
 
 def _p(a):
@@ -330,6 +332,22 @@ class Engine:
         """K best orientations per particle among the owned ones, selected on the device: [nMaps, K] CANDIDATE_DTYPE"""
         out = np.zeros((self.nMaps, K), dtype=CANDIDATE_DTYPE)
         self._chk(self.L.bioem_hip_topk_angles(self.h, K, float(numconst), _p(out)), "topk_angles")
+        return out
+
+    def render_best_maps(self, pmap, p0=0, p1=None, own=False):
+        """the calculated image of the best match of particles [p0, p1): float32 [p1 - p0, N, N] with
+        out[p, (k + X) mod N, (j + Y) mod N] = conv[k, j] / N^2 * norm + mu for the record (orient, conv, X, Y, norm, mu) of
+        pmap (PROB_MAP_DTYPE [nMaps], global particle indices: the block of finish_run or a merged one); own: orient
+        indexes the particle's own list.  Call outside a run.  A refused record raises RuntimeError with .rc == 2."""
+        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
+        assert pmap.shape == (self.nMaps,)
+        p1 = self.nMaps if p1 is None else int(p1)
+        out = np.empty((max(0, p1 - int(p0)), self.N, self.N), dtype=np.float32)
+        rc = self.L.bioem_hip_render_best_maps(self.h, _p(pmap), int(bool(own)), int(p0), p1, _p(out))
+        if rc:
+            e = RuntimeError("render_best_maps: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
         return out
 
     def synchronize(self):

@@ -13,6 +13,7 @@
 #ifndef BIOEM_HOST_H
 #define BIOEM_HOST_H
 
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -78,6 +79,33 @@ struct MrcHeader
 MrcHeader mrc_read_header(const char *file);
 unsigned int mrc_bswap32(unsigned int v);
 
+// the BEST_* file of --PrintBestCalMap (bioem_param::forprintBest, param.cpp:629-907): one best-match record by hand
+struct BestParams
+{
+  float pixelSize = 0;
+  int N = 0;
+  float angle[4] = {0, 0, 0, 0}; // alpha beta gamma, or q1 q2 q3 q4 with USE_QUATERNIONS
+  bool doquater = false, usepsf = false, withnoise = false, doaaradius = true, printrotmod = false;
+  float elecwavel = 0.019866f;
+  float amp = 0, phase = 0, env = 0; // the one CTF / PSF kernel; phase: the defocus already converted
+  int ddx = 0, ddy = 0, shiftX = 0, shiftY = 0;
+  float norm = 0, offset = 0, stnoise = 1;
+};
+// bestmap.cpp: empty string, or the text of the error (the CLI ends with it like the reference does)
+std::string read_best_parameters(const char *file, BestParams &b);
+// the BESTMAP text of bioem.cpp:2041-2079 for the unshifted map v[N][N]; mapOnly: no MAPddx lines (WITHNOISE)
+bool write_bestmap_text(const char *file, const float *v, int N, int ddx, int ddy, bool mapOnly);
+// MRC mode-2 stack nx = ny = N, nz = nMaps in the storage order the --ReadMRC reader expects, written batch by batch
+struct MrcStackWriter
+{
+  FILE *f = nullptr;
+  int N = 0, nMaps = 0, written = 0;
+  bool open(const char *file, int N, int nMaps);
+  bool append(const float *maps, int n); // [n][N][N]
+  bool close();                          // false unless nMaps sections went in
+  ~MrcStackWriter();
+};
+
 struct Model
 {
   std::vector<bioem_hip_model_point> points;
@@ -120,6 +148,10 @@ public:
   // those within W of its log posterior (lists of different lengths); M = 1: the best alone, today's run
   int refineSeeds = 1;
   double refineLogWindow = -1.; // < 0: unlimited
+  std::string bestMapsFile;  // --BestMaps: MRC stack of every particle's calculated best-match image (FILE, FILE_Round2)
+  std::string bestParamFile; // --PrintBestCalMap: the reference's one-record mode, no particles, writes BESTMAP
+  BestParams best;
+  int printBestCalMap();     // bioem::printModel (bioem.cpp:624-657, 1925-2085)
   std::vector<unsigned char> prob;              // merged map entries [nMaps]
   std::vector<bioem_hip_angle_candidate> cand;  // merged K best orientations [nMaps][K] (WRITE_PROB_ANGLES)
 
@@ -148,6 +180,8 @@ private:
   void writeProbabilities(const std::string &file, const bioem_hip_prob_map *pmap, const bioem_hip_param_device &pd,
                           const float *angles, size_t anglesPerMap, bool angProb, const long long *angleOffsets = nullptr,
                           const float *voluPerMap = nullptr);
+  // --BestMaps: the records' images from handle h (bioem_hip_render_best_maps), one batch on the host at a time
+  void writeBestMaps(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
   void runRound2(); // --RefineOrientations: every particle against best (x) grid, OutputFile_Round2
   void runRound2Seeds(); // the same around several seeds per particle (--RefineSeeds >= 2)
   std::vector<Shard> shards;

@@ -1,5 +1,8 @@
 // capi.cpp -- C entry points of the host layer for bindings (tests, bench.py): the one-off precompute
 // the reference performs on the host before the hot loop.
+#include <cstdio>
+#include <cstring>
+
 #include "bioem_host.h"
 
 extern "C" {
@@ -115,5 +118,65 @@ int bioem_host_read_particles(const char *file, int mode, int N, int notnormmap,
     for (size_t e = 0; e < sz; e++)
       maps[(size_t) i * sz + e] = S.maps[(size_t) i * sz + e];
   return S.ntot;
+}
+
+// ---- the calculated best-match image on the host side (bestmap.cpp), without a device ----
+// the BEST_* file of --PrintBestCalMap as the parser holds it; returns 0, or 1 with the error text in err[cap]
+struct bioem_host_best_params
+{
+  float pixelSize;
+  int N;
+  float angle[4];
+  int doquater, usepsf, withnoise, doaaradius, printrotmod;
+  float amp, phase, env;
+  int ddx, ddy, shiftX, shiftY;
+  float norm, offset, stnoise;
+};
+
+int bioem_host_read_best_parameters(const char *file, bioem_host_best_params *out, char *err, int cap)
+{
+  bioem_host::BestParams b;
+  const std::string e = bioem_host::read_best_parameters(file, b);
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  if (!e.empty())
+    return 1;
+  out->pixelSize = b.pixelSize;
+  out->N = b.N;
+  memcpy(out->angle, b.angle, sizeof(b.angle));
+  out->doquater = b.doquater;
+  out->usepsf = b.usepsf;
+  out->withnoise = b.withnoise;
+  out->doaaradius = b.doaaradius;
+  out->printrotmod = b.printrotmod;
+  out->amp = b.amp;
+  out->phase = b.phase;
+  out->env = b.env;
+  out->ddx = b.ddx;
+  out->ddy = b.ddy;
+  out->shiftX = b.shiftX;
+  out->shiftY = b.shiftY;
+  out->norm = b.norm;
+  out->offset = b.offset;
+  out->stnoise = b.stnoise;
+  return 0;
+}
+
+// the BESTMAP text (bioem.cpp:2041-2079) of the unshifted map v[N][N]
+int bioem_host_write_bestmap(const char *file, const float *v, int N, int ddx, int ddy, int mapOnly)
+{
+  return bioem_host::write_bestmap_text(file, v, N, ddx, ddy, mapOnly != 0) ? 0 : 1;
+}
+
+// the MRC stack of --BestMaps: maps [nMaps][N][N] appended in batches of `batch` images
+int bioem_host_write_mrc_stack(const char *file, const float *maps, int nMaps, int N, int batch)
+{
+  bioem_host::MrcStackWriter w;
+  if (batch < 1 || !w.open(file, N, nMaps))
+    return 1;
+  for (int p = 0; p < nMaps; p += batch)
+    if (!w.append(maps + (size_t) p * N * N, nMaps - p < batch ? nMaps - p : batch))
+      return 1;
+  return w.close() ? 0 : 1;
 }
 }

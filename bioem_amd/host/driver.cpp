@@ -12,7 +12,9 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <ctime>
 #include <queue>
+#include <random>
 #include <thread>
 
 #include "bioem_host.h"
@@ -68,6 +70,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"Particlesfile", required_argument, 0, 0},
                                        {"Inputfile", required_argument, 0, 0},
                                        {"PrintBestCalMap", required_argument, 0, 0},
+                                       {"BestMaps", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
                                        {"RefineSeeds", required_argument, 0, 0},
@@ -95,6 +98,9 @@ int Driver::readOptions(int ac, char **av)
     printf("  --RefineSeeds arg      (Optional) Second round around up to arg orientations per particle: the best of the\n");
     printf("                         first round and the next ones in its ranking (default 1)\n");
     printf("  --RefineLogWindow arg  (Optional) ... of which only those within arg of the best log posterior\n");
+    printf("  --BestMaps arg         (Optional) Write the calculated image of every particle's best match as an MRC\n");
+    printf("                         stack (with --RefineOrientations also arg_Round2)\n");
+    printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
     printf("  --ReadMRC              (Optional) If reading particle file in MRC format\n");
@@ -177,6 +183,16 @@ int Driver::readOptions(int ac, char **av)
         fatal("--RefineLogWindow needs a non-negative number");
       std::cout << "Second round: seeds within " << refineLogWindow << " of the best log posterior\n";
     }
+    else if (name == "BestMaps")
+    {
+      std::cout << "Writing the best calculated maps to: " << optarg << "\n";
+      bestMapsFile = optarg;
+    }
+    else if (name == "PrintBestCalMap")
+    {
+      std::cout << "Reading best parameters from file: " << optarg << "\n";
+      bestParamFile = optarg;
+    }
     else if (name == "OutputFile")
     {
       std::cout << "Writing OUTPUT to: " << optarg << "\n";
@@ -207,6 +223,38 @@ int Driver::readOptions(int ac, char **av)
   }
   if (particles.readMultMRC && !particles.readMRC)
     fatal("For multiple MRCs command --ReadMRC is necessary too");
+  if (!bestParamFile.empty())
+  { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
+    // one CTF / PSF kernel, no particles, no grids
+    if (!bestMapsFile.empty() || !refineFile.empty())
+      fatal("--PrintBestCalMap goes without --BestMaps and --RefineOrientations");
+    const std::string err = read_best_parameters(bestParamFile.c_str(), best);
+    if (!err.empty())
+      fatal("%s", err.c_str());
+    param.pixelSize = best.pixelSize;
+    param.N = best.N;
+    param.doquater = best.doquater;
+    param.usepsf = best.usepsf;
+    param.elecwavel = best.elecwavel;
+    param.doaaradius = best.doaaradius;
+    param.printrotmod = best.printrotmod;
+    param.shiftX = best.shiftX;
+    param.shiftY = best.shiftY;
+    param.startGridCTF_amp = param.endGridCTF_amp = best.amp;
+    param.startGridCTF_phase = param.endGridCTF_phase = best.phase;
+    param.startGridEnvelop = param.endGridEnvelop = best.env;
+    param.numberGridPointsCTF_amp = param.numberGridPointsCTF_phase = param.numberGridPointsEnvelop = 1;
+    param.pd.maxDisplaceCenter = 0;
+    param.pd.GridSpaceCenter = 1;
+    param.pd.NumberPixels = best.N;
+    param.pd.NumberFFTPixels1D = best.N / 2 + 1;
+    param.pd.writeAngles = 0;
+    param.pd.tousepsf = best.usepsf ? 1 : 0;
+    param.angles.assign(best.angle, best.angle + 4);
+    param.nTotGridAngles = 1;
+    model.readModel(param, modelfile.c_str());
+    return 0;
+  }
   param.readParameters(infile.c_str());
   if (refineFile.empty() && (refineSeeds != 1 || refineLogWindow >= 0.))
     fatal("--RefineSeeds / --RefineLogWindow go with --RefineOrientations");
@@ -260,6 +308,8 @@ int Driver::configure(int ac, char **av)
   param.r2c = r2c_on_device;
   param.r2c_ctx = &firstDev;
   param.calculateRefCTF();
+  if (!bestParamFile.empty()) // one handle, made where the map is rendered
+    return 0;
   if (getenv("BIOEM_DEBUG_BREAK")) // bioem.cpp:518-525: after volu was computed with the full counts
   {
     const int cut = atoi(getenv("BIOEM_DEBUG_BREAK"));
@@ -381,8 +431,83 @@ void Driver::print_phase_report()
   }
 }
 
+// --BestMaps: every record's calculated image from handle h, batch by batch (one batch of maps on the host at a time)
+void Driver::writeBestMaps(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists)
+{
+  const int nMaps = particles.ntot, N = param.N;
+  int batch = 1;
+  bioem_hip_max_batch(h, &batch, nullptr);
+  batch = std::max(1, std::min(batch, nMaps));
+  const size_t NN = (size_t) N * N;
+  std::vector<float> buf((size_t) batch * NN);
+  MrcStackWriter w;
+  if (!w.open(file.c_str(), N, nMaps))
+    fatal("Opening %s", file.c_str());
+  for (int p0 = 0; p0 < nMaps; p0 += batch)
+  {
+    const int p1 = std::min(nMaps, p0 + batch);
+    int rc = bioem_hip_render_best_maps(h, pmap, ownLists, p0, p1, buf.data());
+    if (rc == 2)
+    { // a record without an image (a particle the round never compared): its section is zero, the others are rendered
+      for (int p = p0; p < p1 && rc != 1; p++)
+      {
+        rc = bioem_hip_render_best_maps(h, pmap, ownLists, p, p + 1, buf.data() + (size_t) (p - p0) * NN);
+        if (rc == 2)
+        {
+          warn("best map of RefMap %d not rendered: %s", p, bioem_hip_last_error(h));
+          std::fill(buf.begin() + (size_t) (p - p0) * NN, buf.begin() + (size_t) (p - p0 + 1) * NN, 0.f);
+        }
+      }
+      rc = rc == 1 ? 1 : 0;
+    }
+    check(h, rc, "render best maps");
+    if (!w.append(buf.data(), p1 - p0))
+      fatal("Writing %s", file.c_str());
+  }
+  if (!w.close())
+    fatal("Writing %s", file.c_str());
+  std::cout << "Best calculated maps of " << nMaps << " particles written to: " << file << "\n";
+}
+
+// --PrintBestCalMap: the record of the BEST_* file rendered on the device and written as the reference's BESTMAP text.
+// The reference's file labels the UNSHIFTED map with shifted coordinates (bioem.cpp:2049-2053), so the device renders with
+// X = Y = 0 and the writer applies BEST_DX / BEST_DY to the labels.
+int Driver::printBestCalMap()
+{
+  std::cout << "\nAnalysis for printing best projection::: \n \n";
+  const int N = param.N;
+  bioem_hip_handle h = nullptr;
+  check(h, bioem_hip_create(&h, firstDev, &param.pd, 1, 1, 1, algo), "bioem_hip_create");
+  check(h, bioem_hip_upload_ctf(h, param.refCTF.data(), param.ctfParam.data()), "upload CTF");
+  check(h, bioem_hip_upload_model(h, model.points.data(), (int) model.points.size(), model.NormDen, param.pixelSize,
+                                  param.shiftX, param.shiftY),
+        "upload model");
+  check(h, bioem_hip_upload_orientations(h, param.angles.data(), 1, param.doquater ? 1 : 0), "upload orientations");
+  bioem_hip_prob_map rec;
+  memset(&rec, 0, sizeof(rec));
+  rec.max_prob_norm = best.norm;
+  rec.max_prob_mu = best.offset;
+  std::vector<float> map((size_t) N * N);
+  std::cout << "...... Calculating Projection and Convolution on the device .......................\n ";
+  check(h, bioem_hip_render_best_maps(h, &rec, 0, 0, 1, map.data()), "render best map");
+  bioem_hip_destroy(h);
+  if (best.withnoise)
+  { // N(0, stnoise) per pixel, seeded by the time like the reference's generator: maps of different runs are uncorrelated
+    std::mt19937 gen((unsigned int) std::time(nullptr));
+    std::normal_distribution<float> noise(0.f, best.stnoise);
+    for (float &v : map)
+      v = v + noise(gen);
+  }
+  if (!write_bestmap_text("BESTMAP", map.data(), N, best.ddx, best.ddy, best.withnoise))
+    fatal("Writing BESTMAP");
+  std::cout << "\n\nBest map printed in file: BESTMAP with gnuplot format in columns 2, 3 and 4. \n\n\n";
+  return 0;
+}
+
 int Driver::run()
 {
+  if (!bestParamFile.empty())
+    return printBestCalMap();
   printf("\tInitializing Probabilities\n");
   const int nMaps = particles.ntot, nAngles = param.nTotGridAngles, nC = param.nTotCTFs;
   const int nShards = (int) shards.size();
@@ -529,6 +654,8 @@ int Driver::run()
     }
   }
   writeOutput();
+  if (!bestMapsFile.empty()) // from the merged records, on the first handle (every handle holds the global list)
+    writeBestMaps(bestMapsFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!refineFile.empty())
   {
     if (refineSeeds >= 2)
@@ -595,6 +722,8 @@ void Driver::runRound2()
   check(h, bioem_hip_start_run(h, pm.data()), "start run (second round)");
   check(h, bioem_hip_compare_own_orientations(h, 0, nMaps), "compare own orientations");
   check(h, bioem_hip_finish_run(h, pm.data()), "finish run (second round)");
+  if (!bestMapsFile.empty())
+    writeBestMaps(bestMapsFile + "_Round2", h, pm.data(), 1);
   bioem_hip_destroy(h);
   writeProbabilities(outfileName + "_Round2", pm.data(), pd2, lists.data(), (size_t) G, false);
 }
@@ -682,6 +811,8 @@ void Driver::runRound2Seeds()
   check(h, bioem_hip_start_run(h, pm.data()), "start run (second round)");
   check(h, bioem_hip_compare_own_orientations(h, 0, nMaps), "compare own orientations");
   check(h, bioem_hip_finish_run(h, pm.data()), "finish run (second round)");
+  if (!bestMapsFile.empty())
+    writeBestMaps(bestMapsFile + "_Round2", h, pm.data(), 1);
   bioem_hip_destroy(h);
   writeProbabilities(outfileName + "_Round2", pm.data(), pd2, lists.data(), 0, false, offsets.data(), volu.data());
 }

@@ -100,3 +100,43 @@ def read_particles(path, N, mode=0, notnormmap=False, cap=4096):
     maps = np.zeros((cap, N, N), dtype=np.float32)
     n = L.bioem_host_read_particles(path.encode(), mode, N, int(notnormmap), maps.ctypes.data, cap)
     return maps[:n].copy()
+
+
+class BestParams(C.Structure):
+    """the BEST_* file of --PrintBestCalMap as the host layer's parser holds it (phase: the defocus converted)"""
+    _fields_ = [("pixelSize", C.c_float), ("N", C.c_int), ("angle", C.c_float * 4), ("doquater", C.c_int),
+                ("usepsf", C.c_int), ("withnoise", C.c_int), ("doaaradius", C.c_int), ("printrotmod", C.c_int),
+                ("amp", C.c_float), ("phase", C.c_float), ("env", C.c_float), ("ddx", C.c_int), ("ddy", C.c_int),
+                ("shiftX", C.c_int), ("shiftY", C.c_int), ("norm", C.c_float), ("offset", C.c_float),
+                ("stnoise", C.c_float)]
+
+
+def read_best_parameters(path):
+    """parses a BEST_* file; raises ValueError with the parser's message where the CLI would end with it"""
+    L = load_host_library()
+    L.bioem_host_read_best_parameters.argtypes = [C.c_char_p, C.POINTER(BestParams), C.c_char_p, C.c_int]
+    b = BestParams()
+    err = C.create_string_buffer(512)
+    if L.bioem_host_read_best_parameters(path.encode(), C.byref(b), err, 512):
+        raise ValueError(err.value.decode())
+    return b
+
+
+def write_bestmap(path, image, ddx=0, ddy=0, map_only=False):
+    """the BESTMAP text file of the unshifted map image[N, N]"""
+    L = load_host_library()
+    L.bioem_host_write_bestmap.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    assert img.ndim == 2 and img.shape[0] == img.shape[1]
+    if L.bioem_host_write_bestmap(path.encode(), img.ctypes.data, img.shape[0], int(ddx), int(ddy), int(bool(map_only))):
+        raise RuntimeError("writing %s failed" % path)
+
+
+def write_mrc_stack(path, maps, batch=64):
+    """MRC mode-2 stack of maps[n, N, N] in the storage order the --ReadMRC reader expects"""
+    L = load_host_library()
+    L.bioem_host_write_mrc_stack.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    assert m.ndim == 3 and m.shape[1] == m.shape[2]
+    if L.bioem_host_write_mrc_stack(path.encode(), m.ctypes.data, m.shape[0], m.shape[1], int(batch)):
+        raise RuntimeError("writing %s failed" % path)

@@ -207,6 +207,29 @@ int bioem_hip_max_batch(bioem_hip_handle h, int *maxOrientations, int *maxRows);
 /* bioem_cuda::deviceFinishRun (bioem_cuda.cu:1013-1021): synchronise, download the probability block. */
 int bioem_hip_finish_run(bioem_hip_handle h, void *pProb_host);
 
+/* The calculated image of the best match of particles [iMapBegin, iMapEnd): what bioem::printModel writes for ONE
+ * hand-copied record (bioem.cpp:624-657, 1925-2085), for every record of a run, on the device.
+ * records = [nMaps] bioem_hip_prob_map on the HOST (the block of finish_run, or a merged one: indices are global).
+ * ownLists = 0: max_prob_orient indexes the shared list (bioem_hip_upload_orientations);
+ * ownLists = 1: it indexes particle p's own list (bioem_hip_upload_particle_orientation_lists).
+ * maps_out = [iMapEnd - iMapBegin][N][N] float on the host.
+ * For the record (o, c, X, Y, norm, mu): Z = P_o conj(CTF_c) in float (bioem.cpp:1952-1955), conv = the unnormalised c2r
+ * of Z (exact DFT, sums in double, rounded to float), out[(k + X) mod N][(j + Y) mod N] = conv[k][j] / N^2 * norm + mu
+ * with the float operations in that order (bioem.cpp:2051-2053).  The reference reports the negative of the
+ * correlation's displacement, so this is the map the posterior laid over the particle: with Ntotpi = N^2, norm and mu
+ * are the least-squares slope and intercept, and the result is the least-squares fit of the particle at the arg-max.
+ * Particles go in batches of at most maxOrientations of bioem_hip_max_batch (gather of the records' orientations,
+ * projection, two inverse DFT passes, one copy to the host per batch) through buffer set 0, like the debug hooks: call
+ * it outside a run; what was staged in set 0 is void afterwards.  Needs no particles and no comparison: every handle kind
+ * serves it (shards hold the global list).  The staging buffers are allocated at the first call (1 when the memory is
+ * not there; the handle is as it was).  Returns 2 with a message naming the particle, handle still usable, for a record
+ * whose max_prob_orient lies outside its list (a particle no run touched), max_prob_conv outside [0, nCTF), |X| or
+ * |Y| >= N; for an empty or reversed range, ownLists = 1 without own lists, model / CTFs / orientations not uploaded.
+ * With bioem_hip_set_phase_timing the batches leave phase records: phase 0 the projection, 1 the column pass, 2 the row
+ * pass, iOrientBegin / iOrientEnd the batch's records relative to iMapBegin. */
+int bioem_hip_render_best_maps(bioem_hip_handle h, const bioem_hip_prob_map *records, int ownLists, int iMapBegin,
+                               int iMapEnd, float *maps_out);
+
 /* WRITE_PROB_ANGLES without moving the table: selects on the device the K best orientations of every particle among
  * the orientations this handle owns, with the reference writer's own rule (a K-entry min-heap on (logp, orientation)
  * walked in orientation order, bioem.cpp:1251-1286; numconst as computed at bioem.cpp:1141-1150).  out = [nMaps][K],
