@@ -42,6 +42,8 @@
 //                          reference's (orientation, CTF) order (bioem_algorithm.h:96-123, bioem.cpp:1527-1600)
 //                        k_fold_own, k_fold_own_angles: the same for the own-list pass (one orientation list per particle,
 //                          of any length: bioem_hip_compare_own_orientations)
+//                        k_fold_ctf, k_fold_own_ctf: the posterior per (CTF set, particle), a second fold of the same
+//                          partials into the [nCTF][nMaps] table of bioem_hip_enable_ctf_table (off by default)
 //   compare_fast_own.hpp k_compare_fast_own, k_nyquist_rows_own (kernels_fast_own.hip): k_compare_fast with a block table,
 //                          one launch per batch of the own-list pass; the other families: one launch per particle
 //   render_kernels.hpp   k_render_gather, k_render_cols, k_render_rows  bioem_hip_render_best_maps: the calculated image of
@@ -198,6 +200,10 @@ struct bioem_hip_ctx
   float4 *dRenderAngles = nullptr;
   float *dRenderOut = nullptr;
   bool ctfUp = false; // bioem_hip_upload_ctf has run
+  // bioem_hip_enable_ctf_table: [nCTF][nMaps] entries, folded beside the particle entries (k_fold_ctf, k_fold_own_ctf);
+  // null = off, nothing allocated and nothing launched
+  bioem_hip_prob_map *dCtfTab = nullptr;
+  bool inRun = false; // between start_run and finish_run
 
   // two pipeline slots + a second stream: projection/convolution of batch k+1 (prepStream) overlap the comparison of
   // batch k.  Slot 0's projection buffers also stage the particle uploads and the debug hooks.
@@ -591,6 +597,14 @@ int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC
     hipLaunchKernelGGL(k_fold_wave<1>, dim3((h->nMaps + 3) / 4), dim3(256), 0, h->stream, h->dPartials, h->maxOC, nOC,
                        h->nMaps, bb.params, h->dSumRef, h->dDisp, P.nd, h->pd, orient0, conv0, convPerOrient, ids,
                        pmap);
+  if (h->dCtfTab)
+  { // one wave per (CTF of the launch, particle); the compat ring's rows name their CTF, so every CTF gets a wave
+    const int nC = ids ? h->nCTF : convPerOrient;
+    const long long pairs = (long long) nC * h->nMaps;
+    hipLaunchKernelGGL(k_fold_ctf, dim3((unsigned) ((pairs + 3) / 4)), dim3(256), 0, h->stream, h->dPartials, h->maxOC, nOC,
+                       h->nMaps, bb.params, h->dSumRef, h->dDisp, P.nd, h->pd, orient0, conv0, convPerOrient, nC, ids,
+                       h->dCtfTab);
+  }
   HIP_CHECK(h, hipGetLastError());
   if (phase_end(h, h->stream)) // comparison = the kernels of the launch and the fold behind them (what compareRefMaps does)
     return 1;
@@ -685,6 +699,10 @@ int launch_compare_own(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC,
                        h->dOwnOff, h->dSlotParticle, nC, h->nMaps, pang);
   hipLaunchKernelGGL(k_fold_own, dim3((pEnd - pFirst + 3) / 4), dim3(256), 0, h->stream, h->dPartials, nOC, row0,
                      h->dOwnOff, nC, pFirst, pEnd, bb.params, h->dSumRef, h->dDisp, P.nd, h->pd, pmap);
+  if (h->dCtfTab)
+    hipLaunchKernelGGL(k_fold_own_ctf, dim3((unsigned) (((long long) nC * (pEnd - pFirst) + 3) / 4)), dim3(256), 0, h->stream,
+                       h->dPartials, nOC, row0, h->dOwnOff, nC, h->nMaps, pFirst, pEnd, bb.params, h->dSumRef, h->dDisp,
+                       P.nd, h->pd, h->dCtfTab);
   HIP_CHECK(h, hipGetLastError());
   if (phase_end(h, h->stream))
     return 1;
@@ -1870,6 +1888,56 @@ int bioem_hip_start_run(bioem_hip_handle h, const void *pProb_host)
     hipLaunchKernelGGL(k_init_angles, dim3(1024), dim3(256), 0, h->stream, pang, (size_t) (h->angO1 - h->angO0) * h->nMaps);
     HIP_CHECK(h, hipGetLastError());
   }
+  if (h->dCtfTab)
+  {
+    hipLaunchKernelGGL(k_init_ctf_table, dim3(256), dim3(256), 0, h->stream, h->dCtfTab, (size_t) h->nCTF * h->nMaps);
+    HIP_CHECK(h, hipGetLastError());
+  }
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  h->inRun = true;
+  return 0;
+}
+
+int bioem_hip_enable_ctf_table(bioem_hip_handle h, int on)
+{
+  if (!h)
+    return 2;
+  if (h->inRun)
+  {
+    h->err = "enable_ctf_table: called inside a run (between bioem_hip_start_run and bioem_hip_finish_run)";
+    return 2;
+  }
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (!on)
+  {
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    dev_release(h, h->dCtfTab);
+    return 0;
+  }
+  if (h->dCtfTab)
+    return 0;
+  if (dev_alloc(h, h->dCtfTab, (size_t) h->nCTF * h->nMaps))
+    return 1;
+  // a table fetched before the first run reads as an untouched one
+  hipLaunchKernelGGL(k_init_ctf_table, dim3(256), dim3(256), 0, h->stream, h->dCtfTab, (size_t) h->nCTF * h->nMaps);
+  HIP_CHECK(h, hipGetLastError());
+  return 0;
+}
+
+int bioem_hip_ctf_table(bioem_hip_handle h, bioem_hip_prob_map *out)
+{
+  if (!h)
+    return 2;
+  if (!h->dCtfTab || !out)
+  {
+    h->err = "ctf_table: the table is not enabled on this handle (bioem_hip_enable_ctf_table)";
+    return 2;
+  }
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (compat_flush(h))
+    return 1;
+  HIP_CHECK(h, hipMemcpyAsync(out, h->dCtfTab, sizeof(bioem_hip_prob_map) * h->nCTF * h->nMaps, hipMemcpyDeviceToHost,
+                              h->stream));
   HIP_CHECK(h, hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -2091,6 +2159,7 @@ int bioem_hip_finish_run(bioem_hip_handle h, void *pProb_host)
     return 1;
   HIP_CHECK(h, hipMemcpyAsync(pProb_host, h->dProb, h->probBytes, hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  h->inRun = false;
   drain_events(h);
   drain_phases(h);
   return 0;

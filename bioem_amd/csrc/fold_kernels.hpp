@@ -257,6 +257,165 @@ __global__ void k_fold_own_angles(const Partial *__restrict__ partials, int nSlo
 }
 
 // ------------------------------------------------------------------------------------------------
+// CTF table (bioem_hip_enable_ctf_table): entry (c, p) of the [nCTF][nMaps] table is what particle p's entry would be had
+// the run compared CTF set c only -- the fold of the partials of rows (o, c) in orientation order by the rules of
+// k_fold_wave (log-sum-exp in double, first maximum = lowest row, norm / mu from the best row), max_prob_conv = c.
+// One wave per (CTF, particle) pair; the pair's rows are first, first + stride, ... (count of them), lane l folds a
+// contiguous chunk of them in row order, the chunks are merged by the first-maximum shuffle reduction and lane 0
+// updates the entry.  Every entry has one writer per launch and launches are ordered on the stream: no atomics, the
+// same bits on every run.  With `ids` (compat ring: row oc belongs to CTF ids[oc].y) the lanes walk all rows of the
+// launch and take those of their CTF.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void fold_ctf_rows(const Partial *__restrict__ P, int first, int stride, int count,
+                                              const int2 *__restrict__ ids, int c, int lane, double &m, double &sacc,
+                                              int &idx)
+{
+  const int chunk = (count + 63) / 64;
+  const int b = min(count, lane * chunk), e = min(count, b + chunk);
+  m = -INFINITY;
+  sacc = 0.;
+  idx = 0x7fffffff;
+  for (int k = b; k < e; k++)
+  {
+    const int oc = first + k * stride;
+    if (ids && ids[oc].y != c)
+      continue;
+    const Partial r = P[oc];
+    const double lp = (double) r.best;
+    if (m < lp)
+    {
+      sacc = (m == -INFINITY) ? 0. : sacc * exp(m - lp);
+      m = lp;
+      idx = oc;
+    }
+    sacc += r.sumExp * exp(lp - m);
+  }
+  for (int off = 32; off > 0; off >>= 1)
+  {
+    const double m2 = __shfl_xor(m, off);
+    const double s2 = __shfl_xor(sacc, off);
+    const int i2 = __shfl_xor(idx, off);
+    if (m2 > m || (m2 == m && i2 < idx))
+    {
+      sacc = ((m == -INFINITY) ? 0. : sacc * exp(m - m2)) + s2;
+      m = m2;
+      idx = i2;
+    }
+    else
+      sacc += (m2 == -INFINITY) ? 0. : s2 * exp(m2 - m);
+  }
+}
+
+// shared-list passes.  Native path (ids == null): row oc of the launch is CTF conv0 + oc % convPerOrient, the wave of
+// (c, p) walks rows c - conv0, c - conv0 + convPerOrient, ...; nC = convPerOrient pairs per particle.  Compat ring:
+// nC = nCTF of the handle, conv0 = 0.  A pair without rows in the launch leaves its entry alone.
+__global__ __launch_bounds__(256) void k_fold_ctf(const Partial *__restrict__ partials, int ldPart, int nOC, int nMaps,
+                                                  const bioem_hip_param5 *__restrict__ params,
+                                                  const float *__restrict__ sumRef, const int *__restrict__ disp,
+                                                  int nd, PD pd, int orient0, int conv0, int convPerOrient, int nC,
+                                                  const int2 *__restrict__ ids, bioem_hip_prob_map *__restrict__ tab)
+{
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long pair = (long long) blockIdx.x * 4 + wave;
+  if (pair >= (long long) nC * nMaps)
+    return;
+  const int cl = (int) (pair / nMaps), p = (int) (pair - (long long) cl * nMaps); // particle fastest: neighbouring entries
+  const int c = conv0 + cl;
+  const Partial *P = partials + (size_t) p * ldPart;
+  const int first = ids ? 0 : cl, stride = ids ? 1 : convPerOrient;
+  const int count = ids ? nOC : (cl < nOC ? (nOC - cl + convPerOrient - 1) / convPerOrient : 0);
+  double m, sacc;
+  int idx;
+  fold_ctf_rows(P, first, stride, count, ids, c, lane, m, sacc, idx);
+  if (lane == 0 && idx != 0x7fffffff)
+  {
+    bioem_hip_prob_map pm = tab[(size_t) c * nMaps + p];
+    if (pm.Constoadd < m)
+    {
+      pm.Total *= exp(-m + pm.Constoadd);
+      pm.Constoadd = m;
+      const Partial r = P[idx];
+      const int ix = r.id / nd, iy = r.id - ix * nd;
+      pm.max_prob_cent_x = -disp[ix];
+      pm.max_prob_cent_y = -disp[iy];
+      pm.max_prob_orient = ids ? ids[idx].x : orient0 + idx / convPerOrient;
+      pm.max_prob_conv = c;
+      const bioem_hip_param5 q = params[idx];
+      const float sumref = sumRef[p];
+      const float value = r.value;
+      pm.max_prob_norm = -(-q.sumC * sumref + pd.Ntotpi * value) / (q.sumC * q.sumC - q.sumsquareC * pd.Ntotpi);
+      pm.max_prob_mu = -(-q.sumC * value + q.sumsquareC * sumref) / (q.sumC * q.sumC - q.sumsquareC * pd.Ntotpi);
+    }
+    pm.Total += sacc * exp(m - pm.Constoadd);
+    tab[(size_t) c * nMaps + p] = pm;
+  }
+}
+
+// own-list pass: the rows of k_fold_own ([particle][list entry][CTF] flat order, the launch holds rows row0 ... row0 + nOC),
+// one wave per (CTF, particle of [pFirst, pEnd)).  A particle's rows begin at a multiple of nCTF, so row row0 + oc is CTF
+// (row0 + oc) % nCTF; max_prob_orient is the index in that particle's list.
+__global__ __launch_bounds__(256) void k_fold_own_ctf(const Partial *__restrict__ partials, int nOC, int row0,
+                                                      const int *__restrict__ off, int nCTF, int nMaps, int pFirst,
+                                                      int pEnd, const bioem_hip_param5 *__restrict__ params,
+                                                      const float *__restrict__ sumRef, const int *__restrict__ disp,
+                                                      int nd, PD pd, bioem_hip_prob_map *__restrict__ tab)
+{
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nP = pEnd - pFirst;
+  const long long pair = (long long) blockIdx.x * 4 + wave;
+  if (pair >= (long long) nCTF * nP)
+    return;
+  const int c = (int) (pair / nP), p = pFirst + (int) (pair - (long long) c * nP);
+  const long long g0 = (long long) off[p] * nCTF, g1 = (long long) off[p + 1] * nCTF;
+  const int rb = (int) (max(g0, (long long) row0) - row0), re = (int) (min(g1, (long long) row0 + nOC) - row0);
+  if (re <= rb)
+    return;
+  const int c0 = (int) (((long long) row0 + rb - g0) % nCTF); // CTF of the particle's first row in the launch
+  const int first = rb + (c - c0 + nCTF) % nCTF;
+  const int count = first < re ? (re - first + nCTF - 1) / nCTF : 0;
+  double m, sacc;
+  int idx;
+  fold_ctf_rows(partials, first, nCTF, count, nullptr, c, lane, m, sacc, idx);
+  if (lane == 0 && idx != 0x7fffffff)
+  {
+    bioem_hip_prob_map pm = tab[(size_t) c * nMaps + p];
+    if (pm.Constoadd < m)
+    {
+      pm.Total *= exp(-m + pm.Constoadd);
+      pm.Constoadd = m;
+      const Partial r = partials[idx];
+      const int ix = r.id / nd, iy = r.id - ix * nd;
+      const int local = (int) ((long long) row0 + idx - g0); // k * nCTF + CTF
+      pm.max_prob_cent_x = -disp[ix];
+      pm.max_prob_cent_y = -disp[iy];
+      pm.max_prob_orient = local / nCTF;
+      pm.max_prob_conv = c;
+      const bioem_hip_param5 q = params[idx];
+      const float sumref = sumRef[p];
+      const float value = r.value;
+      pm.max_prob_norm = -(-q.sumC * sumref + pd.Ntotpi * value) / (q.sumC * q.sumC - q.sumsquareC * pd.Ntotpi);
+      pm.max_prob_mu = -(-q.sumC * value + q.sumsquareC * sumref) / (q.sumC * q.sumC - q.sumsquareC * pd.Ntotpi);
+    }
+    pm.Total += sacc * exp(m - pm.Constoadd);
+    tab[(size_t) c * nMaps + p] = pm;
+  }
+}
+
+// the table as the reference initialises a particle entry (bioem.cpp:681-687)
+__global__ void k_init_ctf_table(bioem_hip_prob_map *__restrict__ tab, size_t n)
+{
+  for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
+  {
+    bioem_hip_prob_map m;
+    m.Total = 0.0;
+    m.Constoadd = MIN_PROB;
+    m.max_prob_cent_x = m.max_prob_cent_y = m.max_prob_orient = m.max_prob_conv = 0;
+    m.max_prob_norm = m.max_prob_mu = 0.f;
+    tab[i] = m;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // shard handles: the angle table never leaves the device
 // ------------------------------------------------------------------------------------------------
 __global__ void k_init_angles(bioem_hip_prob_angle *__restrict__ pang, size_t n)

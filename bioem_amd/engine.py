@@ -74,6 +74,9 @@ def load_library():
         L.bioem_hip_set_own_launch.argtypes = [vp, ci]
     if hasattr(L, "bioem_hip_render_best_maps"):
         L.bioem_hip_render_best_maps.argtypes = [vp, vp, ci, ci, ci, vp]
+    if hasattr(L, "bioem_hip_enable_ctf_table"):
+        L.bioem_hip_enable_ctf_table.argtypes = [vp, ci]
+        L.bioem_hip_ctf_table.argtypes = [vp, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -125,7 +128,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_compare_device", "bioem_hip_max_batch", "bioem_hip_set_phase_timing", "bioem_hip_phase_records",
            "bioem_hip_upload_particle_orientations", "bioem_hip_compare_own_orientations",
            "bioem_hip_upload_particle_orientation_lists", "bioem_hip_plan_own", "bioem_hip_own_kernel_signature",
-           "bioem_hip_set_own_launch", "bioem_hip_render_best_maps"]
+           "bioem_hip_set_own_launch", "bioem_hip_render_best_maps", "bioem_hip_enable_ctf_table",
+           "bioem_hip_ctf_table"]
 
 
 def _p(a):
@@ -350,6 +354,27 @@ class Engine:
             raise e
         return out
 
+    def enable_ctf_table(self, on=True):
+        """keep the posterior per (CTF set, particle) beside the particle entries, from the next start_run on; call it
+        outside a run (inside one it raises, .rc == 2)"""
+        rc = self.L.bioem_hip_enable_ctf_table(self.h, int(bool(on)))
+        if rc:
+            e = RuntimeError("enable_ctf_table: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+
+    def ctf_table(self):
+        """[nCTF, nMaps] PROB_MAP_DTYPE: entry (c, p) is what particle p's entry would be had the run compared CTF set c
+        only (conv == c; orient / cent_x / cent_y / norm / mu of the best match under that CTF set).  Flushes and
+        synchronises.  Without enable_ctf_table it raises with .rc == 2."""
+        out = np.zeros((self.nCTF, self.nMaps), dtype=PROB_MAP_DTYPE)
+        rc = self.L.bioem_hip_ctf_table(self.h, _p(out))
+        if rc:
+            e = RuntimeError("ctf_table: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+        return out
+
     def synchronize(self):
         self._chk(self.L.bioem_hip_synchronize(self.h), "synchronize")
 
@@ -426,5 +451,19 @@ def merge_host(blocks, nMaps, nAngles, writeAngles):
     arr = (C.c_void_p * len(blocks))(*[b.ctypes.data for b in blocks])
     rc = L.bioem_hip_merge_host(len(blocks), nMaps, nAngles, int(writeAngles), arr, _p(out))
     if rc:
+        raise RuntimeError("bioem_hip_merge_host failed")
+    return out
+
+
+def merge_ctf_tables(tables):
+    """Merge of the shards' CTF tables ([nCTF, nMaps] each, Engine.ctf_table; shards in ascending orientation-block
+    order) by bioem_hip_merge_host, entry by entry: log-sum-exp of Total / Constoadd, the record of the lowest shard
+    that holds the largest Constoadd."""
+    L = load_library()
+    tables = [np.ascontiguousarray(t, dtype=PROB_MAP_DTYPE) for t in tables]
+    assert all(t.shape == tables[0].shape for t in tables)
+    out = np.zeros_like(tables[0])
+    arr = (C.c_void_p * len(tables))(*[t.ctypes.data for t in tables])
+    if L.bioem_hip_merge_host(len(tables), tables[0].size, 0, 0, arr, _p(out)):
         raise RuntimeError("bioem_hip_merge_host failed")
     return out

@@ -95,6 +95,20 @@ struct BestParams
 std::string read_best_parameters(const char *file, BestParams &b);
 // the BESTMAP text of bioem.cpp:2041-2079 for the unshifted map v[N][N]; mapOnly: no MAPddx lines (WITHNOISE)
 bool write_bestmap_text(const char *file, const float *v, int N, int ddx, int ddy, bool mapOnly);
+
+// --ProbCTF: the text file of a CTF table tab[nCTF][nMaps] (bioem_hip_ctf_table, merged over shards): the HEADER::
+// NOTATION bar of ANG_PROB, one notation line, then one line per (particle, CTF set), particle-major, fixed, 4 decimals:
+//  i c k0 k1' k2 logP Separated: log(Total) Constoadd numconst Best: A cx cy norm mu
+// k0 k1' k2: the CTF set as the "Maximizing Param" line prints it (ctfParam3[c]; the defocus in micro-m, PSF parameters as
+// they are); logP = log(Total) + Constoadd + numconst with numconst = the constant of the particle's LogProb (log(volu)
+// included; voluPerMap: map i's own volume element, round 2), so that a particle's lines sum, in log-sum-exp, to its
+// LogProb; A: the orientation of the best match under that CTF set (4 numbers with quaternions, else 3) from the list
+// max_prob_orient indexes (angles, anglesPerMap, angleOffsets as in Driver::writeProbabilities).
+// Returns the empty string, or the error: the file cannot be written, or an entry is still as start_run left it (no
+// comparison reached that particle under that CTF set), named by particle and CTF set.
+std::string write_ctf_prob(const char *file, const bioem_hip_prob_map *tab, int nCTF, int nMaps, const float *ctfParam3,
+                           bool usepsf, float elecwavel, bool doquater, const float *angles, size_t anglesPerMap,
+                           const long long *angleOffsets, float Ntotpi, float volu, const float *voluPerMap);
 // MRC mode-2 stack nx = ny = N, nz = nMaps in the storage order the --ReadMRC reader expects, written batch by batch
 struct MrcStackWriter
 {
@@ -149,6 +163,7 @@ public:
   int refineSeeds = 1;
   double refineLogWindow = -1.; // < 0: unlimited
   std::string bestMapsFile;  // --BestMaps: MRC stack of every particle's calculated best-match image (FILE, FILE_Round2)
+  std::string probCtfFile;   // --ProbCTF: the posterior per (particle, CTF set) as text (FILE, FILE_Round2)
   std::string bestParamFile; // --PrintBestCalMap: the reference's one-record mode, no particles, writes BESTMAP
   BestParams best;
   int printBestCalMap();     // bioem::printModel (bioem.cpp:624-657, 1925-2085)
@@ -182,6 +197,10 @@ private:
                           const float *voluPerMap = nullptr);
   // --BestMaps: the records' images from handle h (bioem_hip_render_best_maps), one batch on the host at a time
   void writeBestMaps(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
+  // --ProbCTF: the tables of the handles merged on the host (shards in ascending order) and written
+  void writeCtfProb(const std::string &file, const std::vector<bioem_hip_handle> &hs, const bioem_hip_param_device &pd,
+                    const float *angles, size_t anglesPerMap, const long long *angleOffsets = nullptr,
+                    const float *voluPerMap = nullptr);
   void runRound2(); // --RefineOrientations: every particle against best (x) grid, OutputFile_Round2
   void runRound2Seeds(); // the same around several seeds per particle (--RefineSeeds >= 2)
   std::vector<Shard> shards;

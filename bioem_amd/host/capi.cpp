@@ -2,6 +2,7 @@
 // the reference performs on the host before the hot loop.
 #include <cstdio>
 #include <cstring>
+#include <string>
 
 #include "bioem_host.h"
 
@@ -166,6 +167,19 @@ int bioem_host_read_best_parameters(const char *file, bioem_host_best_params *ou
 int bioem_host_write_bestmap(const char *file, const float *v, int N, int ddx, int ddy, int mapOnly)
 {
   return bioem_host::write_bestmap_text(file, v, N, ddx, ddy, mapOnly != 0) ? 0 : 1;
+}
+
+// the --ProbCTF text of a CTF table tab[nCTF][nMaps] (write_ctf_prob, bioem_host.h); angles: one list for all maps
+// (anglesPerMap = 0) or anglesPerMap entries per map; voluPerMap may be NULL.  Returns 0, or 1 with the text in err[cap]
+int bioem_host_write_ctf_prob(const char *file, const bioem_hip_prob_map *tab, int nCTF, int nMaps, const float *ctfParam3,
+                              int usepsf, float elecwavel, int doquater, const float *angles, int anglesPerMap,
+                              float Ntotpi, float volu, const float *voluPerMap, char *err, int cap)
+{
+  const std::string e = bioem_host::write_ctf_prob(file, tab, nCTF, nMaps, ctfParam3, usepsf != 0, elecwavel, doquater != 0,
+                                                   angles, (size_t) anglesPerMap, nullptr, Ntotpi, volu, voluPerMap);
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return e.empty() ? 0 : 1;
 }
 
 // the MRC stack of --BestMaps: maps [nMaps][N][N] appended in batches of `batch` images

@@ -71,6 +71,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"Inputfile", required_argument, 0, 0},
                                        {"PrintBestCalMap", required_argument, 0, 0},
                                        {"BestMaps", required_argument, 0, 0},
+                                       {"ProbCTF", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
                                        {"RefineSeeds", required_argument, 0, 0},
@@ -100,6 +101,8 @@ int Driver::readOptions(int ac, char **av)
     printf("  --RefineLogWindow arg  (Optional) ... of which only those within arg of the best log posterior\n");
     printf("  --BestMaps arg         (Optional) Write the calculated image of every particle's best match as an MRC\n");
     printf("                         stack (with --RefineOrientations also arg_Round2)\n");
+    printf("  --ProbCTF arg          (Optional) Write the posterior per particle and CTF set (log posterior and best match\n");
+    printf("                         under every CTF set; with --RefineOrientations also arg_Round2)\n");
     printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
@@ -188,6 +191,11 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Writing the best calculated maps to: " << optarg << "\n";
       bestMapsFile = optarg;
     }
+    else if (name == "ProbCTF")
+    {
+      std::cout << "Writing the posterior per CTF set to: " << optarg << "\n";
+      probCtfFile = optarg;
+    }
     else if (name == "PrintBestCalMap")
     {
       std::cout << "Reading best parameters from file: " << optarg << "\n";
@@ -226,8 +234,8 @@ int Driver::readOptions(int ac, char **av)
   if (!bestParamFile.empty())
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
-    if (!bestMapsFile.empty() || !refineFile.empty())
-      fatal("--PrintBestCalMap goes without --BestMaps and --RefineOrientations");
+    if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty())
+      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF and --RefineOrientations");
     const std::string err = read_best_parameters(bestParamFile.c_str(), best);
     if (!err.empty())
       fatal("%s", err.c_str());
@@ -361,6 +369,8 @@ int Driver::configure(int ac, char **av)
                                     param.shiftX, param.shiftY),
           "upload model");
     check(h, bioem_hip_upload_orientations(h, param.angles.data(), nA, param.doquater ? 1 : 0), "upload orientations");
+    if (!probCtfFile.empty())
+      check(h, bioem_hip_enable_ctf_table(h, 1), "enable CTF table");
   }
   // RCCL carries the merge when every shard has a GPU of its own
   // (BIOEM_FORCE_RCCL=1: also with a single shard -- a one-rank communicator, to exercise this path on a one-GPU box)
@@ -654,6 +664,13 @@ int Driver::run()
     }
   }
   writeOutput();
+  if (!probCtfFile.empty())
+  { // the tables never go through RCCL: fetched from every handle and merged on the host, whatever carried the entries
+    std::vector<bioem_hip_handle> hs;
+    for (Shard &sh : shards)
+      hs.push_back(sh.h);
+    writeCtfProb(probCtfFile, hs, param.pd, param.angles.data(), 0);
+  }
   if (!bestMapsFile.empty()) // from the merged records, on the first handle (every handle holds the global list)
     writeBestMaps(bestMapsFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!refineFile.empty())
@@ -712,6 +729,8 @@ void Driver::runRound2()
                                   param.shiftX, param.shiftY),
         "upload model");
   check(h, bioem_hip_upload_particle_orientations(h, lists.data(), G, 1), "upload particle orientations");
+  if (!probCtfFile.empty())
+    check(h, bioem_hip_enable_ctf_table(h, 1), "enable CTF table");
   std::vector<bioem_hip_prob_map> pm(nMaps);
   for (int i = 0; i < nMaps; i++) // bioem.cpp:681-699
   {
@@ -724,6 +743,8 @@ void Driver::runRound2()
   check(h, bioem_hip_finish_run(h, pm.data()), "finish run (second round)");
   if (!bestMapsFile.empty())
     writeBestMaps(bestMapsFile + "_Round2", h, pm.data(), 1);
+  if (!probCtfFile.empty())
+    writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), (size_t) G);
   bioem_hip_destroy(h);
   writeProbabilities(outfileName + "_Round2", pm.data(), pd2, lists.data(), (size_t) G, false);
 }
@@ -801,6 +822,8 @@ void Driver::runRound2Seeds()
                                   param.shiftX, param.shiftY),
         "upload model");
   check(h, bioem_hip_upload_particle_orientation_lists(h, lists.data(), offsets.data(), 1), "upload particle orientation lists");
+  if (!probCtfFile.empty())
+    check(h, bioem_hip_enable_ctf_table(h, 1), "enable CTF table");
   std::vector<bioem_hip_prob_map> pm(nMaps);
   for (int i = 0; i < nMaps; i++) // bioem.cpp:681-699
   {
@@ -813,8 +836,91 @@ void Driver::runRound2Seeds()
   check(h, bioem_hip_finish_run(h, pm.data()), "finish run (second round)");
   if (!bestMapsFile.empty())
     writeBestMaps(bestMapsFile + "_Round2", h, pm.data(), 1);
+  if (!probCtfFile.empty())
+    writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), 0, offsets.data(),
+                 volu.data());
   bioem_hip_destroy(h);
   writeProbabilities(outfileName + "_Round2", pm.data(), pd2, lists.data(), 0, false, offsets.data(), volu.data());
+}
+
+// --ProbCTF (layout: write_ctf_prob, bioem_host.h)
+std::string write_ctf_prob(const char *file, const bioem_hip_prob_map *tab, int nCTF, int nMaps, const float *ctfParam3,
+                           bool usepsf, float elecwavel, bool doquater, const float *angles, size_t anglesPerMap,
+                           const long long *angleOffsets, float Ntotpi, float volu, const float *voluPerMap)
+{
+  char buf[200];
+  for (int i = 0; i < nMaps; i++)
+    for (int c = 0; c < nCTF; c++)
+    {
+      const bioem_hip_prob_map &e = tab[(size_t) c * nMaps + i];
+      if (e.Total == 0.0 && e.Constoadd == -999999.)
+      {
+        snprintf(buf, sizeof(buf), "RefMap %d has no comparison under CTF set %d: its entry of the CTF table is untouched", i, c);
+        return buf;
+      }
+    }
+  const char *bar = "************************* HEADER:: NOTATION *******************************************\n";
+  std::ofstream out;
+  out.precision(4);
+  out.setf(std::ios::fixed);
+  out.open(file);
+  out << bar;
+  out << " RefMap:  MapNumber - CTF set ; " << (usepsf ? "PSF amp - PSF phase - PSF envelope" : "CTF amp - CTF defocus [micro-m] - CTF B-Env")
+      << " - logP - cal log Probability + Constant: Numerical Const. + log (volume) ; Best: "
+      << (doquater ? "q1 - q2 - q3 - q4" : "alpha[rad] - beta[rad] - gamma[rad]")
+      << " - center x - center y - normalization - offsett\n";
+  out << bar;
+  for (int i = 0; i < nMaps; i++)
+  {
+    // the constant of this map's LogProb line (Driver::writeProbabilities), by the same expressions
+    const double numconst = 0.5 * log(M_PI) + (1 - Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(voluPerMap ? voluPerMap[i] : volu);
+    const float *A = angles + 4 * (angleOffsets ? (size_t) angleOffsets[i] : anglesPerMap * (size_t) i); // this map's list
+    for (int c = 0; c < nCTF; c++)
+    {
+      const bioem_hip_prob_map &pm = tab[(size_t) c * nMaps + i];
+      const double lp = log(pm.Total) + pm.Constoadd + 0.5 * log(M_PI) + (1 - Ntotpi * 0.5) * (log(2 * M_PI) + 1) +
+                        log(voluPerMap ? voluPerMap[i] : volu);
+      const float *k = ctfParam3 + 3 * (size_t) c;
+      const float *a = A + 4 * (size_t) pm.max_prob_orient;
+      out << " " << i << " " << c << " " << k[0] << " ";
+      if (!usepsf)
+        out << k[1] / 2.f / M_PI / elecwavel * 0.0001 << " " << k[2] << " ";
+      else
+        out << k[1] << " " << k[2] << " ";
+      out << lp << " Separated: " << log(pm.Total) << " " << pm.Constoadd << " " << numconst << " Best: " << a[0] << " "
+          << a[1] << " " << a[2] << " ";
+      if (doquater)
+        out << a[3] << " ";
+      out << pm.max_prob_cent_x << " " << pm.max_prob_cent_y << " " << pm.max_prob_norm << " " << pm.max_prob_mu << "\n";
+    }
+  }
+  out.close();
+  if (!out)
+    return std::string("Writing ") + file;
+  return "";
+}
+
+void Driver::writeCtfProb(const std::string &file, const std::vector<bioem_hip_handle> &hs, const bioem_hip_param_device &pd,
+                          const float *angles, size_t anglesPerMap, const long long *angleOffsets, const float *voluPerMap)
+{
+  const int nMaps = particles.ntot, nC = param.nTotCTFs;
+  const size_t n = (size_t) nC * nMaps;
+  std::vector<std::vector<bioem_hip_prob_map>> tabs(hs.size(), std::vector<bioem_hip_prob_map>(n));
+  std::vector<const void *> ptrs;
+  for (size_t g = 0; g < hs.size(); g++)
+  {
+    check(hs[g], bioem_hip_ctf_table(hs[g], tabs[g].data()), "CTF table");
+    ptrs.push_back(tabs[g].data());
+  }
+  std::vector<bioem_hip_prob_map> merged(n);
+  if (bioem_hip_merge_host((int) hs.size(), (int) n, 0, 0, ptrs.data(), merged.data()))
+    fatal("merge failed");
+  const std::string err = write_ctf_prob(file.c_str(), merged.data(), nC, nMaps, param.ctfParam.data(), param.usepsf,
+                                         param.elecwavel, param.doquater, angles, anglesPerMap, angleOffsets, pd.Ntotpi,
+                                         pd.volu, voluPerMap);
+  if (!err.empty())
+    fatal("--ProbCTF: %s", err.c_str());
+  std::cout << "Posterior per CTF set of " << nMaps << " particles x " << nC << " CTF sets written to: " << file << "\n";
 }
 
 void Driver::cleanup()

@@ -140,3 +140,28 @@ def write_mrc_stack(path, maps, batch=64):
     assert m.ndim == 3 and m.shape[1] == m.shape[2]
     if L.bioem_host_write_mrc_stack(path.encode(), m.ctypes.data, m.shape[0], m.shape[1], int(batch)):
         raise RuntimeError("writing %s failed" % path)
+
+
+def write_ctf_prob(path, table, ctfParam, angles, Ntotpi, volu, usepsf=False, elecwavel=0.019688, isQuat=True,
+                   angles_per_map=0, volu_per_map=None):
+    """the --ProbCTF text file of a CTF table [nCTF, nMaps] (Engine.ctf_table, merge_ctf_tables): the writer the CLI
+    uses.  angles [n, 4]: the list `orient` indexes, one for all maps, or angles_per_map entries per map.  Raises
+    ValueError with the writer's message where the CLI would end with it (an entry no comparison touched)."""
+    from .engine import PROB_MAP_DTYPE
+    L = load_host_library()
+    L.bioem_host_write_ctf_prob.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float,
+                                            C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_char_p,
+                                            C.c_int]
+    tab = np.ascontiguousarray(table, dtype=PROB_MAP_DTYPE)
+    assert tab.ndim == 2
+    par = np.ascontiguousarray(ctfParam, dtype=np.float32)
+    assert par.shape == (tab.shape[0], 3)
+    ang = np.ascontiguousarray(angles, dtype=np.float32).reshape(-1, 4)
+    vpm = None if volu_per_map is None else np.ascontiguousarray(volu_per_map, dtype=np.float32)
+    assert vpm is None or vpm.shape == (tab.shape[1],)
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_ctf_prob(path.encode(), tab.ctypes.data, tab.shape[0], tab.shape[1], par.ctypes.data,
+                                   int(bool(usepsf)), float(elecwavel), int(bool(isQuat)), ang.ctypes.data,
+                                   int(angles_per_map), float(Ntotpi), float(volu),
+                                   None if vpm is None else vpm.ctypes.data, err, 512):
+        raise ValueError(err.value.decode())

@@ -207,6 +207,28 @@ int bioem_hip_max_batch(bioem_hip_handle h, int *maxOrientations, int *maxRows);
 /* bioem_cuda::deviceFinishRun (bioem_cuda.cu:1013-1021): synchronise, download the probability block. */
 int bioem_hip_finish_run(bioem_hip_handle h, void *pProb_host);
 
+/* The posterior per CTF set and particle (no reference counterpart: the reference would need one process per CTF set).
+ * The CTF table is [nCTF][nMaps] bioem_hip_prob_map, CTF index slowest and GLOBAL.  Entry (c, p) is what particle p's
+ * entry of the probability block would be had the run compared CTF set c only: the fold, in orientation order, of the
+ * comparisons (o, c) by the rules of the particle entries (log-sum-exp in double, first maximum = lowest row,
+ * max_prob_conv = c, the other record fields from the best row), with whatever priors the comparisons carry.  It
+ * accumulates across batches, launches and calls like the particle entries, through every comparison entry of every
+ * handle kind (bioem_hip_compare, the fused and the staged entries, bioem_hip_compare_own_orientations, where
+ * max_prob_orient is the index in the particle's own list).  Per particle the log-sum-exp over c of
+ * log(Total) + Constoadd equals the particle entry's, and the entry of largest Constoadd (lowest c among equals)
+ * carries the particle entry's record.  No atomics: two runs give the same bits.
+ * bioem_hip_enable_ctf_table(h, 1) allocates the nCTF x nMaps entries on the device (on = 0 frees them); call it
+ * outside a run: between bioem_hip_start_run and bioem_hip_finish_run it returns 2 with a message.  The default is off:
+ * a handle that never enables the table allocates nothing and launches nothing for it.  bioem_hip_start_run
+ * initialises the entries as the reference initialises a particle entry (Total = 0, Constoadd = MIN_PROB, the rest 0).
+ * bioem_hip_ctf_table flushes the rows staged through bioem_hip_compare, synchronises and copies the table to
+ * out[nCTF * nMaps]; it returns 2 when the table is not enabled.
+ * Shards (orientation blocks, CTF sub-ranges or both): fetch every handle's table and merge them, shards in ascending
+ * orientation-block order, with bioem_hip_merge_host(nShards, nCTF * nMaps, 0, 0, tables, out) -- the table is an array
+ * of map entries and the merge works entry by entry; an entry a shard never touched drops out of it. */
+int bioem_hip_enable_ctf_table(bioem_hip_handle h, int on);
+int bioem_hip_ctf_table(bioem_hip_handle h, bioem_hip_prob_map *out);
+
 /* The calculated image of the best match of particles [iMapBegin, iMapEnd): what bioem::printModel writes for ONE
  * hand-copied record (bioem.cpp:624-657, 1925-2085), for every record of a run, on the device.
  * records = [nMaps] bioem_hip_prob_map on the HOST (the block of finish_run, or a merged one: indices are global).
