@@ -25,6 +25,9 @@
 //                          are consumed (output pruning), so no radix-7 butterfly is ever needed for N = 224.  The
 //                          transform along ky is a pruned real DFT evaluated from LDS for the window only.
 //                        k_nyquist_rows   the Nyquist column of 128^2 / 256^2 by direct summation
+//                        both also on OwnCompareArgs / OwnNyquistArgs (compare_args.hpp; kernels_fast_own.hip): the same
+//                          kernels with a block table, one launch per batch of the own-list pass ("k_compare_fast_own",
+//                          "k_nyquist_rows_own" in the plan's labels); the other families: one launch per particle
 //                        posterior_batch  the log posterior of a batch of displacements (all comparison kernels)
 //   compare_fastm.hpp    k_compare_fastm  27- / 31-row windows: the same column pass, the window pass as one 32 x 32 tile of
 //                          v_mfma_f32_32x32x2_f32 (exact f32) per comparison on the matrix cores
@@ -44,8 +47,6 @@
 //                          of any length: bioem_hip_compare_own_orientations)
 //                        k_fold_ctf, k_fold_own_ctf: the posterior per (CTF set, particle), a second fold of the same
 //                          partials into the [nCTF][nMaps] table of bioem_hip_enable_ctf_table (off by default)
-//   compare_fast_own.hpp k_compare_fast_own, k_nyquist_rows_own (kernels_fast_own.hip): k_compare_fast with a block table,
-//                          one launch per batch of the own-list pass; the other families: one launch per particle
 //   render_kernels.hpp   k_render_gather, k_render_cols, k_render_rows  bioem_hip_render_best_maps: the calculated image of
 //                          every particle's best-match record (bioem.cpp:1925-2085), the full c2r by exact DFT in double
 //   this file            device context, launch logic, the C ABI
@@ -164,9 +165,9 @@ struct bioem_hip_ctx
   int ownK = 0, ownIsQuat = 1;         // ownK: the longest list
   double ownQuatNormDev = 0.;
   int ownOB = 0;                       // slots (particle, list entry) per batch of the own-list pass
-  // the comparison of a batch as ONE launch (k_compare_fast_own: plans of k_compare_fast, where bioem_hip_set_own_launch
-  // asked for it; ownFnPlan: the plan's own kernel, ownFn: the one in use or null), else one launch of the plan's kernel
-  // per particle, the default.  Block table of the batches of particles [ownTabP0, ownTabP1):
+  // the comparison of a batch as ONE launch (k_compare_fast on OwnCompareArgs: plans of k_compare_fast, where
+  // bioem_hip_set_own_launch asked for it; ownFnPlan: the plan's own kernel, ownFn: the one in use or null), else one
+  // launch of the plan's kernel per particle, the default.  Block table of the batches of particles [ownTabP0, ownTabP1):
   // batch b begins at slot ownTabSlot[b] and owns entries ownTabFirst[b] ... ownTabFirst[b + 1] of dOwnBlocks
   own_kernel_t ownFn = nullptr, ownFnPlan = nullptr;
   nyq_own_kernel_t ownNyqFn = nullptr;
@@ -616,9 +617,9 @@ int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC
 // Own-list pass: the nOC conv rows of the slot are rows [slot0 nC, ...) of the flat [particle][list entry][CTF] order;
 // every row is compared with its own particle and each particle's rows are folded into its entry.  Row oc of the slot
 // leaves its result in partials[oc].
-//   k_compare_fast plans after bioem_hip_set_own_launch(BIOEM_HIP_OWN_LAUNCH_BATCH): ONE launch of k_compare_fast_own over
-//     the batch, its blocks mapped to (particle, four rows) by the block table of the batch (own_block_table); the
-//     Nyquist rows by k_nyquist_rows_own.
+//   k_compare_fast plans after bioem_hip_set_own_launch(BIOEM_HIP_OWN_LAUNCH_BATCH): ONE launch of k_compare_fast on
+//     OwnCompareArgs over the batch, its blocks mapped to (particle, four rows) by the block table of the batch
+//     (own_block_table); the Nyquist rows by k_nyquist_rows on OwnNyquistArgs.
 //   every other family, and the default of all (BIOEM_HIP_OWN_LAUNCH_PARTICLE): the comparison kernels as they are, once
 //     per particle with rows in the slot: a launch over that particle's run of rows with nMaps = 1, ref / sumRef /
 //     sumsqRef pointed at the particle and conv / params / postc / partials / tnyq at the run -- exactly the launch a
@@ -661,8 +662,9 @@ int launch_compare_own(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC,
     dim3 grid, block;
     const CompareArgs a = compare_args(h, bb, nOC, h->nMaps, grid, block);
     if (P.nyq)
-      hipLaunchKernelGGL(h->ownNyqFn, dim3((nOC + 63) / 64), dim3(256), 0, h->stream, a, h->dSlotParticle, row0, nC);
-    hipLaunchKernelGGL(h->ownFn, dim3(nBlocks), dim3(256), P.ldsBytes, h->stream, a, h->dOwnBlocks + first);
+      hipLaunchKernelGGL(h->ownNyqFn, dim3((nOC + 63) / 64), dim3(256), 0, h->stream,
+                         OwnNyquistArgs{a, h->dSlotParticle, row0, nC});
+    hipLaunchKernelGGL(h->ownFn, dim3(nBlocks), dim3(256), P.ldsBytes, h->stream, OwnCompareArgs{a, h->dOwnBlocks + first});
   }
   else
     for (int p = pFirst; p < pEnd; p++)
@@ -725,7 +727,7 @@ std::vector<int> own_batches(const bioem_hip_ctx *h, int p0, int p1)
   return first;
 }
 
-// Block table of k_compare_fast_own for the batches of particles [p0, p1): one entry {particle, first row, end row, 0}
+// Block table of k_compare_fast on OwnCompareArgs for the batches of particles [p0, p1): one entry {particle, first row, end row, 0}
 // per block, rows counted from the batch's first row, at most four consecutive rows of ONE particle's run in the batch
 // (the groups of four begin at the run's first row, as the per-particle launch forms them).  It depends on the offsets,
 // nCTF and the batch cuts only.  Order inside a batch (the order does not change results; DESIGN 2.9 has the

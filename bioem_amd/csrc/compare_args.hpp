@@ -37,6 +37,24 @@ struct CompareArgs
   PD pd;
 };
 
+// The own-list pass (one orientation list per particle, bioem_hip_compare_own_orientations) runs k_compare_fast and
+// k_nyquist_rows over a batch of rows whose particles differ: the same kernels, instantiated on an argument block that
+// adds the mapping of the launch (the ARGS template parameter, compare_fast.hpp).
+// One block-table entry per block: {particle, first row, end row, 0} -- at most four consecutive rows [first, end) of that
+// particle's run in the batch (rows are indices into conv / params / postc / partials / tnyq of the launch)
+typedef int __attribute__((ext_vector_type(4))) own_i32x4;
+typedef const own_i32x4 __attribute__((address_space(4))) *const_int4_ptr;
+struct OwnCompareArgs : CompareArgs
+{
+  const int4 *__restrict__ blocks; // the block table of the batch (own_block_table, bioem_hip.hip)
+};
+struct OwnNyquistArgs : CompareArgs
+{
+  // slotParticle[s] = particle of flat slot s; row oc of the launch is row row0 + oc of the flat order, nCTF rows a slot
+  const int *__restrict__ slotParticle;
+  int row0, nCTF;
+};
+
 // k_compare_fast, static 21-row window: the window pass over |dy| (window_accumulate_sym, compare_fast.hpp) reads
 //   symtab[column pair kp][j] = {cos, sin (2 pi (2 kp) j gs / N), cos, sin (2 pi (2 kp + 1) j gs / N)},  j = |dy| / gs
 // kSymEntries float4 per column pair (|dy| = 0..10 and one entry of zeros: the third lane group reads four entries as the

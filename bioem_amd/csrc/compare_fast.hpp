@@ -4,6 +4,8 @@
 #ifndef BIOEM_COMPARE_FAST_HPP
 #define BIOEM_COMPARE_FAST_HPP
 
+#include <type_traits>
+
 namespace
 {
 
@@ -368,9 +370,16 @@ __device__ __forceinline__ void window_accumulate_sym(const float2 *Trow, const 
 // GS (1..4): row stride of the window in pixels.  T row m (-WD..WD) holds displacement dx = m*GS, so a coarse
 // DISPLACE_CENTER grid whose offsets are all multiples of GS reaches +-15*GS pixels with the same 2*WD+1 rows.
 // (27- and 31-row windows: k_compare_fastm, compare_fastm.hpp)
-template <int WD, int R, bool NYQ, int GS>
-__global__ __launch_bounds__(256, 3) void k_compare_fast(const CompareArgs a)
+// ARGS: CompareArgs, the all-to-all launch (every particle against every row), or OwnCompareArgs, ONE launch over a batch
+// of the own-list pass, rows whose particles differ (kernels_fast_own.hip; the API's label "k_compare_fast_own<...>").
+// The variant is a template parameter of the kernel itself and differs at the three sites marked OWN -- the
+// block-to-work mapping and the index that addresses the per-row buffers -- never a wrapper around a shared body: that
+// changes the code of every instantiation.  Everything a wave computes for a (particle, row) pair is the
+// same arithmetic in the same order, so a row's partial equals the per-particle launch's bit for bit.
+template <int WD, int R, bool NYQ, int GS, class ARGS = CompareArgs>
+__global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
 {
+  constexpr bool OWN = !std::is_same<ARGS, CompareArgs>::value;
   static_assert(WD <= 10, "windows of at most 21 rows; 27 / 31 rows: k_compare_fastm");
   constexpr int NW = 2 * WD + 1;
   constexpr int R2 = R / 2;            // rows (k2 pairs) per k1 step
@@ -421,12 +430,28 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const CompareArgs a)
   // (pchunk/8 particles) x (a few groups): every particle line is then shared through that XCD's L2 by several
   // groups and every conv line by pchunk/8 particles, instead of each particle line being fetched from Infinity
   // Cache/HBM once per group.
-  int p, ocg;
-  if (!fast_block_pair(a, p, ocg))
-    return;
-  const int oc_raw = ocg * 4 + wave;
-  const bool oc_valid = oc_raw < a.nOC;
-  const int oc = oc_valid ? oc_raw : a.nOC - 1;
+  // OWN: block -> one entry of the block table, {particle, first row, end row, 0} (compare_args.hpp).  blockIdx is
+  // uniform, the table is read through the constant address space: scalar loads.  The host builds the table
+  // (own_block_table, bioem_hip.hip): every entry lies inside the launch.
+  int p, ocFirst, ocEnd; // the block's rows: [ocFirst, ocEnd), at most four
+  if constexpr (OWN)
+  {
+    const own_i32x4 be = *((const_int4_ptr) (unsigned long long) (a.blocks + blockIdx.x));
+    p = be.x;
+    ocFirst = be.y;
+    ocEnd = be.z;
+  }
+  else
+  {
+    int ocg;
+    if (!fast_block_pair(a, p, ocg))
+      return;
+    ocFirst = ocg * 4;
+    ocEnd = a.nOC;
+  }
+  const int oc_raw = ocFirst + wave;
+  const bool oc_valid = oc_raw < ocEnd;
+  const int oc = oc_valid ? oc_raw : ocEnd - 1;
   const int Hp = a.Hp; // row-pair pitch in 16-byte words (H, or H + 15: comparison_pitch in bioem_hip.hip)
   const size_t M = (size_t) N * Hp;
   // buffer descriptors built from wave-uniform values only (blockIdx / readfirstlane'd wave id)
@@ -632,7 +657,8 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const CompareArgs a)
   }
   if (NYQ)
   {
-    const float *tq = a.tnyq + ((size_t) p * a.ldPart + oc) * NW;
+    // OWN: one set of Nyquist rows per row of the launch
+    const float *tq = a.tnyq + (OWN ? (size_t) oc : (size_t) p * a.ldPart + oc) * NW;
     const float sg = (dy & 1) ? -1.f : 1.f;
     if (symw)
     { // the column's term is real: it enters A only, with the sign of (-1)^|dy|
@@ -709,7 +735,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const CompareArgs a)
     r.id = L.id;
     r.value = L.val;
     r.pad = 0;
-    a.partials[(size_t) p * a.ldPart + oc] = r;
+    a.partials[OWN ? (size_t) oc : (size_t) p * a.ldPart + oc] = r; // OWN: one partial per row of the launch
   }
 }
 
@@ -722,20 +748,38 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const CompareArgs a)
 // Q = 4 (few particles: 16 x 16 pairs per block are 192 blocks for 10 particles x 3 072 spectra, every thread a chain of
 // N/2 row pairs): the four waves of a block share its 4 x 16 pairs, wave w the w-th quarter of the row pairs in order
 // (the twiddles stay wave-uniform), the quarters added through LDS as (q0 + q1) + (q2 + q3).
-template <int WD, int Q>
-__global__ __launch_bounds__(256) void k_nyquist_rows(const CompareArgs a)
+// ARGS = OwnNyquistArgs (OWN; the API's label "k_nyquist_rows_own<WD>"): the rows of ONE launch of the own-list pass, row
+// oc of the launch against ITS particle -- the four waves of a block share its 64 rows, one thread per row and quarter,
+//   tnyq[oc][m + WD] = the sum above with p = slotParticle[(row0 + oc) / nCTF].
+// The arithmetic is that of Q = 4 -- the kernel a per-particle launch runs --, so the rows equal that launch's bit for bit.
+template <int WD, int Q, class ARGS = CompareArgs>
+__global__ __launch_bounds__(256) void k_nyquist_rows(const ARGS a)
 {
+  constexpr bool OWN = !std::is_same<ARGS, CompareArgs>::value;
   static_assert(Q == 1 || Q == 4, "one thread per pair, or one per pair and wave");
+  static_assert(!OWN || Q == 4, "bit identity with a per-particle launch rests on its (q0 + q1) + (q2 + q3) association");
   constexpr int NW = 2 * WD + 1;
   __shared__ float part[Q == 4 ? 2 * 64 * NW : 1];
   const int N = a.N, H = a.H, N1 = a.N1;
   const int R2 = N / (2 * N1);
-  const int tilesOC = (a.nOC + 15) / 16;
-  const int tp = blockIdx.x / tilesOC, to = blockIdx.x - tp * tilesOC;
   const int q = Q == 1 ? 0 : __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
   const int t = Q == 1 ? threadIdx.x : threadIdx.x & 63;
-  const int p = tp * (16 / Q) + (t >> 4), oc = to * 16 + (t & 15);
-  const bool valid = p < a.nMaps && oc < a.nOC;
+  int p, oc;
+  bool valid;
+  if constexpr (OWN)
+  { // OWN: thread -> row oc of the launch and the particle of that row's slot (compare_args.hpp)
+    oc = blockIdx.x * 64 + t;
+    valid = oc < a.nOC;
+    p = valid ? a.slotParticle[(a.row0 + oc) / a.nCTF] : 0;
+  }
+  else
+  {
+    const int tilesOC = (a.nOC + 15) / 16;
+    const int tp = blockIdx.x / tilesOC, to = blockIdx.x - tp * tilesOC;
+    p = tp * (16 / Q) + (t >> 4);
+    oc = to * 16 + (t & 15);
+    valid = p < a.nMaps && oc < a.nOC;
+  }
   const size_t M = (size_t) N * a.Hp; // an image of the comparison layout (Hp >= H: its row-pair pitch)
   const float2 *F = a.ref + (size_t) (valid ? p : 0) * M;
   const float2 *C = a.conv + (size_t) (valid ? oc : 0) * M;
@@ -815,7 +859,8 @@ __global__ __launch_bounds__(256) void k_nyquist_rows(const CompareArgs a)
   }
   if (valid && q == 0)
   {
-    float *o = a.tnyq + ((size_t) p * a.ldPart + oc) * NW;
+    // OWN: one set of rows per row of the launch
+    float *o = a.tnyq + (OWN ? (size_t) oc : (size_t) p * a.ldPart + oc) * NW;
 #pragma unroll
     for (int d = 0; d < NW; d++)
       o[d] = acc[d];

@@ -35,8 +35,8 @@ BIOEM_HIDDEN const BioemKernelEntry *bioem_kernels_wide2_short(int *n); // regis
 BIOEM_HIDDEN const BioemKernelEntry *bioem_kernels_wide2_16(int *n);
 BIOEM_HIDDEN const BioemKernelEntry *bioem_kernels_wide2_long(int *n);  // 20..32 points
 BIOEM_HIDDEN const BioemKernelEntry *bioem_kernels_odd(int *n);         // k_compare_rows, k_compare_oddfft
-// the own-list pass (kernels_fast_own.hip): k_compare_fast_own<WD, R, NYQ, GS>, void (*)(CompareArgs, const int4 *), under
-// the arguments of its k_compare_fast; k_nyquist_rows_own<WD>, void (*)(CompareArgs, const int *, int, int), for WD 5 / 10
+// the own-list pass (kernels_fast_own.hip): k_compare_fast<WD, R, NYQ, GS, OwnCompareArgs>, void (*)(OwnCompareArgs), under
+// the template arguments of its k_compare_fast; k_nyquist_rows<WD, 4, OwnNyquistArgs>, void (*)(OwnNyquistArgs), for WD 5 / 10
 BIOEM_HIDDEN const BioemKernelEntry *bioem_kernels_fast_own(int *n);
 BIOEM_HIDDEN const void *bioem_nyquist_rows_own(int WD);
 

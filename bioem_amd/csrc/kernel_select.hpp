@@ -88,10 +88,11 @@ fast_kernel_t find_kernel(int family, int a0 = 0, int a1 = 0, int a2 = 0, int a3
   return nullptr;
 }
 
-// the own-list pass: k_compare_fast_own (kernels_fast_own.hip) under the arguments of the plan's k_compare_fast, or null --
-// another family, a tiled plan, an instantiation that was left out: such a shape keeps one launch per particle
-typedef void (*own_kernel_t)(const CompareArgs, const int4 *);
-typedef void (*nyq_own_kernel_t)(const CompareArgs, const int *, int, int);
+// the own-list pass: k_compare_fast on OwnCompareArgs (kernels_fast_own.hip) under the template arguments of the plan's
+// k_compare_fast, or null -- another family, a tiled plan, an instantiation that was left out: such a shape keeps one
+// launch per particle
+typedef void (*own_kernel_t)(const OwnCompareArgs);
+typedef void (*nyq_own_kernel_t)(const OwnNyquistArgs);
 
 own_kernel_t find_own_kernel(int family, int wd, int R, bool nyq, int gs)
 {
@@ -602,7 +603,8 @@ own_kernel_t plan_own_kernel(const KernelPlan &P)
 
 void plan_signature(const KernelPlan &P, char *buf, size_t cap);
 
-// what the own-list pass launches: "k_compare_fast_own<...>" (one launch per batch), or the plan's kernel once per particle
+// what the own-list pass launches: "k_compare_fast_own<...>" (one launch per batch; the label of
+// k_compare_fast<..., OwnCompareArgs>), or the plan's kernel once per particle
 void plan_own_signature(const KernelPlan &P, bool single, char *buf, size_t cap)
 {
   if (single)

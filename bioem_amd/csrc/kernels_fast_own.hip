@@ -1,11 +1,11 @@
-// kernels_fast_own.hip -- the k_compare_fast_own instantiations: the K_FAST lines of kernel_table.inc once more, with the
-// block order of the own-list pass (compare_fast_own.hpp), and the k_nyquist_rows_own kernels that go with them
+// kernels_fast_own.hip -- k_compare_fast on OwnCompareArgs ("k_compare_fast_own<...>" in the API's labels): the K_FAST
+// lines of kernel_table.inc once more, with the block order of the own-list pass (compare_fast.hpp), and the
+// k_nyquist_rows on OwnNyquistArgs ("k_nyquist_rows_own<WD>") that go with them
 #include "engine_types.hpp"
 #include "posterior.hpp"
 #include "fft_registers.hpp"
 #include "compare_args.hpp"
 #include "compare_fast.hpp"
-#include "compare_fast_own.hpp"
 
 namespace
 {
@@ -19,7 +19,7 @@ const void *own_kernel()
   if constexpr (own_left_out(WD, R, NYQ, GS))
     return nullptr;
   else
-    return reinterpret_cast<const void *>(k_compare_fast_own<WD, R, NYQ, GS>);
+    return reinterpret_cast<const void *>(k_compare_fast<WD, R, NYQ, GS, OwnCompareArgs>);
 }
 } // namespace
 
@@ -27,13 +27,13 @@ const void *own_kernel()
 #define BIOEM_FAMILY_FN bioem_kernels_fast_own
 #include "kernels_family.inc"
 
-// the Nyquist-column kernel of a k_compare_fast_own<WD, ...> launch (windows of 11 and 21 rows)
+// the Nyquist-column kernel of a k_compare_fast<WD, ..., OwnCompareArgs> launch (windows of 11 and 21 rows)
 const void *bioem_nyquist_rows_own(int WD)
 {
   switch (WD)
   {
-  case 5: return reinterpret_cast<const void *>(k_nyquist_rows_own<5>);
-  case 10: return reinterpret_cast<const void *>(k_nyquist_rows_own<10>);
+  case 5: return reinterpret_cast<const void *>(k_nyquist_rows<5, 4, OwnNyquistArgs>);
+  case 10: return reinterpret_cast<const void *>(k_nyquist_rows<10, 4, OwnNyquistArgs>);
   default: return nullptr;
   }
 }

@@ -330,7 +330,8 @@ const char *bioem_hip_kernel_signature(bioem_hip_handle h);
  * kernel fits, 2 on invalid arguments. */
 int bioem_hip_plan(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo, char *signature, int cap);
 /* What bioem_hip_compare_own_orientations launches for a configuration once bioem_hip_set_own_launch has asked for one
- * launch per batch, without a device: "k_compare_fast_own<...>" where the shape has that kernel, else the signature of
+ * launch per batch, without a device: "k_compare_fast_own<...>" where the shape has that kernel (the label names the
+ * OwnCompareArgs instantiation of k_compare_fast with those template arguments), else the signature of
  * bioem_hip_plan prefixed "per particle: " (such a shape keeps per-particle launches in every mode).  Same return codes. */
 int bioem_hip_plan_own(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo, char *signature, int cap);
 /* what a handle launches in the mode it is in: "per particle: ..." until bioem_hip_set_own_launch says otherwise */

@@ -62,7 +62,12 @@ def demangle(names):
 def short(name):
     name = name.replace("(anonymous namespace)::", "").replace("void ", "")
     name = re.sub(r"\(CompareArgs\)|\(\(anonymous namespace\)::CompareArgs\)", "", name)
-    return re.sub(r"\(.*\)$", "", name)
+    name = re.sub(r"\(.*\)$", "", name)
+    # k_compare_fast / k_nyquist_rows end in their argument struct; the tables keep the names they have always used:
+    # the all-to-all kernels without it, the own-list instantiations as k_compare_fast_own<...> / k_nyquist_rows_own<WD>
+    name = re.sub(r", CompareArgs>$", ">", name)
+    name = re.sub(r"^k_compare_fast<(.*), OwnCompareArgs>$", r"k_compare_fast_own<\1>", name)
+    return re.sub(r"^k_nyquist_rows<(\d+), 4, OwnNyquistArgs>$", r"k_nyquist_rows_own<\1>", name)
 
 
 def kernels_of(co):
