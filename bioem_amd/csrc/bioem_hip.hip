@@ -49,6 +49,8 @@
 //                          partials into the [nCTF][nMaps] table of bioem_hip_enable_ctf_table (off by default)
 //   render_kernels.hpp   k_render_gather, k_render_cols, k_render_rows  bioem_hip_render_best_maps: the calculated image of
 //                          every particle's best-match record (bioem.cpp:1925-2085), the full c2r by exact DFT in double
+//   ring_kernels.hpp     k_ring_sums, k_ring_fold  bioem_hip_best_match_rings: per Fourier ring the sums of particle x best
+//                          match, particle power and best-match power (kernels_rings.hip; declarations only here)
 //   this file            device context, launch logic, the C ABI
 //   kernels_*.hip        one translation unit per comparison-kernel family (the instantiations of kernel_table.inc),
 //                          linked into the same library: kernels_fast, kernels_fastm, kernels_wide2_{short,16,long},
@@ -114,6 +116,7 @@ struct HipErr
 #include "fold_kernels.hpp"
 #include "window_tiles.hpp"
 #include "render_kernels.hpp"
+#include "ring_kernels.hpp"
 
 struct bioem_hip_ctx
 {
@@ -200,6 +203,14 @@ struct bioem_hip_ctx
   RenderRecord *dRenderRec = nullptr;
   float4 *dRenderAngles = nullptr;
   float *dRenderOut = nullptr;
+  // bioem_hip_best_match_rings / bioem_hip_debug_ring_sums: particle spectra of a batch in reference layout, the scratch of
+  // the ring pass and its result (allocated at the first call)
+  RenderRecord *dRingRec = nullptr;
+  float4 *dRingAngles = nullptr;
+  float2 *dRingRef = nullptr;
+  double *dRingScratch = nullptr;
+  bioem_hip_ring_sums *dRingOut = nullptr;
+  bool refUp = false; // particles uploaded (either entry)
   bool ctfUp = false; // bioem_hip_upload_ctf has run
   // bioem_hip_enable_ctf_table: [nCTF][nMaps] entries, folded beside the particle entries (k_fold_ctf, k_fold_own_ctf);
   // null = off, nothing allocated and nothing launched
@@ -1525,6 +1536,7 @@ int bioem_hip_upload_particles(bioem_hip_handle h, const float *refFFT, const fl
     HIP_CHECK(h, hipGetLastError());
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
+  h->refUp = true;
   return 0;
 }
 
@@ -1554,6 +1566,7 @@ int bioem_hip_upload_particle_maps(bioem_hip_handle h, const float *maps)
     HIP_CHECK(h, hipGetLastError());
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
+  h->refUp = true;
   return 0;
 }
 
@@ -2615,6 +2628,185 @@ int bioem_hip_render_best_maps(bioem_hip_handle h, const bioem_hip_prob_map *rec
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
   drain_phases(h);
+  return 0;
+}
+
+// ---- Fourier ring sums of the particles against their best-match records (ring_kernels.hpp) ----
+static_assert(sizeof(BioemRingRecord) == sizeof(RenderRecord) && sizeof(bioem_hip_ring_sums) == 24, "record / triple layout");
+
+namespace
+{
+// the staging buffers of the ring entries; a failed allocation (return 1) leaves the handle as it was
+int ring_staging(bioem_hip_ctx *h)
+{
+  if (h->dRingOut)
+    return 0;
+  const size_t OB = (size_t) h->OB;
+  RenderRecord *rec = nullptr;
+  float4 *ang = nullptr;
+  float2 *ref = nullptr;
+  double *scr = nullptr;
+  bioem_hip_ring_sums *out = nullptr;
+  if (dev_alloc(h, rec, OB) || dev_alloc(h, ang, OB) || dev_alloc(h, ref, OB * (size_t) h->M) ||
+      dev_alloc(h, scr, bioem_ring_scratch(h->N, h->OB)) || dev_alloc(h, out, OB * (size_t) bioem_ring_count(h->N)))
+  {
+    dev_release(h, rec);
+    dev_release(h, ang);
+    dev_release(h, ref);
+    dev_release(h, scr);
+    dev_release(h, out);
+    (void) hipGetLastError();
+    return 1;
+  }
+  h->dRingRec = rec;
+  h->dRingAngles = ang;
+  h->dRingRef = ref;
+  h->dRingScratch = scr;
+  h->dRingOut = out;
+  return 0;
+}
+
+// the ring pass of n staged images (records in dRingRec, particle spectra in dRingRef, projections in slot 0) and
+// its copy to the host
+int ring_batch(bioem_hip_ctx *h, int n, bioem_hip_ring_sums *out)
+{
+  HIP_CHECK(h, bioem_ring_sums_launch(h->stream, h->dRingRef, h->slot[0].specRef, h->dCTF,
+                                      reinterpret_cast<const BioemRingRecord *>(h->dRingRec), n, h->N, h->dTwD,
+                                      h->dRingScratch, h->dRingOut));
+  HIP_CHECK(h, hipMemcpyAsync(out, h->dRingOut, sizeof(bioem_hip_ring_sums) * (size_t) n * bioem_ring_count(h->N),
+                              hipMemcpyDeviceToHost, h->stream));
+  return 0;
+}
+} // namespace
+
+int bioem_hip_ring_count(int numberPixels) { return bioem_ring_count(numberPixels); }
+
+int bioem_hip_best_match_rings(bioem_hip_handle h, const bioem_hip_prob_map *records, int ownLists, int iMapBegin,
+                               int iMapEnd, bioem_hip_ring_sums *out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[256];
+  auto refuse = [&](const char *why) {
+    h->err = std::string("best_match_rings: ") + why;
+    return 2;
+  };
+  if (!records || !out)
+    return refuse("null argument");
+  if (iMapBegin < 0 || iMapEnd > h->nMaps || iMapBegin >= iMapEnd)
+    return refuse("particle range empty, reversed or outside [0, nMaps)");
+  if (!h->dPts || h->nPts < 1)
+    return refuse("model not uploaded");
+  if (!h->ctfUp)
+    return refuse("CTF kernels not uploaded");
+  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
+    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
+                           : "orientations not uploaded");
+  if (!h->refUp)
+    return refuse("particles not uploaded");
+  const int N = h->N;
+  std::vector<RenderRecord> recs((size_t) (iMapEnd - iMapBegin));
+  for (int p = iMapBegin; p < iMapEnd; p++)
+  {
+    const bioem_hip_prob_map &r = records[p];
+    const int first = ownLists ? h->ownOff[p] : 0, len = ownLists ? h->ownOff[p + 1] - h->ownOff[p] : h->nAnglesUp;
+    const char *why = nullptr;
+    if (r.max_prob_orient < 0 || r.max_prob_orient >= len)
+      why = "max_prob_orient outside its orientation list";
+    else if (r.max_prob_conv < 0 || r.max_prob_conv >= h->nCTF)
+      why = "max_prob_conv outside [0, nCTF)";
+    else if (r.max_prob_cent_x <= -N || r.max_prob_cent_x >= N || r.max_prob_cent_y <= -N || r.max_prob_cent_y >= N)
+      why = "displacement of N pixels or more";
+    if (why)
+    {
+      snprintf(buf, sizeof(buf), "particle %d: %s (orient %d of %d, conv %d, cent %d %d)", p, why, r.max_prob_orient, len,
+               r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y);
+      return refuse(buf);
+    }
+    recs[(size_t) (p - iMapBegin)] = {first + r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y,
+                                      r.max_prob_norm, r.max_prob_mu};
+  }
+  if (ring_staging(h))
+    return 1;
+  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  const OrientList src = ownLists ? own_list(h) : shared_list(h);
+  const OrientList L = {h->dRingAngles, src.isQuat, src.quatNormDev};
+  const int OB = h->OB;
+  const size_t nRings = (size_t) bioem_ring_count(N);
+  for (size_t b0 = 0; b0 < recs.size(); b0 += (size_t) OB)
+  {
+    const int n = (int) std::min<size_t>((size_t) OB, recs.size() - b0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dRingRec, recs.data() + b0, sizeof(RenderRecord) * n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_render_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, src.d, h->dRingRec, n, h->dRingAngles);
+    HIP_CHECK(h, hipGetLastError());
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, (int) b0, (int) b0 + n, 0, 0) ||
+        project_batch(h, s0, h->stream, L, 0, n) || phase_end(h, h->stream))
+      return 1;
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, (int) b0, (int) b0 + n, 0, 0))
+      return 1;
+    hipLaunchKernelGGL(k_unreorder, dim3(1024), dim3(256), 0, h->stream, h->dRef + h->Mc * ((size_t) iMapBegin + b0),
+                       h->dRingRef, n, N, h->H, h->plan.halfR, h->plan.N1, h->Hp);
+    HIP_CHECK(h, hipGetLastError());
+    if (ring_batch(h, n, out + b0 * nRings) || phase_end(h, h->stream))
+      return 1;
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  drain_phases(h);
+  return 0;
+}
+
+int bioem_hip_debug_ring_sums(bioem_hip_handle h, const float *specR, const float *specP, const bioem_hip_prob_map *records,
+                              int n, bioem_hip_ring_sums *out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  auto refuse = [&](const char *why) {
+    h->err = std::string("debug_ring_sums: ") + why;
+    return 2;
+  };
+  if (!specR || !specP || !records || !out || n < 1)
+    return refuse("null argument or no images");
+  if (!h->ctfUp)
+    return refuse("CTF kernels not uploaded");
+  const int N = h->N;
+  std::vector<RenderRecord> recs((size_t) n);
+  for (int p = 0; p < n; p++)
+  {
+    const bioem_hip_prob_map &r = records[p];
+    if (r.max_prob_conv < 0 || r.max_prob_conv >= h->nCTF || r.max_prob_cent_x <= -N || r.max_prob_cent_x >= N ||
+        r.max_prob_cent_y <= -N || r.max_prob_cent_y >= N)
+    {
+      char buf[160];
+      snprintf(buf, sizeof(buf), "image %d: max_prob_conv outside [0, nCTF) or a displacement of N pixels or more (conv %d, cent %d %d)",
+               p, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y);
+      return refuse(buf);
+    }
+    recs[(size_t) p] = {0, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y, r.max_prob_norm, r.max_prob_mu};
+  }
+  if (ring_staging(h))
+    return 1;
+  if (compat_flush(h))
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  const size_t M = (size_t) h->M, nRings = (size_t) bioem_ring_count(N);
+  for (int b0 = 0; b0 < n; b0 += h->OB)
+  {
+    const int nb = std::min(h->OB, n - b0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dRingRec, recs.data() + b0, sizeof(RenderRecord) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dRingRef, specR + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(s0.specRef, specP + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    if (ring_batch(h, nb, out + (size_t) b0 * nRings))
+      return 1;
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
   return 0;
 }
 

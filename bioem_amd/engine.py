@@ -16,6 +16,7 @@ PHASE_RECORD_DTYPE = np.dtype([("phase", "<i4"), ("iOrientBegin", "<i4"), ("iOri
                                ("iConvEnd", "<i4"), ("pad", "<i4"), ("seconds", "<f8")])
 CANDIDATE_DTYPE = np.dtype([("forAngles", "<f8"), ("ConstAngle", "<f8"), ("logp", "<f8"), ("orient", "<i4"),
                             ("pad", "<i4")])
+RING_SUMS_DTYPE = np.dtype([("cross", "<f8"), ("powParticle", "<f8"), ("powModel", "<f8")])
 MIN_PROB = -999999.0
 
 
@@ -77,6 +78,10 @@ def load_library():
     if hasattr(L, "bioem_hip_enable_ctf_table"):
         L.bioem_hip_enable_ctf_table.argtypes = [vp, ci]
         L.bioem_hip_ctf_table.argtypes = [vp, vp]
+    if hasattr(L, "bioem_hip_best_match_rings"):
+        L.bioem_hip_ring_count.argtypes = [ci]
+        L.bioem_hip_best_match_rings.argtypes = [vp, vp, ci, ci, ci, vp]
+        L.bioem_hip_debug_ring_sums.argtypes = [vp, vp, vp, vp, ci, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -129,11 +134,16 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_upload_particle_orientations", "bioem_hip_compare_own_orientations",
            "bioem_hip_upload_particle_orientation_lists", "bioem_hip_plan_own", "bioem_hip_own_kernel_signature",
            "bioem_hip_set_own_launch", "bioem_hip_render_best_maps", "bioem_hip_enable_ctf_table",
-           "bioem_hip_ctf_table"]
+           "bioem_hip_ctf_table", "bioem_hip_ring_count", "bioem_hip_best_match_rings", "bioem_hip_debug_ring_sums"]
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def ring_count(N):
+    """rings of an N x N image (bioem_hip_ring_count): the rounded radius of the corner coefficient plus one; no device"""
+    return int(load_library().bioem_hip_ring_count(int(N)))
 
 
 def new_prob_block(nMaps, nAngles, writeAngles):
@@ -350,6 +360,44 @@ class Engine:
         rc = self.L.bioem_hip_render_best_maps(self.h, _p(pmap), int(bool(own)), int(p0), p1, _p(out))
         if rc:
             e = RuntimeError("render_best_maps: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+        return out
+
+    def best_match_rings(self, pmap, p0=0, p1=None, own=False):
+        """per Fourier ring the sums of particles [p0, p1) against the spectrum of their best match: RING_SUMS_DTYPE
+        [p1 - p0, ring_count(N)] with cross = sum w Re(R conj(M)), powParticle = sum w |R|^2, powModel = sum w |M|^2 (R the
+        particle's spectrum, M the spectrum of the image render_best_maps writes for the record, w the weight of the
+        Hermitian partner; include/bioem_hip.h).  pmap, own and the calling rules as render_best_maps; needs the
+        particles.  A refused record raises RuntimeError with .rc == 2."""
+        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
+        assert pmap.shape == (self.nMaps,)
+        p1 = self.nMaps if p1 is None else int(p1)
+        out = np.zeros((max(0, p1 - int(p0)), ring_count(self.N)), dtype=RING_SUMS_DTYPE)
+        rc = self.L.bioem_hip_best_match_rings(self.h, _p(pmap), int(bool(own)), int(p0), p1, _p(out))
+        if rc:
+            e = RuntimeError("best_match_rings: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+        return out
+
+    def debug_ring_sums(self, specR, specP, records):
+        """test hook: the ring kernel of best_match_rings on n spectrum pairs handed in, float32 [n, N, H, 2] each (or
+        complex64 [n, N, H]); records: PROB_MAP_DTYPE [n], of which conv, cent_x, cent_y, norm and mu are used.  Needs
+        the CTF kernels only.  Returns RING_SUMS_DTYPE [n, ring_count(N)]; a refusal raises with .rc == 2."""
+        def spec(a):
+            a = np.ascontiguousarray(a)
+            if a.dtype.kind == "c":
+                a = np.ascontiguousarray(a.astype(np.complex64)).view(np.float32).reshape(a.shape + (2,))
+            return np.ascontiguousarray(a, dtype=np.float32)
+        specR, specP = spec(specR), spec(specP)
+        records = np.ascontiguousarray(records, dtype=PROB_MAP_DTYPE)
+        n = len(records)
+        assert specR.shape == (n, self.N, self.H, 2) and specP.shape == specR.shape
+        out = np.zeros((n, ring_count(self.N)), dtype=RING_SUMS_DTYPE)
+        rc = self.L.bioem_hip_debug_ring_sums(self.h, _p(specR), _p(specP), _p(records), n, _p(out))
+        if rc:
+            e = RuntimeError("debug_ring_sums: %s" % self.L.bioem_hip_last_error(self.h).decode())
             e.rc = rc
             raise e
         return out

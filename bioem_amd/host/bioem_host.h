@@ -109,6 +109,18 @@ bool write_bestmap_text(const char *file, const float *v, int N, int ddx, int dd
 std::string write_ctf_prob(const char *file, const bioem_hip_prob_map *tab, int nCTF, int nMaps, const float *ctfParam3,
                            bool usepsf, float elecwavel, bool doquater, const float *angles, size_t anglesPerMap,
                            const long long *angleOffsets, float Ntotpi, float volu, const float *voluPerMap);
+// --BestFRC (bestfrc.cpp): the text file of the ring sums sums[nMaps][nRings] of bioem_hip_best_match_rings.  After the
+// HEADER:: NOTATION bar, one notation line and the bar again, per particle one line per ring s >= 0
+//  RING p s resolution weight FRC powParticle powModel powResidual
+// (resolution = N pixelSize / s in Angstrom, 0 for ring 0; weight = coefficients of the full spectrum in the ring;
+// FRC = cross / sqrt(powParticle powModel), 0 where the product is 0; powResidual = powParticle + powModel - 2 cross) and
+//  SUMMARY p CCC residualRMS res05 res0143
+// (CCC: the same quotient over the sums of rings s >= 1; residualRMS = sqrt(sum_s powResidual / N^4), the RMS over the
+// pixels of particle - best map; res05 / res0143: the resolution of the first ring s >= 1 with FRC < 0.5 / < 0.143, -1
+// when none).  Floating values with 16 significant digits.  Returns the empty string, or the error.
+int frc_ring(int N, int k1, int k2);
+std::vector<double> frc_ring_weights(int N);
+std::string write_best_frc(const char *file, const bioem_hip_ring_sums *sums, int nMaps, int N, float pixelSize);
 // MRC mode-2 stack nx = ny = N, nz = nMaps in the storage order the --ReadMRC reader expects, written batch by batch
 struct MrcStackWriter
 {
@@ -164,6 +176,7 @@ public:
   double refineLogWindow = -1.; // < 0: unlimited
   std::string bestMapsFile;  // --BestMaps: MRC stack of every particle's calculated best-match image (FILE, FILE_Round2)
   std::string probCtfFile;   // --ProbCTF: the posterior per (particle, CTF set) as text (FILE, FILE_Round2)
+  std::string bestFrcFile;   // --BestFRC: ring correlation of every particle against its best match (FILE, FILE_Round2)
   std::string bestParamFile; // --PrintBestCalMap: the reference's one-record mode, no particles, writes BESTMAP
   BestParams best;
   int printBestCalMap();     // bioem::printModel (bioem.cpp:624-657, 1925-2085)
@@ -197,6 +210,8 @@ private:
                           const float *voluPerMap = nullptr);
   // --BestMaps: the records' images from handle h (bioem_hip_render_best_maps), one batch on the host at a time
   void writeBestMaps(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
+  // --BestFRC: the records' ring sums from handle h (bioem_hip_best_match_rings), written by write_best_frc
+  void writeBestFrc(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
   // --ProbCTF: the tables of the handles merged on the host (shards in ascending order) and written
   void writeCtfProb(const std::string &file, const std::vector<bioem_hip_handle> &hs, const bioem_hip_param_device &pd,
                     const float *angles, size_t anglesPerMap, const long long *angleOffsets = nullptr,

@@ -182,6 +182,16 @@ int bioem_host_write_ctf_prob(const char *file, const bioem_hip_prob_map *tab, i
   return e.empty() ? 0 : 1;
 }
 
+// the --BestFRC text of ring sums sums[nMaps][nRings] (write_best_frc, bioem_host.h); 0, or 1 with the text in err[cap]
+int bioem_host_write_best_frc(const char *file, const bioem_hip_ring_sums *sums, int nMaps, int N, float pixelSize,
+                              char *err, int cap)
+{
+  const std::string e = bioem_host::write_best_frc(file, sums, nMaps, N, pixelSize);
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return e.empty() ? 0 : 1;
+}
+
 // the MRC stack of --BestMaps: maps [nMaps][N][N] appended in batches of `batch` images
 int bioem_host_write_mrc_stack(const char *file, const float *maps, int nMaps, int N, int batch)
 {

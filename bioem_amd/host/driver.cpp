@@ -72,6 +72,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"PrintBestCalMap", required_argument, 0, 0},
                                        {"BestMaps", required_argument, 0, 0},
                                        {"ProbCTF", required_argument, 0, 0},
+                                       {"BestFRC", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
                                        {"RefineSeeds", required_argument, 0, 0},
@@ -103,6 +104,8 @@ int Driver::readOptions(int ac, char **av)
     printf("                         stack (with --RefineOrientations also arg_Round2)\n");
     printf("  --ProbCTF arg          (Optional) Write the posterior per particle and CTF set (log posterior and best match\n");
     printf("                         under every CTF set; with --RefineOrientations also arg_Round2)\n");
+    printf("  --BestFRC arg          (Optional) Write the Fourier ring correlation of every particle against its best match\n");
+    printf("                         (per ring: FRC and powers; with --RefineOrientations also arg_Round2)\n");
     printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
@@ -196,6 +199,11 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Writing the posterior per CTF set to: " << optarg << "\n";
       probCtfFile = optarg;
     }
+    else if (name == "BestFRC")
+    {
+      std::cout << "Writing the ring correlation of the best matches to: " << optarg << "\n";
+      bestFrcFile = optarg;
+    }
     else if (name == "PrintBestCalMap")
     {
       std::cout << "Reading best parameters from file: " << optarg << "\n";
@@ -234,8 +242,8 @@ int Driver::readOptions(int ac, char **av)
   if (!bestParamFile.empty())
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
-    if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty())
-      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF and --RefineOrientations");
+    if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty())
+      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC and --RefineOrientations");
     const std::string err = read_best_parameters(bestParamFile.c_str(), best);
     if (!err.empty())
       fatal("%s", err.c_str());
@@ -479,6 +487,41 @@ void Driver::writeBestMaps(const std::string &file, bioem_hip_handle h, const bi
   std::cout << "Best calculated maps of " << nMaps << " particles written to: " << file << "\n";
 }
 
+// --BestFRC: every record's ring sums from handle h, batch by batch, then the text file (write_best_frc)
+void Driver::writeBestFrc(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists)
+{
+  const int nMaps = particles.ntot, N = param.N;
+  const size_t nRings = (size_t) bioem_hip_ring_count(N);
+  int batch = 1;
+  bioem_hip_max_batch(h, &batch, nullptr);
+  batch = std::max(1, std::min(batch, nMaps));
+  std::vector<bioem_hip_ring_sums> sums((size_t) nMaps * nRings);
+  const bioem_hip_ring_sums zero = {0., 0., 0.};
+  for (int p0 = 0; p0 < nMaps; p0 += batch)
+  {
+    const int p1 = std::min(nMaps, p0 + batch);
+    int rc = bioem_hip_best_match_rings(h, pmap, ownLists, p0, p1, sums.data() + (size_t) p0 * nRings);
+    if (rc == 2)
+    { // a record without a best match (a particle the round never compared): its sums are zero, the others are computed
+      for (int p = p0; p < p1 && rc != 1; p++)
+      {
+        rc = bioem_hip_best_match_rings(h, pmap, ownLists, p, p + 1, sums.data() + (size_t) p * nRings);
+        if (rc == 2)
+        {
+          warn("ring sums of RefMap %d not computed: %s", p, bioem_hip_last_error(h));
+          std::fill(sums.begin() + (size_t) p * nRings, sums.begin() + (size_t) (p + 1) * nRings, zero);
+        }
+      }
+      rc = rc == 1 ? 1 : 0;
+    }
+    check(h, rc, "best match rings");
+  }
+  const std::string err = write_best_frc(file.c_str(), sums.data(), nMaps, N, param.pixelSize);
+  if (!err.empty())
+    fatal("--BestFRC: %s", err.c_str());
+  std::cout << "Ring correlation of " << nMaps << " particles against their best match written to: " << file << "\n";
+}
+
 // --PrintBestCalMap: the record of the BEST_* file rendered on the device and written as the reference's BESTMAP text.
 // The reference's file labels the UNSHIFTED map with shifted coordinates (bioem.cpp:2049-2053), so the device renders with
 // X = Y = 0 and the writer applies BEST_DX / BEST_DY to the labels.
@@ -673,6 +716,8 @@ int Driver::run()
   }
   if (!bestMapsFile.empty()) // from the merged records, on the first handle (every handle holds the global list)
     writeBestMaps(bestMapsFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
+  if (!bestFrcFile.empty())
+    writeBestFrc(bestFrcFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!refineFile.empty())
   {
     if (refineSeeds >= 2)
@@ -743,6 +788,8 @@ void Driver::runRound2()
   check(h, bioem_hip_finish_run(h, pm.data()), "finish run (second round)");
   if (!bestMapsFile.empty())
     writeBestMaps(bestMapsFile + "_Round2", h, pm.data(), 1);
+  if (!bestFrcFile.empty())
+    writeBestFrc(bestFrcFile + "_Round2", h, pm.data(), 1);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), (size_t) G);
   bioem_hip_destroy(h);
@@ -836,6 +883,8 @@ void Driver::runRound2Seeds()
   check(h, bioem_hip_finish_run(h, pm.data()), "finish run (second round)");
   if (!bestMapsFile.empty())
     writeBestMaps(bestMapsFile + "_Round2", h, pm.data(), 1);
+  if (!bestFrcFile.empty())
+    writeBestFrc(bestFrcFile + "_Round2", h, pm.data(), 1);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), 0, offsets.data(),
                  volu.data());

@@ -165,3 +165,16 @@ def write_ctf_prob(path, table, ctfParam, angles, Ntotpi, volu, usepsf=False, el
                                    int(angles_per_map), float(Ntotpi), float(volu),
                                    None if vpm is None else vpm.ctypes.data, err, 512):
         raise ValueError(err.value.decode())
+
+
+def write_best_frc(path, sums, N, pixelSize):
+    """the --BestFRC text file of ring sums [nMaps, ring_count(N)] (Engine.best_match_rings): the writer the CLI uses;
+    bioem_amd.best_frc.parse reads it back"""
+    from .engine import RING_SUMS_DTYPE
+    L = load_host_library()
+    L.bioem_host_write_best_frc.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_char_p, C.c_int]
+    t = np.ascontiguousarray(sums, dtype=RING_SUMS_DTYPE)
+    assert t.ndim == 2
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_best_frc(path.encode(), t.ctypes.data, t.shape[0], int(N), float(pixelSize), err, 512):
+        raise ValueError(err.value.decode())

@@ -338,6 +338,39 @@ int bioem_hip_plan_own(int numberPixels, int maxDisplaceCenter, int gridSpaceCen
 const char *bioem_hip_own_kernel_signature(bioem_hip_handle h);
 int bioem_hip_synchronize(bioem_hip_handle h);
 
+/* ---- Fourier ring sums of every particle against its best match (no reference counterpart) ----
+ * For particle p with the record (o, c, X, Y, norm, mu), N = NumberPixels, H = N / 2 + 1, spectra [N][H] (re, im):
+ *   R = the particle's spectrum as the handle holds it (bioem_hip_debug_particles), widened to double;
+ *   Z = P_o conj(CTF_c) formed in DOUBLE from the float projection spectrum and CTF kernel (bioem_hip_render_best_maps
+ *       forms it in float: 2^-24 relative apart);
+ *   M[k1][k2] = norm Z[k1][k2] exp(-2 pi i t / N), t = (k1 X + k2 Y) mod N reduced in integers, and mu N^2 added to the real
+ *       part of M[0][0].  In the columns that are their own Hermitian partner (k2 = 0 and, N even, k2 = N / 2) M is the
+ *       Hermitian part (M[k1][k2] + conj(M[(N - k1) mod N][k2])) / 2 of that expression: what the c2r of the render keeps of a
+ *       product that is not the spectrum of a real image (the reference's CTF kernels are not even in k1), and the
+ *       expression itself where it is.  So M is the r2c spectrum of the image bioem_hip_render_best_maps writes.
+ * Ring of a coefficient: k1' = k1 for k1 <= N / 2 else k1 - N, r2 = k1'^2 + k2^2, s = floor(sqrt(r2)) plus one when
+ * r2 > s^2 + s (the radius rounded to nearest, in integers); nRings = s(N / 2, N / 2) + 1, corners included.  Weight of
+ * the Hermitian partner: w = 1 in column 0 and, N even, column N / 2, else 2 (sum w = N^2).  Per (particle, ring), in
+ * double: cross = sum w Re(R conj(M)), powParticle = sum w |R|^2, powModel = sum w |M|^2.  The host derives the rest:
+ * FRC = cross / sqrt(powParticle powModel), residual power = powParticle + powModel - 2 cross (summed over the rings and
+ * divided by N^2: sum over pixels of (particle - best map)^2), resolution of ring s >= 1 = N pixelSize / s.
+ * No floating-point atomics, and how an image is split over blocks depends on N alone: the same bits on every run,
+ * whichever batch a particle sits in. */
+typedef struct { double cross, powParticle, powModel; } bioem_hip_ring_sums;   /* 24 bytes */
+int bioem_hip_ring_count(int numberPixels);            /* nRings; no device; <= 0 for numberPixels < 1 */
+/* Calling rules of bioem_hip_render_best_maps (records on the host, ownLists, batches of at most maxOrientations through
+ * buffer set 0, outside a run, every handle kind) and its refusals (2, the particle named, handle usable), plus: 2 when
+ * no particles were uploaded.  Per batch: gather and projection as in the render, the batch's particle spectra back in
+ * reference layout, one ring pass; nRings x 24 bytes per particle come back.  Staging buffers are allocated at the first
+ * call (1 when the memory is not there; the handle is as it was).  Phase records: phase 0 the projection, phase 2 the
+ * ring pass, iOrientBegin / iOrientEnd the batch's records relative to iMapBegin. */
+int bioem_hip_best_match_rings(bioem_hip_handle h, const bioem_hip_prob_map *records, int ownLists,
+                               int iMapBegin, int iMapEnd, bioem_hip_ring_sums *out /* [iMapEnd-iMapBegin][nRings] */);
+/* test hook: the same ring kernel on spectra handed in by the caller (specR, specP = [n][N][H] (re, im); records[n]:
+ * max_prob_conv, the shift, norm and mu are used, max_prob_orient is ignored; needs the CTF kernels only) */
+int bioem_hip_debug_ring_sums(bioem_hip_handle h, const float *specR, const float *specP,
+                              const bioem_hip_prob_map *records, int n, bioem_hip_ring_sums *out);
+
 #ifdef __cplusplus
 }
 #endif
