@@ -51,6 +51,9 @@
 //                          every particle's best-match record (bioem.cpp:1925-2085), the full c2r by exact DFT in double
 //   ring_kernels.hpp     k_ring_sums, k_ring_fold  bioem_hip_best_match_rings: per Fourier ring the sums of particle x best
 //                          match, particle power and best-match power (kernels_rings.hip; declarations only here)
+//   window_kernels.hpp   k_window_prep, k_window_cols, k_window_cells  bioem_hip_window_posterior: the log posterior of every
+//                          cell of the displacement window of a (particle, orientation, CTF) request (kernels_window.hip;
+//                          declarations only here)
 //   this file            device context, launch logic, the C ABI
 //   kernels_*.hip        one translation unit per comparison-kernel family (the instantiations of kernel_table.inc),
 //                          linked into the same library: kernels_fast, kernels_fastm, kernels_wide2_{short,16,long},
@@ -117,6 +120,7 @@ struct HipErr
 #include "window_tiles.hpp"
 #include "render_kernels.hpp"
 #include "ring_kernels.hpp"
+#include "window_kernels.hpp"
 
 struct bioem_hip_ctx
 {
@@ -210,6 +214,17 @@ struct bioem_hip_ctx
   float2 *dRingRef = nullptr;
   double *dRingScratch = nullptr;
   bioem_hip_ring_sums *dRingOut = nullptr;
+  // bioem_hip_window_posterior / bioem_hip_debug_window: a batch's records, gathered orientations, particle and conv
+  // spectra in reference layout, Parseval terms, parameters, particle sums handed in, the scratch T of the window pass,
+  // the window's shifts in ascending order and the results (allocated at the first call)
+  BioemWindowRecord *dWinRec = nullptr;
+  float4 *dWinAngles = nullptr;
+  float2 *dWinRef = nullptr, *dWinConv = nullptr;
+  float *dWinTerms = nullptr, *dWinSums = nullptr, *dWinCc = nullptr;
+  bioem_hip_param5 *dWinParams = nullptr;
+  double2 *dWinPostc = nullptr, *dWinT = nullptr;
+  int *dWinShifts = nullptr;
+  double *dWinLogp = nullptr;
   bool refUp = false; // particles uploaded (either entry)
   bool ctfUp = false; // bioem_hip_upload_ctf has run
   // bioem_hip_enable_ctf_table: [nCTF][nMaps] entries, folded beside the particle entries (k_fold_ctf, k_fold_own_ctf);
@@ -2804,6 +2819,251 @@ int bioem_hip_debug_ring_sums(bioem_hip_handle h, const float *specR, const floa
     HIP_CHECK(h, hipMemcpyAsync(h->dRingRef, specR + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(h, hipMemcpyAsync(s0.specRef, specP + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
     if (ring_batch(h, nb, out + (size_t) b0 * nRings))
+      return 1;
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
+// ---- log posterior of every cell of the displacement window of a request (window_kernels.hpp) ----
+static_assert(sizeof(BioemWindowRecord) == sizeof(RenderRecord) && sizeof(bioem_hip_window_request) == 12,
+              "record / request layout");
+
+namespace
+{
+// the shifts the reference reports for the displacement list of a plan (max_prob_cent = -displacement), ascending
+void window_shifts(const KernelPlan &P, std::vector<int> &X)
+{
+  X.clear();
+  for (int d : P.disp)
+    X.push_back(-d);
+  std::sort(X.begin(), X.end());
+}
+
+bool window_arguments_valid(int N, int maxD, int grid, int algo)
+{
+  return N >= 2 && N <= kMaxPixels && maxD >= 0 && grid >= 1 && maxD < N / 2 && (algo == 1 || algo == 2);
+}
+
+// the staging buffers of the window entries; a failed allocation (return 1) leaves the handle as it was
+int window_staging(bioem_hip_ctx *h)
+{
+  if (h->dWinLogp)
+    return 0;
+  const size_t OB = (size_t) h->OB, M = (size_t) h->M, M4 = (M + 3) & ~(size_t) 3;
+  std::vector<int> X;
+  window_shifts(h->plan, X);
+  const size_t nd = X.size();
+  BioemWindowRecord *rec = nullptr;
+  float4 *ang = nullptr;
+  float2 *ref = nullptr, *conv = nullptr;
+  float *terms = nullptr, *sums = nullptr, *cc = nullptr;
+  bioem_hip_param5 *par = nullptr;
+  double2 *postc = nullptr, *T = nullptr;
+  int *shifts = nullptr;
+  double *logp = nullptr;
+  if (dev_alloc(h, rec, OB) || dev_alloc(h, ang, OB) || dev_alloc(h, ref, OB * M) || dev_alloc(h, conv, OB * M) ||
+      dev_alloc(h, terms, OB * M4) || dev_alloc(h, sums, 2 * OB) || dev_alloc(h, cc, OB * nd * nd) ||
+      dev_alloc(h, par, OB) || dev_alloc(h, postc, OB) || dev_alloc(h, T, bioem_window_scratch(h->N, (int) nd, h->OB)) ||
+      dev_alloc(h, shifts, nd) || dev_alloc(h, logp, OB * nd * nd) ||
+      hipMemcpy(shifts, X.data(), sizeof(int) * nd, hipMemcpyHostToDevice) != hipSuccess)
+  {
+    dev_release(h, rec);
+    dev_release(h, ang);
+    dev_release(h, ref);
+    dev_release(h, conv);
+    dev_release(h, terms);
+    dev_release(h, sums);
+    dev_release(h, cc);
+    dev_release(h, par);
+    dev_release(h, postc);
+    dev_release(h, T);
+    dev_release(h, shifts);
+    dev_release(h, logp);
+    (void) hipGetLastError();
+    return 1;
+  }
+  h->dWinRec = rec;
+  h->dWinAngles = ang;
+  h->dWinRef = ref;
+  h->dWinConv = conv;
+  h->dWinTerms = terms;
+  h->dWinSums = sums;
+  h->dWinCc = cc;
+  h->dWinParams = par;
+  h->dWinPostc = postc;
+  h->dWinT = T;
+  h->dWinShifts = shifts;
+  h->dWinLogp = logp;
+  return 0;
+}
+
+// the window pass of n staged records (records in dWinRec, conv spectra in dWinConv, particle spectra in dWinRef,
+// parameters complete in dWinParams) and its copies to the host
+int window_batch(bioem_hip_ctx *h, int n, const float *sumRef, const float *sumsqRef, double *logp_out, float *cc_out)
+{
+  const size_t cells = (size_t) h->plan.nd * h->plan.nd * (size_t) n;
+  hipLaunchKernelGGL(k_posterior_consts, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->dWinParams, h->pd, h->dWinPostc, n);
+  HIP_CHECK(h, hipGetLastError());
+  HIP_CHECK(h, bioem_window_launch(h->stream, h->dWinConv, h->dWinRef, h->dWinRec, h->dWinParams, h->dWinPostc, sumRef,
+                                   sumsqRef, h->pd, n, h->N, h->plan.nd, h->dWinShifts, h->dTwD, h->dWinT, h->dWinLogp,
+                                   h->dWinCc));
+  HIP_CHECK(h, hipMemcpyAsync(logp_out, h->dWinLogp, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (cc_out)
+    HIP_CHECK(h, hipMemcpyAsync(cc_out, h->dWinCc, sizeof(float) * cells, hipMemcpyDeviceToHost, h->stream));
+  return 0;
+}
+} // namespace
+
+int bioem_hip_window_offsets(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo, int *shifts, int cap)
+{
+  if (!window_arguments_valid(numberPixels, maxDisplaceCenter, gridSpaceCenter, algo))
+    return 0;
+  std::vector<int> X;
+  window_shifts(plan_kernels(numberPixels, maxDisplaceCenter, gridSpaceCenter, algo), X);
+  for (int i = 0; shifts && i < (int) X.size() && i < cap; i++)
+    shifts[i] = X[(size_t) i];
+  return (int) X.size();
+}
+
+int bioem_hip_window_count(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo)
+{
+  return bioem_hip_window_offsets(numberPixels, maxDisplaceCenter, gridSpaceCenter, algo, nullptr, 0);
+}
+
+int bioem_hip_window_posterior(bioem_hip_handle h, const bioem_hip_window_request *req, int n, int ownLists, double *logp_out,
+                               float *cc_out, bioem_hip_param5 *params_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[256];
+  auto refuse = [&](const char *why) {
+    h->err = std::string("window_posterior: ") + why;
+    return 2;
+  };
+  if (!req || !logp_out || n < 1)
+    return refuse("null argument or no requests");
+  if (!h->dPts || h->nPts < 1)
+    return refuse("model not uploaded");
+  if (!h->ctfUp)
+    return refuse("CTF kernels not uploaded");
+  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
+    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
+                           : "orientations not uploaded");
+  if (!h->refUp)
+    return refuse("particles not uploaded");
+  std::vector<BioemWindowRecord> recs((size_t) n);
+  for (int i = 0; i < n; i++)
+  {
+    const bioem_hip_window_request &r = req[i];
+    const char *why = nullptr;
+    int first = 0, len = 0;
+    if (r.particle < 0 || r.particle >= h->nMaps)
+      why = "particle outside [0, nMaps)";
+    else
+    {
+      first = ownLists ? h->ownOff[(size_t) r.particle] : 0;
+      len = ownLists ? h->ownOff[(size_t) r.particle + 1] - first : h->nAnglesUp;
+      if (r.orient < 0 || r.orient >= len)
+        why = "orient outside its orientation list";
+      else if (r.conv < 0 || r.conv >= h->nCTF)
+        why = "conv outside [0, nCTF)";
+    }
+    if (why)
+    {
+      snprintf(buf, sizeof(buf), "request %d: %s (particle %d of %d, orient %d of %d, conv %d of %d)", i, why, r.particle,
+               h->nMaps, r.orient, len, r.conv, h->nCTF);
+      return refuse(buf);
+    }
+    recs[(size_t) i] = {first + r.orient, r.conv, r.particle, 0, {0.f, 0.f}};
+  }
+  if (window_staging(h))
+    return 1;
+  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  const OrientList src = ownLists ? own_list(h) : shared_list(h);
+  const OrientList L = {h->dWinAngles, src.isQuat, src.quatNormDev};
+  const int N = h->N, OB = h->OB;
+  const size_t M = (size_t) h->M, cells = (size_t) h->plan.nd * h->plan.nd;
+  const int M4 = (int) ((M + 3) & ~(size_t) 3);
+  for (int b0 = 0; b0 < n; b0 += OB)
+  {
+    const int nb = std::min(OB, n - b0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinRec, recs.data() + b0, sizeof(BioemWindowRecord) * nb, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_render_gather, dim3((nb + 255) / 256), dim3(256), 0, h->stream, src.d,
+                       reinterpret_cast<const RenderRecord *>(h->dWinRec), nb, h->dWinAngles);
+    HIP_CHECK(h, hipGetLastError());
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, b0, b0 + nb, 0, 0) ||
+        project_batch(h, s0, h->stream, L, 0, nb) || phase_end(h, h->stream))
+      return 1;
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, b0, b0 + nb, 0, 0))
+      return 1;
+    HIP_CHECK(h, bioem_window_prep_launch(h->stream, s0.specRef, h->dCTF, h->dCtfParam, h->dWinRec, nb, N, h->dWinConv,
+                                          h->dWinTerms, M4, h->dWinParams));
+    hipLaunchKernelGGL(k_parseval_ordered, dim3((nb + 3) / 4), dim3(64), 0, h->stream, h->dWinTerms, (int) M, M4, nb,
+                       (float) (N * N), h->dWinParams);
+    HIP_CHECK(h, hipGetLastError());
+    if (phase_end(h, h->stream) || phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, b0, b0 + nb, 0, 0))
+      return 1;
+    // the particles' spectra back in reference layout: one launch per run of consecutive particles
+    for (int i = 0; i < nb;)
+    {
+      int j = i + 1;
+      while (j < nb && recs[(size_t) (b0 + j)].particle == recs[(size_t) (b0 + j - 1)].particle + 1)
+        j++;
+      hipLaunchKernelGGL(k_unreorder, dim3(std::min(1024, 16 * (j - i))), dim3(256), 0, h->stream,
+                         h->dRef + h->Mc * (size_t) recs[(size_t) (b0 + i)].particle, h->dWinRef + M * (size_t) i, j - i, N, h->H,
+                         h->plan.halfR, h->plan.N1, h->Hp);
+      HIP_CHECK(h, hipGetLastError());
+      i = j;
+    }
+    if (window_batch(h, nb, h->dSumRef, h->dSumsqRef, logp_out + cells * (size_t) b0, cc_out ? cc_out + cells * (size_t) b0 : nullptr))
+      return 1;
+    if (params_out)
+      HIP_CHECK(h, hipMemcpyAsync(params_out + b0, h->dWinParams, sizeof(bioem_hip_param5) * nb, hipMemcpyDeviceToHost, h->stream));
+    if (phase_end(h, h->stream))
+      return 1;
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  drain_phases(h);
+  return 0;
+}
+
+int bioem_hip_debug_window(bioem_hip_handle h, const float *specConv, const float *specRef, const bioem_hip_param5 *params,
+                           const float *sumRef, const float *sumsqRef, int n, double *logp_out, float *cc_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (!specConv || !specRef || !params || !sumRef || !sumsqRef || !logp_out || n < 1)
+  {
+    h->err = "debug_window: null argument or no records";
+    return 2;
+  }
+  if (window_staging(h))
+    return 1;
+  if (compat_flush(h))
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
+  const size_t M = (size_t) h->M, cells = (size_t) h->plan.nd * h->plan.nd;
+  std::vector<BioemWindowRecord> recs((size_t) std::min(n, h->OB));
+  for (size_t i = 0; i < recs.size(); i++)
+    recs[i] = {0, 0, (int) i, 0, {0.f, 0.f}};
+  for (int b0 = 0; b0 < n; b0 += h->OB)
+  {
+    const int nb = std::min(h->OB, n - b0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinRec, recs.data(), sizeof(BioemWindowRecord) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinConv, specConv + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinRef, specRef + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinParams, params + b0, sizeof(bioem_hip_param5) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinSums, sumRef + b0, sizeof(float) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinSums + h->OB, sumsqRef + b0, sizeof(float) * nb, hipMemcpyHostToDevice, h->stream));
+    if (window_batch(h, nb, h->dWinSums, h->dWinSums + h->OB, logp_out + cells * (size_t) b0,
+                     cc_out ? cc_out + cells * (size_t) b0 : nullptr))
       return 1;
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }

@@ -17,6 +17,7 @@ PHASE_RECORD_DTYPE = np.dtype([("phase", "<i4"), ("iOrientBegin", "<i4"), ("iOri
 CANDIDATE_DTYPE = np.dtype([("forAngles", "<f8"), ("ConstAngle", "<f8"), ("logp", "<f8"), ("orient", "<i4"),
                             ("pad", "<i4")])
 RING_SUMS_DTYPE = np.dtype([("cross", "<f8"), ("powParticle", "<f8"), ("powModel", "<f8")])
+WINDOW_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4")])
 MIN_PROB = -999999.0
 
 
@@ -82,6 +83,11 @@ def load_library():
         L.bioem_hip_ring_count.argtypes = [ci]
         L.bioem_hip_best_match_rings.argtypes = [vp, vp, ci, ci, ci, vp]
         L.bioem_hip_debug_ring_sums.argtypes = [vp, vp, vp, vp, ci, vp]
+    if hasattr(L, "bioem_hip_window_posterior"):
+        L.bioem_hip_window_count.argtypes = [ci, ci, ci, ci]
+        L.bioem_hip_window_offsets.argtypes = [ci, ci, ci, ci, vp, ci]
+        L.bioem_hip_window_posterior.argtypes = [vp, vp, ci, ci, vp, vp, vp]
+        L.bioem_hip_debug_window.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -134,7 +140,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_upload_particle_orientations", "bioem_hip_compare_own_orientations",
            "bioem_hip_upload_particle_orientation_lists", "bioem_hip_plan_own", "bioem_hip_own_kernel_signature",
            "bioem_hip_set_own_launch", "bioem_hip_render_best_maps", "bioem_hip_enable_ctf_table",
-           "bioem_hip_ctf_table", "bioem_hip_ring_count", "bioem_hip_best_match_rings", "bioem_hip_debug_ring_sums"]
+           "bioem_hip_ctf_table", "bioem_hip_ring_count", "bioem_hip_best_match_rings", "bioem_hip_debug_ring_sums",
+           "bioem_hip_window_count", "bioem_hip_window_offsets", "bioem_hip_window_posterior", "bioem_hip_debug_window"]
 
 
 def _p(a):
@@ -144,6 +151,18 @@ def _p(a):
 def ring_count(N):
     """rings of an N x N image (bioem_hip_ring_count): the rounded radius of the corner coefficient plus one; no device"""
     return int(load_library().bioem_hip_ring_count(int(N)))
+
+
+def window_offsets(N, maxD, grid, algo):
+    """the shifts X_0 < X_1 < ... the reference can report for this displacement window (bioem_hip_window_offsets): the
+    cell coordinates of a window_posterior table on both axes; int32 [nd].  No device; ValueError on invalid arguments."""
+    L = load_library()
+    nd = int(L.bioem_hip_window_count(int(N), int(maxD), int(grid), int(algo)))
+    if nd <= 0:
+        raise ValueError("no displacement window for N %d, maxD %d, grid %d, ALGO %d" % (N, maxD, grid, algo))
+    X = np.zeros(nd, dtype=np.int32)
+    assert L.bioem_hip_window_offsets(int(N), int(maxD), int(grid), int(algo), _p(X), nd) == nd
+    return X
 
 
 def new_prob_block(nMaps, nAngles, writeAngles):
@@ -401,6 +420,73 @@ class Engine:
             e.rc = rc
             raise e
         return out
+
+    def window_shifts(self):
+        """the cell coordinates of this handle's window tables (window_offsets of its parameters)"""
+        return window_offsets(self.N, self.pd.maxDisplaceCenter, self.pd.GridSpaceCenter, self.algo)
+
+    def window_posterior(self, requests, own=False, want_cc=False, want_params=False):
+        """the log posterior of every cell of the displacement window for each request (particle, orient, conv) of
+        WINDOW_REQUEST_DTYPE [n] (or an [n, 3] integer array): float64 [n, nd, nd], cell [i, j] at the reported shift
+        (X_i, X_j) of window_shifts() (include/bioem_hip.h).  orient indexes the shared list, with own=True the list of
+        the request's particle.  Requests are independent and may repeat particles in any order.  want_cc adds the
+        float32 cross-correlation values [n, nd, nd], want_params the PARAM5_DTYPE [n] of the requests' (orient, conv)
+        pairs; the result is then a tuple in that order.  Outside a run; a refusal raises RuntimeError with .rc == 2."""
+        r = np.asarray(requests)
+        if r.dtype != WINDOW_REQUEST_DTYPE:
+            r = np.asarray(r, dtype=np.int32).reshape(-1, 3)
+            q = np.zeros(len(r), dtype=WINDOW_REQUEST_DTYPE)
+            q["particle"], q["orient"], q["conv"] = r[:, 0], r[:, 1], r[:, 2]
+            r = q
+        r = np.ascontiguousarray(r.reshape(-1))
+        n, nd = len(r), len(self.window_shifts())
+        logp = np.zeros((n, nd, nd), dtype=np.float64)
+        cc = np.zeros((n, nd, nd), dtype=np.float32) if want_cc else None
+        par = np.zeros(n, dtype=PARAM5_DTYPE) if want_params else None
+        rc = self.L.bioem_hip_window_posterior(self.h, _p(r) if n else None, n, int(bool(own)), _p(logp), _p(cc), _p(par))
+        if rc:
+            e = RuntimeError("window_posterior: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+        out = (logp,) + ((cc,) if want_cc else ()) + ((par,) if want_params else ())
+        return out[0] if len(out) == 1 else out
+
+    def best_match_window(self, pmap, p0=0, p1=None, own=False, want_cc=False, want_params=False):
+        """window_posterior of the best record (orient, conv) of particles [p0, p1) of a probability block's map
+        entries (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
+        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
+        assert pmap.shape == (self.nMaps,)
+        p1 = self.nMaps if p1 is None else int(p1)
+        req = np.zeros(max(0, p1 - int(p0)), dtype=WINDOW_REQUEST_DTYPE)
+        req["particle"] = np.arange(int(p0), p1)
+        req["orient"], req["conv"] = pmap["orient"][int(p0):p1], pmap["conv"][int(p0):p1]
+        return self.window_posterior(req, own=own, want_cc=want_cc, want_params=want_params)
+
+    def debug_window(self, specConv, specRef, params, sumRef, sumsqRef):
+        """test hook: the window kernels of window_posterior on n spectrum pairs handed in, float32 [n, N, H, 2] each (or
+        complex64 [n, N, H]), with params PARAM5_DTYPE [n] and the particles' sums float32 [n].  Needs only the handle's
+        parameters.  Returns (logp float64 [n, nd, nd], cc float32 [n, nd, nd]); a refusal raises with .rc == 2."""
+        def spec(a):
+            a = np.ascontiguousarray(a)
+            if a.dtype.kind == "c":
+                a = np.ascontiguousarray(a.astype(np.complex64)).view(np.float32).reshape(a.shape + (2,))
+            return np.ascontiguousarray(a, dtype=np.float32)
+        specConv, specRef = spec(specConv), spec(specRef)
+        params = np.ascontiguousarray(params, dtype=PARAM5_DTYPE)
+        n, nd = len(params), len(self.window_shifts())
+        sumRef = np.ascontiguousarray(sumRef, dtype=np.float32)
+        sumsqRef = np.ascontiguousarray(sumsqRef, dtype=np.float32)
+        assert specConv.shape == (n, self.N, self.H, 2) and specRef.shape == specConv.shape
+        assert sumRef.shape == (n,) and sumsqRef.shape == (n,)
+        logp = np.zeros((n, nd, nd), dtype=np.float64)
+        cc = np.zeros((n, nd, nd), dtype=np.float32)
+        rc = self.L.bioem_hip_debug_window(self.h, _p(specConv), _p(specRef), _p(params), _p(sumRef), _p(sumsqRef), n,
+                                           _p(logp), _p(cc))
+        if rc:
+            e = RuntimeError("debug_window: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+        return logp, cc
 
     def enable_ctf_table(self, on=True):
         """keep the posterior per (CTF set, particle) beside the particle entries, from the next start_run on; call it

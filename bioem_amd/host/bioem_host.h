@@ -121,6 +121,26 @@ std::string write_ctf_prob(const char *file, const bioem_hip_prob_map *tab, int 
 int frc_ring(int N, int k1, int k2);
 std::vector<double> frc_ring_weights(int N);
 std::string write_best_frc(const char *file, const bioem_hip_ring_sums *sums, int nMaps, int N, float pixelSize);
+// --BestWindow (bestwindow.cpp): the text file of the window tables logp[nMaps][nd][nd] of bioem_hip_window_posterior for
+// every particle's best (orientation, CTF) pair; cell [i][j] lies at the reported shift (shifts[i], shifts[j]).  After the
+// HEADER:: NOTATION bar, one notation line and the bar again, per particle
+//  WINDOW p amp pha env orient logP peakX peakY peakLogp meanX meanY sdX sdY edgeMass nEff skipped nd
+// (amp pha env: the CTF columns as --ProbCTF prints them; logP = log-sum-exp of the finite cells + numconst[p], the
+// constant of the particle's LogProb; peak: the arg-max cell, the first in row-major order among equals; mean, sd: of the
+// posterior over the shift on both axes; edgeMass: the mass on cells whose X or Y is the smallest or largest of the set;
+// nEff = 1 / sum w^2; skipped: cells that are not finite, left out of every statistic) followed by nd * nd lines
+//  CELL p X Y logp weight
+// (logp with numconst[p] added, weight = exp(logp - logP), 0 for a skipped cell).  orient[p] < 0: a particle without a
+// table -- orient -1, nd 0, no cells.  Floating values with 16 significant digits, every statistic in double.
+// Returns the empty string, or the error.
+struct WindowStats
+{
+  double logP, peakLogp, meanX, meanY, sdX, sdY, edgeMass, nEff;
+  int peakX, peakY, skipped;
+};
+WindowStats window_stats(const double *logp, const int *shifts, int nd);
+std::string write_best_window(const char *file, const double *logp, const int *shifts, int nd, int nMaps, const int *orient,
+                              const int *conv, const float *ctfParam3, bool usepsf, float elecwavel, const double *numconst);
 // MRC mode-2 stack nx = ny = N, nz = nMaps in the storage order the --ReadMRC reader expects, written batch by batch
 struct MrcStackWriter
 {
@@ -177,6 +197,7 @@ public:
   std::string bestMapsFile;  // --BestMaps: MRC stack of every particle's calculated best-match image (FILE, FILE_Round2)
   std::string probCtfFile;   // --ProbCTF: the posterior per (particle, CTF set) as text (FILE, FILE_Round2)
   std::string bestFrcFile;   // --BestFRC: ring correlation of every particle against its best match (FILE, FILE_Round2)
+  std::string bestWindowFile; // --BestWindow: posterior over the displacement window of every best match (FILE, FILE_Round2)
   std::string bestParamFile; // --PrintBestCalMap: the reference's one-record mode, no particles, writes BESTMAP
   BestParams best;
   int printBestCalMap();     // bioem::printModel (bioem.cpp:624-657, 1925-2085)
@@ -212,6 +233,10 @@ private:
   void writeBestMaps(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
   // --BestFRC: the records' ring sums from handle h (bioem_hip_best_match_rings), written by write_best_frc
   void writeBestFrc(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
+  // --BestWindow: the window tables of the records' (orientation, CTF) pairs from handle h (bioem_hip_window_posterior),
+  // written by write_best_window; voluPerMap as for writeProbabilities
+  void writeBestWindow(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
+                       const bioem_hip_param_device &pd, const float *voluPerMap = nullptr);
   // --ProbCTF: the tables of the handles merged on the host (shards in ascending order) and written
   void writeCtfProb(const std::string &file, const std::vector<bioem_hip_handle> &hs, const bioem_hip_param_device &pd,
                     const float *angles, size_t anglesPerMap, const long long *angleOffsets = nullptr,

@@ -192,6 +192,19 @@ int bioem_host_write_best_frc(const char *file, const bioem_hip_ring_sums *sums,
   return e.empty() ? 0 : 1;
 }
 
+// the --BestWindow text of window tables logp[nMaps][nd][nd] (write_best_window, bioem_host.h); 0, or 1 with the text in
+// err[cap]
+int bioem_host_write_best_window(const char *file, const double *logp, const int *shifts, int nd, int nMaps, const int *orient,
+                                 const int *conv, const float *ctfParam3, int usepsf, float elecwavel, const double *numconst,
+                                 char *err, int cap)
+{
+  const std::string e = bioem_host::write_best_window(file, logp, shifts, nd, nMaps, orient, conv, ctfParam3, usepsf != 0,
+                                                      elecwavel, numconst);
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return e.empty() ? 0 : 1;
+}
+
 // the MRC stack of --BestMaps: maps [nMaps][N][N] appended in batches of `batch` images
 int bioem_host_write_mrc_stack(const char *file, const float *maps, int nMaps, int N, int batch)
 {

@@ -73,6 +73,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"BestMaps", required_argument, 0, 0},
                                        {"ProbCTF", required_argument, 0, 0},
                                        {"BestFRC", required_argument, 0, 0},
+                                       {"BestWindow", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
                                        {"RefineSeeds", required_argument, 0, 0},
@@ -106,6 +107,8 @@ int Driver::readOptions(int ac, char **av)
     printf("                         under every CTF set; with --RefineOrientations also arg_Round2)\n");
     printf("  --BestFRC arg          (Optional) Write the Fourier ring correlation of every particle against its best match\n");
     printf("                         (per ring: FRC and powers; with --RefineOrientations also arg_Round2)\n");
+    printf("  --BestWindow arg       (Optional) Write the posterior over the displacement window of every particle's best match\n");
+    printf("                         (is DISPLACE_CENTER wide enough? with --RefineOrientations also arg_Round2)\n");
     printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
@@ -204,6 +207,11 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Writing the ring correlation of the best matches to: " << optarg << "\n";
       bestFrcFile = optarg;
     }
+    else if (name == "BestWindow")
+    {
+      std::cout << "Writing the posterior over the displacement window of the best matches to: " << optarg << "\n";
+      bestWindowFile = optarg;
+    }
     else if (name == "PrintBestCalMap")
     {
       std::cout << "Reading best parameters from file: " << optarg << "\n";
@@ -242,8 +250,8 @@ int Driver::readOptions(int ac, char **av)
   if (!bestParamFile.empty())
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
-    if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty())
-      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC and --RefineOrientations");
+    if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty() || !bestWindowFile.empty())
+      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow and --RefineOrientations");
     const std::string err = read_best_parameters(bestParamFile.c_str(), best);
     if (!err.empty())
       fatal("%s", err.c_str());
@@ -522,6 +530,59 @@ void Driver::writeBestFrc(const std::string &file, bioem_hip_handle h, const bio
   std::cout << "Ring correlation of " << nMaps << " particles against their best match written to: " << file << "\n";
 }
 
+// --BestWindow: the window table of every record's (orientation, CTF) pair from handle h, batch by batch, then the text
+// file (write_best_window).  A particle no run compared has no record: a warning and an empty block.
+void Driver::writeBestWindow(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
+                             const bioem_hip_param_device &pd, const float *voluPerMap)
+{
+  const int nMaps = particles.ntot;
+  const int nd = bioem_hip_window_count(pd.NumberPixels, pd.maxDisplaceCenter, pd.GridSpaceCenter, algo);
+  if (nd < 1)
+    fatal("--BestWindow: no displacement window for these parameters");
+  std::vector<int> shifts((size_t) nd);
+  bioem_hip_window_offsets(pd.NumberPixels, pd.maxDisplaceCenter, pd.GridSpaceCenter, algo, shifts.data(), nd);
+  const size_t cells = (size_t) nd * nd;
+  int batch = 1;
+  bioem_hip_max_batch(h, &batch, nullptr);
+  batch = std::max(1, batch);
+  std::vector<double> logp(cells * (size_t) nMaps, 0.), table(cells * (size_t) batch), numconst((size_t) nMaps);
+  std::vector<int> orient((size_t) nMaps, -1), conv((size_t) nMaps, 0), who;
+  std::vector<bioem_hip_window_request> req;
+  auto flush = [&]() {
+    if (req.empty())
+      return;
+    check(h, bioem_hip_window_posterior(h, req.data(), (int) req.size(), ownLists, table.data(), nullptr, nullptr),
+          "window posterior");
+    for (size_t i = 0; i < req.size(); i++)
+      std::copy(table.begin() + cells * i, table.begin() + cells * (i + 1), logp.begin() + cells * (size_t) who[i]);
+    req.clear();
+    who.clear();
+  };
+  for (int p = 0; p < nMaps; p++)
+  {
+    numconst[(size_t) p] =
+        0.5 * log(M_PI) + (1 - pd.Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(voluPerMap ? voluPerMap[p] : pd.volu);
+    const bioem_hip_prob_map &r = pmap[p];
+    if (r.Total == 0.0 && r.Constoadd == -999999.)
+    {
+      warn("window of RefMap %d not computed: no run compared it", p);
+      continue;
+    }
+    orient[(size_t) p] = r.max_prob_orient;
+    conv[(size_t) p] = r.max_prob_conv;
+    req.push_back({p, r.max_prob_orient, r.max_prob_conv});
+    who.push_back(p);
+    if ((int) req.size() == batch)
+      flush();
+  }
+  flush();
+  const std::string err = write_best_window(file.c_str(), logp.data(), shifts.data(), nd, nMaps, orient.data(), conv.data(),
+                                            param.ctfParam.data(), param.usepsf, param.elecwavel, numconst.data());
+  if (!err.empty())
+    fatal("--BestWindow: %s", err.c_str());
+  std::cout << "Window posterior of " << nMaps << " particles' best matches written to: " << file << "\n";
+}
+
 // --PrintBestCalMap: the record of the BEST_* file rendered on the device and written as the reference's BESTMAP text.
 // The reference's file labels the UNSHIFTED map with shifted coordinates (bioem.cpp:2049-2053), so the device renders with
 // X = Y = 0 and the writer applies BEST_DX / BEST_DY to the labels.
@@ -718,6 +779,8 @@ int Driver::run()
     writeBestMaps(bestMapsFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!bestFrcFile.empty())
     writeBestFrc(bestFrcFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
+  if (!bestWindowFile.empty())
+    writeBestWindow(bestWindowFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0, param.pd);
   if (!refineFile.empty())
   {
     if (refineSeeds >= 2)
@@ -790,6 +853,8 @@ void Driver::runRound2()
     writeBestMaps(bestMapsFile + "_Round2", h, pm.data(), 1);
   if (!bestFrcFile.empty())
     writeBestFrc(bestFrcFile + "_Round2", h, pm.data(), 1);
+  if (!bestWindowFile.empty())
+    writeBestWindow(bestWindowFile + "_Round2", h, pm.data(), 1, pd2);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), (size_t) G);
   bioem_hip_destroy(h);
@@ -885,6 +950,8 @@ void Driver::runRound2Seeds()
     writeBestMaps(bestMapsFile + "_Round2", h, pm.data(), 1);
   if (!bestFrcFile.empty())
     writeBestFrc(bestFrcFile + "_Round2", h, pm.data(), 1);
+  if (!bestWindowFile.empty())
+    writeBestWindow(bestWindowFile + "_Round2", h, pm.data(), 1, pd2, volu.data());
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), 0, offsets.data(),
                  volu.data());

@@ -178,3 +178,27 @@ def write_best_frc(path, sums, N, pixelSize):
     err = C.create_string_buffer(512)
     if L.bioem_host_write_best_frc(path.encode(), t.ctypes.data, t.shape[0], int(N), float(pixelSize), err, 512):
         raise ValueError(err.value.decode())
+
+
+def write_best_window(path, logp, shifts, orient, conv, ctfParam, numconst, usepsf=False, elecwavel=0.019866):
+    """the --BestWindow text file of window tables [nMaps, nd, nd] (Engine.best_match_window) at the shifts [nd]: the
+    writer the CLI uses; bioem_amd.best_window.parse reads it back.  orient, conv [nMaps]: the records' pair (orient < 0:
+    a particle without a table); ctfParam [nCTF, 3]; numconst: the constant of every particle's LogProb (a scalar or
+    [nMaps])"""
+    L = load_host_library()
+    vp = C.c_void_p
+    L.bioem_host_write_best_window.argtypes = [C.c_char_p, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_float, vp,
+                                               C.c_char_p, C.c_int]
+    t = np.ascontiguousarray(logp, dtype=np.float64)
+    X = np.ascontiguousarray(shifts, dtype=np.int32)
+    assert t.ndim == 3 and t.shape[1:] == (len(X), len(X))
+    o = np.ascontiguousarray(orient, dtype=np.int32)
+    c = np.ascontiguousarray(conv, dtype=np.int32)
+    k = np.ascontiguousarray(ctfParam, dtype=np.float32)
+    nc = np.ascontiguousarray(np.broadcast_to(np.asarray(numconst, dtype=np.float64), (t.shape[0],)))
+    assert o.shape == (t.shape[0],) and c.shape == o.shape and k.ndim == 2 and k.shape[1] == 3
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_best_window(path.encode(), t.ctypes.data, X.ctypes.data, len(X), t.shape[0], o.ctypes.data,
+                                      c.ctypes.data, k.ctypes.data, int(bool(usepsf)), float(elecwavel), nc.ctypes.data,
+                                      err, 512):
+        raise ValueError(err.value.decode())

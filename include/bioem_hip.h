@@ -371,6 +371,43 @@ int bioem_hip_best_match_rings(bioem_hip_handle h, const bioem_hip_prob_map *rec
 int bioem_hip_debug_ring_sums(bioem_hip_handle h, const float *specR, const float *specP,
                               const bioem_hip_prob_map *records, int n, bioem_hip_ring_sums *out);
 
+/* ---- Posterior over the displacement window of any (particle, orientation, CTF) match (no reference counterpart) ----
+ * The comparison kernels fold the window of every comparison to one partial inside the kernel; this entry delivers the
+ * window itself.  For a request (p, o, c), N = NumberPixels, H = N / 2 + 1, spectra [N][H] (re, im):
+ *   conv = P_o conj(CTF_c) in float, the expression of the convolution (bioem_hip_debug_convolution delivers its bits and
+ *       those of {amp, pha, env, sumC, sumsquareC}); F = the particle's spectrum as the handle holds it;
+ *   S(dx, dy) = sum_ky w_ky Re( exp(+2 pi i ((ky dy) mod N) / N) sum_kx conv[kx][ky] conj(F[kx][ky]) exp(+2 pi i ((kx dx) mod N) / N) ),
+ *       w = 1 in column 0 and, N even, column N / 2, else 2; the product is formed in double from the float spectra, the
+ *       twiddle indices are reduced in integers, the sums run in double in a fixed order;
+ *   cc = (float) S / (float) (N N) (one rounding, then the reference's float division, bioem_algorithm.h:163-164);
+ *   logp = the reference's calc_logpro at cc, kept in double (narrowed to float for neither ALGO).
+ * Cells are indexed by the shift the reference reports: X_0 < X_1 < ... are the values max_prob_cent_x can take for the
+ * handle's (NumberPixels, maxDisplaceCenter, GridSpaceCenter, ALGO) -- ALGO 1 with maxDisplaceCenter 5, GridSpaceCenter 2
+ * gives {-4, -2, 0, 1, 3, 5} -- and cell [i][j] of a table holds dx = -X_i, dy = -X_j: the arg-max cell of the table of a
+ * particle's best (o, c) is (max_prob_cent_x, max_prob_cent_y), and the log-sum-exp over the cells is the pair's
+ * log(Total) + Constoadd.  No atomics, a fixed summation order, and a record's split over blocks depends on (N, nd)
+ * alone: the same bits on every run, in every batch, at any position of the request list. */
+typedef struct { int particle, orient, conv; } bioem_hip_window_request;            /* 12 bytes */
+/* nd, the cells per axis; no device; <= 0 on invalid arguments (N < 2, grid < 1, maxD < 0 or >= N / 2, ALGO not 1 or 2) */
+int bioem_hip_window_count(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo);
+/* X_0 .. X_{nd-1} into shifts[cap] (as many as fit; shifts may be null); returns nd */
+int bioem_hip_window_offsets(int numberPixels, int maxDisplaceCenter, int gridSpaceCenter, int algo, int *shifts, int cap);
+/* Calling rules of bioem_hip_best_match_rings: requests on the host, outside a run, every handle kind, batches of at most
+ * maxOrientations through buffer set 0; staging allocated at the first call (1 when the memory is not there; the handle is
+ * as it was).  Requests are independent: any particle any number of times, in any order.  orient indexes the shared list,
+ * or with ownLists = 1 the list of the request's particle.  Refused with 2, the request index named and the handle
+ * usable: a null argument or n < 1; particle outside [0, nMaps); orient outside its list; conv outside [0, nCTF); model,
+ * CTF kernels, orientations or particles not uploaded; ownLists = 1 without own lists.  A cell whose firstele is not
+ * positive and finite holds what the formula gives (NaN or an infinity).  Phase records: 0 the projection, 1 conv and
+ * the ordered Parseval sums, 2 the window pass; iOrientBegin / iOrientEnd the batch's requests. */
+int bioem_hip_window_posterior(bioem_hip_handle h, const bioem_hip_window_request *req, int n, int ownLists,
+                               double *logp_out /* [n][nd][nd] */, float *cc_out /* [n][nd][nd] or NULL */,
+                               bioem_hip_param5 *params_out /* [n] or NULL */);
+/* test hook: the same window kernels on spectra handed in (specConv, specRef = [n][N][H] (re, im), reference layout;
+ * params[n] complete; the particles' sums per record).  Needs only the handle's parameters. */
+int bioem_hip_debug_window(bioem_hip_handle h, const float *specConv, const float *specRef, const bioem_hip_param5 *params,
+                           const float *sumRef, const float *sumsqRef, int n, double *logp_out, float *cc_out);
+
 #ifdef __cplusplus
 }
 #endif
