@@ -54,6 +54,9 @@
 //   window_kernels.hpp   k_window_prep, k_window_cols, k_window_cells  bioem_hip_window_posterior: the log posterior of every
 //                          cell of the displacement window of a (particle, orientation, CTF) request (kernels_window.hip;
 //                          declarations only here)
+//   orient_kernels.hpp   k_orient_max, k_orient_sums, k_orient_fold, k_orient_products  bioem_hip_orientation_sums: the
+//                          orientation posterior of every particle reduced where the angle table lives
+//                          (kernels_orient.hip; declarations only here)
 //   this file            device context, launch logic, the C ABI
 //   kernels_*.hip        one translation unit per comparison-kernel family (the instantiations of kernel_table.inc),
 //                          linked into the same library: kernels_fast, kernels_fastm, kernels_wide2_{short,16,long},
@@ -121,6 +124,7 @@ struct HipErr
 #include "render_kernels.hpp"
 #include "ring_kernels.hpp"
 #include "window_kernels.hpp"
+#include "orient_kernels.hpp"
 
 struct bioem_hip_ctx
 {
@@ -225,6 +229,10 @@ struct bioem_hip_ctx
   double2 *dWinPostc = nullptr, *dWinT = nullptr;
   int *dWinShifts = nullptr;
   double *dWinLogp = nullptr;
+  // bioem_hip_orientation_sums: scratch of the two passes, the products q_i q_j of the owned orientations, their priors
+  // and the result (allocated at the first call)
+  double *dOrientScratch = nullptr, *dOrientQQ = nullptr, *dOrientPrior = nullptr;
+  bioem_hip_orient_sums *dOrientOut = nullptr;
   bool refUp = false; // particles uploaded (either entry)
   bool ctfUp = false; // bioem_hip_upload_ctf has run
   // bioem_hip_enable_ctf_table: [nCTF][nMaps] entries, folded beside the particle entries (k_fold_ctf, k_fold_own_ctf);
@@ -3068,6 +3076,218 @@ int bioem_hip_debug_window(bioem_hip_handle h, const float *specConv, const floa
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
   return 0;
+}
+
+// ---- summaries of the orientation posterior, reduced where the angle table lives (orient_kernels.hpp) ----
+int bioem_hip_orientation_sums(bioem_hip_handle h, const double *logPrior, int iMapBegin, int iMapEnd, int ownLists,
+                               bioem_hip_orient_sums *out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  auto refuse = [&](const char *why) {
+    h->err = std::string("orientation_sums: ") + why;
+    return 2;
+  };
+  if (!h->pd.writeAngles)
+    return refuse("handle was created without WRITE_PROB_ANGLES");
+  if (!out)
+    return refuse("null argument");
+  if (iMapBegin < 0 || iMapEnd > h->nMaps || iMapBegin >= iMapEnd)
+    return refuse("particle range empty, reversed or outside [0, nMaps)");
+  if (ownLists && (!h->dOwnAngles || h->ownOff.empty()))
+    return refuse("no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)");
+  if (ownLists && logPrior)
+    return refuse("a prior per orientation does not go with per-particle orientation lists");
+  if (!ownLists && h->nAnglesUp < h->angO1)
+    return refuse("orientations not uploaded");
+  if (compat_flush(h))
+    return 1;
+  const int nO = h->angO1 - h->angO0, np = iMapEnd - iMapBegin;
+  if (!h->dOrientOut)
+  {
+    double *scr = nullptr, *qq = nullptr, *pri = nullptr;
+    bioem_hip_orient_sums *res = nullptr;
+    if (dev_alloc(h, scr, bioem_orient_scratch(nO, h->nMaps)) || dev_alloc(h, qq, (size_t) nO * 10) ||
+        dev_alloc(h, pri, (size_t) nO) || dev_alloc(h, res, (size_t) h->nMaps))
+    {
+      dev_release(h, scr);
+      dev_release(h, qq);
+      dev_release(h, pri);
+      dev_release(h, res);
+      (void) hipGetLastError();
+      return 1;
+    }
+    h->dOrientScratch = scr;
+    h->dOrientQQ = qq;
+    h->dOrientPrior = pri;
+    h->dOrientOut = res;
+  }
+  if (logPrior)
+    HIP_CHECK(h, hipMemcpyAsync(h->dOrientPrior, logPrior + h->angO0, sizeof(double) * (size_t) nO, hipMemcpyHostToDevice, h->stream));
+  const bool moments = ownLists ? h->ownIsQuat != 0 : h->isQuat != 0;
+  const bioem_hip_prob_angle *pang =
+      reinterpret_cast<const bioem_hip_prob_angle *>(h->dProb + sizeof(bioem_hip_prob_map) * h->nMaps);
+  if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, iMapBegin, iMapEnd, 0, 0))
+    return 1;
+  hipError_t le = hipSuccess;
+  if (!ownLists && moments)
+    le = bioem_orient_products_launch(h->stream, h->dAngles + h->angO0, nO, h->dOrientQQ);
+  if (le == hipSuccess)
+    le = bioem_orient_sums_launch(h->stream, pang, nO, h->nMaps, iMapBegin, np, ownLists ? 0 : h->angO0,
+                                  logPrior ? h->dOrientPrior : nullptr, !ownLists && moments ? h->dOrientQQ : nullptr,
+                                  ownLists ? h->dOwnAngles : nullptr, ownLists ? h->dOwnOff : nullptr, h->ownIsQuat,
+                                  h->dOrientScratch, h->dOrientOut);
+  if (le != hipSuccess || phase_end(h, h->stream))
+  { // a launch failed: the phase that was opened is dropped, its events go back to the pool
+    if (h->phaseTiming && !h->phasePending.empty())
+    {
+      h->evPool.push_back(h->phasePending.back().a);
+      h->evPool.push_back(h->phasePending.back().b);
+      h->phasePending.pop_back();
+    }
+    if (le != hipSuccess)
+      h->err = std::string("orientation_sums: launch failed: ") + hipGetErrorString(le);
+    return 1;
+  }
+  HIP_CHECK(h, hipMemcpyAsync(out, h->dOrientOut, sizeof(bioem_hip_orient_sums) * (size_t) np, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  drain_phases(h);
+  return 0;
+}
+
+int bioem_hip_merge_orient_sums_host(int nShards, int nMaps, const bioem_hip_orient_sums *const *sums, bioem_hip_orient_sums *out)
+{
+  if (nShards < 1 || nMaps < 0 || !sums || !out)
+    return 2;
+  for (int s = 0; s < nShards; s++)
+    if (!sums[s])
+      return 2;
+  for (int i = 0; i < nMaps; i++)
+  {
+    int who = -1;
+    for (int s = 0; s < nShards; s++) // the maximum, ties to the lowest shard
+      if (sums[s][i].count > 0. && (who < 0 || sums[s][i].m > sums[who][i].m))
+        who = s;
+    bioem_hip_orient_sums r;
+    memset(&r, 0, sizeof(r));
+    r.m = MIN_PROB;
+    r.omax = -1.;
+    r.hasMoments = sums[0][i].hasMoments;
+    if (who >= 0)
+    {
+      r.m = sums[who][i].m;
+      r.omax = sums[who][i].omax;
+      for (int s = 0; s < nShards; s++)
+      {
+        const bioem_hip_orient_sums &a = sums[s][i];
+        if (!(a.count > 0.))
+          continue;
+        const double d = a.m - r.m, e = exp(d);
+        r.count += a.count;
+        r.S0 += a.S0 * e;
+        r.S1 += (a.S1 + d * a.S0) * e;
+        r.S2 += a.S2 * (e * e);
+        for (int k = 0; k < 10; k++)
+          r.Q[k] += a.Q[k] * e;
+      }
+    }
+    out[i] = r;
+  }
+  return 0;
+}
+
+namespace
+{
+// device buffers of one debug call
+struct OrientDebugBufs
+{
+  std::vector<void *> p;
+  ~OrientDebugBufs()
+  {
+    for (void *q : p)
+      hipFree(q);
+  }
+  // bytes on the device, filled from src when there is one
+  hipError_t get(void *d_, const void *src, size_t bytes)
+  {
+    void **d = static_cast<void **>(d_);
+    *d = nullptr;
+    hipError_t e = hipMalloc(d, std::max<size_t>(bytes, 1));
+    if (e != hipSuccess)
+      return e;
+    p.push_back(*d);
+    return src && bytes ? hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+  }
+};
+
+int debug_orient(bioem_hip_ctx *h, const char *what, const bioem_hip_prob_angle *table, int nO, int nMaps, const float *angles4,
+                 const long long *offsets, int isQuat, const double *logPrior, bioem_hip_orient_sums *out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  auto refuse = [&](const char *why) {
+    h->err = std::string(what) + ": " + why;
+    return 2;
+  };
+  if (!table || !out || nO < 1 || nMaps < 1 || (offsets && !angles4))
+    return refuse("null argument or an empty table");
+  std::vector<int> off;
+  if (offsets)
+  {
+    off.resize((size_t) nMaps + 1);
+    for (int p = 0; p <= nMaps; p++)
+    {
+      if (offsets[p] < 0 || offsets[p] > 0x7fffffffLL || (p && (offsets[p] < offsets[p - 1] || offsets[p] - offsets[p - 1] > nO)))
+        return refuse("offsets negative, descending or a list longer than the table");
+      off[(size_t) p] = (int) offsets[p];
+    }
+  }
+  OrientDebugBufs B;
+  bioem_hip_prob_angle *dTab = nullptr;
+  float4 *dAng = nullptr;
+  double *dQQ = nullptr, *dPri = nullptr, *dScr = nullptr;
+  int *dOff = nullptr;
+  bioem_hip_orient_sums *dOut = nullptr;
+  const bool moments = angles4 && isQuat;
+  const size_t nAng = offsets ? (size_t) off.back() : (size_t) nO;
+  HIP_CHECK(h, B.get(&dTab, table, sizeof(bioem_hip_prob_angle) * (size_t) nO * nMaps));
+  HIP_CHECK(h, B.get(&dScr, nullptr, sizeof(double) * bioem_orient_scratch(nO, nMaps)));
+  HIP_CHECK(h, B.get(&dOut, nullptr, sizeof(bioem_hip_orient_sums) * (size_t) nMaps));
+  if (angles4)
+    HIP_CHECK(h, B.get(&dAng, angles4, sizeof(float4) * nAng));
+  if (offsets)
+    HIP_CHECK(h, B.get(&dOff, off.data(), sizeof(int) * off.size()));
+  if (logPrior && !offsets)
+    HIP_CHECK(h, B.get(&dPri, logPrior, sizeof(double) * (size_t) nO));
+  if (moments && !offsets)
+  {
+    HIP_CHECK(h, B.get(&dQQ, nullptr, sizeof(double) * (size_t) nO * 10));
+    HIP_CHECK(h, bioem_orient_products_launch(h->stream, dAng, nO, dQQ));
+  }
+  HIP_CHECK(h, bioem_orient_sums_launch(h->stream, dTab, nO, nMaps, 0, nMaps, 0, dPri, dQQ, dAng, dOff, moments, dScr, dOut));
+  HIP_CHECK(h, hipMemcpyAsync(out, dOut, sizeof(bioem_hip_orient_sums) * (size_t) nMaps, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+} // namespace
+
+int bioem_hip_debug_orient_sums(bioem_hip_handle h, const bioem_hip_prob_angle *table, int nO, int nMaps, const float *angles4,
+                                int isQuat, const double *logPrior, bioem_hip_orient_sums *out)
+{
+  return debug_orient(h, "debug_orient_sums", table, nO, nMaps, angles4, nullptr, isQuat, logPrior, out);
+}
+
+int bioem_hip_debug_orient_sums_own(bioem_hip_handle h, const bioem_hip_prob_angle *table, int nO, int nMaps,
+                                    const float *angles4, const long long *offsets, int isQuat, bioem_hip_orient_sums *out)
+{
+  if (h && !offsets)
+  {
+    h->err = "debug_orient_sums_own: null argument";
+    return 2;
+  }
+  return debug_orient(h, "debug_orient_sums_own", table, nO, nMaps, angles4, offsets, isQuat, nullptr, out);
 }
 
 int bioem_hip_debug_projection(bioem_hip_handle h, int iOrient, float *spec_out)

@@ -17,6 +17,8 @@ PHASE_RECORD_DTYPE = np.dtype([("phase", "<i4"), ("iOrientBegin", "<i4"), ("iOri
 CANDIDATE_DTYPE = np.dtype([("forAngles", "<f8"), ("ConstAngle", "<f8"), ("logp", "<f8"), ("orient", "<i4"),
                             ("pad", "<i4")])
 RING_SUMS_DTYPE = np.dtype([("cross", "<f8"), ("powParticle", "<f8"), ("powModel", "<f8")])
+ORIENT_SUMS_DTYPE = np.dtype([("m", "<f8"), ("omax", "<f8"), ("count", "<f8"), ("hasMoments", "<f8"), ("S0", "<f8"),
+                              ("S1", "<f8"), ("S2", "<f8"), ("Q", "<f8", (10,))])
 WINDOW_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4")])
 MIN_PROB = -999999.0
 
@@ -88,6 +90,11 @@ def load_library():
         L.bioem_hip_window_offsets.argtypes = [ci, ci, ci, ci, vp, ci]
         L.bioem_hip_window_posterior.argtypes = [vp, vp, ci, ci, vp, vp, vp]
         L.bioem_hip_debug_window.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp]
+    if hasattr(L, "bioem_hip_orientation_sums"):
+        L.bioem_hip_orientation_sums.argtypes = [vp, vp, ci, ci, ci, vp]
+        L.bioem_hip_merge_orient_sums_host.argtypes = [ci, ci, C.POINTER(vp), vp]
+        L.bioem_hip_debug_orient_sums.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp]
+        L.bioem_hip_debug_orient_sums_own.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -141,7 +148,9 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_upload_particle_orientation_lists", "bioem_hip_plan_own", "bioem_hip_own_kernel_signature",
            "bioem_hip_set_own_launch", "bioem_hip_render_best_maps", "bioem_hip_enable_ctf_table",
            "bioem_hip_ctf_table", "bioem_hip_ring_count", "bioem_hip_best_match_rings", "bioem_hip_debug_ring_sums",
-           "bioem_hip_window_count", "bioem_hip_window_offsets", "bioem_hip_window_posterior", "bioem_hip_debug_window"]
+           "bioem_hip_window_count", "bioem_hip_window_offsets", "bioem_hip_window_posterior", "bioem_hip_debug_window",
+           "bioem_hip_orientation_sums", "bioem_hip_merge_orient_sums_host", "bioem_hip_debug_orient_sums",
+           "bioem_hip_debug_orient_sums_own"]
 
 
 def _p(a):
@@ -488,6 +497,52 @@ class Engine:
             raise e
         return logp, cc
 
+    def orientation_sums(self, prior=None, p0=0, p1=None, own=False):
+        """the orientation posterior of particles [p0, p1) reduced where the angle table lives: ORIENT_SUMS_DTYPE
+        [p1 - p0] with m = max l, omax (global index; with own lists the index in the particle's list), count, hasMoments
+        and the sums S0, S1, S2, Q relative to m, over the entries with forAngles > 0 and l = log forAngles + ConstAngle +
+        prior (include/bioem_hip.h; orient_stats.derive turns them into entropy, nEff, mean orientation and spread).
+        prior: None, or nAngles log priors by global orientation index (not with own lists).  Call after finish_run on a
+        handle with WRITE_PROB_ANGLES; a shard sums over its own block.  A refusal raises RuntimeError with .rc == 2."""
+        p1 = self.nMaps if p1 is None else int(p1)
+        if prior is not None:
+            prior = np.ascontiguousarray(prior, dtype=np.float64)
+            assert prior.shape == (self.nAngles,)
+        out = np.zeros(max(0, p1 - int(p0)), dtype=ORIENT_SUMS_DTYPE)
+        rc = self.L.bioem_hip_orientation_sums(self.h, _p(prior), int(p0), p1, int(bool(own)), _p(out))
+        if rc:
+            e = RuntimeError("orientation_sums: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+        return out
+
+    def debug_orient_sums(self, table, angles=None, isQuat=True, prior=None, offsets=None):
+        """test hook: the kernels of orientation_sums on a table handed in, PROB_ANGLE_DTYPE [nO, nMaps]; angles float32
+        [nO, 4] or None (no moments), prior float64 [nO] or None.  offsets (int64 [nMaps + 1]): the own-list instantiation,
+        angles = the flat lists.  Returns ORIENT_SUMS_DTYPE [nMaps]; a refusal raises with .rc == 2."""
+        table = np.ascontiguousarray(table, dtype=PROB_ANGLE_DTYPE)
+        nO, nMaps = table.shape
+        if angles is not None:
+            angles = np.ascontiguousarray(angles, dtype=np.float32).reshape(-1, 4)
+        out = np.zeros(nMaps, dtype=ORIENT_SUMS_DTYPE)
+        if offsets is None:
+            assert angles is None or len(angles) == nO
+            if prior is not None:
+                prior = np.ascontiguousarray(prior, dtype=np.float64)
+                assert prior.shape == (nO,)
+            rc = self.L.bioem_hip_debug_orient_sums(self.h, _p(table), nO, nMaps, _p(angles), int(bool(isQuat)), _p(prior),
+                                                    _p(out))
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            assert offsets.shape == (nMaps + 1,) and prior is None and angles is not None and len(angles) >= offsets[-1]
+            rc = self.L.bioem_hip_debug_orient_sums_own(self.h, _p(table), nO, nMaps, _p(angles), _p(offsets),
+                                                        int(bool(isQuat)), _p(out))
+        if rc:
+            e = RuntimeError("debug_orient_sums: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+        return out
+
     def enable_ctf_table(self, on=True):
         """keep the posterior per (CTF set, particle) beside the particle entries, from the next start_run on; call it
         outside a run (inside one it raises, .rc == 2)"""
@@ -600,4 +655,18 @@ def merge_ctf_tables(tables):
     arr = (C.c_void_p * len(tables))(*[t.ctypes.data for t in tables])
     if L.bioem_hip_merge_host(len(tables), tables[0].size, 0, 0, arr, _p(out)):
         raise RuntimeError("bioem_hip_merge_host failed")
+    return out
+
+
+def merge_orient_sums(sums):
+    """Merge of the shards' orientation sums ([nMaps] of ORIENT_SUMS_DTYPE each, Engine.orientation_sums; shards in
+    ascending orientation-block order) by bioem_hip_merge_orient_sums_host: the maximum m with ties to the lowest shard,
+    every shard's sums rescaled by e^(m_s - m) and added in shard order.  No device."""
+    L = load_library()
+    sums = [np.ascontiguousarray(t, dtype=ORIENT_SUMS_DTYPE) for t in sums]
+    assert sums and all(t.shape == sums[0].shape and t.ndim == 1 for t in sums)
+    out = np.zeros_like(sums[0])
+    arr = (C.c_void_p * len(sums))(*[t.ctypes.data for t in sums])
+    if L.bioem_hip_merge_orient_sums_host(len(sums), sums[0].size, arr, _p(out) if out.size else None):
+        raise RuntimeError("bioem_hip_merge_orient_sums_host failed")
     return out

@@ -141,6 +141,26 @@ struct WindowStats
 WindowStats window_stats(const double *logp, const int *shifts, int nd);
 std::string write_best_window(const char *file, const double *logp, const int *shifts, int nd, int nMaps, const int *orient,
                               const int *conv, const float *ctfParam3, bool usepsf, float elecwavel, const double *numconst);
+// --OrientStats (orientstats.cpp): the text file of the sums sums[nMaps] of bioem_hip_orientation_sums.  After the
+// HEADER:: NOTATION bar, one notation line (it carries the constant as NumericalConst) and the bar again, per particle
+//  ORIENT p count logZ omax A pTop entropy nEff meanq1 meanq2 meanq3 meanq4 spreadDeg
+// (count: entries of the angle table that were compared; logZ = m + log S0 + numconst, the constant of ANG_PROB; omax: the
+// arg-max orientation and A its 4 numbers with quaternions, else 3, from the list angles4 (angleOffsets: particle p's list
+// begins at entry angleOffsets[p]); pTop = 1 / S0; entropy = log S0 - S1 / S0; nEff = S0^2 / S2; mean: the eigenvector of
+// Q / S0 of the largest eigenvalue lambda, signed to a non-negative dot product with the arg-max quaternion; spreadDeg =
+// 2 acos(sqrt(lambda)) in degrees).  Euler lists print "- -" for the mean and the spread; a particle with count 0 prints
+// logZ -inf, omax -1, zeros.  Floating values with 16 significant digits.  Returns the empty string, or the error.
+struct OrientStats
+{
+  long long count;
+  int omax;
+  bool hasMean;
+  double logZ, pTop, entropy, nEff, mean[4], spreadDeg; // logZ without the constant
+};
+void jacobi4(const double a[4][4], double w[4], double v[4][4]); // eigenvalues descending, v[k] the vector of w[k]
+OrientStats orient_derive(const bioem_hip_orient_sums &s, const float *angles4, bool doquater);
+std::string write_orient_stats(const char *file, const bioem_hip_orient_sums *sums, int nMaps, const float *angles4,
+                               const long long *angleOffsets, bool doquater, double numconst);
 // MRC mode-2 stack nx = ny = N, nz = nMaps in the storage order the --ReadMRC reader expects, written batch by batch
 struct MrcStackWriter
 {
@@ -198,6 +218,7 @@ public:
   std::string probCtfFile;   // --ProbCTF: the posterior per (particle, CTF set) as text (FILE, FILE_Round2)
   std::string bestFrcFile;   // --BestFRC: ring correlation of every particle against its best match (FILE, FILE_Round2)
   std::string bestWindowFile; // --BestWindow: posterior over the displacement window of every best match (FILE, FILE_Round2)
+  std::string orientStatsFile; // --OrientStats: summaries of every particle's orientation posterior (WRITE_PROB_ANGLES)
   std::string bestParamFile; // --PrintBestCalMap: the reference's one-record mode, no particles, writes BESTMAP
   BestParams best;
   int printBestCalMap();     // bioem::printModel (bioem.cpp:624-657, 1925-2085)
@@ -237,6 +258,9 @@ private:
   // written by write_best_window; voluPerMap as for writeProbabilities
   void writeBestWindow(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
                        const bioem_hip_param_device &pd, const float *voluPerMap = nullptr);
+  // --OrientStats: the shards' orientation sums (bioem_hip_orientation_sums) merged on the host, written by
+  // write_orient_stats; numconst: the constant of ANG_PROB
+  void writeOrientStats(const std::string &file, double numconst);
   // --ProbCTF: the tables of the handles merged on the host (shards in ascending order) and written
   void writeCtfProb(const std::string &file, const std::vector<bioem_hip_handle> &hs, const bioem_hip_param_device &pd,
                     const float *angles, size_t anglesPerMap, const long long *angleOffsets = nullptr,

@@ -205,6 +205,31 @@ int bioem_host_write_best_window(const char *file, const double *logp, const int
   return e.empty() ? 0 : 1;
 }
 
+// the --OrientStats text of sums[nMaps] (write_orient_stats, bioem_host.h): angles4 one list for all maps; 0, or 1 with
+// the text in err[cap]
+int bioem_host_write_orient_stats(const char *file, const bioem_hip_orient_sums *sums, int nMaps, const float *angles4,
+                                  int doquater, double numconst, char *err, int cap)
+{
+  const std::string e = bioem_host::write_orient_stats(file, sums, nMaps, angles4, nullptr, doquater != 0, numconst);
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return e.empty() ? 0 : 1;
+}
+
+// the 4 x 4 Jacobi eigen-solver of --OrientStats: a[16] symmetric, row-major -> w[4] descending, v[4][4] with row k the
+// unit eigenvector of w[k]
+void bioem_host_jacobi4(const double *a, double *w, double *v)
+{
+  double A[4][4], V[4][4];
+  for (int i = 0; i < 4; i++)
+    for (int j = 0; j < 4; j++)
+      A[i][j] = a[4 * i + j];
+  bioem_host::jacobi4(A, w, V);
+  for (int i = 0; i < 4; i++)
+    for (int j = 0; j < 4; j++)
+      v[4 * i + j] = V[i][j];
+}
+
 // the MRC stack of --BestMaps: maps [nMaps][N][N] appended in batches of `batch` images
 int bioem_host_write_mrc_stack(const char *file, const float *maps, int nMaps, int N, int batch)
 {

@@ -74,6 +74,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"ProbCTF", required_argument, 0, 0},
                                        {"BestFRC", required_argument, 0, 0},
                                        {"BestWindow", required_argument, 0, 0},
+                                       {"OrientStats", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
                                        {"RefineSeeds", required_argument, 0, 0},
@@ -109,6 +110,8 @@ int Driver::readOptions(int ac, char **av)
     printf("                         (per ring: FRC and powers; with --RefineOrientations also arg_Round2)\n");
     printf("  --BestWindow arg       (Optional) Write the posterior over the displacement window of every particle's best match\n");
     printf("                         (is DISPLACE_CENTER wide enough? with --RefineOrientations also arg_Round2)\n");
+    printf("  --OrientStats arg      (Optional) Write per particle the summaries of its orientation posterior (entropy, effective\n");
+    printf("                         number of orientations, mean orientation, spread; needs WRITE_PROB_ANGLES)\n");
     printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
@@ -212,6 +215,11 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Writing the posterior over the displacement window of the best matches to: " << optarg << "\n";
       bestWindowFile = optarg;
     }
+    else if (name == "OrientStats")
+    {
+      std::cout << "Writing the summaries of the orientation posteriors to: " << optarg << "\n";
+      orientStatsFile = optarg;
+    }
     else if (name == "PrintBestCalMap")
     {
       std::cout << "Reading best parameters from file: " << optarg << "\n";
@@ -250,8 +258,9 @@ int Driver::readOptions(int ac, char **av)
   if (!bestParamFile.empty())
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
-    if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty() || !bestWindowFile.empty())
-      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow and --RefineOrientations");
+    if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty() || !bestWindowFile.empty() ||
+        !orientStatsFile.empty())
+      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow, --OrientStats and --RefineOrientations");
     const std::string err = read_best_parameters(bestParamFile.c_str(), best);
     if (!err.empty())
       fatal("%s", err.c_str());
@@ -282,6 +291,13 @@ int Driver::readOptions(int ac, char **av)
   param.readParameters(infile.c_str());
   if (refineFile.empty() && (refineSeeds != 1 || refineLogWindow >= 0.))
     fatal("--RefineSeeds / --RefineLogWindow go with --RefineOrientations");
+  if (!orientStatsFile.empty())
+  { // the summaries are reduced from the angle table: it must exist, and round 2 goes without it
+    if (!refineFile.empty())
+      fatal("--OrientStats is not valid with --RefineOrientations (which goes without WRITE_PROB_ANGLES)");
+    if (!param.pd.writeAngles)
+      fatal("--OrientStats needs WRITE_PROB_ANGLES in the parameter file: the summaries are reduced from the angle table");
+  }
   if (!refineFile.empty())
   { // round 2 multiplies quaternions and evaluates lists of its own: no prior per orientation, no ANG_PROB (yet)
     if (!param.doquater)
@@ -390,6 +406,8 @@ int Driver::configure(int ac, char **av)
   }
   // RCCL carries the merge when every shard has a GPU of its own
   // (BIOEM_FORCE_RCCL=1: also with a single shard -- a one-rank communicator, to exercise this path on a one-GPU box)
+  if (splitCTF && !orientStatsFile.empty())
+    fatal("--OrientStats is not valid with more shards than orientations: an orientation's entry is spread over shards");
   useRccl = (nShards > 1 || getenv("BIOEM_FORCE_RCCL")) && nDevUsed == nShards && !splitCTF && !getenv("BIOEM_HOST_MERGE");
   return 0;
 }
@@ -581,6 +599,32 @@ void Driver::writeBestWindow(const std::string &file, bioem_hip_handle h, const 
   if (!err.empty())
     fatal("--BestWindow: %s", err.c_str());
   std::cout << "Window posterior of " << nMaps << " particles' best matches written to: " << file << "\n";
+}
+
+// --OrientStats: every shard's sums over the orientations it owns (bioem_hip_orientation_sums), merged on the host in
+// shard order, then the text file (write_orient_stats)
+void Driver::writeOrientStats(const std::string &file, double numconst)
+{
+  const int nMaps = particles.ntot, nShards = (int) shards.size();
+  std::vector<double> prior;
+  if (param.yespriorAngles)
+    prior.assign(param.angprior.begin(), param.angprior.end());
+  std::vector<std::vector<bioem_hip_orient_sums>> part((size_t) nShards);
+  std::vector<const bioem_hip_orient_sums *> ptrs((size_t) nShards);
+  for (int g = 0; g < nShards; g++)
+  {
+    part[(size_t) g].resize((size_t) nMaps);
+    check(shards[g].h, bioem_hip_orientation_sums(shards[g].h, prior.empty() ? nullptr : prior.data(), 0, nMaps, 0,
+                                                  part[(size_t) g].data()), "orientation sums");
+    ptrs[(size_t) g] = part[(size_t) g].data();
+  }
+  std::vector<bioem_hip_orient_sums> sums((size_t) nMaps);
+  if (bioem_hip_merge_orient_sums_host(nShards, nMaps, ptrs.data(), sums.data()))
+    fatal("merge failed");
+  const std::string err = write_orient_stats(file.c_str(), sums.data(), nMaps, param.angles.data(), nullptr, param.doquater, numconst);
+  if (!err.empty())
+    fatal("--OrientStats: %s", err.c_str());
+  std::cout << "Orientation posterior summaries of " << nMaps << " particles written to: " << file << "\n";
 }
 
 // --PrintBestCalMap: the record of the BEST_* file rendered on the device and written as the reference's BESTMAP text.
@@ -775,6 +819,8 @@ int Driver::run()
       hs.push_back(sh.h);
     writeCtfProb(probCtfFile, hs, param.pd, param.angles.data(), 0);
   }
+  if (!orientStatsFile.empty())
+    writeOrientStats(orientStatsFile, numconst);
   if (!bestMapsFile.empty()) // from the merged records, on the first handle (every handle holds the global list)
     writeBestMaps(bestMapsFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!bestFrcFile.empty())

@@ -202,3 +202,32 @@ def write_best_window(path, logp, shifts, orient, conv, ctfParam, numconst, usep
                                       c.ctypes.data, k.ctypes.data, int(bool(usepsf)), float(elecwavel), nc.ctypes.data,
                                       err, 512):
         raise ValueError(err.value.decode())
+
+
+def write_orient_stats(path, sums, angles, doquater, numconst):
+    """the --OrientStats text file of orientation sums [nMaps] (Engine.orientation_sums) against the orientation list
+    `angles` [nO, 4]: the writer the CLI uses; bioem_amd.orient_stats.parse reads it back"""
+    from .engine import ORIENT_SUMS_DTYPE
+    L = load_host_library()
+    L.bioem_host_write_orient_stats.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double,
+                                                C.c_char_p, C.c_int]
+    t = np.ascontiguousarray(sums, dtype=ORIENT_SUMS_DTYPE)
+    a = np.ascontiguousarray(angles, dtype=np.float32).reshape(-1, 4)
+    assert t.ndim == 1
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_orient_stats(path.encode(), t.ctypes.data, t.shape[0], a.ctypes.data, int(bool(doquater)),
+                                       float(numconst), err, 512):
+        raise ValueError(err.value.decode())
+
+
+def jacobi4(A):
+    """eigenvalues (descending) and eigenvectors (row k belongs to eigenvalue k) of a symmetric 4 x 4 matrix by the Jacobi
+    solver of the --OrientStats writer"""
+    L = load_host_library()
+    L.bioem_host_jacobi4.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bioem_host_jacobi4.restype = None
+    a = np.ascontiguousarray(A, dtype=np.float64)
+    assert a.shape == (4, 4)
+    w, v = np.zeros(4), np.zeros((4, 4))
+    L.bioem_host_jacobi4(a.ctypes.data, w.ctypes.data, v.ctypes.data)
+    return w, v

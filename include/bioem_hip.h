@@ -408,6 +408,51 @@ int bioem_hip_window_posterior(bioem_hip_handle h, const bioem_hip_window_reques
 int bioem_hip_debug_window(bioem_hip_handle h, const float *specConv, const float *specRef, const bioem_hip_param5 *params,
                            const float *sumRef, const float *sumsqRef, int n, double *logp_out, float *cc_out);
 
+/* ---- Summaries of the orientation posterior of every particle (WRITE_PROB_ANGLES; no reference counterpart) ----
+ * The [orientations][nMaps] table of bioem_hip_prob_angle stays on the device; this entry reduces it there.  Let
+ * F = forAngles, C = ConstAngle of entry (o, p).  Only entries with F > 0 count (entries never compared, or beyond a
+ * particle's own list, keep F = 0), and for those l_o = (log F + C) + prior_o in double, prior_o = 0 without logPrior:
+ * the key the ANG_PROB lines carry, minus their constant.  Per particle, in two passes (the maximum first, exact and
+ * order-free; then every sum relative to it, so no term is ever rescaled):
+ *   m      max over o of l_o                         (MIN_PROB = -999999 when count is 0)
+ *   omax   the lowest orientation index attaining m  (-1 when count is 0); the index is GLOBAL, with own lists the index
+ *          in the particle's list
+ *   count  entries with F > 0
+ *   hasMoments  1 when the orientations are quaternions, else 0 (Euler angles: Q stays 0, the scalar sums are delivered)
+ *   S0 = sum e^(l-m),  S1 = sum e^(l-m) (l-m),  S2 = sum e^(2(l-m))
+ *   Q[10]  upper triangle (00 01 02 03 11 12 13 22 23 33) of sum e^(l-m) q q^T, q the entry's quaternion in the
+ *          reference's (x, y, z, w) storage, widened to double and divided by its length (q and -q give the same q q^T)
+ * All fields are double.  The host derives (bioem_amd/orient_stats.py: derive): logZ = m + log S0, the entropy
+ * H = log S0 - S1 / S0, nEff = S0^2 / S2, pTop = 1 / S0, the mean orientation = the eigenvector of Q / S0 of the largest
+ * eigenvalue lambda, and the spread 2 acos(sqrt(lambda)) (lambda = E[cos^2(theta / 2)] of the rotation angle to the mean).
+ * The orientation range is cut into chunks of 256, summed in orientation order and folded in chunk order; no atomics:
+ * the same bits on every run, for any nMaps, any particle range and any position of a particle in the table. */
+typedef struct { double m, omax, count, hasMoments, S0, S1, S2, Q[10]; } bioem_hip_orient_sums;   /* 136 bytes */
+/* Calling rules of bioem_hip_topk_angles (after finish_run, every handle kind that holds an angle table; a shard sums
+ * over the orientations it owns and reports global indices).  logPrior: NULL, or nAngles doubles by global orientation
+ * index; refused with own lists.  ownLists = 1: the table rows are positions in the particles' own lists
+ * (bioem_hip_compare_own_orientations with WRITE_PROB_ANGLES).  Refused with 2, the reason in bioem_hip_last_error and
+ * the handle usable: no WRITE_PROB_ANGLES, a particle range that is empty, reversed or outside [0, nMaps), a null
+ * `out`, ownLists without lists, logPrior with own lists.  Buffers are allocated at the first call (1 when the memory is
+ * not there).  Phase record: one of phase 2 over the call's kernels, iOrientBegin / iOrientEnd the particle range. */
+int bioem_hip_orientation_sums(bioem_hip_handle h, const double *logPrior, int iMapBegin, int iMapEnd, int ownLists,
+                               bioem_hip_orient_sums *out /* [iMapEnd - iMapBegin] */);
+/* Merge of the shards' sums on the host, no device: sums[s] = [nMaps]; per particle the maximum m with ties to the
+ * lowest shard (shards in ascending orientation-block order: the lowest index), every shard's sums scaled by
+ * e^(m_s - m) and added in shard order, S1 with the extra term (m_s - m) S0_s e^(m_s - m), S2 scaled by
+ * e^(2(m_s - m)); counts add; shards with count 0 are left out.  Returns 2 for nShards < 1 or a null argument. */
+int bioem_hip_merge_orient_sums_host(int nShards, int nMaps, const bioem_hip_orient_sums *const *sums,
+                                     bioem_hip_orient_sums *out);
+/* test hooks: the same kernels on a table handed in, table = [nO][nMaps] entries on the host; angles4 = [nO][4] (NULL
+ * or isQuat = 0: no moments); logPrior NULL or nO doubles; out = [nMaps].  The _own variant runs the own-list
+ * instantiation: angles4 = the flat lists, offsets[nMaps + 1] into them (list lengths at most nO); a table entry with
+ * F > 0 beyond its particle's list does not count. */
+int bioem_hip_debug_orient_sums(bioem_hip_handle h, const bioem_hip_prob_angle *table, int nO, int nMaps,
+                                const float *angles4, int isQuat, const double *logPrior, bioem_hip_orient_sums *out);
+int bioem_hip_debug_orient_sums_own(bioem_hip_handle h, const bioem_hip_prob_angle *table, int nO, int nMaps,
+                                    const float *angles4, const long long *offsets, int isQuat,
+                                    bioem_hip_orient_sums *out);
+
 #ifdef __cplusplus
 }
 #endif
