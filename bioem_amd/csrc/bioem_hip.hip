@@ -56,7 +56,8 @@
 //                          declarations only here)
 //   orient_kernels.hpp   k_orient_max, k_orient_sums, k_orient_fold, k_orient_products  bioem_hip_orientation_sums: the
 //                          orientation posterior of every particle reduced where the angle table lives
-//                          (kernels_orient.hip; declarations only here)
+//                          (kernels_orient.hip; declarations only here); k_orient_occ  bioem_hip_orientation_occupancy:
+//                          the same table reduced along the particles, per orientation
 //   this file            device context, launch logic, the C ABI
 //   kernels_*.hip        one translation unit per comparison-kernel family (the instantiations of kernel_table.inc),
 //                          linked into the same library: kernels_fast, kernels_fastm, kernels_wide2_{short,16,long},
@@ -233,6 +234,11 @@ struct bioem_hip_ctx
   // and the result (allocated at the first call)
   double *dOrientScratch = nullptr, *dOrientQQ = nullptr, *dOrientPrior = nullptr;
   bioem_hip_orient_sums *dOrientOut = nullptr;
+  // bioem_hip_orientation_occupancy: the particles' normalisers m, 1 / S0, omax, the priors of the owned orientations and
+  // the result (allocated at the first call)
+  double *dOccM = nullptr, *dOccRS0 = nullptr, *dOccPrior = nullptr;
+  int *dOccOmax = nullptr;
+  bioem_hip_orient_occ *dOccOut = nullptr;
   bool refUp = false; // particles uploaded (either entry)
   bool ctfUp = false; // bioem_hip_upload_ctf has run
   // bioem_hip_enable_ctf_table: [nCTF][nMaps] entries, folded beside the particle entries (k_fold_ctf, k_fold_own_ctf);
@@ -3288,6 +3294,146 @@ int bioem_hip_debug_orient_sums_own(bioem_hip_handle h, const bioem_hip_prob_ang
     return 2;
   }
   return debug_orient(h, "debug_orient_sums_own", table, nO, nMaps, angles4, offsets, isQuat, nullptr, out);
+}
+
+// ---- occupancy of every orientation over the particles (orient_kernels.hpp: k_orient_occ) ----
+namespace
+{
+// the normalisers of the particles as the kernel reads them: m, 1 / S0 (0: the particle is left out), omax (-1 then)
+struct OccNormalisers
+{
+  std::vector<double> m, rS0;
+  std::vector<int> omax;
+  explicit OccNormalisers(const bioem_hip_orient_sums *sums, int np) : m((size_t) np), rS0((size_t) np), omax((size_t) np)
+  {
+    for (int i = 0; i < np; i++)
+    {
+      const bioem_hip_orient_sums &s = sums[i];
+      const bool counts = s.count > 0. && s.S0 > 0. && s.S0 < INFINITY && s.omax >= 0. && s.omax <= 2147483647.;
+      m[(size_t) i] = counts ? s.m : 0.;
+      rS0[(size_t) i] = counts ? 1. / s.S0 : 0.;
+      omax[(size_t) i] = counts ? (int) s.omax : -1;
+    }
+  }
+};
+} // namespace
+
+int bioem_hip_orientation_occupancy(bioem_hip_handle h, const double *logPrior, const bioem_hip_orient_sums *sums, int iMapBegin,
+                                    int iMapEnd, bioem_hip_orient_occ *out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  auto refuse = [&](const char *why) {
+    h->err = std::string("orientation_occupancy: ") + why;
+    return 2;
+  };
+  if (!h->pd.writeAngles)
+    return refuse("handle was created without WRITE_PROB_ANGLES");
+  if (!sums || !out)
+    return refuse("null argument");
+  if (iMapBegin < 0 || iMapEnd > h->nMaps || iMapBegin >= iMapEnd)
+    return refuse("particle range empty, reversed or outside [0, nMaps)");
+  if (h->dOwnAngles && !h->ownOff.empty())
+    return refuse("the handle holds per-particle orientation lists: its rows are list positions, not shared orientations");
+  if (h->nAnglesUp < h->angO1)
+    return refuse("orientations not uploaded");
+  if (compat_flush(h))
+    return 1;
+  const int nO = h->angO1 - h->angO0, np = iMapEnd - iMapBegin;
+  if (!h->dOccOut)
+  {
+    double *m = nullptr, *rs = nullptr, *pri = nullptr;
+    int *om = nullptr;
+    bioem_hip_orient_occ *res = nullptr;
+    if (dev_alloc(h, m, (size_t) h->nMaps) || dev_alloc(h, rs, (size_t) h->nMaps) || dev_alloc(h, pri, (size_t) nO) ||
+        dev_alloc(h, om, (size_t) h->nMaps) || dev_alloc(h, res, (size_t) nO))
+    {
+      dev_release(h, m);
+      dev_release(h, rs);
+      dev_release(h, pri);
+      dev_release(h, om);
+      dev_release(h, res);
+      (void) hipGetLastError();
+      return 1;
+    }
+    h->dOccM = m;
+    h->dOccRS0 = rs;
+    h->dOccPrior = pri;
+    h->dOccOmax = om;
+    h->dOccOut = res;
+  }
+  const OccNormalisers N(sums, np);
+  // the copies below read N and the caller's buffers asynchronously: whichever way this call ends, the stream is drained
+  // before N goes (the guard is destroyed first)
+  struct Drain
+  {
+    hipStream_t st;
+    ~Drain() { (void) hipStreamSynchronize(st); }
+  } drain = {h->stream};
+  HIP_CHECK(h, hipMemcpyAsync(h->dOccM, N.m.data(), sizeof(double) * (size_t) np, hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(h, hipMemcpyAsync(h->dOccRS0, N.rS0.data(), sizeof(double) * (size_t) np, hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(h, hipMemcpyAsync(h->dOccOmax, N.omax.data(), sizeof(int) * (size_t) np, hipMemcpyHostToDevice, h->stream));
+  if (logPrior)
+    HIP_CHECK(h, hipMemcpyAsync(h->dOccPrior, logPrior + h->angO0, sizeof(double) * (size_t) nO, hipMemcpyHostToDevice, h->stream));
+  const bioem_hip_prob_angle *pang =
+      reinterpret_cast<const bioem_hip_prob_angle *>(h->dProb + sizeof(bioem_hip_prob_map) * h->nMaps);
+  if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, iMapBegin, iMapEnd, 0, 0))
+    return 1;
+  const hipError_t le = bioem_orient_occ_launch(h->stream, pang, nO, h->nMaps, iMapBegin, np, h->angO0,
+                                                logPrior ? h->dOccPrior : nullptr, h->dOccM, h->dOccRS0, h->dOccOmax, h->dOccOut);
+  if (le != hipSuccess || phase_end(h, h->stream))
+  { // the launch failed: the phase that was opened is dropped, its events go back to the pool
+    if (h->phaseTiming && !h->phasePending.empty())
+    {
+      h->evPool.push_back(h->phasePending.back().a);
+      h->evPool.push_back(h->phasePending.back().b);
+      h->phasePending.pop_back();
+    }
+    if (le != hipSuccess)
+      h->err = std::string("orientation_occupancy: launch failed: ") + hipGetErrorString(le);
+    return 1;
+  }
+  HIP_CHECK(h, hipMemcpyAsync(out, h->dOccOut, sizeof(bioem_hip_orient_occ) * (size_t) nO, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  drain_phases(h);
+  return 0;
+}
+
+int bioem_hip_debug_orient_occupancy(bioem_hip_handle h, const bioem_hip_prob_angle *table, int nO, int nMaps, const double *logPrior,
+                                     const bioem_hip_orient_sums *sums, int p0, int p1, int o0, bioem_hip_orient_occ *out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  auto refuse = [&](const char *why) {
+    h->err = std::string("debug_orient_occupancy: ") + why;
+    return 2;
+  };
+  if (!table || !sums || !out || nO < 1 || nMaps < 1)
+    return refuse("null argument or an empty table");
+  if (p0 < 0 || p1 > nMaps || p0 >= p1)
+    return refuse("particle range empty, reversed or outside [0, nMaps)");
+  if (o0 < 0 || o0 > 0x7fffffff - nO)
+    return refuse("first orientation index negative or too large");
+  const int np = p1 - p0;
+  const OccNormalisers N(sums, np);
+  OrientDebugBufs B;
+  bioem_hip_prob_angle *dTab = nullptr;
+  double *dPri = nullptr, *dM = nullptr, *dRS0 = nullptr;
+  int *dOmax = nullptr;
+  bioem_hip_orient_occ *dOut = nullptr;
+  HIP_CHECK(h, B.get(&dTab, table, sizeof(bioem_hip_prob_angle) * (size_t) nO * nMaps));
+  HIP_CHECK(h, B.get(&dM, N.m.data(), sizeof(double) * (size_t) np));
+  HIP_CHECK(h, B.get(&dRS0, N.rS0.data(), sizeof(double) * (size_t) np));
+  HIP_CHECK(h, B.get(&dOmax, N.omax.data(), sizeof(int) * (size_t) np));
+  HIP_CHECK(h, B.get(&dOut, nullptr, sizeof(bioem_hip_orient_occ) * (size_t) nO));
+  if (logPrior)
+    HIP_CHECK(h, B.get(&dPri, logPrior, sizeof(double) * (size_t) nO));
+  HIP_CHECK(h, bioem_orient_occ_launch(h->stream, dTab, nO, nMaps, p0, np, o0, dPri, dM, dRS0, dOmax, dOut));
+  HIP_CHECK(h, hipMemcpyAsync(out, dOut, sizeof(bioem_hip_orient_occ) * (size_t) nO, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 int bioem_hip_debug_projection(bioem_hip_handle h, int iOrient, float *spec_out)

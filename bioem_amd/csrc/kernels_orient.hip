@@ -1,8 +1,10 @@
-// kernels_orient.hip -- the two passes of bioem_hip_orientation_sums (orient_kernels.hpp) and their launcher
+// kernels_orient.hip -- the two passes of bioem_hip_orientation_sums, the row pass of bioem_hip_orientation_occupancy
+// (orient_kernels.hpp) and their launchers
 #define BIOEM_ORIENT_TU 1
 #include "orient_kernels.hpp"
 
 static_assert(sizeof(BioemOrientMax) == 16 && sizeof(bioem_hip_orient_sums) == 17 * sizeof(double), "partial / result layout");
+static_assert(sizeof(bioem_hip_orient_occ) == 6 * sizeof(double), "occupancy result layout");
 
 namespace
 {
@@ -45,5 +47,17 @@ hipError_t bioem_orient_sums_launch(hipStream_t st, const bioem_hip_prob_angle *
     hipLaunchKernelGGL(k_orient_sums<false>, grid, block, 0, st, pang, nO, nMaps, p0, np, prior, qq, (const float4 *) nullptr,
                        (const int *) nullptr, moments, (const double *) gmax, psum);
   hipLaunchKernelGGL(k_orient_fold<true>, fgrid, fblock, 0, st, (const void *) psum, nC, np, o0, moments, gmax, out);
+  return hipGetLastError();
+}
+
+hipError_t bioem_orient_occ_launch(hipStream_t st, const bioem_hip_prob_angle *pang, int nO, int nMaps, int p0, int np, int o0,
+                                   const double *prior, const double *m, const double *rS0, const int *omax,
+                                   bioem_hip_orient_occ *out)
+{
+  if (nO < 1 || np < 1 || p0 < 0 || p0 + np > nMaps)
+    return hipErrorInvalidValue;
+  const int rowsPerBlock = kOccWaves * kOccRows;
+  hipLaunchKernelGGL(k_orient_occ, dim3((nO + rowsPerBlock - 1) / rowsPerBlock), dim3(64 * kOccWaves), 0, st, pang, nO, nMaps,
+                     p0, np, o0, prior, m, rS0, omax, out);
   return hipGetLastError();
 }

@@ -1,5 +1,6 @@
 // orient_kernels.hpp -- summaries of the orientation posterior, reduced where the angle table lives
-// (bioem_hip_orientation_sums, bioem_hip_debug_orient_sums).  For entry (o, p) of the [nO][nMaps] table with
+// (bioem_hip_orientation_sums, bioem_hip_debug_orient_sums), and, further down, the same table reduced along
+// the particles (bioem_hip_orientation_occupancy).  For entry (o, p) of the [nO][nMaps] table with
 // F = forAngles > 0:  l = (log F + ConstAngle) + prior_o, and per particle
 //   m = max l, omax = first o attaining it, count,  S0 = sum e^(l-m), S1 = sum e^(l-m)(l-m), S2 = sum e^(2(l-m)),
 //   Q = upper triangle of sum e^(l-m) q q^T, q the orientation's quaternion normalised in double.
@@ -35,11 +36,26 @@ BIOEM_HIDDEN hipError_t bioem_orient_sums_launch(hipStream_t st, const bioem_hip
                                                  const float4 *ownAngles, const int *ownOff, int ownIsQuat,
                                                  double *scratch, bioem_hip_orient_sums *out);
 
+// ---- occupancy of every orientation over the particles (bioem_hip_orientation_occupancy) ----
+// The same table reduced along the other axis: per orientation row the sums over the particles [p0, p0 + np) of
+//   w(o, p) = e^(orient_key(entry, prior_o) - m_p) / S0_p,
+// m_p, S0_p, omax_p the particle's (merged) orientation sums, handed in as m[np], rS0[np] = 1 / S0_p (0: the particle is
+// left out) and omax[np] (-1 when left out).  One wave per row, kOccRows rows after one another per wave so that a
+// lane reads a particle's normalisers once for them; lane j takes the particles j, j + 64, ... in order, two per trip
+// with their eight row loads issued together; the 64 lanes are folded by a fixed butterfly.  A row's bits depend on its entries of the range, its prior and the normalisers only.
+const int kOccRows = 4;  // rows a wave walks side by side
+const int kOccWaves = 4; // waves of a block
+// out[nO] for the rows of pang[nO][nMaps]; o0 = global index of row 0; prior: null or [nO] by row
+BIOEM_HIDDEN hipError_t bioem_orient_occ_launch(hipStream_t st, const bioem_hip_prob_angle *pang, int nO, int nMaps, int p0,
+                                                int np, int o0, const double *prior, const double *m, const double *rS0,
+                                                const int *omax, bioem_hip_orient_occ *out);
+
 #ifdef BIOEM_ORIENT_TU
 namespace
 {
 
-// the key of an entry: both passes evaluate this one expression, so the entry that gave m has l - m = 0 exactly
+// the key of an entry: both passes, and the occupancy pass after them, evaluate this one expression, so the entry that
+// gave m has l - m = 0 exactly
 __device__ inline double orient_key(const bioem_hip_prob_angle a, double prior) { return (log(a.forAngles) + a.ConstAngle) + prior; }
 
 // the ten products of a quaternion normalised in double; the prep kernel and the own-list lanes share the expression
@@ -216,6 +232,124 @@ __global__ void k_orient_fold(const void *__restrict__ part, int nChunks, int np
     out[p].omax = r.count ? (double) (o0 + r.idx) : -1.;
     out[p].count = (double) r.count;
     out[p].hasMoments = moments ? 1. : 0.;
+  }
+}
+
+// the butterfly of the occupancy fold: every lane ends with the value of the whole wave, the pairing is fixed
+template <class T>
+__device__ inline T occ_wave_sum(T v)
+{
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1)
+    v += __shfl_xor(v, s, 64);
+  return v;
+}
+
+// block of kOccWaves waves, wave v of block b: rows (b kOccWaves + v) kOccRows ... + kOccRows - 1
+__global__ __launch_bounds__(64 * kOccWaves) void k_orient_occ(const bioem_hip_prob_angle *__restrict__ pang, int nO, int nMaps,
+                                                               int p0, int np, int o0, const double *__restrict__ prior,
+                                                               const double *__restrict__ gm, const double *__restrict__ grS0,
+                                                               const int *__restrict__ gomax,
+                                                               bioem_hip_orient_occ *__restrict__ out)
+{
+  const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int r0 = (blockIdx.x * kOccWaves + wave) * kOccRows; // wave-uniform
+  if (r0 >= nO)
+    return;
+  const bioem_hip_prob_angle *row[kOccRows];
+  double pr[kOccRows], occ[kOccRows], occ2[kOccRows], wmax[kOccRows];
+  int pmax[kOccRows], cnt[kOccRows], hard[kOccRows], glob[kOccRows];
+#pragma unroll
+  for (int k = 0; k < kOccRows; k++)
+  {
+    const int r = min(r0 + k, nO - 1); // a row beyond the table re-reads the last one and is not written
+    row[k] = pang + (size_t) r * nMaps + p0;
+    pr[k] = prior ? prior[r] : 0.; // wave-uniform: a scalar load
+    glob[k] = o0 + r;
+    occ[k] = occ2[k] = 0.;
+    wmax[k] = -1.; // below every w: the first counted entry takes it, w = 0 included
+    pmax[k] = 0x7fffffff;
+    cnt[k] = hard[k] = 0;
+  }
+  // Two particles of the lane per trip, j and j + 64.  All eight row loads and the normalisers of both are issued before
+  // anything is tested: the body has no branch a load could sink into.  An entry that does not count (F <= 0, or its
+  // particle left out, or j + 64 beyond the range, which re-reads j) goes through the arithmetic with d = 0 and adds
+  // w = 0, count 0: adding +0 leaves a sum of non-negative terms bit for bit, and no 0 * inf is formed.
+  for (int j = lane; j < np; j += 128)
+  {
+    const bool has2 = j + 64 < np;
+    const int jj[2] = {j, has2 ? j + 64 : j};
+    bioem_hip_prob_angle a[2][kOccRows];
+    double m[2], rs[2];
+    int om[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+    {
+#pragma unroll
+      for (int k = 0; k < kOccRows; k++)
+      { // one 16-byte load per entry; the table is read once: non-temporal
+        typedef double entry2 __attribute__((ext_vector_type(2)));
+        const entry2 v = __builtin_nontemporal_load(reinterpret_cast<const entry2 *>(row[k] + jj[h]));
+        a[h][k].forAngles = v.x;
+        a[h][k].ConstAngle = v.y;
+      }
+      m[h] = gm[jj[h]];
+      rs[h] = grS0[jj[h]];
+      om[h] = gomax[jj[h]];
+    }
+    if (!has2)
+    {
+      rs[1] = 0.;
+      om[1] = -1;
+    }
+#pragma unroll
+    for (int h = 0; h < 2; h++) // in particle order
+#pragma unroll
+      for (int k = 0; k < kOccRows; k++)
+      {
+        const bool counts = (a[h][k].forAngles > 0.) & (rs[h] > 0.); // om = -1 where the particle is left out
+        bioem_hip_prob_angle e = a[h][k];
+        e.forAngles = counts ? e.forAngles : 1.;
+        const double d = counts ? orient_key(e, pr[k]) - m[h] : 0.;
+        const double w = counts ? exp(d) * rs[h] : 0.;
+        hard[k] += om[h] == glob[k];
+        occ[k] += w;
+        occ2[k] = fma(w, w, occ2[k]);
+        cnt[k] += counts;
+        const bool up = counts & (w > wmax[k]); // strictly: the lane's lowest particle keeps a tie
+        wmax[k] = up ? w : wmax[k];
+        pmax[k] = up ? p0 + jj[h] : pmax[k];
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < kOccRows; k++)
+  {
+    const double s0 = occ_wave_sum(occ[k]), s2 = occ_wave_sum(occ2[k]);
+    const int c = occ_wave_sum(cnt[k]), hd = occ_wave_sum(hard[k]);
+    double wm = wmax[k];
+    int pm = pmax[k];
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1)
+    {
+      const double ow = __shfl_xor(wm, s, 64);
+      const int op = __shfl_xor(pm, s, 64);
+      if (ow > wm || (ow == wm && op < pm)) // the lower particle index wins a tie
+      {
+        wm = ow;
+        pm = op;
+      }
+    }
+    if (lane == 0 && r0 + k < nO)
+    {
+      bioem_hip_orient_occ r;
+      r.occ = s0;
+      r.occ2 = s2;
+      r.wmax = c ? wm : 0.;
+      r.pmax = c ? (double) pm : -1.;
+      r.count = (double) c;
+      r.hard = (double) hd;
+      out[r0 + k] = r;
+    }
   }
 }
 

@@ -19,6 +19,8 @@ CANDIDATE_DTYPE = np.dtype([("forAngles", "<f8"), ("ConstAngle", "<f8"), ("logp"
 RING_SUMS_DTYPE = np.dtype([("cross", "<f8"), ("powParticle", "<f8"), ("powModel", "<f8")])
 ORIENT_SUMS_DTYPE = np.dtype([("m", "<f8"), ("omax", "<f8"), ("count", "<f8"), ("hasMoments", "<f8"), ("S0", "<f8"),
                               ("S1", "<f8"), ("S2", "<f8"), ("Q", "<f8", (10,))])
+ORIENT_OCC_DTYPE = np.dtype([("occ", "<f8"), ("occ2", "<f8"), ("wmax", "<f8"), ("pmax", "<f8"), ("count", "<f8"),
+                             ("hard", "<f8")])
 WINDOW_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4")])
 MIN_PROB = -999999.0
 
@@ -95,6 +97,9 @@ def load_library():
         L.bioem_hip_merge_orient_sums_host.argtypes = [ci, ci, C.POINTER(vp), vp]
         L.bioem_hip_debug_orient_sums.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp]
         L.bioem_hip_debug_orient_sums_own.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp]
+    if hasattr(L, "bioem_hip_orientation_occupancy"):
+        L.bioem_hip_orientation_occupancy.argtypes = [vp, vp, vp, ci, ci, vp]
+        L.bioem_hip_debug_orient_occupancy.argtypes = [vp, vp, ci, ci, vp, vp, ci, ci, ci, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -150,7 +155,7 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_ctf_table", "bioem_hip_ring_count", "bioem_hip_best_match_rings", "bioem_hip_debug_ring_sums",
            "bioem_hip_window_count", "bioem_hip_window_offsets", "bioem_hip_window_posterior", "bioem_hip_debug_window",
            "bioem_hip_orientation_sums", "bioem_hip_merge_orient_sums_host", "bioem_hip_debug_orient_sums",
-           "bioem_hip_debug_orient_sums_own"]
+           "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy"]
 
 
 def _p(a):
@@ -543,6 +548,52 @@ class Engine:
             raise e
         return out
 
+    def orientation_occupancy(self, sums, prior=None, p0=0, p1=None):
+        """the angle table reduced along the particles [p0, p1): ORIENT_OCC_DTYPE [orientations the handle owns] with
+        occ = sum_p w, occ2 = sum_p w^2, wmax, pmax (lowest particle index attaining it, -1 for an empty row), count and
+        hard (particles whose arg-max is this orientation), w(o, p) = e^(l - m_p) / S0_p the posterior of orientation o for
+        particle p (include/bioem_hip.h).  sums: ORIENT_SUMS_DTYPE [p1 - p0], the particles' orientation sums under the
+        same prior -- for shards the merged ones (merge_orient_sums).  prior: None, or nAngles log priors by global index.
+        Call after finish_run on a handle with WRITE_PROB_ANGLES; a shard returns its block, merge_orient_occupancy
+        concatenates them.  A refusal raises RuntimeError with .rc == 2."""
+        p1 = self.nMaps if p1 is None else int(p1)
+        sums = np.ascontiguousarray(sums, dtype=ORIENT_SUMS_DTYPE)
+        assert sums.ndim == 1
+        if 0 <= int(p0) < p1 <= self.nMaps:              # (a range the entry refuses reads no sums)
+            assert len(sums) == p1 - int(p0)
+        if prior is not None:
+            prior = np.ascontiguousarray(prior, dtype=np.float64)
+            assert prior.shape == (self.nAngles,)
+        o0, o1 = self.shard if self.shard is not None else (0, self.nAngles)
+        out = np.zeros(o1 - o0, dtype=ORIENT_OCC_DTYPE)
+        rc = self.L.bioem_hip_orientation_occupancy(self.h, _p(prior), _p(sums) if sums.size else None, int(p0), p1, _p(out))
+        if rc:
+            e = RuntimeError("orientation_occupancy: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+        return out
+
+    def debug_orient_occupancy(self, table, sums, prior=None, p0=0, p1=None, o0=0):
+        """test hook: the kernel of orientation_occupancy on a table handed in, PROB_ANGLE_DTYPE [nO, nMaps]; sums
+        ORIENT_SUMS_DTYPE [p1 - p0] for the particles [p0, p1); prior float64 [nO] by row or None; o0 the global index of
+        row 0.  Returns ORIENT_OCC_DTYPE [nO]; a refusal raises with .rc == 2."""
+        table = np.ascontiguousarray(table, dtype=PROB_ANGLE_DTYPE)
+        nO, nMaps = table.shape
+        p1 = nMaps if p1 is None else int(p1)
+        sums = np.ascontiguousarray(sums, dtype=ORIENT_SUMS_DTYPE)
+        assert sums.shape == (p1 - int(p0),)
+        if prior is not None:
+            prior = np.ascontiguousarray(prior, dtype=np.float64)
+            assert prior.shape == (nO,)
+        out = np.zeros(nO, dtype=ORIENT_OCC_DTYPE)
+        rc = self.L.bioem_hip_debug_orient_occupancy(self.h, _p(table), nO, nMaps, _p(prior), _p(sums), int(p0), p1, int(o0),
+                                                     _p(out))
+        if rc:
+            e = RuntimeError("debug_orient_occupancy: %s" % self.L.bioem_hip_last_error(self.h).decode())
+            e.rc = rc
+            raise e
+        return out
+
     def enable_ctf_table(self, on=True):
         """keep the posterior per (CTF set, particle) beside the particle entries, from the next start_run on; call it
         outside a run (inside one it raises, .rc == 2)"""
@@ -670,3 +721,12 @@ def merge_orient_sums(sums):
     if L.bioem_hip_merge_orient_sums_host(len(sums), sums[0].size, arr, _p(out) if out.size else None):
         raise RuntimeError("bioem_hip_merge_orient_sums_host failed")
     return out
+
+
+def merge_orient_occupancy(blocks):
+    """The shards' occupancy blocks (Engine.orientation_occupancy on every shard, with the merged sums handed in; shards
+    in ascending orientation-block order) concatenated: rows are independent, so this is the unsharded result bit for
+    bit.  No device."""
+    blocks = [np.ascontiguousarray(b, dtype=ORIENT_OCC_DTYPE) for b in blocks]
+    assert blocks and all(b.ndim == 1 for b in blocks)
+    return np.concatenate(blocks)

@@ -161,6 +161,40 @@ void jacobi4(const double a[4][4], double w[4], double v[4][4]); // eigenvalues 
 OrientStats orient_derive(const bioem_hip_orient_sums &s, const float *angles4, bool doquater);
 std::string write_orient_stats(const char *file, const bioem_hip_orient_sums *sums, int nMaps, const float *angles4,
                                const long long *angleOffsets, bool doquater, double numconst);
+// --OrientOccupancy (orientocc.cpp): the text file of the occupancy occ[nO] of bioem_hip_orientation_occupancy (the
+// shards' blocks concatenated).  After the HEADER:: NOTATION bar, one notation line and the bar again, per orientation
+//  OCC o A count occ fraction nEffParticles hard wmax pmax
+// (A: the orientation's 4 numbers with quaternions, else 3; count: particles compared with it; occ = sum over the
+// particles of its posterior; fraction = occ / nCounted, nCounted the particles with a posterior at all; nEffParticles =
+// occ^2 / occ2, 0 for an empty row; hard: particles whose arg-max it is; wmax and pmax: the largest posterior any
+// particle gives it and the lowest such particle, -1 for an empty row), then one line
+//  DATASET nCounted nEffViews maxFraction argmax
+// (nEffViews = exp of the entropy of the fractions) and, with --FitOrientPrior, one line per EM iteration
+//  FIT t logLikelihood nEffViews
+// (logLikelihood = sum over the counted particles of m + log S0 under the prior of iteration t, without the numerical
+// constant; nEffViews of that prior).  Floating values with 16 significant digits.  Returns the empty string, or the error.
+const double kOrientPriorFloor = -1.0e6; // the log prior of an orientation no particle supports: finite, e^it = 0, and
+                                         // twelve characters in the list file (-1.00000e+06)
+struct OccDataset
+{
+  long long nCounted;
+  double nEffViews, maxFraction;
+  int argmax;
+};
+struct OccFit
+{
+  double logLikelihood, nEffViews;
+};
+OccDataset occ_dataset(const bioem_hip_orient_occ *occ, int nO, long long nCounted);
+double log_prior_views(const double *logPrior, int nO); // exp of the entropy of e^logPrior
+// the EM update: logPrior[o] = log(occ_o / nCounted), kOrientPriorFloor where occ_o = 0
+void occ_next_prior(const bioem_hip_orient_occ *occ, int nO, long long nCounted, double *logPrior);
+std::string write_orient_occupancy(const char *file, const bioem_hip_orient_occ *occ, int nO, const float *angles4, bool doquater,
+                                   long long nCounted, const OccFit *fits, int nFits);
+// the orientation list in the --ReadOrientation format (count line, twelve-character columns, angles to eight decimals)
+// with the additive log prior as the last column, clamped to [kOrientPriorFloor, 0] and printed as %12.5e: what a run
+// with PRIOR_ANGLES --ReadOrientation reads
+std::string write_orient_prior(const char *file, const float *angles4, int nO, bool doquater, const double *logPrior);
 // MRC mode-2 stack nx = ny = N, nz = nMaps in the storage order the --ReadMRC reader expects, written batch by batch
 struct MrcStackWriter
 {
@@ -219,6 +253,8 @@ public:
   std::string bestFrcFile;   // --BestFRC: ring correlation of every particle against its best match (FILE, FILE_Round2)
   std::string bestWindowFile; // --BestWindow: posterior over the displacement window of every best match (FILE, FILE_Round2)
   std::string orientStatsFile; // --OrientStats: summaries of every particle's orientation posterior (WRITE_PROB_ANGLES)
+  std::string orientOccFile;   // --OrientOccupancy: occupancy of every orientation over the data set (WRITE_PROB_ANGLES)
+  int fitOrientPrior = 0;      // --FitOrientPrior N: N EM iterations of the orientation prior, FILE_prior
   std::string bestParamFile; // --PrintBestCalMap: the reference's one-record mode, no particles, writes BESTMAP
   BestParams best;
   int printBestCalMap();     // bioem::printModel (bioem.cpp:624-657, 1925-2085)
@@ -261,6 +297,11 @@ private:
   // --OrientStats: the shards' orientation sums (bioem_hip_orientation_sums) merged on the host, written by
   // write_orient_stats; numconst: the constant of ANG_PROB
   void writeOrientStats(const std::string &file, double numconst);
+  // --OrientOccupancy / --FitOrientPrior: every shard's sums merged on the host, every shard's occupancy block under the
+  // merged sums, written by write_orient_occupancy; nIter EM iterations of the prior, written by write_orient_prior
+  void writeOrientOccupancy(const std::string &file, int nIter);
+  // one pass under logPrior (null: none): the merged sums and the concatenated occupancy blocks
+  void orientOccupancyPass(const double *logPrior, std::vector<bioem_hip_orient_sums> &sums, std::vector<bioem_hip_orient_occ> &occ);
   // --ProbCTF: the tables of the handles merged on the host (shards in ascending order) and written
   void writeCtfProb(const std::string &file, const std::vector<bioem_hip_handle> &hs, const bioem_hip_param_device &pd,
                     const float *angles, size_t anglesPerMap, const long long *angleOffsets = nullptr,

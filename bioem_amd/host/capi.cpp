@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "bioem_host.h"
 
@@ -228,6 +229,59 @@ void bioem_host_jacobi4(const double *a, double *w, double *v)
   for (int i = 0; i < 4; i++)
     for (int j = 0; j < 4; j++)
       v[4 * i + j] = V[i][j];
+}
+
+// the --OrientOccupancy text of occ[nO] (write_orient_occupancy, bioem_host.h); fits = nFits pairs (logLikelihood,
+// nEffViews) or NULL; 0, or 1 with the text in err[cap]
+int bioem_host_write_orient_occupancy(const char *file, const bioem_hip_orient_occ *occ, int nO, const float *angles4, int doquater,
+                                      long long nCounted, const double *fits, int nFits, char *err, int cap)
+{
+  std::vector<bioem_host::OccFit> F;
+  for (int t = 0; fits && t < nFits; t++)
+    F.push_back({fits[2 * t], fits[2 * t + 1]});
+  const std::string e = bioem_host::write_orient_occupancy(file, occ, nO, angles4, doquater != 0, nCounted, F.data(), (int) F.size());
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return e.empty() ? 0 : 1;
+}
+
+// the FILE_prior of --FitOrientPrior (write_orient_prior, bioem_host.h); 0, or 1 with the text in err[cap]
+int bioem_host_write_orient_prior(const char *file, const float *angles4, int nO, int doquater, const double *logPrior, char *err,
+                                  int cap)
+{
+  const std::string e = bioem_host::write_orient_prior(file, angles4, nO, doquater != 0, logPrior);
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return e.empty() ? 0 : 1;
+}
+
+// the EM update of --FitOrientPrior: logPrior[nO] from occ[nO] (occ_next_prior); returns the floor written for occ = 0
+double bioem_host_occ_next_prior(const bioem_hip_orient_occ *occ, int nO, long long nCounted, double *logPrior)
+{
+  bioem_host::occ_next_prior(occ, nO, nCounted, logPrior);
+  return bioem_host::kOrientPriorFloor;
+}
+
+// readParameters + CalculateGridsParam as bioem_host_setup_from_files, returning what the reader keeps of the list:
+// angles4[cap][4] and, under PRIOR_ANGLES, prior[cap]; returns the number of orientations, *hasPrior set
+int bioem_host_read_orientation_list(const char *paramfile, const char *anglefile, float *angles4, float *prior, int cap,
+                                     int *hasPrior)
+{
+  bioem_host::InputParams P;
+  P.notuniformangles = (anglefile && anglefile[0]);
+  P.readParameters(paramfile);
+  P.calculateGridsParam(anglefile ? anglefile : "");
+  const int n = P.nTotGridAngles;
+  if (hasPrior)
+    *hasPrior = P.yespriorAngles ? 1 : 0;
+  for (int o = 0; o < n && o < cap; o++)
+  {
+    for (int i = 0; i < 4 && angles4; i++)
+      angles4[4 * (size_t) o + i] = P.angles[4 * (size_t) o + i];
+    if (prior && P.yespriorAngles)
+      prior[o] = P.angprior[(size_t) o];
+  }
+  return n;
 }
 
 // the MRC stack of --BestMaps: maps [nMaps][N][N] appended in batches of `batch` images

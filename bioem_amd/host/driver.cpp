@@ -75,6 +75,8 @@ int Driver::readOptions(int ac, char **av)
                                        {"BestFRC", required_argument, 0, 0},
                                        {"BestWindow", required_argument, 0, 0},
                                        {"OrientStats", required_argument, 0, 0},
+                                       {"OrientOccupancy", required_argument, 0, 0},
+                                       {"FitOrientPrior", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
                                        {"RefineSeeds", required_argument, 0, 0},
@@ -112,6 +114,10 @@ int Driver::readOptions(int ac, char **av)
     printf("                         (is DISPLACE_CENTER wide enough? with --RefineOrientations also arg_Round2)\n");
     printf("  --OrientStats arg      (Optional) Write per particle the summaries of its orientation posterior (entropy, effective\n");
     printf("                         number of orientations, mean orientation, spread; needs WRITE_PROB_ANGLES)\n");
+    printf("  --OrientOccupancy arg  (Optional) Write per orientation its occupancy over the data set (which views are in it, how\n");
+    printf("                         many particles stand behind each; needs WRITE_PROB_ANGLES)\n");
+    printf("  --FitOrientPrior arg   (Optional) With --OrientOccupancy: arg EM iterations of the orientation prior, written as\n");
+    printf("                         arg_prior of --OrientOccupancy in the --ReadOrientation format for PRIOR_ANGLES\n");
     printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
@@ -220,6 +226,17 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Writing the summaries of the orientation posteriors to: " << optarg << "\n";
       orientStatsFile = optarg;
     }
+    else if (name == "OrientOccupancy")
+    {
+      std::cout << "Writing the occupancy of the orientations to: " << optarg << "\n";
+      orientOccFile = optarg;
+    }
+    else if (name == "FitOrientPrior")
+    {
+      fitOrientPrior = atoi(optarg);
+      if (fitOrientPrior < 1)
+        fatal("--FitOrientPrior needs a positive number of iterations");
+    }
     else if (name == "PrintBestCalMap")
     {
       std::cout << "Reading best parameters from file: " << optarg << "\n";
@@ -259,8 +276,9 @@ int Driver::readOptions(int ac, char **av)
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
     if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty() || !bestWindowFile.empty() ||
-        !orientStatsFile.empty())
-      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow, --OrientStats and --RefineOrientations");
+        !orientStatsFile.empty() || !orientOccFile.empty())
+      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow, --OrientStats, --OrientOccupancy and "
+            "--RefineOrientations");
     const std::string err = read_best_parameters(bestParamFile.c_str(), best);
     if (!err.empty())
       fatal("%s", err.c_str());
@@ -297,6 +315,15 @@ int Driver::readOptions(int ac, char **av)
       fatal("--OrientStats is not valid with --RefineOrientations (which goes without WRITE_PROB_ANGLES)");
     if (!param.pd.writeAngles)
       fatal("--OrientStats needs WRITE_PROB_ANGLES in the parameter file: the summaries are reduced from the angle table");
+  }
+  if (fitOrientPrior && orientOccFile.empty())
+    fatal("--FitOrientPrior is only valid with --OrientOccupancy");
+  if (!orientOccFile.empty())
+  { // the occupancy is reduced from the angle table: it must exist, and round 2 goes without it
+    if (!refineFile.empty())
+      fatal("--OrientOccupancy is not valid with --RefineOrientations (which goes without WRITE_PROB_ANGLES)");
+    if (!param.pd.writeAngles)
+      fatal("--OrientOccupancy needs WRITE_PROB_ANGLES in the parameter file: the occupancy is reduced from the angle table");
   }
   if (!refineFile.empty())
   { // round 2 multiplies quaternions and evaluates lists of its own: no prior per orientation, no ANG_PROB (yet)
@@ -408,6 +435,8 @@ int Driver::configure(int ac, char **av)
   // (BIOEM_FORCE_RCCL=1: also with a single shard -- a one-rank communicator, to exercise this path on a one-GPU box)
   if (splitCTF && !orientStatsFile.empty())
     fatal("--OrientStats is not valid with more shards than orientations: an orientation's entry is spread over shards");
+  if (splitCTF && !orientOccFile.empty())
+    fatal("--OrientOccupancy is not valid with more shards than orientations: an orientation's entry is spread over shards");
   useRccl = (nShards > 1 || getenv("BIOEM_FORCE_RCCL")) && nDevUsed == nShards && !splitCTF && !getenv("BIOEM_HOST_MERGE");
   return 0;
 }
@@ -627,6 +656,87 @@ void Driver::writeOrientStats(const std::string &file, double numconst)
   std::cout << "Orientation posterior summaries of " << nMaps << " particles written to: " << file << "\n";
 }
 
+// one pass of --OrientOccupancy under logPrior: every shard's sums over the orientations it owns merged on the host in
+// shard order (as --OrientStats does), then every shard's occupancy block under the merged sums, in block order
+void Driver::orientOccupancyPass(const double *logPrior, std::vector<bioem_hip_orient_sums> &sums, std::vector<bioem_hip_orient_occ> &occ)
+{
+  const int nMaps = particles.ntot, nShards = (int) shards.size(), nO = param.nTotGridAngles;
+  std::vector<std::vector<bioem_hip_orient_sums>> part((size_t) nShards);
+  std::vector<const bioem_hip_orient_sums *> ptrs((size_t) nShards);
+  for (int g = 0; g < nShards; g++)
+  {
+    part[(size_t) g].resize((size_t) nMaps);
+    check(shards[g].h, bioem_hip_orientation_sums(shards[g].h, logPrior, 0, nMaps, 0, part[(size_t) g].data()), "orientation sums");
+    ptrs[(size_t) g] = part[(size_t) g].data();
+  }
+  sums.resize((size_t) nMaps);
+  if (bioem_hip_merge_orient_sums_host(nShards, nMaps, ptrs.data(), sums.data()))
+    fatal("merge failed");
+  occ.assign((size_t) nO, bioem_hip_orient_occ());
+  for (int g = 0; g < nShards; g++)
+  {
+    if (shards[g].o0 < 0 || shards[g].o1 > nO || shards[g].o0 >= shards[g].o1)
+      fatal("--OrientOccupancy: a shard without an orientation block");
+    check(shards[g].h, bioem_hip_orientation_occupancy(shards[g].h, logPrior, sums.data(), 0, nMaps, occ.data() + shards[g].o0),
+          "orientation occupancy");
+  }
+}
+
+// --OrientOccupancy: the pass under the run's prior (param.angprior under PRIOR_ANGLES) written as OCC / DATASET lines;
+// --FitOrientPrior N: N EM iterations pi <- occ / nCounted from the run's prior normalised (uniform without one), one FIT
+// line each, the last update written as FILE_prior
+void Driver::writeOrientOccupancy(const std::string &file, int nIter)
+{
+  const int nO = param.nTotGridAngles;
+  std::vector<double> prior;
+  if (param.yespriorAngles)
+    prior.assign(param.angprior.begin(), param.angprior.end());
+  std::vector<bioem_hip_orient_sums> sums;
+  std::vector<bioem_hip_orient_occ> occ, occIt;
+  orientOccupancyPass(prior.empty() ? nullptr : prior.data(), sums, occ);
+  auto counted = [](const std::vector<bioem_hip_orient_sums> &s) {
+    long long n = 0;
+    for (const bioem_hip_orient_sums &x : s)
+      n += x.count > 0. && x.S0 > 0.;
+    return n;
+  };
+  const long long nCounted = counted(sums);
+  std::vector<OccFit> fits;
+  if (nIter > 0)
+  {
+    std::vector<double> lp((size_t) nO, -log((double) nO));
+    if (!prior.empty())
+    { // the run's prior minus its log-sum-exp
+      double top = prior[0], s = 0.;
+      for (double v : prior)
+        top = std::max(top, v);
+      for (double v : prior)
+        s += exp(v - top);
+      for (int o = 0; o < nO; o++)
+        lp[(size_t) o] = std::max(kOrientPriorFloor, prior[(size_t) o] - (top + log(s)));
+    }
+    for (int t = 0; t < nIter; t++)
+    {
+      orientOccupancyPass(lp.data(), sums, occIt);
+      OccFit f = {0., log_prior_views(lp.data(), nO)};
+      for (const bioem_hip_orient_sums &x : sums)
+        if (x.count > 0. && x.S0 > 0.)
+          f.logLikelihood += x.m + log(x.S0);
+      fits.push_back(f);
+      occ_next_prior(occIt.data(), nO, counted(sums), lp.data());
+    }
+    const std::string perr = write_orient_prior((file + "_prior").c_str(), param.angles.data(), nO, param.doquater, lp.data());
+    if (!perr.empty())
+      fatal("--FitOrientPrior: %s", perr.c_str());
+    std::cout << "Orientation prior after " << nIter << " EM iterations written to: " << file << "_prior\n";
+  }
+  const std::string err = write_orient_occupancy(file.c_str(), occ.data(), nO, param.angles.data(), param.doquater, nCounted,
+                                                 fits.data(), (int) fits.size());
+  if (!err.empty())
+    fatal("--OrientOccupancy: %s", err.c_str());
+  std::cout << "Occupancy of " << nO << " orientations over " << nCounted << " particles written to: " << file << "\n";
+}
+
 // --PrintBestCalMap: the record of the BEST_* file rendered on the device and written as the reference's BESTMAP text.
 // The reference's file labels the UNSHIFTED map with shifted coordinates (bioem.cpp:2049-2053), so the device renders with
 // X = Y = 0 and the writer applies BEST_DX / BEST_DY to the labels.
@@ -821,6 +931,8 @@ int Driver::run()
   }
   if (!orientStatsFile.empty())
     writeOrientStats(orientStatsFile, numconst);
+  if (!orientOccFile.empty())
+    writeOrientOccupancy(orientOccFile, fitOrientPrior);
   if (!bestMapsFile.empty()) // from the merged records, on the first handle (every handle holds the global list)
     writeBestMaps(bestMapsFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!bestFrcFile.empty())

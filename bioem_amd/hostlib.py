@@ -231,3 +231,63 @@ def jacobi4(A):
     w, v = np.zeros(4), np.zeros((4, 4))
     L.bioem_host_jacobi4(a.ctypes.data, w.ctypes.data, v.ctypes.data)
     return w, v
+
+
+def write_orient_occupancy(path, occ, angles, doquater, nCounted, fits=None):
+    """the --OrientOccupancy text file of an occupancy [nO] (Engine.orientation_occupancy) against the orientation list
+    `angles` [nO, 4]; fits: None or [T, 2] of (logLikelihood, nEffViews), the FIT lines: the writer the CLI uses;
+    bioem_amd.orient_occupancy.parse reads it back"""
+    from .engine import ORIENT_OCC_DTYPE
+    L = load_host_library()
+    L.bioem_host_write_orient_occupancy.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong,
+                                                    C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+    t = np.ascontiguousarray(occ, dtype=ORIENT_OCC_DTYPE)
+    a = np.ascontiguousarray(angles, dtype=np.float32).reshape(-1, 4)
+    assert t.ndim == 1 and len(a) >= len(t)
+    F = np.ascontiguousarray(fits if fits is not None else np.zeros((0, 2)), dtype=np.float64).reshape(-1, 2)
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_orient_occupancy(path.encode(), t.ctypes.data, t.shape[0], a.ctypes.data, int(bool(doquater)),
+                                           int(nCounted), F.ctypes.data if len(F) else None, len(F), err, 512):
+        raise ValueError(err.value.decode())
+
+
+def write_orient_prior(path, angles, doquater, logPrior):
+    """the FILE_prior of --FitOrientPrior: the orientation list in the --ReadOrientation format with the additive log
+    prior as its last column (clamped to [orient_occupancy.L0, 0], %12.5e)"""
+    L = load_host_library()
+    L.bioem_host_write_orient_prior.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_int]
+    a = np.ascontiguousarray(angles, dtype=np.float32).reshape(-1, 4)
+    lp = np.ascontiguousarray(logPrior, dtype=np.float64)
+    assert lp.shape == (len(a),)
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_orient_prior(path.encode(), a.ctypes.data, len(a), int(bool(doquater)), lp.ctypes.data, err, 512):
+        raise ValueError(err.value.decode())
+
+
+def occ_next_prior(occ, nCounted):
+    """the EM update of --FitOrientPrior as the CLI forms it: (log prior [nO], the floor written where occ = 0)"""
+    from .engine import ORIENT_OCC_DTYPE
+    L = load_host_library()
+    L.bioem_host_occ_next_prior.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p]
+    L.bioem_host_occ_next_prior.restype = C.c_double
+    t = np.ascontiguousarray(occ, dtype=ORIENT_OCC_DTYPE)
+    lp = np.zeros(len(t))
+    floor = L.bioem_host_occ_next_prior(t.ctypes.data, len(t), int(nCounted), lp.ctypes.data)
+    return lp, floor
+
+
+def read_orientation_list(paramfile, anglefile, cap=1 << 20):
+    """the orientation list as the host parameter reader keeps it (readParameters + CalculateGridsParam): angles
+    float32 [n, 4] and, under PRIOR_ANGLES, the prior column float32 [n], else None"""
+    L = load_host_library()
+    L.bioem_host_read_orientation_list.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                   C.POINTER(C.c_int)]
+    L.bioem_host_read_orientation_list.restype = C.c_int
+    has = C.c_int(0)
+    af = anglefile.encode() if anglefile else None
+    n = L.bioem_host_read_orientation_list(paramfile.encode(), af, None, None, 0, C.byref(has))
+    assert n <= cap
+    ang = np.zeros((n, 4), dtype=np.float32)
+    pri = np.zeros(n, dtype=np.float32)
+    L.bioem_host_read_orientation_list(paramfile.encode(), af, ang.ctypes.data, pri.ctypes.data, n, C.byref(has))
+    return ang, (pri if has.value else None)

@@ -453,6 +453,42 @@ int bioem_hip_debug_orient_sums_own(bioem_hip_handle h, const bioem_hip_prob_ang
                                     const float *angles4, const long long *offsets, int isQuat,
                                     bioem_hip_orient_sums *out);
 
+/* ---- Occupancy of every orientation over the particles (WRITE_PROB_ANGLES; no reference counterpart) ----
+ * The same table reduced along the other axis: which views does the data set hold, and how many particles stand behind
+ * each?  With the key l = (log F + C) + prior_o of bioem_hip_orientation_sums and a particle's sums m_p, S0_p, omax_p,
+ * count_p (for shards: the MERGED sums, which is why the host hands them in), entry (o, p) with F > 0 of a particle with
+ * count_p > 0 and S0_p > 0 carries the posterior weight
+ *   w(o, p) = e^(l - m_p) / S0_p          (the device multiplies by 1 / S0_p, formed once per particle)
+ * -- the key is the expression the sums evaluated, so a particle's arg-max entry gives 1 / S0_p exactly, the pTop of
+ * --OrientStats.  Per orientation row, over the particles [iMapBegin, iMapEnd):
+ *   occ    sum of w                         (over all rows it adds up to the particles counted)
+ *   occ2   sum of w^2                       (occ^2 / occ2: the effective number of particles behind the view)
+ *   wmax   the largest w of the row         (0 for an empty row)
+ *   pmax   the lowest particle index attaining wmax; the index in the table, -1 for an empty row
+ *   count  particles of the range that count and have F > 0 in this row
+ *   hard   particles of the range that count and whose omax_p is this row's global index (integer compare)
+ * All fields are double.  One wave per row, lane j takes the particles iMapBegin + j, + 64, ... in order, the lanes are
+ * folded by a fixed butterfly; no atomics: the same bits on every run, and a row's bits depend on its entries of the
+ * range, its prior and the particles' normalisers only -- not on nMaps, iMapBegin (pmax moves with it) or the row's
+ * position in the table.  A finite prior as low as -1e6 gives w = 0, never NaN. */
+typedef struct { double occ, occ2, wmax, pmax, count, hard; } bioem_hip_orient_occ;   /* 48 bytes */
+/* Calling rules of bioem_hip_orientation_sums (after finish_run, every handle kind that holds an angle table; logPrior
+ * NULL or nAngles doubles by global orientation index).  sums = [iMapEnd - iMapBegin] on the host, entry i the sums of
+ * particle iMapBegin + i.  out = one entry per orientation the handle owns: a shard writes its [o0, o1) block in row
+ * order, and the shards' blocks concatenated in block order are the unsharded result.  Refused with 2, the reason in
+ * bioem_hip_last_error and the handle usable: no WRITE_PROB_ANGLES, a particle range that is empty, reversed or outside
+ * [0, nMaps), a null `sums` or `out`, a handle with per-particle orientation lists (its rows are list positions, not
+ * shared orientations).  Buffers are allocated at the first call (1 when the memory is not there).  Phase record: one of
+ * phase 2 over the call's kernel, iOrientBegin / iOrientEnd the particle range. */
+int bioem_hip_orientation_occupancy(bioem_hip_handle h, const double *logPrior, const bioem_hip_orient_sums *sums,
+                                    int iMapBegin, int iMapEnd, bioem_hip_orient_occ *out /* [orientations owned] */);
+/* test hook: the same kernel on a table handed in, table = [nO][nMaps] entries on the host; logPrior NULL or nO doubles
+ * by row; sums = [p1 - p0] for the particles [p0, p1); o0 = the global index of row 0 (what omax is compared with);
+ * out = [nO]. */
+int bioem_hip_debug_orient_occupancy(bioem_hip_handle h, const bioem_hip_prob_angle *table, int nO, int nMaps,
+                                     const double *logPrior, const bioem_hip_orient_sums *sums, int p0, int p1, int o0,
+                                     bioem_hip_orient_occ *out);
+
 #ifdef __cplusplus
 }
 #endif
