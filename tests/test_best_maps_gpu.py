@@ -472,10 +472,10 @@ def test_cli_print_best_cal_map(tmp_path):
     assert clean_text.count(" \n") == N
     # noise
     (d / "noisy.txt").write_text(text + "WITHNOISE 0.5\n")
-    t0 = int(time.time())
     run_cli(["--Modelfile", "model.txt", "--PrintBestCalMap", "noisy.txt"], d)
     first = open(d / "BESTMAP").read()
-    while int(time.time()) == t0:    # (the generator is seeded with the second, like the reference's; a run takes longer)
+    t0 = int(time.time())            # (taken AFTER the run: a run that crosses into the next second was seeded with either)
+    while int(time.time()) == t0:    # (the generator is seeded with the second, like the reference's)
         time.sleep(0.05)
     run_cli(["--Modelfile", "model.txt", "--PrintBestCalMap", "noisy.txt"], d)
     second = open(d / "BESTMAP").read()
