@@ -51,6 +51,8 @@
 //                          every particle's best-match record (bioem.cpp:1925-2085), the full c2r by exact DFT in double
 //   ring_kernels.hpp     k_ring_sums, k_ring_fold  bioem_hip_best_match_rings: per Fourier ring the sums of particle x best
 //                          match, particle power and best-match power (kernels_rings.hip; declarations only here)
+//   view_kernels.hpp     k_view_accumulate, k_view_tau, k_view_wiener  bioem_hip_view_sums / _view_averages: the aligned,
+//                          CTF-weighted average of the particles of a view (kernels_views.hip; declarations only here)
 //   window_kernels.hpp   k_window_prep, k_window_cols, k_window_cells  bioem_hip_window_posterior: the log posterior of every
 //                          cell of the displacement window of a (particle, orientation, CTF) request (kernels_window.hip;
 //                          declarations only here)
@@ -124,6 +126,7 @@ struct HipErr
 #include "window_tiles.hpp"
 #include "render_kernels.hpp"
 #include "ring_kernels.hpp"
+#include "view_kernels.hpp"
 #include "window_kernels.hpp"
 #include "orient_kernels.hpp"
 
@@ -219,6 +222,14 @@ struct bioem_hip_ctx
   float2 *dRingRef = nullptr;
   double *dRingScratch = nullptr;
   bioem_hip_ring_sums *dRingOut = nullptr;
+  // bioem_hip_view_sums / _view_averages / _debug_view_sums: the accumulators of a chunk of groups, their Wiener constants,
+  // the members and group offsets of a batch, a CTF buffer of 1 + 0i and the rendered maps (allocated at the first call)
+  double2 *dViewNum = nullptr;
+  double *dViewDen = nullptr, *dViewTau = nullptr;
+  BioemViewMember *dViewMem = nullptr;
+  int *dViewOff = nullptr;
+  float2 *dViewUnit = nullptr;
+  float *dViewMaps = nullptr;
   // bioem_hip_window_posterior / bioem_hip_debug_window: a batch's records, gathered orientations, particle and conv
   // spectra in reference layout, Parseval terms, parameters, particle sums handed in, the scratch T of the window pass,
   // the window's shifts in ascending order and the results (allocated at the first call)
@@ -2836,6 +2847,332 @@ int bioem_hip_debug_ring_sums(bioem_hip_handle h, const float *specR, const floa
       return 1;
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
+  return 0;
+}
+
+// ---- aligned averages of the particles of a view (view_kernels.hpp) ----
+namespace
+{
+// the buffers of the view entries (maps: the chain's renders too); a failed allocation (return 1) leaves the handle as it was
+int view_staging(bioem_hip_ctx *h, bool maps)
+{
+  const size_t OB = (size_t) h->OB, M = (size_t) h->M;
+  if (!h->dViewNum)
+  {
+    double2 *num = nullptr;
+    double *den = nullptr, *tau = nullptr;
+    BioemViewMember *mem = nullptr;
+    int *off = nullptr;
+    float2 *unit = nullptr;
+    const std::vector<float2> ones(M, make_float2(1.f, 0.f));
+    if (dev_alloc(h, num, OB * M) || dev_alloc(h, den, OB * M) || dev_alloc(h, tau, OB) || dev_alloc(h, mem, OB) ||
+        dev_alloc(h, off, OB + 1) || dev_alloc(h, unit, M) ||
+        hipMemcpy(unit, ones.data(), sizeof(float2) * M, hipMemcpyHostToDevice) != hipSuccess)
+    {
+      dev_release(h, num);
+      dev_release(h, den);
+      dev_release(h, tau);
+      dev_release(h, mem);
+      dev_release(h, off);
+      dev_release(h, unit);
+      (void) hipGetLastError();
+      return 1;
+    }
+    h->dViewNum = num;
+    h->dViewDen = den;
+    h->dViewTau = tau;
+    h->dViewMem = mem;
+    h->dViewOff = off;
+    h->dViewUnit = unit;
+  }
+  if (maps && !h->dViewMaps)
+  {
+    float *out = nullptr;
+    if (dev_alloc(h, out, OB * (size_t) h->N * h->N))
+    {
+      (void) hipGetLastError();
+      return 1;
+    }
+    h->dViewMaps = out;
+  }
+  return 0;
+}
+
+// The arguments every view entry checks, and the members the kernel reads: mem[p] for every particle with a group (slot
+// unset).  Returns 0, or 2 with the handle's message set.
+int view_members(bioem_hip_ctx *h, const char *what, const bioem_hip_prob_map *records, const double *weights,
+                 const int *groupOf, int nP, int nGroups, int g0, int g1, std::vector<BioemViewMember> &mem)
+{
+  char buf[256];
+  auto refuse = [&](const char *why) {
+    h->err = std::string(what) + ": " + why;
+    return 2;
+  };
+  if (nGroups < 1 || g0 < 0 || g1 > nGroups || g0 >= g1)
+    return refuse("group range empty, reversed or outside [0, nGroups)");
+  if (!h->ctfUp)
+    return refuse("CTF kernels not uploaded");
+  const int N = h->N;
+  mem.assign((size_t) nP, BioemViewMember{});
+  for (int p = 0; p < nP; p++)
+  {
+    const int g = groupOf[p];
+    if (g == -1)
+      continue;
+    const bioem_hip_prob_map &r = records[p];
+    const double w = weights ? weights[p] : 1.;
+    const char *why = nullptr;
+    if (g < -1 || g >= nGroups)
+      why = "group outside [0, nGroups) and not -1";
+    else if (!(w >= 0.) || !std::isfinite(w))
+      why = "weight negative or not finite";
+    else if (r.max_prob_conv < 0 || r.max_prob_conv >= h->nCTF)
+      why = "max_prob_conv outside [0, nCTF)";
+    else if (r.max_prob_cent_x <= -N || r.max_prob_cent_x >= N || r.max_prob_cent_y <= -N || r.max_prob_cent_y >= N)
+      why = "displacement of N pixels or more";
+    if (why)
+    {
+      snprintf(buf, sizeof(buf), "particle %d: %s (group %d of %d, weight %g, conv %d, cent %d %d)", p, why, g, nGroups, w,
+               r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y);
+      return refuse(buf);
+    }
+    BioemViewMember &m = mem[(size_t) p];
+    m.conv = r.max_prob_conv;
+    m.xm = (r.max_prob_cent_x % N + N) % N;
+    m.ym = (r.max_prob_cent_y % N + N) % N;
+    m.s = w * (double) r.max_prob_norm;
+    m.s2 = m.s * (double) r.max_prob_norm;
+    m.dc = (double) r.max_prob_mu * (double) N * (double) N;
+  }
+  return 0;
+}
+
+// num / den of the groups [ga, gb) (at most maxOrientations of them) into dViewNum / dViewDen: zeroed, then one launch per
+// batch of maxOrientations particles that holds a member, in particle order on the handle's stream.  specHost: the
+// spectra of the caller (reference layout) instead of the handle's particles.
+int view_accumulate_chunk(bioem_hip_ctx *h, const float *specHost, const std::vector<BioemViewMember> &mem, const int *groupOf,
+                          int nP, int ga, int gb)
+{
+  const int nG = gb - ga, OB = h->OB, N = h->N;
+  const size_t M = (size_t) h->M;
+  HIP_CHECK(h, hipMemsetAsync(h->dViewNum, 0, sizeof(double2) * M * nG, h->stream));
+  HIP_CHECK(h, hipMemsetAsync(h->dViewDen, 0, sizeof(double) * M * nG, h->stream));
+  std::vector<int> off((size_t) nG + 1), cur((size_t) nG);
+  std::vector<BioemViewMember> bm;
+  for (int b0 = 0; b0 < nP; b0 += OB)
+  {
+    const int nb = std::min(OB, nP - b0);
+    std::fill(off.begin(), off.end(), 0);
+    for (int p = b0; p < b0 + nb; p++)
+      if (groupOf[p] >= ga && groupOf[p] < gb)
+        off[(size_t) (groupOf[p] - ga) + 1]++;
+    for (int g = 0; g < nG; g++)
+    {
+      cur[(size_t) g] = off[(size_t) g];
+      off[(size_t) g + 1] += off[(size_t) g];
+    }
+    if (off[(size_t) nG] == 0)
+      continue;
+    bm.resize((size_t) off[(size_t) nG]);
+    for (int p = b0; p < b0 + nb; p++) // ascending within every group
+      if (groupOf[p] >= ga && groupOf[p] < gb)
+      {
+        BioemViewMember m = mem[(size_t) p];
+        m.slot = p - b0;
+        bm[(size_t) cur[(size_t) (groupOf[p] - ga)]++] = m;
+      }
+    HIP_CHECK(h, hipMemcpyAsync(h->dViewMem, bm.data(), sizeof(BioemViewMember) * bm.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dViewOff, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, h->stream));
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, b0, b0 + nb, 0, 0))
+      return 1;
+    if (specHost)
+      HIP_CHECK(h, hipMemcpyAsync(h->dRingRef, specHost + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice,
+                                  h->stream));
+    else
+    {
+      hipLaunchKernelGGL(k_unreorder, dim3(1024), dim3(256), 0, h->stream, h->dRef + h->Mc * (size_t) b0, h->dRingRef, nb, N,
+                         h->H, h->plan.halfR, h->plan.N1, h->Hp);
+      HIP_CHECK(h, hipGetLastError());
+    }
+    HIP_CHECK(h, bioem_view_accumulate_launch(h->stream, h->dRingRef, h->dCTF, h->dViewMem, h->dViewOff, nG, N, h->dTwD,
+                                              h->dViewNum, h->dViewDen));
+    if (phase_end(h, h->stream))
+      return 1;
+    HIP_CHECK(h, hipStreamSynchronize(h->stream)); // bm and off are rewritten for the next batch
+  }
+  return 0;
+}
+
+// the sums of the groups [g0, g1) to the host, chunk by chunk; stats on the host in particle order
+int view_sums_run(bioem_hip_ctx *h, const float *specHost, const std::vector<BioemViewMember> &mem, const double *weights,
+                  const int *groupOf, int nP, int g0, int g1, double *num_out, double *den_out, double *stats_out)
+{
+  if (ring_staging(h) || view_staging(h, false))
+    return 1;
+  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
+  const size_t M = (size_t) h->M;
+  for (int ga = g0; ga < g1; ga += h->OB)
+  {
+    const int gb = std::min(g1, ga + h->OB);
+    if (view_accumulate_chunk(h, specHost, mem, groupOf, nP, ga, gb))
+      return 1;
+    HIP_CHECK(h, hipMemcpyAsync(num_out + 2 * M * (size_t) (ga - g0), h->dViewNum, sizeof(double2) * M * (gb - ga),
+                                hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(den_out + M * (size_t) (ga - g0), h->dViewDen, sizeof(double) * M * (gb - ga),
+                                hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  drain_phases(h);
+  for (int g = g0; g < g1; g++)
+    stats_out[2 * (size_t) (g - g0)] = stats_out[2 * (size_t) (g - g0) + 1] = 0.;
+  for (int p = 0; p < nP; p++)
+    if (groupOf[p] >= g0 && groupOf[p] < g1)
+    {
+      stats_out[2 * (size_t) (groupOf[p] - g0)] += 1.;
+      stats_out[2 * (size_t) (groupOf[p] - g0) + 1] += weights ? weights[p] : 1.;
+    }
+  return 0;
+}
+} // namespace
+
+int bioem_hip_view_sums(bioem_hip_handle h, const bioem_hip_prob_map *records, const double *weights, const int *groupOf,
+                        int nGroups, int g0, int g1, double *num_out, double *den_out, double *stats_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (!records || !groupOf || !num_out || !den_out || !stats_out)
+  {
+    h->err = "view_sums: null argument";
+    return 2;
+  }
+  std::vector<BioemViewMember> mem;
+  if (const int rc = view_members(h, "view_sums", records, weights, groupOf, h->nMaps, nGroups, g0, g1, mem))
+    return rc;
+  if (!h->refUp)
+  {
+    h->err = "view_sums: particles not uploaded";
+    return 2;
+  }
+  return view_sums_run(h, nullptr, mem, weights, groupOf, h->nMaps, g0, g1, num_out, den_out, stats_out);
+}
+
+int bioem_hip_debug_view_sums(bioem_hip_handle h, const float *specR, const bioem_hip_prob_map *records, const double *weights,
+                              const int *groupOf, int n, int nGroups, double *num_out, double *den_out, double *stats_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (!specR || !records || !groupOf || !num_out || !den_out || !stats_out || n < 1)
+  {
+    h->err = "debug_view_sums: null argument or no images";
+    return 2;
+  }
+  std::vector<BioemViewMember> mem;
+  if (const int rc = view_members(h, "debug_view_sums", records, weights, groupOf, n, nGroups, 0, nGroups, mem))
+    return rc;
+  return view_sums_run(h, specR, mem, weights, groupOf, n, 0, nGroups, num_out, den_out, stats_out);
+}
+
+int bioem_hip_view_averages(bioem_hip_handle h, const bioem_hip_prob_map *records, const double *weights, const int *groupOf,
+                            const int *groupOrient, int nGroups, double wiener, int g0, int g1, bioem_hip_ring_sums *rings_out,
+                            float *avg_maps_out, float *proj_maps_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[160];
+  auto refuse = [&](const char *why) {
+    h->err = std::string("view_averages: ") + why;
+    return 2;
+  };
+  if (!records || !groupOf || !groupOrient || !rings_out)
+    return refuse("null argument");
+  if (!(wiener >= 0.) || !std::isfinite(wiener))
+    return refuse("wiener negative or not finite");
+  std::vector<BioemViewMember> mem;
+  if (const int rc = view_members(h, "view_averages", records, weights, groupOf, h->nMaps, nGroups, g0, g1, mem))
+    return rc;
+  if (!h->dPts || h->nPts < 1)
+    return refuse("model not uploaded");
+  if (h->nAnglesUp < 1)
+    return refuse("orientations not uploaded");
+  if (!h->refUp)
+    return refuse("particles not uploaded");
+  for (int g = g0; g < g1; g++)
+    if (groupOrient[g] < -1 || groupOrient[g] >= h->nAnglesUp)
+    {
+      snprintf(buf, sizeof(buf), "group %d: orientation %d outside the list of %d and not -1", g, groupOrient[g], h->nAnglesUp);
+      return refuse(buf);
+    }
+  const bool maps = avg_maps_out || proj_maps_out;
+  if (ring_staging(h) || view_staging(h, maps))
+    return 1;
+  const int N = h->N, H = h->H, OB = h->OB;
+  const size_t M = (size_t) h->M, NN = (size_t) N * N, nRings = (size_t) bioem_ring_count(N);
+  const size_t lds = sizeof(double2) * 2 * (size_t) N;
+  int A, B;
+  dft_split(N, A, B);
+  if (maps)
+  {
+    HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_cols), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+    HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+  }
+  if (compat_flush(h))
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  const OrientList src = shared_list(h);
+  const OrientList L = {h->dRingAngles, src.isQuat, src.quatNormDev};
+  std::vector<RenderRecord> recs;
+  for (int ga = g0; ga < g1; ga += OB)
+  {
+    const int gb = std::min(g1, ga + OB), nG = gb - ga;
+    if (view_accumulate_chunk(h, nullptr, mem, groupOf, h->nMaps, ga, gb))
+      return 1;
+    // P^ of the chunk where the ring pass and the render read the particle spectra; P_o of the chunk in buffer set 0.
+    // The unit record and the kernel 1 + 0i make M = P_o in the ring pass and leave the renders the plain c2r / N^2.
+    HIP_CHECK(h, bioem_view_wiener_launch(h->stream, h->dViewNum, h->dViewDen, nG, N, wiener, h->dViewTau, h->dRingRef));
+    recs.assign((size_t) nG, RenderRecord{0, 0, 0, 0, 1.f, 0.f});
+    for (int g = ga; g < gb; g++)
+      recs[(size_t) (g - ga)].src = std::max(0, groupOrient[g]);
+    HIP_CHECK(h, hipMemcpyAsync(h->dRingRec, recs.data(), sizeof(RenderRecord) * nG, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_render_gather, dim3((nG + 255) / 256), dim3(256), 0, h->stream, src.d, h->dRingRec, nG, h->dRingAngles);
+    HIP_CHECK(h, hipGetLastError());
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, ga, gb, 0, 0) || project_batch(h, s0, h->stream, L, 0, nG) ||
+        phase_end(h, h->stream))
+      return 1;
+    bioem_hip_ring_sums *ro = rings_out + nRings * (size_t) (ga - g0);
+    HIP_CHECK(h, bioem_ring_sums_launch(h->stream, h->dRingRef, s0.specRef, h->dViewUnit,
+                                        reinterpret_cast<const BioemRingRecord *>(h->dRingRec), nG, N, h->dTwD, h->dRingScratch,
+                                        h->dRingOut));
+    HIP_CHECK(h, hipMemcpyAsync(ro, h->dRingOut, sizeof(bioem_hip_ring_sums) * nRings * nG, hipMemcpyDeviceToHost, h->stream));
+    for (int which = 0; which < 2; which++)
+    {
+      float *dst = which ? proj_maps_out : avg_maps_out;
+      if (!dst)
+        continue;
+      hipLaunchKernelGGL(k_render_cols, dim3(H, nG), dim3(256), lds, h->stream, which ? s0.specRef : h->dRingRef, h->dViewUnit,
+                         h->dRingRec, N, H, A, B, h->dTwD, s0.rowSpec);
+      hipLaunchKernelGGL(k_render_rows, dim3(N, nG), dim3(256), lds, h->stream, s0.rowSpec, h->dRingRec, N, H, A, B, h->dTwD,
+                         h->dViewMaps);
+      HIP_CHECK(h, hipGetLastError());
+      HIP_CHECK(h, hipMemcpyAsync(dst + NN * (size_t) (ga - g0), h->dViewMaps, sizeof(float) * NN * nG, hipMemcpyDeviceToHost,
+                                  h->stream));
+    }
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    for (int g = ga; g < gb; g++)
+      if (groupOrient[g] < 0)
+      { // no projection to compare with
+        memset(ro + nRings * (size_t) (g - ga), 0, sizeof(bioem_hip_ring_sums) * nRings);
+        if (proj_maps_out)
+          memset(proj_maps_out + NN * (size_t) (g - g0), 0, sizeof(float) * NN);
+      }
+  }
+  drain_phases(h);
   return 0;
 }
 

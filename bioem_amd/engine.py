@@ -100,6 +100,10 @@ def load_library():
     if hasattr(L, "bioem_hip_orientation_occupancy"):
         L.bioem_hip_orientation_occupancy.argtypes = [vp, vp, vp, ci, ci, vp]
         L.bioem_hip_debug_orient_occupancy.argtypes = [vp, vp, ci, ci, vp, vp, ci, ci, ci, vp]
+    if hasattr(L, "bioem_hip_view_sums"):
+        L.bioem_hip_view_sums.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]
+        L.bioem_hip_view_averages.argtypes = [vp, vp, vp, vp, vp, ci, C.c_double, ci, ci, vp, vp, vp]
+        L.bioem_hip_debug_view_sums.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -155,7 +159,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_ctf_table", "bioem_hip_ring_count", "bioem_hip_best_match_rings", "bioem_hip_debug_ring_sums",
            "bioem_hip_window_count", "bioem_hip_window_offsets", "bioem_hip_window_posterior", "bioem_hip_debug_window",
            "bioem_hip_orientation_sums", "bioem_hip_merge_orient_sums_host", "bioem_hip_debug_orient_sums",
-           "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy"]
+           "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy",
+           "bioem_hip_view_sums", "bioem_hip_view_averages", "bioem_hip_debug_view_sums"]
 
 
 def _p(a):
@@ -434,6 +439,79 @@ class Engine:
             e.rc = rc
             raise e
         return out
+
+    def _view_args(self, pmap, group_of, weights, n):
+        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
+        group_of = np.ascontiguousarray(group_of, dtype=np.int32)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+            assert weights.shape == (n,)
+        assert pmap.shape == (n,) and group_of.shape == (n,)
+        return pmap, group_of, weights
+
+    def _view_raise(self, what, rc):
+        e = RuntimeError("%s: %s" % (what, self.L.bioem_hip_last_error(self.h).decode()))
+        e.rc = rc
+        raise e
+
+    def view_sums(self, pmap, group_of, weights=None, g0=0, g1=None, n_groups=None):
+        """the normal equations of the aligned average of every group in [g0, g1) (include/bioem_hip.h): returns
+        (num complex128 [g1 - g0, N, H], den float64 [g1 - g0, N, H], stats float64 [g1 - g0, 2] = count, sumw).
+        pmap: PROB_MAP_DTYPE [nMaps] (conv, cent_x, cent_y, norm, mu are read); group_of: int [nMaps], -1 = left out;
+        weights: float64 [nMaps] >= 0 or None (1); n_groups: max(group_of) + 1 unless given.  Needs the particles and the
+        CTF kernels.  A refusal raises RuntimeError with .rc == 2."""
+        pmap, group_of, weights = self._view_args(pmap, group_of, weights, self.nMaps)
+        nG = int(group_of.max()) + 1 if n_groups is None else int(n_groups)
+        g1 = nG if g1 is None else int(g1)
+        n = max(0, g1 - int(g0))
+        num = np.zeros((n, self.N, self.H), dtype=np.complex128)
+        den = np.zeros((n, self.N, self.H), dtype=np.float64)
+        stats = np.zeros((n, 2), dtype=np.float64)
+        rc = self.L.bioem_hip_view_sums(self.h, _p(pmap), _p(weights), _p(group_of), nG, int(g0), g1, _p(num), _p(den),
+                                        _p(stats))
+        if rc:
+            self._view_raise("view_sums", rc)
+        return num, den, stats
+
+    def view_averages(self, pmap, group_of, group_orient, weights=None, wiener=0.1, g0=0, g1=None, maps=True):
+        """the aligned average of every group in [g0, g1) against the projection of its orientation: returns
+        (rings RING_SUMS_DTYPE [g1 - g0, ring_count(N)], avg float32 [g1 - g0, N, N], proj likewise); maps=False: rings only
+        (avg = proj = None).  group_orient: int [nGroups] into the shared orientation list, -1 = no projection.  P^ = num /
+        (den + wiener * mean den); rings: powParticle = power of P^, powModel = power of the projection spectrum."""
+        pmap, group_of, weights = self._view_args(pmap, group_of, weights, self.nMaps)
+        group_orient = np.ascontiguousarray(group_orient, dtype=np.int32)
+        nG = len(group_orient)
+        g1 = nG if g1 is None else int(g1)
+        n = max(0, g1 - int(g0))
+        rings = np.zeros((n, ring_count(self.N)), dtype=RING_SUMS_DTYPE)
+        avg = np.zeros((n, self.N, self.N), dtype=np.float32) if maps else None
+        proj = np.zeros((n, self.N, self.N), dtype=np.float32) if maps else None
+        rc = self.L.bioem_hip_view_averages(self.h, _p(pmap), _p(weights), _p(group_of), _p(group_orient), nG, float(wiener),
+                                            int(g0), g1, _p(rings), _p(avg), _p(proj))
+        if rc:
+            self._view_raise("view_averages", rc)
+        return rings, avg, proj
+
+    def debug_view_sums(self, specR, pmap, group_of, weights=None, n_groups=None):
+        """test hook: the accumulation kernel of view_sums on n spectra handed in, float32 [n, N, H, 2] or complex64
+        [n, N, H] in reference layout; pmap, group_of, weights run over the n spectra.  Needs the CTF kernels only.
+        Returns (num, den, stats) for all groups as view_sums does."""
+        specR = np.ascontiguousarray(specR)
+        if specR.dtype.kind == "c":
+            specR = np.ascontiguousarray(specR.astype(np.complex64)).view(np.float32).reshape(specR.shape + (2,))
+        specR = np.ascontiguousarray(specR, dtype=np.float32)
+        n = len(specR)
+        assert specR.shape == (n, self.N, self.H, 2)
+        pmap, group_of, weights = self._view_args(pmap, group_of, weights, n)
+        nG = int(group_of.max()) + 1 if n_groups is None else int(n_groups)
+        num = np.zeros((max(nG, 0), self.N, self.H), dtype=np.complex128)
+        den = np.zeros((max(nG, 0), self.N, self.H), dtype=np.float64)
+        stats = np.zeros((max(nG, 0), 2), dtype=np.float64)
+        rc = self.L.bioem_hip_debug_view_sums(self.h, _p(specR), _p(pmap), _p(weights), _p(group_of), n, nG, _p(num),
+                                              _p(den), _p(stats))
+        if rc:
+            self._view_raise("debug_view_sums", rc)
+        return num, den, stats
 
     def window_shifts(self):
         """the cell coordinates of this handle's window tables (window_offsets of its parameters)"""

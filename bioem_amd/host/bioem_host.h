@@ -195,6 +195,24 @@ std::string write_orient_occupancy(const char *file, const bioem_hip_orient_occ 
 // with the additive log prior as the last column, clamped to [kOrientPriorFloor, 0] and printed as %12.5e: what a run
 // with PRIOR_ANGLES --ReadOrientation reads
 std::string write_orient_prior(const char *file, const float *angles4, int nO, bool doquater, const double *logPrior);
+// --ViewAverages (viewavg.cpp).  view_groups_by_orientation: the particles grouped by the arg-max orientation of their
+// records (weight 1): groupOrient = the orientations with at least max(minCount, 1) particles, ascending; groupOf[p] = the
+// view of particle p, -1 where its orientation has too few particles or no run compared it.  Returns the number of views.
+// write_view_averages: the text file of the ring sums rings[nViews][nRings] of bioem_hip_view_averages.  After the HEADER::
+// NOTATION bar, one notation line and the bar again, per view
+//  VIEW v o A count CCC res05 res0143
+// (o: the orientation and A its 4 numbers with quaternions, else 3; count: its particles; CCC = cross / sqrt(powAverage
+// powProjection) over the sums of rings s >= 1; res05 / res0143: the resolution of the first ring s >= 1 with FRC < 0.5 /
+// < 0.143, -1 when none) followed by one line per ring s >= 0
+//  RING v s resolution weight FRC cross powAverage powProjection
+// (resolution = N pixelSize / s in Angstrom, 0 for ring 0; weight = coefficients of the full spectrum in the ring; FRC =
+// cross / sqrt(powAverage powProjection), 0 where the product is 0).  Floating values with 16 significant digits.
+// Returns the empty string, or the error.
+int view_groups_by_orientation(const bioem_hip_prob_map *pmap, int nMaps, int nOrient, int minCount, std::vector<int> &groupOf,
+                               std::vector<int> &groupOrient);
+std::string write_view_averages(const char *file, const bioem_hip_ring_sums *rings, int nViews, const int *groupOrient,
+                                const int *counts, const float *angles4, bool doquater, int N, float pixelSize, int minCount,
+                                double wiener);
 // MRC mode-2 stack nx = ny = N, nz = nMaps in the storage order the --ReadMRC reader expects, written batch by batch
 struct MrcStackWriter
 {
@@ -255,6 +273,12 @@ public:
   std::string orientStatsFile; // --OrientStats: summaries of every particle's orientation posterior (WRITE_PROB_ANGLES)
   std::string orientOccFile;   // --OrientOccupancy: occupancy of every orientation over the data set (WRITE_PROB_ANGLES)
   int fitOrientPrior = 0;      // --FitOrientPrior N: N EM iterations of the orientation prior, FILE_prior
+  // --ViewAverages: per view the aligned average of its particles against the projection (FILE, FILE_avg.mrc,
+  // FILE_proj.mrc); --ViewMinParticles n: views with fewer particles are left out; --ViewWiener t: tau = t * mean den.
+  // Both defaults are conventional values, not tuned ones
+  std::string viewAvgFile;
+  int viewMinParticles = 2;
+  double viewWiener = 0.1;
   std::string bestParamFile; // --PrintBestCalMap: the reference's one-record mode, no particles, writes BESTMAP
   BestParams best;
   int printBestCalMap();     // bioem::printModel (bioem.cpp:624-657, 1925-2085)
@@ -290,6 +314,9 @@ private:
   void writeBestMaps(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
   // --BestFRC: the records' ring sums from handle h (bioem_hip_best_match_rings), written by write_best_frc
   void writeBestFrc(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
+  // --ViewAverages: the records grouped by orientation, the chain on handle h (bioem_hip_view_averages) in chunks of
+  // views, written by write_view_averages and two MRC stacks
+  void writeViewAverages(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap);
   // --BestWindow: the window tables of the records' (orientation, CTF) pairs from handle h (bioem_hip_window_posterior),
   // written by write_best_window; voluPerMap as for writeProbabilities
   void writeBestWindow(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,

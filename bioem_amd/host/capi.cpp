@@ -284,6 +284,31 @@ int bioem_host_read_orientation_list(const char *paramfile, const char *anglefil
   return n;
 }
 
+// the grouping of --ViewAverages (view_groups_by_orientation): groupOf[nMaps], groupOrient[cap]; returns the number of views
+int bioem_host_view_groups(const bioem_hip_prob_map *pmap, int nMaps, int nOrient, int minCount, int *groupOf, int *groupOrient,
+                           int cap)
+{
+  std::vector<int> go, gor;
+  const int n = bioem_host::view_groups_by_orientation(pmap, nMaps, nOrient, minCount, go, gor);
+  for (int p = 0; p < nMaps && groupOf; p++)
+    groupOf[p] = go[(size_t) p];
+  for (int g = 0; g < n && g < cap && groupOrient; g++)
+    groupOrient[g] = gor[(size_t) g];
+  return n;
+}
+
+// the --ViewAverages text of rings[nViews][nRings] (write_view_averages, bioem_host.h); 0, or 1 with the text in err[cap]
+int bioem_host_write_view_averages(const char *file, const bioem_hip_ring_sums *rings, int nViews, const int *groupOrient,
+                                   const int *counts, const float *angles4, int doquater, int N, float pixelSize, int minCount,
+                                   double wiener, char *err, int cap)
+{
+  const std::string e = bioem_host::write_view_averages(file, rings, nViews, groupOrient, counts, angles4, doquater != 0, N,
+                                                        pixelSize, minCount, wiener);
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return e.empty() ? 0 : 1;
+}
+
 // the MRC stack of --BestMaps: maps [nMaps][N][N] appended in batches of `batch` images
 int bioem_host_write_mrc_stack(const char *file, const float *maps, int nMaps, int N, int batch)
 {

@@ -65,6 +65,7 @@ Driver::~Driver() { cleanup(); }
 int Driver::readOptions(int ac, char **av)
 {
   std::string infile, modelfile, mapfile, anglefile;
+  bool viewOptions = false;
   std::cout << " ++++++++++++ FROM COMMAND LINE +++++++++++\n\n";
   static const struct option opts[] = {{"Modelfile", required_argument, 0, 0},
                                        {"Particlesfile", required_argument, 0, 0},
@@ -77,6 +78,9 @@ int Driver::readOptions(int ac, char **av)
                                        {"OrientStats", required_argument, 0, 0},
                                        {"OrientOccupancy", required_argument, 0, 0},
                                        {"FitOrientPrior", required_argument, 0, 0},
+                                       {"ViewAverages", required_argument, 0, 0},
+                                       {"ViewMinParticles", required_argument, 0, 0},
+                                       {"ViewWiener", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
                                        {"RefineSeeds", required_argument, 0, 0},
@@ -118,6 +122,10 @@ int Driver::readOptions(int ac, char **av)
     printf("                         many particles stand behind each; needs WRITE_PROB_ANGLES)\n");
     printf("  --FitOrientPrior arg   (Optional) With --OrientOccupancy: arg EM iterations of the orientation prior, written as\n");
     printf("                         arg_prior of --OrientOccupancy in the --ReadOrientation format for PRIOR_ANGLES\n");
+    printf("  --ViewAverages arg     (Optional) Write per view (orientation) the aligned, CTF-corrected average of its particles\n");
+    printf("                         against the model's projection: ring correlation in arg, stacks arg_avg.mrc and arg_proj.mrc\n");
+    printf("  --ViewMinParticles arg (Optional) With --ViewAverages: views with fewer particles are left out (default 2)\n");
+    printf("  --ViewWiener arg       (Optional) With --ViewAverages: the Wiener constant as a fraction of the mean weight (default 0.1)\n");
     printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
@@ -237,6 +245,25 @@ int Driver::readOptions(int ac, char **av)
       if (fitOrientPrior < 1)
         fatal("--FitOrientPrior needs a positive number of iterations");
     }
+    else if (name == "ViewAverages")
+    {
+      std::cout << "Writing the view averages to: " << optarg << "\n";
+      viewAvgFile = optarg;
+    }
+    else if (name == "ViewMinParticles")
+    {
+      viewMinParticles = atoi(optarg);
+      viewOptions = true;
+      if (viewMinParticles < 1)
+        fatal("--ViewMinParticles needs a positive number");
+    }
+    else if (name == "ViewWiener")
+    {
+      viewWiener = atof(optarg);
+      viewOptions = true;
+      if (!(viewWiener >= 0.) || !std::isfinite(viewWiener))
+        fatal("--ViewWiener needs a non-negative number");
+    }
     else if (name == "PrintBestCalMap")
     {
       std::cout << "Reading best parameters from file: " << optarg << "\n";
@@ -276,9 +303,9 @@ int Driver::readOptions(int ac, char **av)
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
     if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty() || !bestWindowFile.empty() ||
-        !orientStatsFile.empty() || !orientOccFile.empty())
-      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow, --OrientStats, --OrientOccupancy and "
-            "--RefineOrientations");
+        !orientStatsFile.empty() || !orientOccFile.empty() || !viewAvgFile.empty())
+      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow, --OrientStats, --OrientOccupancy, "
+            "--ViewAverages and --RefineOrientations");
     const std::string err = read_best_parameters(bestParamFile.c_str(), best);
     if (!err.empty())
       fatal("%s", err.c_str());
@@ -316,6 +343,10 @@ int Driver::readOptions(int ac, char **av)
     if (!param.pd.writeAngles)
       fatal("--OrientStats needs WRITE_PROB_ANGLES in the parameter file: the summaries are reduced from the angle table");
   }
+  if (viewOptions && viewAvgFile.empty())
+    fatal("--ViewMinParticles / --ViewWiener go with --ViewAverages");
+  if (!viewAvgFile.empty() && !refineFile.empty()) // the views are orientations of the shared list
+    fatal("--ViewAverages is not valid with --RefineOrientations (own lists share no orientation index)");
   if (fitOrientPrior && orientOccFile.empty())
     fatal("--FitOrientPrior is only valid with --OrientOccupancy");
   if (!orientOccFile.empty())
@@ -575,6 +606,48 @@ void Driver::writeBestFrc(const std::string &file, bioem_hip_handle h, const bio
   if (!err.empty())
     fatal("--BestFRC: %s", err.c_str());
   std::cout << "Ring correlation of " << nMaps << " particles against their best match written to: " << file << "\n";
+}
+
+// --ViewAverages: the merged records grouped by their arg-max orientation (weight 1), the chain on handle h chunk by
+// chunk of views, then the text file (write_view_averages) and the stacks FILE_avg.mrc / FILE_proj.mrc
+void Driver::writeViewAverages(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap)
+{
+  const int nMaps = particles.ntot, N = param.N;
+  const size_t nRings = (size_t) bioem_hip_ring_count(N), NN = (size_t) N * N;
+  std::vector<int> groupOf, groupOrient;
+  const int nViews = view_groups_by_orientation(pmap, nMaps, param.nTotGridAngles, viewMinParticles, groupOf, groupOrient);
+  std::vector<int> counts((size_t) nViews, 0);
+  for (int p = 0; p < nMaps; p++)
+    if (groupOf[(size_t) p] >= 0)
+      counts[(size_t) groupOf[(size_t) p]]++;
+  if (nViews < 1)
+    warn("--ViewAverages: no orientation has %d particles or more; the files hold no view", viewMinParticles);
+  int batch = 1;
+  bioem_hip_max_batch(h, &batch, nullptr);
+  batch = std::max(1, batch);
+  std::vector<bioem_hip_ring_sums> rings((size_t) nViews * nRings);
+  std::vector<float> avg((size_t) batch * NN), proj((size_t) batch * NN);
+  const std::string avgFile = file + "_avg.mrc", projFile = file + "_proj.mrc";
+  MrcStackWriter wa, wp;
+  if (nViews > 0 && (!wa.open(avgFile.c_str(), N, nViews) || !wp.open(projFile.c_str(), N, nViews)))
+    fatal("Opening %s / %s", avgFile.c_str(), projFile.c_str());
+  for (int g0 = 0; g0 < nViews; g0 += batch)
+  {
+    const int g1 = std::min(nViews, g0 + batch);
+    check(h, bioem_hip_view_averages(h, pmap, nullptr, groupOf.data(), groupOrient.data(), nViews, viewWiener, g0, g1,
+                                     rings.data() + (size_t) g0 * nRings, avg.data(), proj.data()),
+          "view averages");
+    if (!wa.append(avg.data(), g1 - g0) || !wp.append(proj.data(), g1 - g0))
+      fatal("Writing %s / %s", avgFile.c_str(), projFile.c_str());
+  }
+  if (nViews > 0 && (!wa.close() || !wp.close()))
+    fatal("Writing %s / %s", avgFile.c_str(), projFile.c_str());
+  const std::string err = write_view_averages(file.c_str(), rings.data(), nViews, groupOrient.data(), counts.data(),
+                                              param.angles.data(), param.doquater, N, param.pixelSize, viewMinParticles,
+                                              viewWiener);
+  if (!err.empty())
+    fatal("--ViewAverages: %s", err.c_str());
+  std::cout << "Averages of " << nViews << " views written to: " << file << ", " << avgFile << ", " << projFile << "\n";
 }
 
 // --BestWindow: the window table of every record's (orientation, CTF) pair from handle h, batch by batch, then the text
@@ -939,6 +1012,8 @@ int Driver::run()
     writeBestFrc(bestFrcFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!bestWindowFile.empty())
     writeBestWindow(bestWindowFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0, param.pd);
+  if (!viewAvgFile.empty())
+    writeViewAverages(viewAvgFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
   if (!refineFile.empty())
   {
     if (refineSeeds >= 2)

@@ -180,6 +180,38 @@ def write_best_frc(path, sums, N, pixelSize):
         raise ValueError(err.value.decode())
 
 
+def view_groups(pmap, nOrient, min_count=2):
+    """the grouping the CLI uses for --ViewAverages (view_groups_by_orientation): (group_of int32 [nMaps], group_orient
+    int32 [nViews]) from the arg-max orientation of the records; bioem_amd.view_average.groups_by_orientation restates it"""
+    from .engine import PROB_MAP_DTYPE
+    L = load_host_library()
+    L.bioem_host_view_groups.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
+    group_of = np.zeros(len(pmap), dtype=np.int32)
+    group_orient = np.zeros(max(int(nOrient), 1), dtype=np.int32)
+    n = L.bioem_host_view_groups(pmap.ctypes.data, len(pmap), int(nOrient), int(min_count), group_of.ctypes.data,
+                                 group_orient.ctypes.data, len(group_orient))
+    return group_of, group_orient[:n].copy()
+
+
+def write_view_averages(path, rings, group_orient, counts, angles, doquater, N, pixelSize, min_count=2, wiener=0.1):
+    """the --ViewAverages text file of ring sums [nViews, ring_count(N)] (Engine.view_averages): the writer the CLI uses;
+    bioem_amd.view_average.parse reads it back.  angles: the orientation list [nOrient, 4] group_orient indexes."""
+    from .engine import RING_SUMS_DTYPE
+    L = load_host_library()
+    L.bioem_host_write_view_averages.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_int, C.c_float, C.c_int, C.c_double, C.c_char_p, C.c_int]
+    t = np.ascontiguousarray(rings, dtype=RING_SUMS_DTYPE)
+    go = np.ascontiguousarray(group_orient, dtype=np.int32)
+    cn = np.ascontiguousarray(counts, dtype=np.int32)
+    ang = np.ascontiguousarray(angles, dtype=np.float32)
+    assert t.ndim == 2 and go.shape == cn.shape == (t.shape[0],) and ang.ndim == 2 and ang.shape[1] == 4
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_view_averages(path.encode(), t.ctypes.data, t.shape[0], go.ctypes.data, cn.ctypes.data, ang.ctypes.data,
+                                        int(bool(doquater)), int(N), float(pixelSize), int(min_count), float(wiener), err, 512):
+        raise ValueError(err.value.decode())
+
+
 def write_best_window(path, logp, shifts, orient, conv, ctfParam, numconst, usepsf=False, elecwavel=0.019866):
     """the --BestWindow text file of window tables [nMaps, nd, nd] (Engine.best_match_window) at the shifts [nd]: the
     writer the CLI uses; bioem_amd.best_window.parse reads it back.  orient, conv [nMaps]: the records' pair (orient < 0:

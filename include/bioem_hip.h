@@ -489,6 +489,46 @@ int bioem_hip_debug_orient_occupancy(bioem_hip_handle h, const bioem_hip_prob_an
                                      const double *logPrior, const bioem_hip_orient_sums *sums, int p0, int p1, int o0,
                                      bioem_hip_orient_occ *out);
 
+/* ---- Aligned averages of the particles of a view (no reference counterpart) ----
+ * Particle p has the record (c, X, Y, norm, mu) = (max_prob_conv, max_prob_cent_x, max_prob_cent_y, max_prob_norm,
+ * max_prob_mu) (max_prob_orient is not read), a weight w_p >= 0 (weights == NULL: 1) and a group groupOf[p] in
+ * [0, nGroups), or -1 for "left out".  With R_p the particle's spectrum as the handle holds it
+ * (bioem_hip_debug_particles), K_c the uploaded CTF kernel and tw[j] = exp(+2 pi i j / N), everything in double, [N][H]:
+ *   A_p[k1][k2] = (R_p[k1][k2] - mu_p N^2 [k1 = k2 = 0]) tw[(k1 X_p + k2 Y_p) mod N]
+ *   K~_c = K_c; in the columns that are their own Hermitian partner (k2 = 0 and, N even, k2 = N / 2) its Hermitian part
+ *          (K_c[k1][k2] + conj(K_c[(N - k1) mod N][k2])) / 2: a particle is a real image, so there its spectrum carries
+ *          only that part of P conj(K_c) (the convention of M in the ring sums above), and P^ comes out Hermitian as P is
+ *   num_g[k] = sum_p (w_p norm_p) K~_c[k] A_p[k]            (re, im)
+ *   den_g[k] = sum_p (w_p norm_p^2) |K~_c[k]|^2
+ * over the members of g in ascending p, count_g and sumw_g = sum w_p: the normal equations of the model of the ring pass,
+ * R ~ norm P conj(K~_c) tw[-(k1 X + k2 Y) mod N] + mu N^2 delta, for the projection P of the view.  The estimate is
+ *   P^_g[k] = num_g[k] / (den_g[k] + tau_g),  tau_g = wiener * mean_k den_g[k],  0 where the denominator is 0.
+ * One lane owns a (group, coefficient) and adds its members one after the other; accumulators of a group that spans
+ * batches of maxOrientations particles continue in device memory.  No atomics: the bits of a group depend on its members
+ * alone, not on the batch size, the other groups of the call, the range [g0, g1) or the run.
+ * Calling rules as bioem_hip_best_match_rings (outside a run, every handle kind, buffers allocated at the first call: 1
+ * when the memory is not there).  Refusals (2, the particle or group named, handle usable): a null argument, an empty or
+ * reversed group range, a group >= nGroups or < -1, a negative or non-finite weight, max_prob_conv outside [0, nCTF), a
+ * displacement of N pixels or more, groupOrient outside the orientation list, a negative wiener, and particles, CTF
+ * kernels or (bioem_hip_view_averages) model or orientations not uploaded.  Records of particles left out are not read.
+ * Phase records: phase 2 per particle batch of the accumulation, phase 0 per chunk of projections. */
+/* records, weights, groupOf run over all nMaps particles; out for the groups [g0, g1): num [g][N][H] (re, im) doubles,
+ * den [g][N][H] doubles, stats [g] {count, sumw}.  Needs the particles and the CTF kernels. */
+int bioem_hip_view_sums(bioem_hip_handle h, const bioem_hip_prob_map *records, const double *weights, const int *groupOf,
+                        int nGroups, int g0, int g1, double *num_out, double *den_out, double *stats_out);
+/* The chain: P^_g as above; groupOrient[g] indexes the shared orientation list, -1 = no projection (that group's rings and
+ * projection map are zero).  rings_out [g][nRings]: the sums of bioem_hip_best_match_rings with R = P^_g (rounded to float)
+ * and M = P_o, the projection spectrum of groupOrient[g]: powParticle is the power of P^, powModel of P_o.  avg_maps_out /
+ * proj_maps_out (each may be NULL): [g][N][N] float, c2r(P^) / N^2 and c2r(P_o) / N^2 in the convention of
+ * bioem_hip_render_best_maps.  Groups go through in chunks of at most maxOrientations. */
+int bioem_hip_view_averages(bioem_hip_handle h, const bioem_hip_prob_map *records, const double *weights, const int *groupOf,
+                            const int *groupOrient, int nGroups, double wiener, int g0, int g1,
+                            bioem_hip_ring_sums *rings_out, float *avg_maps_out, float *proj_maps_out);
+/* test hook: the accumulation on n spectra handed in (specR [n][N][H] (re, im), reference layout) for all nGroups groups;
+ * records, weights, groupOf run over the n spectra; needs the CTF kernels only */
+int bioem_hip_debug_view_sums(bioem_hip_handle h, const float *specR, const bioem_hip_prob_map *records, const double *weights,
+                              const int *groupOf, int n, int nGroups, double *num_out, double *den_out, double *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

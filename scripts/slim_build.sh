@@ -6,15 +6,17 @@ set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
 mkdir -p abl
-# (the fast r2c is its own translation unit with its own flag, the ring, window and orientation-sum passes are units
+# (the fast r2c is its own translation unit with its own flag, the ring, window, orientation-sum and view passes are units
 # without comparison kernels: the objects of the regular build are linked in)
 [ -f bioem_amd/csrc/build/kernels_r2c.o ] || make -s -C bioem_amd/csrc build/kernels_r2c.o
 [ -f bioem_amd/csrc/build/kernels_rings.o ] || make -s -C bioem_amd/csrc build/kernels_rings.o
 [ -f bioem_amd/csrc/build/kernels_window.o ] || make -s -C bioem_amd/csrc build/kernels_window.o
 [ -f bioem_amd/csrc/build/kernels_orient.o ] || make -s -C bioem_amd/csrc build/kernels_orient.o
+[ -f bioem_amd/csrc/build/kernels_views.o ] || make -s -C bioem_amd/csrc build/kernels_views.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -fPIC -std=c++17 \
   -Wno-unused-value -DBIOEM_SLIM "$@" -Iinclude -c -o abl/$name.o bioem_amd/csrc/bioem_hip.hip
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abl/$name.so abl/$name.o bioem_amd/csrc/build/kernels_r2c.o \
-  bioem_amd/csrc/build/kernels_rings.o bioem_amd/csrc/build/kernels_window.o bioem_amd/csrc/build/kernels_orient.o
+  bioem_amd/csrc/build/kernels_rings.o bioem_amd/csrc/build/kernels_window.o bioem_amd/csrc/build/kernels_orient.o \
+  bioem_amd/csrc/build/kernels_views.o
 rm -f abl/$name.o
 python scripts/check_code_object.py --so abl/$name.so 2>&1 | grep -E "k_compare_(fast|fastm2|wide2)|kernels,"
