@@ -185,6 +185,8 @@ struct bioem_hip_ctx
   // launch of the plan's kernel per particle, the default.  Block table of the batches of particles [ownTabP0, ownTabP1):
   // batch b begins at slot ownTabSlot[b] and owns entries ownTabFirst[b] ... ownTabFirst[b + 1] of dOwnBlocks
   own_kernel_t ownFn = nullptr, ownFnPlan = nullptr;
+  own_kernel_t ownFnPlanLean = nullptr; // the lean variant of ownFnPlan, or null (compare_fast.hpp)
+  bool lean = true;                     // bioem_hip_set_compare_variant: lean instantiations where a launch qualifies
   nyq_own_kernel_t ownNyqFn = nullptr;
   bool ownXcdOrder = true;
   int4 *dOwnBlocks = nullptr;
@@ -483,6 +485,32 @@ void launch_nyquist(bioem_hip_ctx *h, const CompareArgs &aw, int WD, int nOC)
     launch_nyquist_rows<1>(h, aw, WD, nOC);
 }
 
+// k_compare_fast / k_compare_fastm: a last column block of at most 32 columns is shared by the half-waves
+// (with the Nyquist split the blocks hold the H - 1 columns below N / 2: whole ones, or -- 192^2, 320^2, 448^2, which
+// were planned that way -- a last one of 32, and then the split is not optional)
+int last_block_split(const bioem_hip_ctx *h)
+{
+  const KernelPlan &P = h->plan;
+  const int cols = P.nyq ? h->H - 1 : h->H;
+  const int nblkF = (cols + 63) / 64, rem = cols - (nblkF - 1) * 64;
+  return (P.family == KF_FAST || P.family == KF_FASTM) && rem <= 32 && P.N1 >= 2 && (P.nyq || !getenv("BIOEM_NO_SPLIT_LAST"));
+}
+
+// The lean variant of k_compare_fast is the full instantiation's static, unsplit path and nothing else (compare_fast.hpp):
+// a launch takes it exactly where the kernel's own run-time tests would take that path -- the whole window of 2 winD + 1
+// rows (symw) and no split last block -- and the handle's variant switch is on.  Decided per launch: `split` reads the
+// environment every time, and a tile launch carries its own nd / maxD.
+bool lean_launch_ok(const bioem_hip_ctx *h, int nd, int maxD, int split)
+{
+  const KernelPlan &P = h->plan;
+  return h->lean && !h->direct && P.family == KF_FAST && P.fnLean && sym_window_ok(P.winD, 2 * P.halfR, P.nyq, P.gs) &&
+         nd == 2 * P.winD + 1 && maxD / P.gs == P.winD && !split;
+}
+fast_kernel_t compare_fn(const bioem_hip_ctx *h, const CompareArgs &a)
+{
+  return lean_launch_ok(h, a.nd, a.maxD, a.split) ? h->plan.fnLean : h->plan.fn;
+}
+
 // argument block, grid and block of a comparison launch: the nOC conv rows of a slot against nMaps particles (the
 // handle's, or ONE in the own-list pass, whose launches point ref / sumRef / sumsqRef at that particle)
 CompareArgs compare_args(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC, int nMaps, dim3 &grid, dim3 &block)
@@ -518,15 +546,7 @@ CompareArgs compare_args(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nO
   a.gs = P.gs;
   a.ndx = a.ndy = P.nd;
   a.nyqWD = P.nyqWD;
-  {
-    // k_compare_fast / k_compare_fastm: a last column block of at most 32 columns is shared by the half-waves
-    // (with the Nyquist split the blocks hold the H - 1 columns below N / 2: whole ones, or -- 192^2, 320^2, 448^2, which
-    // were planned that way -- a last one of 32, and then the split is not optional)
-    const int cols = P.nyq ? h->H - 1 : h->H;
-    const int nblkF = (cols + 63) / 64, rem = cols - (nblkF - 1) * 64;
-    a.split = (fam == KF_FAST || fam == KF_FASTM) && rem <= 32 && P.N1 >= 2 &&
-              (P.nyq || !getenv("BIOEM_NO_SPLIT_LAST"));
-  }
+  a.split = last_block_split(h);
   a.pchunk = h->pchunk > 0 ? std::min(h->pchunk, nMaps) : nMaps;
   if (a.pchunk >= 8) // a multiple of 8: a particle then stays on one XCD (65 particles: chunks of 64 + 1, 43.6 -> 45.3 M/s)
     a.pchunk &= ~7;
@@ -564,7 +584,7 @@ int launch_compare_fold(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC
   auto launch = [&](const CompareArgs &aw) {
     if (P.nyq)
       launch_nyquist(h, aw, P.nyqWD, nOC);
-    hipLaunchKernelGGL(P.fn, grid, block, P.ldsBytes, h->stream, aw);
+    hipLaunchKernelGGL(compare_fn(h, aw), grid, block, P.ldsBytes, h->stream, aw);
   };
   hipEvent_t e0 = get_event(h), e1 = get_event(h);
   if (!e0 || !e1)
@@ -715,7 +735,8 @@ int launch_compare_own(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC,
     if (P.nyq)
       hipLaunchKernelGGL(h->ownNyqFn, dim3((nOC + 63) / 64), dim3(256), 0, h->stream,
                          OwnNyquistArgs{a, h->dSlotParticle, row0, nC});
-    hipLaunchKernelGGL(h->ownFn, dim3(nBlocks), dim3(256), P.ldsBytes, h->stream, OwnCompareArgs{a, h->dOwnBlocks + first});
+    const own_kernel_t fn = h->ownFnPlanLean && lean_launch_ok(h, a.nd, a.maxD, a.split) ? h->ownFnPlanLean : h->ownFn;
+    hipLaunchKernelGGL(fn, dim3(nBlocks), dim3(256), P.ldsBytes, h->stream, OwnCompareArgs{a, h->dOwnBlocks + first});
   }
   else
     for (int p = pFirst; p < pEnd; p++)
@@ -738,7 +759,7 @@ int launch_compare_own(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, int nOC,
         a.tnyq += (size_t) rb * (2 * P.nyqWD + 1);
         launch_nyquist(h, a, P.nyqWD, n);
       }
-      hipLaunchKernelGGL(P.fn, grid, block, P.ldsBytes, h->stream, a);
+      hipLaunchKernelGGL(compare_fn(h, a), grid, block, P.ldsBytes, h->stream, a);
     }
   HIP_CHECK(h, hipGetLastError());
   HIP_CHECK(h, hipEventRecord(e1, h->stream));
@@ -1270,6 +1291,9 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
   }
   HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(P.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int) P.ldsBytes));
+  if (P.fnLean)
+    HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(P.fnLean), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int) P.ldsBytes));
   const int mD = maxD / P.gs;
   const char *directEnv = getenv("BIOEM_CC_DIRECT");
   h->direct = directEnv && atoi(directEnv) != 0;
@@ -1294,6 +1318,10 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
       h->ownNyqFn = P.nyq ? reinterpret_cast<nyq_own_kernel_t>(const_cast<void *>(bioem_nyquist_rows_own(P.nyqWD))) : nullptr;
       HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(h->ownFnPlan), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int) P.ldsBytes));
+      h->ownFnPlanLean = plan_own_kernel(P, 1);
+      if (h->ownFnPlanLean)
+        HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(h->ownFnPlanLean),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int) P.ldsBytes));
     }
   }
   // Pitch of the comparison layout.  A lane block of the fast kernels keeps eight rows of one 64-column block in flight;
@@ -1895,6 +1923,18 @@ int bioem_hip_set_own_launch(bioem_hip_handle h, int mode)
   h->ownXcdOrder = mode != BIOEM_HIP_OWN_LAUNCH_BATCH_ROWS;
   h->ownTabP0 = h->ownTabP1 = -1; // the block table follows at the next pass
   return 0;
+}
+
+// lean = 0: the full instantiations only; 1 (the default of every handle): the lean variant of k_compare_fast where a launch
+// qualifies.  Returns 1 if the launches of this handle -- its plan, its shape, the tiles of a tiled plan -- now take a lean
+// kernel, else 0 (BIOEM_NO_SPLIT_LAST as it reads now; a launch reads it again).
+int bioem_hip_set_compare_variant(bioem_hip_handle h, int lean)
+{
+  if (!h)
+    return 0;
+  h->lean = lean != 0;
+  const KernelPlan &P = h->plan;
+  return lean_launch_ok(h, P.tileT ? P.tileT : P.nd, P.tileT ? P.winD * P.gs : h->pd.maxDisplaceCenter, last_block_split(h)) ? 1 : 0;
 }
 
 int bioem_hip_compare_own_orientations(bioem_hip_handle h, int iMapBegin, int iMapEnd)

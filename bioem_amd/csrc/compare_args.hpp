@@ -1,5 +1,6 @@
 // compare_args.hpp -- argument block shared by the comparison kernels
-// Part of libbioem_hip.so; included by bioem_hip.hip only (one translation unit, anonymous namespace).
+// Part of libbioem_hip.so; included by bioem_hip.hip and by every kernels_*.hip unit of a comparison family (anonymous
+// namespace).
 #ifndef BIOEM_COMPARE_ARGS_HPP
 #define BIOEM_COMPARE_ARGS_HPP
 

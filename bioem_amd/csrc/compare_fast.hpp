@@ -376,10 +376,17 @@ __device__ __forceinline__ void window_accumulate_sym(const float2 *Trow, const 
 // block-to-work mapping and the index that addresses the per-row buffers -- never a wrapper around a shared body: that
 // changes the code of every instantiation.  Everything a wave computes for a (particle, row) pair is the
 // same arithmetic in the same order, so a row's partial equals the per-particle launch's bit for bit.
-template <int WD, int R, bool NYQ, int GS, class ARGS = CompareArgs>
+// LEAN: the instantiation of ONE path through this kernel, the launch of the whole static 21-row window with no split
+// last block (the headline launch): symw is a compile-time true, split a compile-time false, and the general window pass,
+// the twiddle copy, the general posterior branch and the split block are not instantiated.  The host takes it exactly
+// where the run-time tests below would take that path (lean_launch_ok, bioem_hip.hip); what a wave computes is the full
+// instantiation's arithmetic in its order, bit for bit.  The paths never taken cost the full instantiation 18 vector
+// registers and 47 scalar spills into vector lanes, with 17 lane moves inside the k1 loop (<10, 16, false, 1>).
+template <int WD, int R, bool NYQ, int GS, class ARGS = CompareArgs, bool LEAN = false>
 __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
 {
   constexpr bool OWN = !std::is_same<ARGS, CompareArgs>::value;
+  static_assert(!LEAN || sym_window_ok(WD, R, NYQ, GS), "the lean variant is the static window pass over |dy| alone");
   static_assert(WD <= 10, "windows of at most 21 rows; 27 / 31 rows: k_compare_fastm");
   constexpr int NW = 2 * WD + 1;
   constexpr int R2 = R / 2;            // rows (k2 pairs) per k1 step
@@ -406,12 +413,13 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
   float2 *Tl = Tall + (size_t) wave * NW * TS;
 
   int *dinv = displ + 32; // visiting rank of window row m (displacement m*GS), index m + mD
-  const int mD = a.maxD / GS;
+  const int mD = LEAN ? WD : a.maxD / GS;
   // (the rows -WD..WD, all of them: what is_static below says of a 21-row window)
-  const bool symw = SYM && a.nd == NW && mD == WD;
-  if (!symw)
-    for (int t = threadIdx.x; t <= N; t += blockDim.x)
-      twl[t] = a.tw[t];
+  const bool symw = LEAN || (SYM && a.nd == NW && mD == WD);
+  if constexpr (!LEAN)
+    if (!symw)
+      for (int t = threadIdx.x; t <= N; t += blockDim.x)
+        twl[t] = a.tw[t];
   for (int t = threadIdx.x; t < a.nd; t += blockDim.x)
   {
     const int dv = a.disp[t];
@@ -460,8 +468,8 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
   const auto rsrcC = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<float2 *>(a.conv + (size_t) oc * M)), 0,
                                                        (int) (M * sizeof(float2)), 0x00020000);
 
-  // window lanes
-  const int nd = a.nd;
+  // window lanes (LEAN reads none of the general pass's: G ... rowbase stay unreferenced there)
+  const int nd = LEAN ? NW : a.nd;
   const int G = 64 / nd;
   const int nr = (nd + G - 1) / G;
   const int iy = lane % nd, grp = lane / nd;
@@ -505,7 +513,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
   // recombination twiddles -- wave-uniform as everywhere --, w^(dx (k1 + sHalf)) = w^(dx k1) w^(dx sHalf): the high half's
   // sums are turned by w^(dx sHalf) once, after the loop, and the halves added with v_permlane32_swap.  The pass then
   // costs sHalf instead of N1 steps: 1.5 instead of 2 passes at 160^2.
-  constexpr bool SPLIT_OK = !(NYQ && R == 32); // (the 32-point Nyquist kernels have no registers left for it)
+  constexpr bool SPLIT_OK = !LEAN && !(NYQ && R == 32); // (the 32-point Nyquist kernels have no registers left for it)
   const int sHalf = (N1 + 1) >> 1;
   const int hsel = lane >> 5;
   const unsigned halfoff = (unsigned) (hsel * sHalf * R2) * rowbytes;
@@ -599,6 +607,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
         Ti[d + WD] = ti;
       }
     }
+    if constexpr (SPLIT_OK)
     if (split)
     {
       const float2 *ws = a.twk + (size_t) sHalf * NW; // w^(dx sHalf), the table's row sHalf
@@ -633,9 +642,11 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
           twl[u * 256 + threadIdx.x] = tabv[u];
       }
       __syncthreads();
-      const int idx0 = (int) (((long long) (blk * 64) * step) % N);
+      const int idx0 = LEAN ? 0 : (int) (((long long) (blk * 64) * step) % N);
       const int npairs = min(32, (H - blk * 64 + 1) >> 1); // columns of this block that exist, in pairs
-      if (symw)
+      if constexpr (LEAN)
+        window_accumulate_sym<TS>(Trow, stab, acc, npairs);
+      else if (symw)
       {
         if constexpr (SYM)
           window_accumulate_sym<TS>(Trow, stab, acc, npairs);
@@ -669,7 +680,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
           acc[j] = fmaf((((sgrp * 4 + j) * GS) & 1) ? -1.f : 1.f, tq[srow], acc[j]);
       }
     }
-    else
+    else if constexpr (!LEAN)
     {
 #pragma unroll
       for (int r = 0; r < NR; r++)
@@ -710,7 +721,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
           }
         }
       }
-      else
+      else if constexpr (!LEAN)
       {
 #pragma unroll
         for (int j = 0; j < PB; j++)
@@ -737,6 +748,17 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
     r.pad = 0;
     a.partials[OWN ? (size_t) oc : (size_t) p * a.ldPart + oc] = r; // OWN: one partial per row of the launch
   }
+}
+
+// the LEAN instantiation for a registry row (a[4] = 1 behind the K_FAST row of the same arguments), or a null stub where
+// the kernel has no window pass over |dy|: find_kernel skips null stubs, such a shape launches the full instantiation
+template <int WD, int R, bool NYQ, int GS, class ARGS = CompareArgs>
+const void *fast_lean_kernel()
+{
+  if constexpr (sym_window_ok(WD, R, NYQ, GS))
+    return reinterpret_cast<const void *>(k_compare_fast<WD, R, NYQ, GS, ARGS, true>);
+  else
+    return nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -20,7 +20,8 @@
 //   BIOEM_COMPAT_RING=<rows>    rows per half of bioem_hip_compare's staging ring (test_gpu_parity.py: odd ring sizes)
 //   BIOEM_SIGNATURE_LOG=<file>  one line per handle with its kernel instantiations (tests/conftest.py for
 //                               scripts/check_kernel_coverage.py)
-// (The launch mode of the own-list pass is no environment knob: bioem_hip_set_own_launch, include/bioem_hip.h.)
+// (The launch mode of the own-list pass is no environment knob: bioem_hip_set_own_launch, include/bioem_hip.h.  Nor is the
+// variant of k_compare_fast a launch takes, full or lean: bioem_hip_set_compare_variant.)
 // Outside the library: BIOEM_HIP_LIBRARY (Python loader, bioem_amd/engine.py: an experiment build) and the options of
 // the host layer (bioem_amd/host: the reference's environment, devices and merge).
 #ifndef BIOEM_KERNEL_SELECT_HPP
@@ -41,6 +42,7 @@ typedef BioemKernelEntry KernelEntry;
 const KernelEntry kSlimTable[] = {
 #ifdef BIOEM_SLIM_FAST
     {KF_FAST, {BIOEM_SLIM_FAST, 0, 0}, reinterpret_cast<const void *>(k_compare_fast<BIOEM_SLIM_FAST>)},
+    {KF_FAST, {BIOEM_SLIM_FAST, 1, 0}, fast_lean_kernel<BIOEM_SLIM_FAST>()},
 #endif
 #ifdef BIOEM_SLIM_FASTM
     {KF_FASTM, {BIOEM_SLIM_FASTM, 0, 0}, reinterpret_cast<const void *>(k_compare_fastm<BIOEM_SLIM_FASTM>)},
@@ -90,11 +92,11 @@ fast_kernel_t find_kernel(int family, int a0 = 0, int a1 = 0, int a2 = 0, int a3
 
 // the own-list pass: k_compare_fast on OwnCompareArgs (kernels_fast_own.hip) under the template arguments of the plan's
 // k_compare_fast, or null -- another family, a tiled plan, an instantiation that was left out: such a shape keeps one
-// launch per particle
+// launch per particle.  lean = 1: its lean variant (the registry row with a[4] = 1), or null
 typedef void (*own_kernel_t)(const OwnCompareArgs);
 typedef void (*nyq_own_kernel_t)(const OwnNyquistArgs);
 
-own_kernel_t find_own_kernel(int family, int wd, int R, bool nyq, int gs)
+own_kernel_t find_own_kernel(int family, int wd, int R, bool nyq, int gs, int lean = 0)
 {
 #ifdef BIOEM_SLIM
   return nullptr;
@@ -106,7 +108,7 @@ own_kernel_t find_own_kernel(int family, int wd, int R, bool nyq, int gs)
   for (int i = 0; i < n; i++)
   {
     const KernelEntry &e = tab[i];
-    if (e.fn && e.family == KF_FAST && e.a[0] == wd && e.a[1] == R && e.a[2] == (int) nyq && e.a[3] == gs)
+    if (e.fn && e.family == KF_FAST && e.a[0] == wd && e.a[1] == R && e.a[2] == (int) nyq && e.a[3] == gs && e.a[4] == lean)
       return reinterpret_cast<own_kernel_t>(const_cast<void *>(e.fn));
   }
   return nullptr;
@@ -165,6 +167,9 @@ struct KernelPlan
   int genericRows = 0; // k_compare_generic: window rows per pass through the LDS (0 = all)
   size_t ldsBytes = 0;
   fast_kernel_t fn = nullptr;
+  // k_compare_fast: the lean variant of fn (compare_fast.hpp), or null; which of the two a launch takes is decided per
+  // launch, once its argument block is known (lean_launch_ok, bioem_hip.hip)
+  fast_kernel_t fnLean = nullptr;
   const char *err = nullptr;
 };
 
@@ -348,6 +353,7 @@ bool take_window(KernelPlan &P, int family, fast_kernel_t fn, int N, int R, bool
 {
   P.family = family;
   P.fn = fn;
+  P.fnLean = family == KF_FAST ? find_kernel(KF_FAST, wd, R, nyq, P.gs, 1) : nullptr;
   P.halfR = R / 2;
   P.N1 = N / R;
   P.nyq = nyq;
@@ -596,9 +602,9 @@ KernelPlan plan_kernels(int N, int maxD, int grid, int algo)
 }
 
 // single launch of the own-list pass for this plan (null: one launch per particle)
-own_kernel_t plan_own_kernel(const KernelPlan &P)
+own_kernel_t plan_own_kernel(const KernelPlan &P, int lean = 0)
 {
-  return P.tileT ? nullptr : find_own_kernel(P.family, P.winD, 2 * P.halfR, P.nyq, P.gs);
+  return P.tileT ? nullptr : find_own_kernel(P.family, P.winD, 2 * P.halfR, P.nyq, P.gs, lean);
 }
 
 void plan_signature(const KernelPlan &P, char *buf, size_t cap);

@@ -21,9 +21,22 @@ const void *own_kernel()
   else
     return reinterpret_cast<const void *>(k_compare_fast<WD, R, NYQ, GS, OwnCompareArgs>);
 }
+
+// the lean variant of an own instantiation (compare_fast.hpp), where both exist
+template <int WD, int R, bool NYQ, int GS>
+const void *own_lean_kernel()
+{
+  if constexpr (own_left_out(WD, R, NYQ, GS))
+    return nullptr;
+  else
+    return fast_lean_kernel<WD, R, NYQ, GS, OwnCompareArgs>();
+}
 } // namespace
 
-#define K_FAST(WD, R, NYQ, GS) {KF_FAST, {WD, R, NYQ, GS, 0, 0}, own_kernel<WD, R, NYQ, GS>()},
+// every line twice, as in kernels_fast.hip: a[4] = 1 holds the lean variant or a null stub
+#define K_FAST(WD, R, NYQ, GS)                                                                                          \
+  {KF_FAST, {WD, R, NYQ, GS, 0, 0}, own_kernel<WD, R, NYQ, GS>()},                                                      \
+      {KF_FAST, {WD, R, NYQ, GS, 1, 0}, own_lean_kernel<WD, R, NYQ, GS>()},
 #define BIOEM_FAMILY_FN bioem_kernels_fast_own
 #include "kernels_family.inc"
 

@@ -78,6 +78,8 @@ def load_library():
         L.bioem_hip_own_kernel_signature.argtypes = [vp]
         L.bioem_hip_own_kernel_signature.restype = C.c_char_p
         L.bioem_hip_set_own_launch.argtypes = [vp, ci]
+    if hasattr(L, "bioem_hip_set_compare_variant"):
+        L.bioem_hip_set_compare_variant.argtypes = [vp, ci]
     if hasattr(L, "bioem_hip_render_best_maps"):
         L.bioem_hip_render_best_maps.argtypes = [vp, vp, ci, ci, ci, vp]
     if hasattr(L, "bioem_hip_enable_ctf_table"):
@@ -160,7 +162,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_window_count", "bioem_hip_window_offsets", "bioem_hip_window_posterior", "bioem_hip_debug_window",
            "bioem_hip_orientation_sums", "bioem_hip_merge_orient_sums_host", "bioem_hip_debug_orient_sums",
            "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy",
-           "bioem_hip_view_sums", "bioem_hip_view_averages", "bioem_hip_debug_view_sums"]
+           "bioem_hip_view_sums", "bioem_hip_view_averages", "bioem_hip_debug_view_sums",
+           "bioem_hip_set_compare_variant"]
 
 
 def _p(a):
@@ -261,6 +264,12 @@ class Engine:
         "batch" (one launch per batch where the shape has the kernel, bioem_hip_plan_own) or "rows" (the same with the
         block table in plain row order); results do not depend on it"""
         self._chk(self.L.bioem_hip_set_own_launch(self.h, {"particle": 0, "batch": 1, "rows": 2}[mode]), "set_own_launch")
+
+    def set_compare_variant(self, lean):
+        """lean (the default of every handle): launches of k_compare_fast that take its static, unsplit 21-row path run the
+        lean instantiation of that path; not lean: the full instantiations only.  Same bits either way.  Returns True if
+        the launches of this handle now take a lean kernel"""
+        return bool(self.L.bioem_hip_set_compare_variant(self.h, 1 if lean else 0))
 
     def upload_particles(self, refFFT, sumRef, sumsqRef):
         refFFT = np.ascontiguousarray(refFFT, dtype=np.float32)

@@ -186,6 +186,13 @@ int bioem_hip_compare_own_orientations(bioem_hip_handle h, int iMapBegin, int iM
 #define BIOEM_HIP_OWN_LAUNCH_BATCH 1
 #define BIOEM_HIP_OWN_LAUNCH_BATCH_ROWS 2
 int bioem_hip_set_own_launch(bioem_hip_handle h, int mode);
+/* Which instantiation of k_compare_fast the comparison launches of this handle take, from the next launch on.  The kernels
+ * with the static 21-row window pass have a lean variant that holds that one path alone -- the whole window, no split last
+ * column block -- with fewer registers; a launch that would take that path through the full instantiation computes the same
+ * bits in either.  lean = 1, the default of every handle: such launches take the lean variant; lean = 0: the full
+ * instantiations only.  Returns 1 if the launches of this handle at its plan and shape now take a lean kernel, else 0.
+ * The labels of bioem_hip_kernel_signature / bioem_hip_plan do not depend on it. */
+int bioem_hip_set_compare_variant(bioem_hip_handle h, int lean);
 
 /* The same three stages as separate entries, for an integrator who keeps the reference's loop (bioem.cpp:763-891) and
  * replaces its body piece by piece: every call is asynchronous and batched, and what one stage produces stays on the

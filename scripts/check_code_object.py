@@ -65,6 +65,11 @@ def short(name):
     name = re.sub(r"\(.*\)$", "", name)
     # k_compare_fast / k_nyquist_rows end in their argument struct; the tables keep the names they have always used:
     # the all-to-all kernels without it, the own-list instantiations as k_compare_fast_own<...> / k_nyquist_rows_own<WD>
+    # (k_compare_fast ends in its LEAN flag behind the struct: the lean variants as k_compare_fast_lean<...> /
+    # k_compare_fast_own_lean<...>, so every full instantiation keeps its row and pairs with its parent's)
+    name = re.sub(r"^k_compare_fast<(.*), (Own)?CompareArgs, true>$",
+                  lambda m: "k_compare_fast%s_lean<%s>" % ("_own" if m.group(2) else "", m.group(1)), name)
+    name = re.sub(r"^(k_compare_fast<.*CompareArgs), false>$", r"\1>", name)
     name = re.sub(r", CompareArgs>$", ">", name)
     name = re.sub(r"^k_compare_fast<(.*), OwnCompareArgs>$", r"k_compare_fast_own<\1>", name)
     return re.sub(r"^k_nyquist_rows<(\d+), 4, OwnNyquistArgs>$", r"k_nyquist_rows_own<\1>", name)
