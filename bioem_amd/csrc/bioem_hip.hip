@@ -56,6 +56,9 @@
 //   window_kernels.hpp   k_window_prep, k_window_cols, k_window_cells  bioem_hip_window_posterior: the log posterior of every
 //                          cell of the displacement window of a (particle, orientation, CTF) request (kernels_window.hip;
 //                          declarations only here)
+//   scan_kernels.hpp     k_scan_pack, k_scan_prep, k_ctf_scan  bioem_hip_ctf_scan: the log posterior of a (particle,
+//                          orientation, shift) request under every CTF set of a list, lane = candidate (kernels_scan.hip;
+//                          declarations only here)
 //   orient_kernels.hpp   k_orient_max, k_orient_sums, k_orient_fold, k_orient_products  bioem_hip_orientation_sums: the
 //                          orientation posterior of every particle reduced where the angle table lives
 //                          (kernels_orient.hip; declarations only here); k_orient_occ  bioem_hip_orientation_occupancy:
@@ -128,6 +131,7 @@ struct HipErr
 #include "ring_kernels.hpp"
 #include "view_kernels.hpp"
 #include "window_kernels.hpp"
+#include "scan_kernels.hpp"
 #include "orient_kernels.hpp"
 
 struct bioem_hip_ctx
@@ -243,6 +247,18 @@ struct bioem_hip_ctx
   double2 *dWinPostc = nullptr, *dWinT = nullptr;
   int *dWinShifts = nullptr;
   double *dWinLogp = nullptr;
+  // bioem_hip_ctf_scan / bioem_hip_debug_ctf_scan: a batch's shifts; the records, projections and Z in walk order and the
+  // sums handed in of the batches one scan launch serves (scan_capacity) and one chunk of candidates as handed in
+  // (allocated at the first call, with the window staging the entry shares); the packed candidates, their parameters
+  // and the results (grown to the largest G asked for)
+  BioemScanShift *dScanShift = nullptr;
+  BioemWindowRecord *dScanRec = nullptr;
+  float2 *dScanPw = nullptr, *dScanRaw = nullptr, *dScanPacked = nullptr;
+  double2 *dScanZ = nullptr;
+  float *dScanCtf = nullptr, *dScanCc = nullptr, *dScanSums = nullptr;
+  double *dScanLogp = nullptr;
+  bioem_hip_param5 *dScanParams = nullptr;
+  int scanCapG = 0;
   // bioem_hip_orientation_sums: scratch of the two passes, the products q_i q_j of the owned orientations, their priors
   // and the result (allocated at the first call)
   double *dOrientScratch = nullptr, *dOrientQQ = nullptr, *dOrientPrior = nullptr;
@@ -3458,6 +3474,296 @@ int bioem_hip_debug_window(bioem_hip_handle h, const float *specConv, const floa
       return 1;
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
+  return 0;
+}
+
+// ---- log posterior of a (particle, orientation, shift) record under every CTF set of a list (scan_kernels.hpp) ----
+static_assert(sizeof(bioem_hip_scan_request) == 16, "request layout");
+
+namespace
+{
+// records one launch of the scan serves: as many whole batches as keep Pw and Z within 512 MiB, at most 16 batches or
+// 4 096 records (a batch alone is a few hundred waves, each a chain of N H memory latencies: too few to fill the device)
+int scan_capacity(const bioem_hip_ctx *h)
+{
+  const size_t OB = (size_t) h->OB, perRecord = (size_t) h->M * (sizeof(float2) + sizeof(double2));
+  const size_t fit = ((size_t) 512 << 20) / perRecord / OB;
+  return (int) (OB * std::max<size_t>(1, std::min<size_t>(std::min<size_t>(fit, 16), std::max<size_t>(1, 4096 / OB))));
+}
+
+// the staging buffers of the scan entries for G candidates; a failed allocation (return 1) leaves the handle as it was
+int scan_staging(bioem_hip_ctx *h, int G)
+{
+  if (window_staging(h)) // a batch's records for the gather, gathered orientations, particle spectra, spectra handed in
+    return 1;
+  const size_t OB = (size_t) h->OB, M = (size_t) h->M, cap = (size_t) scan_capacity(h);
+  if (!h->dScanZ)
+  {
+    BioemScanShift *sh = nullptr;
+    BioemWindowRecord *rec = nullptr;
+    float2 *pw = nullptr, *raw = nullptr;
+    double2 *z = nullptr;
+    float *sums = nullptr;
+    if (dev_alloc(h, sh, OB) || dev_alloc(h, rec, cap) || dev_alloc(h, pw, cap * M) ||
+        dev_alloc(h, raw, (size_t) kScanLanes * M) || dev_alloc(h, z, cap * M) || dev_alloc(h, sums, 2 * cap))
+    {
+      dev_release(h, sh);
+      dev_release(h, rec);
+      dev_release(h, pw);
+      dev_release(h, raw);
+      dev_release(h, z);
+      dev_release(h, sums);
+      (void) hipGetLastError();
+      return 1;
+    }
+    h->dScanShift = sh;
+    h->dScanRec = rec;
+    h->dScanPw = pw;
+    h->dScanRaw = raw;
+    h->dScanZ = z;
+    h->dScanSums = sums;
+  }
+  if (G <= h->scanCapG)
+    return 0;
+  const size_t chunks = ((size_t) G + kScanLanes - 1) / kScanLanes;
+  float2 *packed = nullptr;
+  float *ctf = nullptr, *cc = nullptr;
+  double *logp = nullptr;
+  bioem_hip_param5 *par = nullptr;
+  if (dev_alloc(h, packed, chunks * kScanLanes * M) || dev_alloc(h, ctf, 3 * (size_t) G) || dev_alloc(h, cc, cap * G) ||
+      dev_alloc(h, logp, cap * G) || dev_alloc(h, par, cap * G))
+  {
+    dev_release(h, packed);
+    dev_release(h, ctf);
+    dev_release(h, cc);
+    dev_release(h, logp);
+    dev_release(h, par);
+    (void) hipGetLastError();
+    return 1;
+  }
+  dev_release(h, h->dScanPacked);
+  dev_release(h, h->dScanCtf);
+  dev_release(h, h->dScanCc);
+  dev_release(h, h->dScanLogp);
+  dev_release(h, h->dScanParams);
+  h->dScanPacked = packed;
+  h->dScanCtf = ctf;
+  h->dScanCc = cc;
+  h->dScanLogp = logp;
+  h->dScanParams = par;
+  h->scanCapG = G;
+  return 0;
+}
+
+// the candidates into the walk order, a chunk of 64 at a time through dScanRaw, and their parameters
+int scan_candidates(bioem_hip_ctx *h, const float *kernels, const float *ctfParam3, int G)
+{
+  const size_t M = (size_t) h->M;
+  for (int g0 = 0; g0 < G; g0 += kScanLanes)
+  {
+    const int nG = std::min(kScanLanes, G - g0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanRaw, kernels + 2 * M * (size_t) g0, sizeof(float2) * M * nG, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, bioem_scan_pack_launch(h->stream, h->dScanRaw, nG, h->N, h->dScanPacked + M * (size_t) g0));
+  }
+  HIP_CHECK(h, hipMemcpyAsync(h->dScanCtf, ctfParam3, sizeof(float) * 3 * G, hipMemcpyHostToDevice, h->stream));
+  return 0;
+}
+
+// the preparation of a batch of nb records (shifts in dScanShift, projections in proj, particle spectra in dWinRef) into
+// the places [at, at + nb) of the launch being gathered, with their records (host) -- inside the caller's open phase 1
+int scan_prepare(bioem_hip_ctx *h, int at, int nb, const float2 *proj, const BioemWindowRecord *recs)
+{
+  const size_t M = (size_t) h->M;
+  HIP_CHECK(h, hipMemcpyAsync(h->dScanRec + at, recs, sizeof(BioemWindowRecord) * nb, hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(h, bioem_scan_prep_launch(h->stream, proj, h->dWinRef, h->dScanShift, nb, h->N, h->dTwD, h->dScanPw + M * (size_t) at,
+                                      h->dScanZ + M * (size_t) at));
+  return phase_end(h, h->stream);
+}
+
+// the scan of the n records gathered (the requests [r0, r0 + n) of the call: phase 2) and the copies to the host
+int scan_flush(bioem_hip_ctx *h, int r0, int n, int G, const float *sumRef, const float *sumsqRef, double *logp_out,
+               float *cc_out, bioem_hip_param5 *params_out)
+{
+  const size_t cells = (size_t) n * G;
+  if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, r0, r0 + n, 0, 0))
+    return 1;
+  HIP_CHECK(h, bioem_scan_launch(h->stream, h->dScanPacked, h->dScanCtf, G, h->dScanPw, h->dScanZ, h->dScanRec, sumRef, sumsqRef,
+                                 h->pd, n, h->N, h->dScanLogp, h->dScanCc, h->dScanParams));
+  HIP_CHECK(h, hipMemcpyAsync(logp_out, h->dScanLogp, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (cc_out)
+    HIP_CHECK(h, hipMemcpyAsync(cc_out, h->dScanCc, sizeof(float) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (params_out)
+    HIP_CHECK(h, hipMemcpyAsync(params_out, h->dScanParams, sizeof(bioem_hip_param5) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (phase_end(h, h->stream))
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+} // namespace
+
+int bioem_hip_ctf_scan(bioem_hip_handle h, const bioem_hip_scan_request *req, int n, int ownLists, const float *kernels,
+                       const float *ctfParam3, int G, double *logp_out, float *cc_out, bioem_hip_param5 *params_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[256];
+  auto refuse = [&](const char *why) {
+    h->err = std::string("ctf_scan: ") + why;
+    return 2;
+  };
+  if (!req || !logp_out || n < 1)
+    return refuse("null argument or no requests");
+  if (G < 1)
+  {
+    snprintf(buf, sizeof(buf), "no candidates (G = %d)", G);
+    return refuse(buf);
+  }
+  if (!kernels || !ctfParam3)
+    return refuse("null candidate kernels or parameters");
+  if (!h->dPts || h->nPts < 1)
+    return refuse("model not uploaded");
+  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
+    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
+                           : "orientations not uploaded");
+  if (!h->refUp)
+    return refuse("particles not uploaded");
+  const int N = h->N, OB = h->OB;
+  std::vector<BioemWindowRecord> recs((size_t) n);
+  std::vector<BioemScanShift> shifts((size_t) n);
+  for (int i = 0; i < n; i++)
+  {
+    const bioem_hip_scan_request &r = req[i];
+    const char *why = nullptr;
+    int first = 0, len = 0;
+    if (r.particle < 0 || r.particle >= h->nMaps)
+      why = "particle outside [0, nMaps)";
+    else
+    {
+      first = ownLists ? h->ownOff[(size_t) r.particle] : 0;
+      len = ownLists ? h->ownOff[(size_t) r.particle + 1] - first : h->nAnglesUp;
+      if (r.orient < 0 || r.orient >= len)
+        why = "orient outside its orientation list";
+      else if (r.shiftX <= -N || r.shiftX >= N || r.shiftY <= -N || r.shiftY >= N)
+        why = "shift outside (-N, N)";
+    }
+    if (why)
+    {
+      snprintf(buf, sizeof(buf), "request %d: %s (particle %d of %d, orient %d of %d, shift %d %d, N %d)", i, why, r.particle,
+               h->nMaps, r.orient, len, r.shiftX, r.shiftY, N);
+      return refuse(buf);
+    }
+    recs[(size_t) i] = {first + r.orient, 0, r.particle, 0, {0.f, 0.f}};
+    shifts[(size_t) i] = {r.shiftX, r.shiftY};
+  }
+  if (scan_staging(h, G))
+    return 1;
+  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  const OrientList src = ownLists ? own_list(h) : shared_list(h);
+  const OrientList L = {h->dWinAngles, src.isQuat, src.quatNormDev};
+  const size_t M = (size_t) h->M;
+  const int cap = scan_capacity(h);
+  for (int b0 = 0, r0 = 0; b0 < n; b0 += OB) // r0: the first request of the launch being gathered
+  {
+    const int nb = std::min(OB, n - b0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinRec, recs.data() + b0, sizeof(BioemWindowRecord) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shifts.data() + b0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_render_gather, dim3((nb + 255) / 256), dim3(256), 0, h->stream, src.d,
+                       reinterpret_cast<const RenderRecord *>(h->dWinRec), nb, h->dWinAngles);
+    HIP_CHECK(h, hipGetLastError());
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, b0, b0 + nb, 0, 0) ||
+        project_batch(h, s0, h->stream, L, 0, nb) || phase_end(h, h->stream))
+      return 1;
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, b0, b0 + nb, 0, 0))
+      return 1;
+    if (b0 == 0 && scan_candidates(h, kernels, ctfParam3, G)) // (part of the first batch's preparation)
+      return 1;
+    // the particles' spectra back in reference layout: one launch per run of consecutive particles
+    for (int i = 0; i < nb;)
+    {
+      int j = i + 1;
+      while (j < nb && recs[(size_t) (b0 + j)].particle == recs[(size_t) (b0 + j - 1)].particle + 1)
+        j++;
+      hipLaunchKernelGGL(k_unreorder, dim3(std::min(1024, 16 * (j - i))), dim3(256), 0, h->stream,
+                         h->dRef + h->Mc * (size_t) recs[(size_t) (b0 + i)].particle, h->dWinRef + M * (size_t) i, j - i, N, h->H,
+                         h->plan.halfR, h->plan.N1, h->Hp);
+      HIP_CHECK(h, hipGetLastError());
+      i = j;
+    }
+    if (scan_prepare(h, b0 - r0, nb, s0.specRef, recs.data() + b0))
+      return 1;
+    if (b0 + nb - r0 + OB > cap || b0 + nb == n)
+    { // no room for another batch, or the last one: one launch over what is gathered
+      const size_t o = (size_t) r0 * G;
+      if (scan_flush(h, r0, b0 + nb - r0, G, h->dSumRef, h->dSumsqRef, logp_out + o, cc_out ? cc_out + o : nullptr,
+                     params_out ? params_out + o : nullptr))
+        return 1;
+      r0 = b0 + nb;
+    }
+  }
+  drain_phases(h);
+  return 0;
+}
+
+int bioem_hip_debug_ctf_scan(bioem_hip_handle h, const float *specP, const float *specRef, const float *sumRef,
+                             const float *sumsqRef, const int *shiftXY, int n, const float *kernels, const float *ctfParam3,
+                             int G, double *logp_out, float *cc_out, bioem_hip_param5 *params_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[160];
+  if (!specP || !specRef || !sumRef || !sumsqRef || !shiftXY || !kernels || !ctfParam3 || !logp_out || n < 1 || G < 1)
+  {
+    h->err = "debug_ctf_scan: null argument, no records or no candidates";
+    return 2;
+  }
+  const int N = h->N, OB = h->OB;
+  for (int i = 0; i < n; i++)
+    if (shiftXY[2 * i] <= -N || shiftXY[2 * i] >= N || shiftXY[2 * i + 1] <= -N || shiftXY[2 * i + 1] >= N)
+    {
+      snprintf(buf, sizeof(buf), "debug_ctf_scan: record %d: shift outside (-N, N) (shift %d %d, N %d)", i, shiftXY[2 * i],
+               shiftXY[2 * i + 1], N);
+      h->err = buf;
+      return 2;
+    }
+  if (scan_staging(h, G))
+    return 1;
+  if (compat_flush(h))
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
+  const size_t M = (size_t) h->M;
+  const int cap = scan_capacity(h);
+  std::vector<BioemWindowRecord> recs((size_t) std::min(n, cap)); // a record's sums lie at its place in the launch
+  for (size_t i = 0; i < recs.size(); i++)
+    recs[i] = {0, 0, (int) i, 0, {0.f, 0.f}};
+  if (scan_candidates(h, kernels, ctfParam3, G))
+    return 1;
+  for (int b0 = 0, r0 = 0; b0 < n; b0 += OB)
+  {
+    const int nb = std::min(OB, n - b0), at = b0 - r0;
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shiftXY + 2 * (size_t) b0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinConv, specP + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinRef, specRef + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanSums + at, sumRef + b0, sizeof(float) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanSums + cap + at, sumsqRef + b0, sizeof(float) * nb, hipMemcpyHostToDevice, h->stream));
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, b0, b0 + nb, 0, 0) ||
+        scan_prepare(h, at, nb, h->dWinConv, recs.data() + at))
+      return 1;
+    if (at + nb + OB > cap || b0 + nb == n)
+    {
+      const size_t o = (size_t) r0 * G;
+      if (scan_flush(h, r0, at + nb, G, h->dScanSums, h->dScanSums + cap, logp_out + o, cc_out ? cc_out + o : nullptr,
+                     params_out ? params_out + o : nullptr))
+        return 1;
+      r0 = b0 + nb;
+    }
+  }
+  drain_phases(h);
   return 0;
 }
 

@@ -22,6 +22,7 @@ ORIENT_SUMS_DTYPE = np.dtype([("m", "<f8"), ("omax", "<f8"), ("count", "<f8"), (
 ORIENT_OCC_DTYPE = np.dtype([("occ", "<f8"), ("occ2", "<f8"), ("wmax", "<f8"), ("pmax", "<f8"), ("count", "<f8"),
                              ("hard", "<f8")])
 WINDOW_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4")])
+SCAN_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("shiftX", "<i4"), ("shiftY", "<i4")])
 MIN_PROB = -999999.0
 
 
@@ -94,6 +95,9 @@ def load_library():
         L.bioem_hip_window_offsets.argtypes = [ci, ci, ci, ci, vp, ci]
         L.bioem_hip_window_posterior.argtypes = [vp, vp, ci, ci, vp, vp, vp]
         L.bioem_hip_debug_window.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp]
+    if hasattr(L, "bioem_hip_ctf_scan"):
+        L.bioem_hip_ctf_scan.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp, vp, vp]
+        L.bioem_hip_debug_ctf_scan.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]
     if hasattr(L, "bioem_hip_orientation_sums"):
         L.bioem_hip_orientation_sums.argtypes = [vp, vp, ci, ci, ci, vp]
         L.bioem_hip_merge_orient_sums_host.argtypes = [ci, ci, C.POINTER(vp), vp]
@@ -160,6 +164,7 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_set_own_launch", "bioem_hip_render_best_maps", "bioem_hip_enable_ctf_table",
            "bioem_hip_ctf_table", "bioem_hip_ring_count", "bioem_hip_best_match_rings", "bioem_hip_debug_ring_sums",
            "bioem_hip_window_count", "bioem_hip_window_offsets", "bioem_hip_window_posterior", "bioem_hip_debug_window",
+           "bioem_hip_ctf_scan", "bioem_hip_debug_ctf_scan",
            "bioem_hip_orientation_sums", "bioem_hip_merge_orient_sums_host", "bioem_hip_debug_orient_sums",
            "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy",
            "bioem_hip_view_sums", "bioem_hip_view_averages", "bioem_hip_debug_view_sums",
@@ -588,6 +593,88 @@ class Engine:
             e.rc = rc
             raise e
         return logp, cc
+
+    @staticmethod
+    def _spectra(a):
+        a = np.ascontiguousarray(a)
+        if a.dtype.kind == "c":
+            a = np.ascontiguousarray(a.astype(np.complex64)).view(np.float32).reshape(a.shape + (2,))
+        return np.ascontiguousarray(a, dtype=np.float32)
+
+    def _scan_candidates(self, kernels, ctf_params):
+        kernels = self._spectra(kernels)
+        ctf_params = np.ascontiguousarray(ctf_params, dtype=np.float32)
+        assert kernels.ndim == 4 and kernels.shape[1:] == (self.N, self.H, 2), kernels.shape
+        assert ctf_params.shape == (len(kernels), 3), ctf_params.shape
+        return kernels, ctf_params
+
+    def _scan_raise(self, name, rc):
+        e = RuntimeError("%s: %s" % (name, self.L.bioem_hip_last_error(self.h).decode()))
+        e.rc = rc
+        raise e
+
+    def ctf_scan(self, requests, kernels, ctf_params, own=False, want_cc=False, want_params=False):
+        """the log posterior of each request (particle, orient, shiftX, shiftY) of SCAN_REQUEST_DTYPE [n] (or an [n, 4]
+        integer array) under every candidate CTF set: kernels float32 [G, N, H, 2] (or complex64 [G, N, H]) in the layout
+        upload_ctf takes, ctf_params float32 [G, 3] = (amp, phase, env).  Returns float64 [n, G]: entry [r, g] is the cell
+        (shiftX, shiftY) of the window_posterior table had candidate g been a CTF set of the handle (include/bioem_hip.h);
+        a shift need not be a cell of the handle's window, |shift| < N.  orient indexes the shared list, with own=True the
+        list of the request's particle.  want_cc adds the float32 cross-correlation values [n, G], want_params the
+        PARAM5_DTYPE [n, G] of the (request, candidate) pairs; the result is then a tuple in that order.  Outside a run;
+        a refusal raises RuntimeError with .rc == 2."""
+        r = np.asarray(requests)
+        if r.dtype != SCAN_REQUEST_DTYPE:
+            r = np.asarray(r, dtype=np.int32).reshape(-1, 4)
+            q = np.zeros(len(r), dtype=SCAN_REQUEST_DTYPE)
+            q["particle"], q["orient"], q["shiftX"], q["shiftY"] = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
+            r = q
+        r = np.ascontiguousarray(r.reshape(-1))
+        kernels, ctf_params = self._scan_candidates(kernels, ctf_params)
+        n, G = len(r), len(kernels)
+        logp = np.zeros((n, G), dtype=np.float64)
+        cc = np.zeros((n, G), dtype=np.float32) if want_cc else None
+        par = np.zeros((n, G), dtype=PARAM5_DTYPE) if want_params else None
+        rc = self.L.bioem_hip_ctf_scan(self.h, _p(r) if n else None, n, int(bool(own)), _p(kernels) if G else None,
+                                       _p(ctf_params) if G else None, G, _p(logp), _p(cc), _p(par))
+        if rc:
+            self._scan_raise("ctf_scan", rc)
+        out = (logp,) + ((cc,) if want_cc else ()) + ((par,) if want_params else ())
+        return out[0] if len(out) == 1 else out
+
+    def best_match_ctf_scan(self, pmap, kernels, ctf_params, p0=0, p1=None, own=False, want_cc=False, want_params=False):
+        """ctf_scan of the best record (orient, cent_x, cent_y) of particles [p0, p1) of a probability block's map entries
+        (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
+        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
+        assert pmap.shape == (self.nMaps,)
+        p1 = self.nMaps if p1 is None else int(p1)
+        req = np.zeros(max(0, p1 - int(p0)), dtype=SCAN_REQUEST_DTYPE)
+        req["particle"] = np.arange(int(p0), p1)
+        req["orient"] = pmap["orient"][int(p0):p1]
+        req["shiftX"], req["shiftY"] = pmap["cent_x"][int(p0):p1], pmap["cent_y"][int(p0):p1]
+        return self.ctf_scan(req, kernels, ctf_params, own=own, want_cc=want_cc, want_params=want_params)
+
+    def debug_ctf_scan(self, specP, specRef, sumRef, sumsqRef, shifts, kernels, ctf_params):
+        """test hook: the kernels of ctf_scan on n (projection, particle) spectrum pairs handed in, float32 [n, N, H, 2] each
+        (or complex64 [n, N, H]), with the particles' sums float32 [n] and the shifts int [n, 2].  Needs only the handle's
+        parameters.  Returns (logp float64 [n, G], cc float32 [n, G], params PARAM5_DTYPE [n, G]); a refusal raises with
+        .rc == 2."""
+        specP, specRef = self._spectra(specP), self._spectra(specRef)
+        kernels, ctf_params = self._scan_candidates(kernels, ctf_params)
+        n, G = len(specP), len(kernels)
+        sumRef = np.ascontiguousarray(sumRef, dtype=np.float32)
+        sumsqRef = np.ascontiguousarray(sumsqRef, dtype=np.float32)
+        shifts = np.ascontiguousarray(shifts, dtype=np.int32)
+        assert specP.shape == (n, self.N, self.H, 2) and specRef.shape == specP.shape
+        assert sumRef.shape == (n,) and sumsqRef.shape == (n,) and shifts.shape == (n, 2)
+        logp = np.zeros((n, G), dtype=np.float64)
+        cc = np.zeros((n, G), dtype=np.float32)
+        par = np.zeros((n, G), dtype=PARAM5_DTYPE)
+        rc = self.L.bioem_hip_debug_ctf_scan(self.h, _p(specP), _p(specRef), _p(sumRef), _p(sumsqRef), _p(shifts), n,
+                                             _p(kernels) if G else None, _p(ctf_params) if G else None, G, _p(logp), _p(cc),
+                                             _p(par))
+        if rc:
+            self._scan_raise("debug_ctf_scan", rc)
+        return logp, cc, par
 
     def orientation_sums(self, prior=None, p0=0, p1=None, own=False):
         """the orientation posterior of particles [p0, p1) reduced where the angle table lives: ORIENT_SUMS_DTYPE

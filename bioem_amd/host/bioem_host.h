@@ -65,6 +65,10 @@ struct InputParams
 int ctf_kernels(int N, float pixelSize, bool usepsf, float startAmp, float endAmp, int nAmp, float startPhase,
                 float endPhase, int nPhase, float startEnv, float endEnv, int nEnv, float *refCTF, float *ctfParam,
                 float *steps, void (*r2c)(void *, int, const float *, float *), void *ctx);
+// the kernels out[G][N][H][2] of G triples {amp, phase, env} handed in: per triple the expression of ctf_kernels, so a
+// triple that is a grid point carries the grid kernel's bits
+void ctf_kernel_list(int N, float pixelSize, bool usepsf, const float *triples, int G, float *out,
+                     void (*r2c)(void *, int, const float *, float *), void *ctx);
 // a quaternion list in the format --ReadOrientation reads (header line with the count, four 12-character columns)
 std::vector<float> read_quaternion_list(const char *file);
 float volume_element(float voluang, int gridSpaceCenter, int maxDisplaceCenter, float pixelSize, int nAmp,
@@ -141,6 +145,36 @@ struct WindowStats
 WindowStats window_stats(const double *logp, const int *shifts, int nd);
 std::string write_best_window(const char *file, const double *logp, const int *shifts, int nd, int nMaps, const int *orient,
                               const int *conv, const float *ctfParam3, bool usepsf, float elecwavel, const double *numconst);
+// --CTFScan (ctfscan.cpp): the posterior of every particle's best record (orientation, shift) over candidate CTF sets that
+// refine the parameter file's grid (bioem_hip_ctf_scan).  Candidates: on every axis with n > 1 points the n k values
+// (float) i * (g / (float) k) + start, g the grid's step, k = 1, 2, 4, 8 or 16 (every k-th value is a grid value bit for
+// bit); an axis with one point keeps it.  Candidate index: amp outermost, envelope innermost, as the CTF sets of a run.
+const int kCtfScanMaxCandidates = 4096; // bounds the host's tables; a choice, not a measurement
+bool ctf_scan_factor_valid(int k);
+// counts[3] and, when triples is given and there are at most kCtfScanMaxCandidates of them, the candidates
+// triples[G][3]; returns G
+int ctf_scan_refine(const float start[3], const float step[3], const int n[3], int k, int counts[3], float *triples);
+// statistics of one particle's logp[G] over the finite candidates, in double and in the units of the triples: logP the
+// log-sum-exp, best the arg-max candidate (the first among equals; -1 when none is finite), per axis the mean and sd of the
+// marginal posterior and the mass on its two outermost values (on its one value: 1), nEff = 1 / sum w^2
+struct CtfScanStats
+{
+  double logP, mean[3], sd[3], edgeMass[3], nEff;
+  int best, skipped;
+};
+CtfScanStats ctf_scan_stats(const double *logp, const float *triples, const int counts[3]);
+// the text file of logp[nMaps][G].  After the HEADER:: NOTATION bar, one notation line and the bar again, per particle
+//  SCAN p amp pha env orient shiftX shiftY best logP  nAmp meanAmp sdAmp edgeAmp  nPha meanPha sdPha edgePha
+//       nEnv meanEnv sdEnv edgeEnv  skipped G nEff
+// (amp pha env: the arg-max candidate as --ProbCTF prints the CTF columns, the phase statistics in that unit; logP with
+// numconst[p], the constant of the particle's LogProb, added) followed by G lines
+//  CAND p g amp pha env logP weight
+// (logP = the candidate's log posterior + numconst[p], weight = its share of the posterior, 0 when not finite).
+// orient[p] < 0: a particle without a table -- orient -1, G 0, no candidates.  16 significant digits.  Returns the empty
+// string, or the error.
+std::string write_ctf_scan(const char *file, const double *logp, const float *triples, const int counts[3], int nMaps,
+                           const int *orient, const int *shiftX, const int *shiftY, bool usepsf, float elecwavel,
+                           const double *numconst);
 // --OrientStats (orientstats.cpp): the text file of the sums sums[nMaps] of bioem_hip_orientation_sums.  After the
 // HEADER:: NOTATION bar, one notation line (it carries the constant as NumericalConst) and the bar again, per particle
 //  ORIENT p count logZ omax A pTop entropy nEff meanq1 meanq2 meanq3 meanq4 spreadDeg
@@ -270,6 +304,10 @@ public:
   std::string probCtfFile;   // --ProbCTF: the posterior per (particle, CTF set) as text (FILE, FILE_Round2)
   std::string bestFrcFile;   // --BestFRC: ring correlation of every particle against its best match (FILE, FILE_Round2)
   std::string bestWindowFile; // --BestWindow: posterior over the displacement window of every best match (FILE, FILE_Round2)
+  // --CTFScan FILE / --CTFScanFactor k: the posterior of every best record over the CTF grid refined k-fold (FILE,
+  // FILE_Round2); k = 4 is a conventional choice, not a tuned one
+  std::string ctfScanFile;
+  int ctfScanFactor = 4;
   std::string orientStatsFile; // --OrientStats: summaries of every particle's orientation posterior (WRITE_PROB_ANGLES)
   std::string orientOccFile;   // --OrientOccupancy: occupancy of every orientation over the data set (WRITE_PROB_ANGLES)
   int fitOrientPrior = 0;      // --FitOrientPrior N: N EM iterations of the orientation prior, FILE_prior
@@ -321,6 +359,10 @@ private:
   // written by write_best_window; voluPerMap as for writeProbabilities
   void writeBestWindow(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
                        const bioem_hip_param_device &pd, const float *voluPerMap = nullptr);
+  // --CTFScan: the records' (orientation, shift) against the refined CTF grid from handle h (bioem_hip_ctf_scan), in
+  // chunks of candidates, written by write_ctf_scan; voluPerMap as for writeProbabilities
+  void writeCtfScan(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
+                    const bioem_hip_param_device &pd, const float *voluPerMap = nullptr);
   // --OrientStats: the shards' orientation sums (bioem_hip_orientation_sums) merged on the host, written by
   // write_orient_stats; numconst: the constant of ANG_PROB
   void writeOrientStats(const std::string &file, double numconst);

@@ -18,6 +18,52 @@ int bioem_host_ctf_kernels(int N, float pixelSize, float startAmp, float endAmp,
                                  endEnv, nEnv, refCTF, ctfParam, steps, nullptr, nullptr);
 }
 
+// the kernels of G triples handed in (ctf_kernel_list), CTF mode, or PSF mode through the device transform of `device`
+static void capi_r2c_on_device(void *ctx, int N, const float *in, float *out)
+{
+  if (bioem_hip_r2c(*(int *) ctx, N, 1, in, out))
+    bioem_host::fatal("device r2c failed");
+}
+int bioem_host_ctf_kernel_list(int N, float pixelSize, int usepsf, const float *triples, int G, float *out, int device)
+{
+  if (N < 2 || G < 1 || !triples || !out)
+    return 1;
+  bioem_host::ctf_kernel_list(N, pixelSize, usepsf != 0, triples, G, out, usepsf ? capi_r2c_on_device : nullptr, &device);
+  return 0;
+}
+
+// the grid loop of ctf_kernels in PSF mode, transformed on `device` as the CLI's set-up transforms them
+int bioem_host_psf_kernels(int N, float pixelSize, float startAmp, float endAmp, int nAmp, float startPhase, float endPhase,
+                           int nPhase, float startEnv, float endEnv, int nEnv, float *refCTF, float *ctfParam, float *steps,
+                           int device)
+{
+  return bioem_host::ctf_kernels(N, pixelSize, true, startAmp, endAmp, nAmp, startPhase, endPhase, nPhase, startEnv, endEnv,
+                                 nEnv, refCTF, ctfParam, steps, capi_r2c_on_device, &device);
+}
+
+// the --CTFScan candidates (ctf_scan_refine): counts[3] and, when triples is not null, triples[G][3]; returns G, or -1 for
+// a factor that is not 1, 2, 4, 8 or 16
+int bioem_host_ctf_scan_refine(const float *start3, const float *step3, const int *n3, int k, int *counts3, float *triples)
+{
+  if (!bioem_host::ctf_scan_factor_valid(k))
+    return -1;
+  return bioem_host::ctf_scan_refine(start3, step3, n3, k, counts3, triples);
+}
+
+// the --CTFScan text of logp[nMaps][G] (write_ctf_scan, bioem_host.h); 0, or 1 with the text in err[cap]
+int bioem_host_write_ctf_scan(const char *file, const double *logp, const float *triples, const int *counts3, int nMaps,
+                              const int *orient, const int *shiftX, const int *shiftY, int usepsf, float elecwavel,
+                              const double *numconst, char *err, int cap)
+{
+  const std::string e = bioem_host::write_ctf_scan(file, logp, triples, counts3, nMaps, orient, shiftX, shiftY, usepsf != 0,
+                                                   elecwavel, numconst);
+  if (e.empty())
+    return 0;
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return 1;
+}
+
 // == volume element (param.cpp:1600-1607)
 float bioem_host_volume_element(float voluang, int gridSpaceCenter, int maxDisplaceCenter, float pixelSize, int nAmp,
                                 float gridEnvelop, float gridPhase, float sigB, float sigDef, float sigAmp)

@@ -65,7 +65,7 @@ Driver::~Driver() { cleanup(); }
 int Driver::readOptions(int ac, char **av)
 {
   std::string infile, modelfile, mapfile, anglefile;
-  bool viewOptions = false;
+  bool viewOptions = false, scanOptions = false;
   std::cout << " ++++++++++++ FROM COMMAND LINE +++++++++++\n\n";
   static const struct option opts[] = {{"Modelfile", required_argument, 0, 0},
                                        {"Particlesfile", required_argument, 0, 0},
@@ -75,6 +75,8 @@ int Driver::readOptions(int ac, char **av)
                                        {"ProbCTF", required_argument, 0, 0},
                                        {"BestFRC", required_argument, 0, 0},
                                        {"BestWindow", required_argument, 0, 0},
+                                       {"CTFScan", required_argument, 0, 0},
+                                       {"CTFScanFactor", required_argument, 0, 0},
                                        {"OrientStats", required_argument, 0, 0},
                                        {"OrientOccupancy", required_argument, 0, 0},
                                        {"FitOrientPrior", required_argument, 0, 0},
@@ -116,6 +118,11 @@ int Driver::readOptions(int ac, char **av)
     printf("                         (per ring: FRC and powers; with --RefineOrientations also arg_Round2)\n");
     printf("  --BestWindow arg       (Optional) Write the posterior over the displacement window of every particle's best match\n");
     printf("                         (is DISPLACE_CENTER wide enough? with --RefineOrientations also arg_Round2)\n");
+    printf("  --CTFScan arg          (Optional) Write the posterior of every particle's best match over CTF sets between the points\n");
+    printf("                         of the parameter file's grid (is the grid fine and wide enough? with --RefineOrientations\n");
+    printf("                         also arg_Round2)\n");
+    printf("  --CTFScanFactor arg    (Optional) With --CTFScan: every CTF axis with more than one point is refined arg-fold;\n");
+    printf("                         1, 2, 4, 8 or 16 (default 4)\n");
     printf("  --OrientStats arg      (Optional) Write per particle the summaries of its orientation posterior (entropy, effective\n");
     printf("                         number of orientations, mean orientation, spread; needs WRITE_PROB_ANGLES)\n");
     printf("  --OrientOccupancy arg  (Optional) Write per orientation its occupancy over the data set (which views are in it, how\n");
@@ -229,6 +236,24 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Writing the posterior over the displacement window of the best matches to: " << optarg << "\n";
       bestWindowFile = optarg;
     }
+    else if (name == "CTFScan")
+    {
+      std::cout << "Writing the posterior over the refined CTF grid of the best matches to: " << optarg << "\n";
+      ctfScanFile = optarg;
+    }
+    else if (name == "CTFScanFactor")
+    {
+      char *end = nullptr;
+      const long k = strtol(optarg, &end, 10);
+      scanOptions = true;
+      if (end == optarg || *end || !ctf_scan_factor_valid((int) std::max(-1L, std::min(k, 1000L))))
+      {
+        printf("Error - --CTFScanFactor needs one of 1, 2, 4, 8, 16 (got %s)\n", optarg);
+        usage();
+        return 1;
+      }
+      ctfScanFactor = (int) k;
+    }
     else if (name == "OrientStats")
     {
       std::cout << "Writing the summaries of the orientation posteriors to: " << optarg << "\n";
@@ -303,8 +328,8 @@ int Driver::readOptions(int ac, char **av)
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
     if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty() || !bestWindowFile.empty() ||
-        !orientStatsFile.empty() || !orientOccFile.empty() || !viewAvgFile.empty())
-      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow, --OrientStats, --OrientOccupancy, "
+        !ctfScanFile.empty() || !orientStatsFile.empty() || !orientOccFile.empty() || !viewAvgFile.empty())
+      fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow, --CTFScan, --OrientStats, --OrientOccupancy, "
             "--ViewAverages and --RefineOrientations");
     const std::string err = read_best_parameters(bestParamFile.c_str(), best);
     if (!err.empty())
@@ -333,6 +358,8 @@ int Driver::readOptions(int ac, char **av)
     model.readModel(param, modelfile.c_str());
     return 0;
   }
+  if (scanOptions && ctfScanFile.empty())
+    fatal("--CTFScanFactor goes with --CTFScan");
   param.readParameters(infile.c_str());
   if (refineFile.empty() && (refineSeeds != 1 || refineLogWindow >= 0.))
     fatal("--RefineSeeds / --RefineLogWindow go with --RefineOrientations");
@@ -342,6 +369,16 @@ int Driver::readOptions(int ac, char **av)
       fatal("--OrientStats is not valid with --RefineOrientations (which goes without WRITE_PROB_ANGLES)");
     if (!param.pd.writeAngles)
       fatal("--OrientStats needs WRITE_PROB_ANGLES in the parameter file: the summaries are reduced from the angle table");
+  }
+  if (!ctfScanFile.empty())
+  { // the candidates are counted before anything is read or computed for the run
+    const int n[3] = {param.numberGridPointsCTF_amp, param.numberGridPointsCTF_phase, param.numberGridPointsEnvelop};
+    int counts[3];
+    const int G = ctf_scan_refine(nullptr, nullptr, n, ctfScanFactor, counts, nullptr);
+    if (G > kCtfScanMaxCandidates)
+      fatal("--CTFScan: %d candidate CTF sets (%d x %d x %d, the grid refined %d-fold) are more than the %d this option takes; "
+            "use a smaller --CTFScanFactor",
+            G, counts[0], counts[1], counts[2], ctfScanFactor, kCtfScanMaxCandidates);
   }
   if (viewOptions && viewAvgFile.empty())
     fatal("--ViewMinParticles / --ViewWiener go with --ViewAverages");
@@ -703,6 +740,66 @@ void Driver::writeBestWindow(const std::string &file, bioem_hip_handle h, const 
   std::cout << "Window posterior of " << nMaps << " particles' best matches written to: " << file << "\n";
 }
 
+// --CTFScan: every record's (orientation, shift) from handle h against the parameter file's CTF grid refined
+// ctfScanFactor-fold, the candidates' kernels made on the host as the run's are and scanned in chunks of at most 256
+// (bioem_hip_ctf_scan), then the text file (write_ctf_scan).  A particle no run compared has no record: a warning and an
+// empty block.
+void Driver::writeCtfScan(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
+                          const bioem_hip_param_device &pd, const float *voluPerMap)
+{
+  const int nMaps = particles.ntot, N = param.N;
+  const float start[3] = {param.startGridCTF_amp, param.startGridCTF_phase, param.startGridEnvelop};
+  const float step[3] = {param.gridCTF_amp, param.gridCTF_phase, param.gridEnvelop};
+  const int n[3] = {param.numberGridPointsCTF_amp, param.numberGridPointsCTF_phase, param.numberGridPointsEnvelop};
+  int counts[3];
+  const int G = ctf_scan_refine(start, step, n, ctfScanFactor, counts, nullptr);
+  if (G < 1 || G > kCtfScanMaxCandidates)
+    fatal("--CTFScan: %d candidate CTF sets", G);
+  std::vector<float> triples(3 * (size_t) G);
+  ctf_scan_refine(start, step, n, ctfScanFactor, counts, triples.data());
+  std::vector<double> logp((size_t) G * nMaps, 0.), numconst((size_t) nMaps);
+  std::vector<int> orient((size_t) nMaps, -1), shiftX((size_t) nMaps, 0), shiftY((size_t) nMaps, 0), who;
+  std::vector<bioem_hip_scan_request> req;
+  for (int p = 0; p < nMaps; p++)
+  {
+    numconst[(size_t) p] =
+        0.5 * log(M_PI) + (1 - pd.Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(voluPerMap ? voluPerMap[p] : pd.volu);
+    const bioem_hip_prob_map &r = pmap[p];
+    if (r.Total == 0.0 && r.Constoadd == -999999.)
+    {
+      warn("CTF scan of RefMap %d not computed: no run compared it", p);
+      continue;
+    }
+    orient[(size_t) p] = r.max_prob_orient;
+    shiftX[(size_t) p] = r.max_prob_cent_x;
+    shiftY[(size_t) p] = r.max_prob_cent_y;
+    req.push_back({p, r.max_prob_orient, r.max_prob_cent_x, r.max_prob_cent_y});
+    who.push_back(p);
+  }
+  const int chunk = 256;
+  const size_t M = (size_t) N * (N / 2 + 1);
+  std::vector<float> kernels(2 * M * (size_t) std::min(chunk, G));
+  std::vector<double> table(req.size() * (size_t) std::min(chunk, G));
+  for (int g0 = 0; g0 < G && !req.empty(); g0 += chunk)
+  {
+    const int nG = std::min(chunk, G - g0);
+    ctf_kernel_list(N, param.pixelSize, param.usepsf, triples.data() + 3 * (size_t) g0, nG, kernels.data(), param.r2c,
+                    param.r2c_ctx);
+    check(h, bioem_hip_ctf_scan(h, req.data(), (int) req.size(), ownLists, kernels.data(), triples.data() + 3 * (size_t) g0, nG,
+                                table.data(), nullptr, nullptr),
+          "CTF scan");
+    for (size_t i = 0; i < req.size(); i++)
+      std::copy(table.begin() + (size_t) nG * i, table.begin() + (size_t) nG * (i + 1),
+                logp.begin() + (size_t) G * (size_t) who[i] + (size_t) g0);
+  }
+  const std::string err = write_ctf_scan(file.c_str(), logp.data(), triples.data(), counts, nMaps, orient.data(), shiftX.data(),
+                                         shiftY.data(), param.usepsf, param.elecwavel, numconst.data());
+  if (!err.empty())
+    fatal("--CTFScan: %s", err.c_str());
+  std::cout << "CTF scan of " << nMaps << " particles' best matches over " << G << " candidate sets written to: " << file
+            << "\n";
+}
+
 // --OrientStats: every shard's sums over the orientations it owns (bioem_hip_orientation_sums), merged on the host in
 // shard order, then the text file (write_orient_stats)
 void Driver::writeOrientStats(const std::string &file, double numconst)
@@ -1012,6 +1109,8 @@ int Driver::run()
     writeBestFrc(bestFrcFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!bestWindowFile.empty())
     writeBestWindow(bestWindowFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0, param.pd);
+  if (!ctfScanFile.empty())
+    writeCtfScan(ctfScanFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0, param.pd);
   if (!viewAvgFile.empty())
     writeViewAverages(viewAvgFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
   if (!refineFile.empty())
@@ -1088,6 +1187,8 @@ void Driver::runRound2()
     writeBestFrc(bestFrcFile + "_Round2", h, pm.data(), 1);
   if (!bestWindowFile.empty())
     writeBestWindow(bestWindowFile + "_Round2", h, pm.data(), 1, pd2);
+  if (!ctfScanFile.empty())
+    writeCtfScan(ctfScanFile + "_Round2", h, pm.data(), 1, pd2);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), (size_t) G);
   bioem_hip_destroy(h);
@@ -1185,6 +1286,8 @@ void Driver::runRound2Seeds()
     writeBestFrc(bestFrcFile + "_Round2", h, pm.data(), 1);
   if (!bestWindowFile.empty())
     writeBestWindow(bestWindowFile + "_Round2", h, pm.data(), 1, pd2, volu.data());
+  if (!ctfScanFile.empty())
+    writeCtfScan(ctfScanFile + "_Round2", h, pm.data(), 1, pd2, volu.data());
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), 0, offsets.data(),
                  volu.data());

@@ -582,10 +582,58 @@ void InputParams::calculateGridsParam(const char *anglefile)
   }
 }
 
+// One CTF (Fourier space) or PSF (real space + r2c) kernel [N][H] (re, im) for the triple (amp, phase, env); real: N N
+// floats of scratch in PSF mode.  In CTF mode frequency index i is written to rows i AND N-1-i, for i < N/2+1 (kept).
+static void ctf_kernel_one(int N, float pixelSize, bool usepsf, float amp, float phase, float env, float *cur,
+                           std::vector<float> &real, void (*r2c)(void *, int, const float *, float *), void *ctx)
+{
+  const int H = N / 2 + 1;
+  const size_t M = (size_t) N * H;
+  const int half = N / 2;
+  for (size_t e = 0; e < 2 * M; e++)
+    cur[e] = 0.f;
+  const float quad = sqrtf(1 - amp * amp); // float sqrt of a float argument
+  if (usepsf)
+  {
+    float norm = 0.f;
+    for (int i = 0; i < N; i++)
+      for (int j = 0; j < N; j++)
+      {
+        const int ri = i <= half ? i : N - i;
+        const int rj = j <= half ? j : N - j;
+        const float radsq = (float) (ri * ri + rj * rj) * pixelSize * pixelSize;
+        const float v = (float) (exp(-radsq * env / 2.0) *
+                                 (-amp * cos(radsq * phase / 2.0) - quad * sin(radsq * phase / 2.0)));
+        real[(size_t) i * N + j] = v;
+        norm += v;
+      }
+    for (size_t e = 0; e < (size_t) N * N; e++)
+      real[e] = real[e] / norm;
+    r2c(ctx, N, real.data(), cur);
+  }
+  else
+  {
+    if (amp < 0.0000000001)
+      fatal("CTF normalization AMP less than threshold < 10^-10");
+    float norm = 0.f;
+    for (int i = 0; i < H; i++)
+      for (int j = 0; j < H; j++)
+      {
+        const float radsq = (float) (i * i + j * j) / N / N / pixelSize / pixelSize;
+        const float v = (float) (exp(-env * radsq / 2.) *
+                                 (-amp * cos(phase * radsq / 2.) - quad * sin(phase * radsq / 2.)));
+        if (i == 0 && j == 0)
+          norm = v;
+        const float k = v / norm;
+        cur[2 * ((size_t) i * H + j)] = k;
+        cur[2 * ((size_t) (N - 1 - i) * H + j)] = k;
+      }
+  }
+}
+
 // CTF (Fourier space) or PSF (real space + r2c) kernels on the amp x phase x env grid.
 // Quirks kept on purpose (they shift log P systematically):
-//  * a one-point grid uses step := start;
-//  * in CTF mode frequency index i is written to rows i AND N-1-i, for i < N/2+1.
+//  * a one-point grid uses step := start.
 int ctf_kernels(int N, float pixelSize, bool usepsf, float startAmp, float endAmp, int nAmp, float startPhase,
                 float endPhase, int nPhase, float startEnv, float endEnv, int nEnv, float *refCTF, float *ctfParam,
                 float *steps, void (*r2c)(void *, int, const float *, float *), void *ctx)
@@ -624,7 +672,6 @@ int ctf_kernels(int N, float pixelSize, bool usepsf, float startAmp, float endAm
       fatal("PSF mode needs a forward transform");
     real.resize((size_t) N * N);
   }
-  const int half = N / 2;
   int n = 0;
   for (int ia = 0; ia < nAmp; ia++)
   {
@@ -635,46 +682,7 @@ int ctf_kernels(int N, float pixelSize, bool usepsf, float startAmp, float endAm
       for (int ie = 0; ie < nEnv; ie++)
       {
         const float env = (float) ie * gEnv + startEnv;
-        float *cur = refCTF + 2 * M * (size_t) n;
-        for (size_t e = 0; e < 2 * M; e++)
-          cur[e] = 0.f;
-        const float quad = sqrtf(1 - amp * amp); // float sqrt of a float argument
-        if (usepsf)
-        {
-          float norm = 0.f;
-          for (int i = 0; i < N; i++)
-            for (int j = 0; j < N; j++)
-            {
-              const int ri = i <= half ? i : N - i;
-              const int rj = j <= half ? j : N - j;
-              const float radsq = (float) (ri * ri + rj * rj) * pixelSize * pixelSize;
-              const float v = (float) (exp(-radsq * env / 2.0) *
-                                       (-amp * cos(radsq * phase / 2.0) - quad * sin(radsq * phase / 2.0)));
-              real[(size_t) i * N + j] = v;
-              norm += v;
-            }
-          for (size_t e = 0; e < (size_t) N * N; e++)
-            real[e] = real[e] / norm;
-          r2c(ctx, N, real.data(), cur);
-        }
-        else
-        {
-          if (amp < 0.0000000001)
-            fatal("CTF normalization AMP less than threshold < 10^-10");
-          float norm = 0.f;
-          for (int i = 0; i < H; i++)
-            for (int j = 0; j < H; j++)
-            {
-              const float radsq = (float) (i * i + j * j) / N / N / pixelSize / pixelSize;
-              const float v = (float) (exp(-env * radsq / 2.) *
-                                       (-amp * cos(phase * radsq / 2.) - quad * sin(phase * radsq / 2.)));
-              if (i == 0 && j == 0)
-                norm = v;
-              const float k = v / norm;
-              cur[2 * ((size_t) i * H + j)] = k;
-              cur[2 * ((size_t) (N - 1 - i) * H + j)] = k;
-            }
-        }
+        ctf_kernel_one(N, pixelSize, usepsf, amp, phase, env, refCTF + 2 * M * (size_t) n, real, r2c, ctx);
         ctfParam[3 * n + 0] = amp;
         ctfParam[3 * n + 1] = phase;
         ctfParam[3 * n + 2] = env;
@@ -683,6 +691,24 @@ int ctf_kernels(int N, float pixelSize, bool usepsf, float startAmp, float endAm
     }
   }
   return n;
+}
+
+// the kernels of G triples {amp, phase, env} handed in (the --CTFScan candidates): the same expression per triple as the
+// grid's, so a triple that is a grid point carries the grid kernel's bits
+void ctf_kernel_list(int N, float pixelSize, bool usepsf, const float *triples, int G, float *out,
+                     void (*r2c)(void *, int, const float *, float *), void *ctx)
+{
+  const size_t M = (size_t) N * (N / 2 + 1);
+  std::vector<float> real;
+  if (usepsf)
+  {
+    if (!r2c)
+      fatal("PSF mode needs a forward transform");
+    real.resize((size_t) N * N);
+  }
+  for (int g = 0; g < G; g++)
+    ctf_kernel_one(N, pixelSize, usepsf, triples[3 * g], triples[3 * g + 1], triples[3 * g + 2], out + 2 * M * (size_t) g, real,
+                   r2c, ctx);
 }
 
 // param.cpp:1600-1607.  The expression is float up to the first double literal; the second displacement

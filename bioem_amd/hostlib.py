@@ -45,6 +45,21 @@ def ctf_kernels(N, pixelSize, amp, phase, env):
     return ref, par, steps
 
 
+def psf_kernels(N, pixelSize, amp, phase, env, device=0):
+    """ctf_kernels in PSF mode: the real-space kernels transformed on `device`, as the CLI's set-up makes them"""
+    L = load_host_library()
+    ci, cf, vp = C.c_int, C.c_float, C.c_void_p
+    L.bioem_host_psf_kernels.argtypes = [ci, cf, cf, cf, ci, cf, cf, ci, cf, cf, ci, vp, vp, vp, ci]
+    n = amp[2] * phase[2] * env[2]
+    ref = np.zeros((n, N, N // 2 + 1, 2), dtype=np.float32)
+    par = np.zeros((n, 3), dtype=np.float32)
+    steps = np.zeros(3, dtype=np.float32)
+    got = L.bioem_host_psf_kernels(N, pixelSize, amp[0], amp[1], amp[2], phase[0], phase[1], phase[2], env[0], env[1],
+                                   env[2], ref.ctypes.data, par.ctypes.data, steps.ctypes.data, int(device))
+    assert got == n
+    return ref, par, steps
+
+
 def volume_element(voluang, gridSpace, maxD, pixelSize, nAmp, gridEnv, gridPhase, sigB, sigDef, sigAmp):
     return load_host_library().bioem_host_volume_element(voluang, gridSpace, maxD, pixelSize, nAmp, gridEnv,
                                                         gridPhase, sigB, sigDef, sigAmp)
@@ -323,3 +338,60 @@ def read_orientation_list(paramfile, anglefile, cap=1 << 20):
     pri = np.zeros(n, dtype=np.float32)
     L.bioem_host_read_orientation_list(paramfile.encode(), af, ang.ctypes.data, pri.ctypes.data, n, C.byref(has))
     return ang, (pri if has.value else None)
+
+
+def ctf_kernel_list(N, pixelSize, triples, usepsf=False, device=0):
+    """the kernels float32 [G, N, H, 2] of G triples (amp, phase, env) in the reference's internal units: per triple the
+    expression of ctf_kernels, so a triple of the grid carries the grid kernel's bits.  PSF mode transforms on `device`."""
+    L = load_host_library()
+    L.bioem_host_ctf_kernel_list.argtypes = [C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    t = np.ascontiguousarray(triples, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros((len(t), int(N), int(N) // 2 + 1, 2), dtype=np.float32)
+    if L.bioem_host_ctf_kernel_list(int(N), float(pixelSize), int(bool(usepsf)), t.ctypes.data, len(t), out.ctypes.data,
+                                    int(device)):
+        raise ValueError("ctf_kernel_list: N < 2 or no triples")
+    return out
+
+
+def ctf_scan_refine(start, step, n, k):
+    """the --CTFScan candidates as the CLI forms them (ctf_scan_refine): (triples float32 [G, 3], counts int32 [3]) from the
+    grid's start, step and point count per axis (amp, phase, env); ValueError for a factor the CLI refuses"""
+    L = load_host_library()
+    L.bioem_host_ctf_scan_refine.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]
+    a = np.ascontiguousarray(start, dtype=np.float32)
+    g = np.ascontiguousarray(step, dtype=np.float32)
+    m = np.ascontiguousarray(n, dtype=np.int32)
+    assert a.shape == g.shape == m.shape == (3,)
+    counts = np.zeros(3, dtype=np.int32)
+    G = L.bioem_host_ctf_scan_refine(a.ctypes.data, g.ctypes.data, m.ctypes.data, int(k), counts.ctypes.data, None)
+    if G < 0:
+        raise ValueError("factor %r is not one of 1, 2, 4, 8, 16" % (k,))
+    t = np.zeros((G, 3), dtype=np.float32)
+    assert L.bioem_host_ctf_scan_refine(a.ctypes.data, g.ctypes.data, m.ctypes.data, int(k), counts.ctypes.data,
+                                        t.ctypes.data) == G
+    return t, counts
+
+
+def write_ctf_scan(path, logp, triples, counts, orient, shiftX, shiftY, numconst, usepsf=False, elecwavel=0.019866):
+    """the --CTFScan text file of scan tables [nMaps, G] (Engine.best_match_ctf_scan) over the candidates triples [G, 3]
+    with counts [3] values per axis: the writer the CLI uses; bioem_amd.ctf_scan.parse reads it back.  orient, shiftX,
+    shiftY [nMaps]: the records (orient < 0: a particle without a table); numconst: the constant of every particle's
+    LogProb (a scalar or [nMaps])"""
+    L = load_host_library()
+    vp = C.c_void_p
+    L.bioem_host_write_ctf_scan.argtypes = [C.c_char_p, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_float, vp, C.c_char_p,
+                                            C.c_int]
+    t = np.ascontiguousarray(logp, dtype=np.float64)
+    k = np.ascontiguousarray(triples, dtype=np.float32)
+    cn = np.ascontiguousarray(counts, dtype=np.int32)
+    assert t.ndim == 2 and k.shape == (t.shape[1], 3) and cn.shape == (3,) and int(cn.prod()) == t.shape[1]
+    o = np.ascontiguousarray(orient, dtype=np.int32)
+    sx = np.ascontiguousarray(shiftX, dtype=np.int32)
+    sy = np.ascontiguousarray(shiftY, dtype=np.int32)
+    nc = np.ascontiguousarray(np.broadcast_to(np.asarray(numconst, dtype=np.float64), (t.shape[0],)))
+    assert o.shape == sx.shape == sy.shape == (t.shape[0],)
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_ctf_scan(path.encode(), t.ctypes.data, k.ctypes.data, cn.ctypes.data, t.shape[0], o.ctypes.data,
+                                   sx.ctypes.data, sy.ctypes.data, int(bool(usepsf)), float(elecwavel), nc.ctypes.data, err,
+                                   512):
+        raise ValueError(err.value.decode())

@@ -415,6 +415,44 @@ int bioem_hip_window_posterior(bioem_hip_handle h, const bioem_hip_window_reques
 int bioem_hip_debug_window(bioem_hip_handle h, const float *specConv, const float *specRef, const bioem_hip_param5 *params,
                            const float *sumRef, const float *sumsqRef, int n, double *logp_out, float *cc_out);
 
+/* ---- Posterior over a list of CTF sets at any match: one projection against many kernels (no reference counterpart) ----
+ * The counterpart of bioem_hip_window_posterior on the CTF axes: that entry gives every cell of the displacement window
+ * for one CTF set of the handle, this one every CTF set of an arbitrary list for one cell.  With the symbols of the
+ * section above, for request (p, o, X, Y) and candidate g with kernel K_g and parameters {amp, pha, env}_g:
+ *   conv_g = P_o conj(K_g) in float, the unfused expression of the convolution; sumC its real part at the origin;
+ *   sumsquareC = the reference's sequential float chain over the Parseval terms in the reference's order (rows; inside a
+ *       row the interior columns doubled, then column 0, then column N / 2 for even N), then the division by N N: for a
+ *       candidate that is one of the handle's own CTF sets, sumC and sumsquareC carry the bits of
+ *       bioem_hip_debug_convolution;
+ *   S = sum_k w_ky Re( conv_g[k] conj(F_p[k]) exp(+2 pi i ((kx dx + ky dy) mod N) / N) ), dx = -X, dy = -Y: the products
+ *       in double from the float spectra, the twiddle index reduced in integers, the sum in double in a fixed order;
+ *   cc = (float) S / (float) (N N);  logp = the reference's calc_logpro at cc with {amp, pha, env, sumC, sumsquareC} of
+ *       the candidate (the CTF priors enter as in a run), kept in double for both ALGOs.
+ * This is the cell (X, Y) of what bioem_hip_window_posterior would give had K_g been CTF set g of the handle; a shift
+ * need not be a cell of the handle's window.  The kernels are taken as handed in (PSF-mode kernels included).  A
+ * (request, candidate) result depends on its own inputs alone: the same bits for any G, any order or subset of candidates
+ * or requests, and any batch size.
+ * Calling rules of bioem_hip_window_posterior (the handle's CTF sets need not be uploaded).  Refused with 2, the request
+ * named and the handle usable: a null argument or n < 1; null kernels or ctfParam3; G < 1; particle outside [0, nMaps);
+ * orient outside its list; |shiftX| or |shiftY| >= N; model, orientations or particles not uploaded; ownLists = 1 without
+ * own lists.  Staging is allocated at the first call and grown to the largest G (1 when the memory is not there; the
+ * handle is as it was).  Batches of maxOrientations requests are projected and prepared one after the other; one launch
+ * of the scan serves up to 16 of them (as many as keep the prepared spectra within 512 MiB).  Phase records: 0 the
+ * projection and 1 the preparation of a batch (with the first batch the packing of the candidates), 2 the scan of the
+ * batches gathered; iOrientBegin / iOrientEnd the requests of the batch, for phase 2 of the launch. */
+typedef struct { int particle, orient, shiftX, shiftY; } bioem_hip_scan_request;   /* 16 bytes */
+int bioem_hip_ctf_scan(bioem_hip_handle h, const bioem_hip_scan_request *req, int n, int ownLists,
+                       const float *kernels   /* [G][N][H] (re, im), the layout bioem_hip_upload_ctf takes */,
+                       const float *ctfParam3 /* [G] {amp, phase, env} */, int G,
+                       double *logp_out /* [n][G] */, float *cc_out /* [n][G] or NULL */,
+                       bioem_hip_param5 *params_out /* [n][G] or NULL */);
+/* test hook: the same kernels on spectra handed in (specP, specRef = [n][N][H] (re, im), reference layout; the particles'
+ * sums per record; needs only the handle's parameters) */
+int bioem_hip_debug_ctf_scan(bioem_hip_handle h, const float *specP, const float *specRef, const float *sumRef,
+                             const float *sumsqRef, const int *shiftXY /* [n][2] */, int n, const float *kernels,
+                             const float *ctfParam3, int G, double *logp_out, float *cc_out,
+                             bioem_hip_param5 *params_out);
+
 /* ---- Summaries of the orientation posterior of every particle (WRITE_PROB_ANGLES; no reference counterpart) ----
  * The [orientations][nMaps] table of bioem_hip_prob_angle stays on the device; this entry reduces it there.  Let
  * F = forAngles, C = ConstAngle of entry (o, p).  Only entries with F > 0 count (entries never compared, or beyond a
