@@ -1022,23 +1022,78 @@ struct OrientList
 OrientList shared_list(const bioem_hip_ctx *h) { return {h->dAngles, h->isQuat, h->quatNormDev}; }
 OrientList own_list(const bioem_hip_ctx *h) { return {h->dOwnAngles, h->ownIsQuat, h->ownQuatNormDev}; }
 
-int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, const OrientList &L, int o0, int nO)
+// what a projection of this model under this list takes: kProjectBox (k_project_box), kProjectBands (k_project_coords +
+// k_project_bands) or kProjectAtomics (k_project), with the geometry the launch needs
+enum
 {
+  kProjectAuto = 0,
+  kProjectBox = 1,
+  kProjectBands = 2,
+  kProjectAtomics = 3
+};
+struct ProjectPlan
+{
+  int path;
+  int boxLo, boxSide, compact; // the box the host sizes for the model, whatever the path; compact: the box alone is stored
+  int TR;                      // rows of one LDS band
+  const char *refused;         // a forced path whose preconditions do not hold: why (path is then kProjectAuto)
+};
+
+// force = kProjectAuto: what a run takes; else that path, or `refused` where its preconditions do not hold
+ProjectPlan project_plan(const bioem_hip_ctx *h, const OrientList &L, int force)
+{
+  ProjectPlan P = {};
   const int N = h->N;
   // the pixels a point of the model can reach in any orientation, with its footprint: a box around the map centre
   const double reach = h->modelRadius / (double) h->pixelSize;
   const int boxLo = std::max(0, (int) std::floor(N / 2.0 + 0.5 - reach) - 1 - h->iradMax - std::max(0, std::max(h->shiftX, h->shiftY)));
   const int boxHi = std::min(N - 1, (int) std::floor(N / 2.0 + 0.5 + reach) + 1 + h->iradMax - std::min(0, std::min(h->shiftX, h->shiftY)));
   const int boxSide = boxHi - boxLo + 1;
+  P.boxLo = boxLo;
+  P.boxSide = boxSide;
   // (orientations that stretch the model -- quaternions that are not of unit length -- take the band kernel: the box
   // has one pixel of margin; the matrix entries of a quaternion with |q|^2 = 1 + e are off by at most ~3 e, and half a
   // pixel is granted to that)
   const bool keepLength = L.quatNormDev * 4.0 * std::max(1.0, reach) < 0.5;
-  if (h->dStamp && boxSide >= 1 && (size_t) boxSide * boxSide * sizeof(double) <= 52 * 1024 && N < 32768 &&
-      keepLength)
+  P.TR = 40960 / (8 * N); // rows of one LDS band: three blocks per CU
+  // the record of every (orientation, point) borrows the row-pass buffer of the r2c that follows
+  const bool coordsFit = (size_t) h->nPts * sizeof(ProjectRecord) <= (size_t) N * h->H * sizeof(double2);
+  const bool boxFits = boxSide >= 1 && (size_t) boxSide * boxSide * sizeof(double) <= 52 * 1024;
+  const bool boxOk = h->dStamp && boxFits && N < 32768 && keepLength;
+  const bool bandsOk = P.TR >= 12 && h->iradMax <= 16 && h->dStamp && N < 32768 && coordsFit;
+  if (force == kProjectBox && !boxOk)
+    P.refused = !h->dStamp ? "the model has no footprint table" : !boxFits ? "the model's box does not fit 52 KiB of LDS"
+                : !keepLength ? "the list holds quaternions that are not of unit length" : "the image is too large";
+  else if (force == kProjectBands && !bandsOk)
+    P.refused = !h->dStamp       ? "the model has no footprint table"
+                : P.TR < 12      ? "a band of the image holds fewer than 12 rows"
+                : h->iradMax > 16 ? "a footprint is wider than 33 pixels"
+                : !coordsFit     ? "the records of the points do not fit the row-pass buffer"
+                                 : "the image is too large";
+  else
+    P.path = force != kProjectAuto ? force : boxOk ? kProjectBox : bandsOk ? kProjectBands : kProjectAtomics;
+  // with the fast r2c behind it the box kernel stores the box alone and the transform skips everything outside it
+  P.compact = P.path == kProjectBox && r2c_use_fft(N);
+  return P;
+}
+
+// force, taken: bioem_hip_debug_projection_maps; a refused path returns 2 with the reason in h->err and launches nothing
+int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, const OrientList &L, int o0, int nO,
+                  int force = kProjectAuto, ProjectPlan *taken = nullptr)
+{
+  const int N = h->N;
+  const ProjectPlan P = project_plan(h, L, force);
+  if (taken)
+    *taken = P;
+  if (P.refused)
   {
-    // with the fast r2c behind it the kernel stores the box alone and the transform skips everything outside it
-    const int compact = r2c_use_fft(N);
+    h->err = std::string("projection path ") + std::to_string(force) + ": " + P.refused;
+    return 2;
+  }
+  const int boxLo = P.boxLo, boxSide = P.boxSide, TR = P.TR;
+  if (P.path == kProjectBox)
+  {
+    const int compact = P.compact;
     hipLaunchKernelGGL(k_project_box, dim3(std::min(nO, 3 * h->nCU)), dim3(256), sizeof(double) * boxSide * boxSide, st,
                        h->dPts, h->nPts, L.d, o0, L.isQuat, N, h->pixelSize, h->shiftX, h->shiftY, h->iradMax,
                        h->dStamp, boxLo, boxSide, nO, compact, bb.projReal, bb.tempDen);
@@ -1046,10 +1101,7 @@ int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t s
     return compact ? run_r2c(h, bb, st, bb.projReal, nullptr, nO, boxLo, boxSide) : run_r2c(h, bb, st, bb.projReal, nullptr, nO);
   }
   HIP_CHECK(h, hipMemsetAsync(bb.tempDen, 0, sizeof(double) * nO, st)); // (k_project_box writes its sums itself)
-  const int TR = 40960 / (8 * N); // rows of one LDS band: three blocks per CU
-  // the record of every (orientation, point) borrows the row-pass buffer of the r2c that follows
-  const bool coordsFit = (size_t) h->nPts * sizeof(ProjectRecord) <= (size_t) N * h->H * sizeof(double2);
-  if (TR >= 12 && h->iradMax <= 16 && h->dStamp && N < 32768 && coordsFit)
+  if (P.path == kProjectBands)
   {
     ProjectRecord *coords = reinterpret_cast<ProjectRecord *>(bb.rowSpec);
     hipLaunchKernelGGL(k_project_coords, dim3((h->nPts + 255) / 256, nO), dim3(256), 0, st, h->dPts, h->nPts, L.d,
@@ -4128,6 +4180,78 @@ int bioem_hip_debug_projection(bioem_hip_handle h, int iOrient, float *spec_out)
     return 1;
   HIP_CHECK(h, hipMemcpyAsync(spec_out, s0.specRef, sizeof(float2) * (size_t) h->M, hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int bioem_hip_debug_projection_maps(bioem_hip_handle h, int o0, int nO, int path, double *maps_out, double *tempden_out,
+                                    float *spec_out, int *info_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  auto refuse = [&](const std::string &why) {
+    h->err = "debug_projection_maps: " + why;
+    return 2;
+  };
+  if (!maps_out || !tempden_out || !info_out)
+    return refuse("null argument");
+  if (!h->dPts || h->nAnglesUp < 1)
+    return refuse("model or orientations not uploaded");
+  if (path < kProjectAuto || path > kProjectAtomics)
+    return refuse("path must be 0 (as a run), 1 (box), 2 (bands) or 3 (global atomics)");
+  if (nO < 1 || nO > h->OB)
+    return refuse("between 1 and maxOrientations (" + std::to_string(h->OB) + ") orientations per call");
+  if (o0 < 0 || o0 > h->nAnglesUp - nO)
+    return refuse("orientations outside the uploaded list");
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  ProjectPlan P;
+  const int rc = project_batch(h, s0, h->stream, shared_list(h), o0, nO, path, &P);
+  if (rc == 2)
+    return refuse(h->err);
+  if (rc)
+    return rc;
+  const int N = h->N;
+  const size_t NN = (size_t) N * N;
+  HIP_CHECK(h, hipMemcpyAsync(tempden_out, s0.tempDen, sizeof(double) * (size_t) nO, hipMemcpyDeviceToHost, h->stream));
+  if (spec_out)
+    HIP_CHECK(h, hipMemcpyAsync(spec_out, s0.specRef, sizeof(float2) * (size_t) h->M * nO, hipMemcpyDeviceToHost, h->stream));
+  if (P.compact)
+  { // [nO][side][side] on the device: the box goes into place, zeros around it
+    const size_t side = (size_t) P.boxSide;
+    std::vector<double> box(side * side * nO);
+    HIP_CHECK(h, hipMemcpyAsync(box.data(), s0.projReal, sizeof(double) * box.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    std::fill(maps_out, maps_out + NN * nO, 0.);
+    for (int b = 0; b < nO; b++)
+      for (size_t r = 0; r < side; r++)
+        std::copy(box.begin() + (b * side + r) * side, box.begin() + (b * side + r + 1) * side,
+                  maps_out + b * NN + (P.boxLo + r) * N + P.boxLo);
+  }
+  else
+  {
+    HIP_CHECK(h, hipMemcpyAsync(maps_out, s0.projReal, sizeof(double) * NN * nO, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  const int info[6] = {P.path, P.boxLo, P.boxSide, P.compact, P.TR, h->iradMax};
+  std::copy(info, info + 6, info_out);
+  return 0;
+}
+
+int bioem_hip_debug_stamps(bioem_hip_handle h, double *stamps_out, int *iradMax_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (!iradMax_out || !h->dStamp)
+  {
+    h->err = !h->dStamp ? "debug_stamps: the model has no footprint table" : "debug_stamps: null argument";
+    return 2;
+  }
+  const size_t S = 2 * (size_t) h->iradMax + 1;
+  *iradMax_out = h->iradMax;
+  if (stamps_out) // (null: the caller asks for iradMax to size the table)
+    HIP_CHECK(h, hipMemcpy(stamps_out, h->dStamp, sizeof(double) * (size_t) h->nPts * S * S, hipMemcpyDeviceToHost));
   return 0;
 }
 

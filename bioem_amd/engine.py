@@ -131,6 +131,9 @@ def load_library():
     L.bioem_hip_merge.argtypes = [C.POINTER(vp), ci, vp, ci, C.c_double, vp]
     L.bioem_hip_merge_host.argtypes = [ci, ci, ci, ci, C.POINTER(vp), vp]
     L.bioem_hip_debug_projection.argtypes = [vp, ci, vp]
+    if hasattr(L, "bioem_hip_debug_projection_maps"):
+        L.bioem_hip_debug_projection_maps.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp]
+        L.bioem_hip_debug_stamps.argtypes = [vp, vp, C.POINTER(ci)]
     L.bioem_hip_debug_convolution.argtypes = [vp, ci, ci, vp, C.POINTER(cf), C.POINTER(cf)]
     L.bioem_hip_debug_particles.argtypes = [vp, vp, vp, vp]
     L.bioem_hip_kernel_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
@@ -168,7 +171,7 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_orientation_sums", "bioem_hip_merge_orient_sums_host", "bioem_hip_debug_orient_sums",
            "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy",
            "bioem_hip_view_sums", "bioem_hip_view_averages", "bioem_hip_debug_view_sums",
-           "bioem_hip_set_compare_variant"]
+           "bioem_hip_set_compare_variant", "bioem_hip_debug_projection_maps", "bioem_hip_debug_stamps"]
 
 
 def _p(a):
@@ -299,6 +302,7 @@ class Engine:
         assert points.dtype.itemsize == 24
         self._chk(self.L.bioem_hip_upload_model(self.h, _p(points), len(points), float(NormDen), float(pixelSize),
                                                 int(shiftX), int(shiftY)), "upload_model")
+        self._nPts = len(points)
 
     def upload_orientations(self, angles, isQuat):
         angles = np.ascontiguousarray(angles, dtype=np.float32)
@@ -796,6 +800,39 @@ class Engine:
         out = np.empty((self.N, self.H, 2), dtype=np.float32)
         self._chk(self.L.bioem_hip_debug_projection(self.h, iOrient, _p(out)), "debug_projection")
         return out
+
+    PROJECTION_PATHS = {"auto": 0, "box": 1, "bands": 2, "atomics": 3}
+
+    def debug_projection_maps(self, o0, nO, path="auto", want_spec=False):
+        """the real-space projections of orientations [o0, o0 + nO) of the shared list (bioem_hip_debug_projection_maps;
+        nO <= max_batch()[0]): (maps float64 [nO, N, N], tempden float64 [nO], spec float32 [nO, N, H, 2] or None,
+        info).  path: "auto" (what a run takes), "box", "bands", "atomics" or 0...3; info: dict path / boxLo / boxSide /
+        compact / TR / iradMax.  A forced path the model, list or size does not allow raises with .rc == 2; the handle
+        stays usable."""
+        nO = int(nO)
+        maps = np.zeros((max(nO, 0), self.N, self.N), dtype=np.float64)
+        td = np.zeros(max(nO, 0), dtype=np.float64)
+        spec = np.zeros((max(nO, 0), self.N, self.H, 2), dtype=np.float32) if want_spec else None
+        info = np.zeros(6, dtype=np.int32)
+        rc = self.L.bioem_hip_debug_projection_maps(self.h, int(o0), nO, int(self.PROJECTION_PATHS.get(path, path)),
+                                                    _p(maps), _p(td), _p(spec), _p(info))
+        if rc:
+            self._view_raise("debug_projection_maps", rc)
+        return maps, td, spec, dict(zip(("path", "boxLo", "boxSide", "compact", "TR", "iradMax"), map(int, info)))
+
+    def debug_stamps(self):
+        """the footprint table of the uploaded model (bioem_hip_debug_stamps): (stamps float64 [nPts, S, S], iradMax),
+        S = 2 iradMax + 1; raises with .rc == 2 where the model has none"""
+        irad = C.c_int()
+        rc = self.L.bioem_hip_debug_stamps(self.h, None, C.byref(irad))
+        if rc:
+            self._view_raise("debug_stamps", rc)
+        S = 2 * irad.value + 1
+        out = np.zeros((self._nPts, S, S), dtype=np.float64)
+        rc = self.L.bioem_hip_debug_stamps(self.h, _p(out), C.byref(irad))
+        if rc:
+            self._view_raise("debug_stamps", rc)
+        return out, irad.value
 
     def debug_convolution(self, iOrient, iConv):
         out = np.empty((self.N, self.H, 2), dtype=np.float32)

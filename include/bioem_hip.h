@@ -313,6 +313,18 @@ int bioem_hip_phase_records(bioem_hip_handle h, bioem_hip_phase_record *out, int
 /* ---- instrumentation / test hooks (no reference equivalent) ---- */
 /* projection spectrum of one orientation in reference layout [N][N/2+1][2] */
 int bioem_hip_debug_projection(bioem_hip_handle h, int iOrient, float *spec_out);
+/* The real-space projections of orientations [o0, o0 + nO) of the shared list, one batch through buffer set 0 (outside a
+ * run; nO <= maxOrientations of bioem_hip_max_batch): maps_out [nO][N][N] double (a box stored compactly on the device
+ * is put into place, zeros around it), tempden_out [nO] double, spec_out NULL or [nO][N][N/2+1][2] float in reference
+ * layout, info_out [6] int = {path taken, boxLo, boxSide, compact, TR, iradMax}.  path: 0 what a run takes, 1 the box
+ * kernel, 2 records + bands, 3 global atomics.  A forced path whose preconditions do not hold (no footprint table, box
+ * beyond 52 KiB, a quaternion list not of unit length, bands of fewer than 12 rows, footprints beyond 33 pixels, records
+ * that do not fit) and every other invalid argument are refused with 2 and a message; the handle stays usable. */
+int bioem_hip_debug_projection_maps(bioem_hip_handle h, int o0, int nO, int path, double *maps_out, double *tempden_out,
+                                    float *spec_out, int *info_out);
+/* the footprint table of the model, stamps_out [nPts][S][S] double with S = 2 iradMax + 1 (stamps_out NULL: iradMax
+ * alone); 2 where the model has none (a footprint beyond 33 pixels, no points) */
+int bioem_hip_debug_stamps(bioem_hip_handle h, double *stamps_out, int *iradMax_out);
 /* conv spectrum + {sumC, sumsquareC} of (iOrient, iConv) in reference layout */
 int bioem_hip_debug_convolution(bioem_hip_handle h, int iOrient, int iConv, float *spec_out, float *sumC,
                                 float *sumsquareC);
