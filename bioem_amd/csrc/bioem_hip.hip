@@ -59,6 +59,9 @@
 //   scan_kernels.hpp     k_scan_pack, k_scan_prep, k_ctf_scan  bioem_hip_ctf_scan: the log posterior of a (particle,
 //                          orientation, shift) request under every CTF set of a list, lane = candidate (kernels_scan.hip;
 //                          declarations only here)
+//   grad_kernels.hpp     k_grad_coef, k_grad_spectrum, k_grad_cols, k_grad_rows, k_grad_gather, k_grad_norm, k_grad_fold
+//                          bioem_hip_model_gradient: the derivative of a request's log posterior with respect to the
+//                          density of every model point (kernels_grad.hip; declarations only here)
 //   orient_kernels.hpp   k_orient_max, k_orient_sums, k_orient_fold, k_orient_products  bioem_hip_orientation_sums: the
 //                          orientation posterior of every particle reduced where the angle table lives
 //                          (kernels_orient.hip; declarations only here); k_orient_occ  bioem_hip_orientation_occupancy:
@@ -132,6 +135,7 @@ struct HipErr
 #include "view_kernels.hpp"
 #include "window_kernels.hpp"
 #include "scan_kernels.hpp"
+#include "grad_kernels.hpp"
 #include "orient_kernels.hpp"
 
 struct bioem_hip_ctx
@@ -259,6 +263,17 @@ struct bioem_hip_ctx
   double *dScanLogp = nullptr;
   bioem_hip_param5 *dScanParams = nullptr;
   int scanCapG = 0;
+  // bioem_hip_model_gradient / bioem_hip_debug_grad_image / _gather: a batch's records, coefficients {a, b, g, m}, weights,
+  // {m, T}, parameters, gradient spectra and maps (allocated at the first call, with the scan staging the entry shares);
+  // u, v sigma, the tiles' partial sums and the rows of a batch and the sums per point (grown to the largest model)
+  BioemGradRecord *dGradRec = nullptr;
+  double *dGradCoef = nullptr, *dGradW = nullptr, *dGradMT = nullptr, *dGradMap = nullptr;
+  bioem_hip_param5 *dGradParams = nullptr;
+  double2 *dGradSpec = nullptr;
+  float4 *dGradAngles = nullptr;
+  double *dGradU = nullptr, *dGradVS = nullptr, *dGradPart = nullptr, *dGradRows = nullptr;
+  bioem_hip_grad_point *dGradAcc = nullptr;
+  int gradCapPts = 0;
   // bioem_hip_orientation_sums: scratch of the two passes, the products q_i q_j of the owned orientations, their priors
   // and the result (allocated at the first call)
   double *dOrientScratch = nullptr, *dOrientQQ = nullptr, *dOrientPrior = nullptr;
@@ -3816,6 +3831,360 @@ int bioem_hip_debug_ctf_scan(bioem_hip_handle h, const float *specP, const float
     }
   }
   drain_phases(h);
+  return 0;
+}
+
+// ---- density gradient of the log posterior of a request per model point (grad_kernels.hpp) ----
+static_assert(sizeof(bioem_hip_grad_request) == 20, "request layout");
+
+namespace
+{
+// the staging buffers of the gradient entries; a failed allocation (return 1) leaves the handle as it was
+int grad_staging(bioem_hip_ctx *h, int G, int nPts)
+{
+  if (scan_staging(h, G)) // records, gathered orientations, particle spectra, the scan's preparation and results
+    return 1;
+  const size_t OB = (size_t) h->OB, M = (size_t) h->M, NN = (size_t) h->N * h->N, cap = (size_t) scan_capacity(h);
+  if (!h->dGradMap)
+  { // per record of a launch of the scan: records, coefficients, weights, parameters, orientations; the rest per batch
+    BioemGradRecord *rec = nullptr;
+    double *coef = nullptr, *w = nullptr, *mT = nullptr, *map = nullptr;
+    bioem_hip_param5 *par = nullptr;
+    double2 *spec = nullptr;
+    float4 *ang = nullptr;
+    if (dev_alloc(h, rec, cap) || dev_alloc(h, coef, 4 * cap) || dev_alloc(h, w, cap) || dev_alloc(h, mT, 2 * OB) ||
+        dev_alloc(h, map, OB * NN) || dev_alloc(h, par, cap) || dev_alloc(h, spec, OB * M) || dev_alloc(h, ang, cap))
+    {
+      dev_release(h, ang);
+      dev_release(h, rec);
+      dev_release(h, coef);
+      dev_release(h, w);
+      dev_release(h, mT);
+      dev_release(h, map);
+      dev_release(h, par);
+      dev_release(h, spec);
+      (void) hipGetLastError();
+      return 1;
+    }
+    h->dGradRec = rec;
+    h->dGradCoef = coef;
+    h->dGradW = w;
+    h->dGradMT = mT;
+    h->dGradMap = map;
+    h->dGradParams = par;
+    h->dGradSpec = spec;
+    h->dGradAngles = ang;
+  }
+  if (nPts <= h->gradCapPts)
+    return 0;
+  const size_t P = (size_t) nPts, tiles = (size_t) bioem_grad_tiles(nPts);
+  double *u = nullptr, *vs = nullptr, *part = nullptr, *rows = nullptr;
+  bioem_hip_grad_point *acc = nullptr;
+  if (dev_alloc(h, u, OB * P) || dev_alloc(h, vs, OB * P) || dev_alloc(h, part, 2 * OB * tiles) || dev_alloc(h, rows, OB * P) ||
+      dev_alloc(h, acc, P))
+  {
+    dev_release(h, u);
+    dev_release(h, vs);
+    dev_release(h, part);
+    dev_release(h, rows);
+    dev_release(h, acc);
+    (void) hipGetLastError();
+    return 1;
+  }
+  dev_release(h, h->dGradU);
+  dev_release(h, h->dGradVS);
+  dev_release(h, h->dGradPart);
+  dev_release(h, h->dGradRows);
+  dev_release(h, h->dGradAcc);
+  h->dGradU = u;
+  h->dGradVS = vs;
+  h->dGradPart = part;
+  h->dGradRows = rows;
+  h->dGradAcc = acc;
+  h->gradCapPts = nPts;
+  return 0;
+}
+
+// the handle's own CTF sets as the candidates of the scan: packed from the device copy, a chunk of 64 at a time
+int grad_candidates(bioem_hip_ctx *h)
+{
+  const size_t M = (size_t) h->M;
+  for (int g0 = 0; g0 < h->nCTF; g0 += kScanLanes)
+    HIP_CHECK(h, bioem_scan_pack_launch(h->stream, h->dCTF + M * (size_t) g0, std::min(kScanLanes, h->nCTF - g0), h->N,
+                                        h->dScanPacked + M * (size_t) g0));
+  HIP_CHECK(h, hipMemcpyAsync(h->dScanCtf, h->dCtfParam, sizeof(float) * 3 * h->nCTF, hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+} // namespace
+
+int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *req, const double *weights, int n, int ownLists,
+                             double *grad_out, bioem_hip_grad_point *points_out, bioem_hip_param5 *params_out,
+                             double *coef_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[256];
+  auto refuse = [&](const char *why) {
+    h->err = std::string("model_gradient: ") + why;
+    return 2;
+  };
+  if (!req || n < 1)
+    return refuse("null argument or no requests");
+  if (!grad_out && !points_out)
+    return refuse("grad_out and points_out both null");
+  if (!h->dPts || h->nPts < 1)
+    return refuse("model not uploaded");
+  if (!h->ctfUp)
+    return refuse("CTF kernels not uploaded");
+  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
+    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
+                           : "orientations not uploaded");
+  if (!h->refUp)
+    return refuse("particles not uploaded");
+  const int N = h->N, OB = h->OB, G = h->nCTF, nPts = h->nPts;
+  const int cap = scan_capacity(h); // records one launch of the scan serves: whole batches
+  std::vector<BioemWindowRecord> recs((size_t) n);
+  std::vector<BioemScanShift> shifts((size_t) n);
+  std::vector<BioemGradRecord> grecs((size_t) n);
+  std::vector<double> ws((size_t) n, 1.);
+  for (int i = 0; i < n; i++)
+  {
+    const bioem_hip_grad_request &r = req[i];
+    const char *why = nullptr;
+    int first = 0, len = 0;
+    if (r.particle < 0 || r.particle >= h->nMaps)
+      why = "particle outside [0, nMaps)";
+    else
+    {
+      first = ownLists ? h->ownOff[(size_t) r.particle] : 0;
+      len = ownLists ? h->ownOff[(size_t) r.particle + 1] - first : h->nAnglesUp;
+      if (r.orient < 0 || r.orient >= len)
+        why = "orient outside its orientation list";
+      else if (r.conv < 0 || r.conv >= G)
+        why = "conv outside [0, nCTF)";
+      else if (r.shiftX <= -N || r.shiftX >= N || r.shiftY <= -N || r.shiftY >= N)
+        why = "shift outside (-N, N)";
+      else if (weights && !std::isfinite(weights[i]))
+        why = "weight not finite";
+    }
+    if (why)
+    {
+      snprintf(buf, sizeof(buf), "request %d: %s (particle %d of %d, orient %d of %d, conv %d of %d, shift %d %d, N %d)", i, why,
+               r.particle, h->nMaps, r.orient, len, r.conv, G, r.shiftX, r.shiftY, N);
+      return refuse(buf);
+    }
+    recs[(size_t) i] = {first + r.orient, r.conv, r.particle, 0, {0.f, 0.f}};
+    shifts[(size_t) i] = {r.shiftX, r.shiftY};
+    grecs[(size_t) i] = {r.conv, r.particle, (i % cap) * G + r.conv, 0};
+    if (weights)
+      ws[(size_t) i] = weights[i];
+  }
+  if (grad_staging(h, G, nPts))
+    return 1;
+  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  const OrientList src = ownLists ? own_list(h) : shared_list(h);
+  const OrientList L = {h->dGradAngles, src.isQuat, src.quatNormDev};
+  const size_t M = (size_t) h->M;
+  int A, B;
+  dft_split(N, A, B);
+  HIP_CHECK(h, hipMemsetAsync(h->dGradAcc, 0, sizeof(bioem_hip_grad_point) * nPts, h->stream));
+  for (int g0 = 0; g0 < n; g0 += cap) // the requests one launch of the scan serves
+  {
+    const int ng = std::min(cap, n - g0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradRec, grecs.data() + g0, sizeof(BioemGradRecord) * ng, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradW, ws.data() + g0, sizeof(double) * ng, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_render_gather, dim3((ng + 255) / 256), dim3(256), 0, h->stream, src.d,
+                       reinterpret_cast<const RenderRecord *>(h->dScanRec), ng, h->dGradAngles);
+    HIP_CHECK(h, hipGetLastError());
+    // per batch: the projection and the scan's preparation of its records, into their places of the launch
+    for (int b0 = 0; b0 < ng; b0 += OB)
+    {
+      const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
+      HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shifts.data() + r0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
+      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, r0, r0 + nb, 0, 0) ||
+          project_batch(h, s0, h->stream, L, b0, nb) || phase_end(h, h->stream))
+        return 1;
+      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, r0, r0 + nb, 0, 0))
+        return 1;
+      if (r0 == 0 && grad_candidates(h)) // (part of the first batch's preparation)
+        return 1;
+      // the particles' spectra back in reference layout: one launch per run of consecutive particles
+      for (int i = 0; i < nb;)
+      {
+        int j = i + 1;
+        while (j < nb && recs[(size_t) (r0 + j)].particle == recs[(size_t) (r0 + j - 1)].particle + 1)
+          j++;
+        hipLaunchKernelGGL(k_unreorder, dim3(std::min(1024, 16 * (j - i))), dim3(256), 0, h->stream,
+                           h->dRef + h->Mc * (size_t) recs[(size_t) (r0 + i)].particle, h->dWinRef + M * (size_t) i, j - i, N, h->H,
+                           h->plan.halfR, h->plan.N1, h->Hp);
+        HIP_CHECK(h, hipGetLastError());
+        i = j;
+      }
+      HIP_CHECK(h, bioem_scan_prep_launch(h->stream, s0.specRef, h->dWinRef, h->dScanShift, nb, N, h->dTwD,
+                                          h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0));
+      if (phase_end(h, h->stream))
+        return 1;
+    }
+    // the linearisation point: one scan of the launch's records against the handle's own CTF sets, of which each record
+    // takes its own; then a, b, g
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, g0, g0 + ng, 0, 0))
+      return 1;
+    HIP_CHECK(h, bioem_scan_launch(h->stream, h->dScanPacked, h->dScanCtf, G, h->dScanPw, h->dScanZ, h->dScanRec, h->dSumRef,
+                                   h->dSumsqRef, h->pd, ng, N, h->dScanLogp, h->dScanCc, h->dScanParams));
+    HIP_CHECK(h, bioem_grad_coef_launch(h->stream, h->dGradRec, h->dScanCc, h->dScanParams, h->dSumRef, h->dSumsqRef, ng, N,
+                                        h->dGradCoef, h->dGradParams));
+    if (phase_end(h, h->stream))
+      return 1;
+    for (int b0 = 0; b0 < ng; b0 += OB)
+    {
+      const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
+      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, r0, r0 + nb, 0, 0))
+        return 1;
+      HIP_CHECK(h, bioem_grad_spectrum_launch(h->stream, h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0, h->dCTF,
+                                              h->dGradRec + b0, h->dGradCoef + 4 * (size_t) b0, 0, nb, N, h->dGradSpec));
+      HIP_CHECK(h, bioem_grad_inverse_launch(h->stream, h->dGradSpec, nb, N, A, B, h->dTwD, s0.rowSpec, h->dGradMap));
+      if (phase_end(h, h->stream) || phase_begin(h, h->stream, 3, r0, r0 + nb, 0, 0))
+        return 1;
+      HIP_CHECK(h, bioem_grad_gather_launch(h->stream, h->dPts, nPts, h->dGradAngles, b0, L.isQuat, N, h->pixelSize, h->shiftX,
+                                            h->shiftY, h->dGradMap, nb, h->dGradU, h->dGradVS, h->dGradPart));
+      HIP_CHECK(h, bioem_grad_fold_launch(h->stream, h->dGradU, h->dGradVS, h->dGradPart, h->dGradW + b0, nb, nPts, h->NormDen,
+                                          h->dGradMT, h->dGradCoef + 4 * (size_t) b0, grad_out ? h->dGradRows : nullptr,
+                                          h->dGradAcc));
+      if (phase_end(h, h->stream))
+        return 1;
+      if (grad_out)
+      { // (the rows' staging is reused by the next batch)
+        HIP_CHECK(h, hipMemcpyAsync(grad_out + (size_t) r0 * nPts, h->dGradRows, sizeof(double) * (size_t) nb * nPts,
+                                    hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(h, hipStreamSynchronize(h->stream));
+      }
+    }
+    if (params_out)
+      HIP_CHECK(h, hipMemcpyAsync(params_out + g0, h->dGradParams, sizeof(bioem_hip_param5) * ng, hipMemcpyDeviceToHost, h->stream));
+    if (coef_out)
+      HIP_CHECK(h, hipMemcpyAsync(coef_out + 4 * (size_t) g0, h->dGradCoef, sizeof(double) * 4 * ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  if (points_out)
+    HIP_CHECK(h, hipMemcpy(points_out, h->dGradAcc, sizeof(bioem_hip_grad_point) * nPts, hipMemcpyDeviceToHost));
+  drain_phases(h);
+  return 0;
+}
+
+int bioem_hip_debug_grad_image(bioem_hip_handle h, const float *specConv, const float *specRef, const float *kernels,
+                               const bioem_hip_param5 *params, const float *sumRef, const float *sumsqRef, const int *shiftXY,
+                               int n, double *gmap_out, double *coef_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[160];
+  if (!specConv || !specRef || !kernels || !params || !sumRef || !sumsqRef || !shiftXY || !gmap_out || !coef_out || n < 1)
+  {
+    h->err = "debug_grad_image: null argument or no records";
+    return 2;
+  }
+  const int N = h->N, OB = h->OB;
+  for (int i = 0; i < n; i++)
+    if (shiftXY[2 * i] <= -N || shiftXY[2 * i] >= N || shiftXY[2 * i + 1] <= -N || shiftXY[2 * i + 1] >= N)
+    {
+      snprintf(buf, sizeof(buf), "debug_grad_image: record %d: shift outside (-N, N) (shift %d %d, N %d)", i, shiftXY[2 * i],
+               shiftXY[2 * i + 1], N);
+      h->err = buf;
+      return 2;
+    }
+  if (grad_staging(h, 1, std::max(1, h->nPts)))
+    return 1;
+  if (compat_flush(h))
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  void_slot(s0);
+  const size_t M = (size_t) h->M, NN = (size_t) N * N;
+  int A, B;
+  dft_split(N, A, B);
+  // cc: the scan of the conv spectra against one candidate, the kernel 1 + 0i (the products reproduce conv)
+  std::vector<float2> unit(M, make_float2(1.f, 0.f));
+  const float zero3[3] = {0.f, 0.f, 0.f};
+  HIP_CHECK(h, hipMemcpyAsync(h->dScanRaw, unit.data(), sizeof(float2) * M, hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(h, bioem_scan_pack_launch(h->stream, h->dScanRaw, 1, N, h->dScanPacked));
+  HIP_CHECK(h, hipMemcpyAsync(h->dScanCtf, zero3, sizeof(zero3), hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream)); // (unit and zero3 are read by then)
+  std::vector<BioemWindowRecord> recs((size_t) OB);
+  std::vector<BioemGradRecord> grecs((size_t) OB);
+  for (int b0 = 0; b0 < n; b0 += OB)
+  {
+    const int nb = std::min(OB, n - b0);
+    for (int i = 0; i < nb; i++)
+    {
+      recs[(size_t) i] = {0, 0, i, 0, {0.f, 0.f}};
+      grecs[(size_t) i] = {i, i, i, 0};
+    }
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, recs.data(), sizeof(BioemWindowRecord) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradRec, grecs.data(), sizeof(BioemGradRecord) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shiftXY + 2 * (size_t) b0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinConv, specConv + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinRef, specRef + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(s0.specRef, kernels + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanSums, sumRef + b0, sizeof(float) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanSums + OB, sumsqRef + b0, sizeof(float) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, bioem_scan_prep_launch(h->stream, h->dWinConv, h->dWinRef, h->dScanShift, nb, N, h->dTwD, h->dScanPw, h->dScanZ));
+    HIP_CHECK(h, bioem_scan_launch(h->stream, h->dScanPacked, h->dScanCtf, 1, h->dScanPw, h->dScanZ, h->dScanRec, h->dScanSums,
+                                   h->dScanSums + OB, h->pd, nb, N, h->dScanLogp, h->dScanCc, nullptr));
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradParams, params + b0, sizeof(bioem_hip_param5) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, bioem_grad_coef_launch(h->stream, h->dGradRec, h->dScanCc, h->dGradParams, h->dScanSums, h->dScanSums + OB, nb,
+                                        N, h->dGradCoef, nullptr));
+    HIP_CHECK(h, bioem_grad_spectrum_launch(h->stream, h->dScanPw, h->dScanZ, s0.specRef, h->dGradRec, h->dGradCoef, 1, nb, N,
+                                            h->dGradSpec));
+    HIP_CHECK(h, bioem_grad_inverse_launch(h->stream, h->dGradSpec, nb, N, A, B, h->dTwD, s0.rowSpec, h->dGradMap));
+    HIP_CHECK(h, hipMemcpyAsync(gmap_out + NN * (size_t) b0, h->dGradMap, sizeof(double) * NN * nb, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    std::vector<double> c4(4 * (size_t) nb);
+    HIP_CHECK(h, hipMemcpy(c4.data(), h->dGradCoef, sizeof(double) * 4 * nb, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nb; i++)
+      for (int q = 0; q < 3; q++)
+        coef_out[3 * (size_t) (b0 + i) + q] = c4[4 * (size_t) i + q];
+  }
+  return 0;
+}
+
+int bioem_hip_debug_grad_gather(bioem_hip_handle h, const double *gmaps, int o0, int nO, double *u_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (!gmaps || !u_out || nO < 1 || o0 < 0 || o0 + nO > h->nAnglesUp)
+  {
+    h->err = "debug_grad_gather: null argument, or orientations empty or outside the uploaded list";
+    return 2;
+  }
+  if (!h->dPts || h->nPts < 1)
+  {
+    h->err = "debug_grad_gather: model not uploaded";
+    return 2;
+  }
+  if (grad_staging(h, 1, h->nPts))
+    return 1;
+  if (compat_flush(h))
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
+  const int N = h->N, OB = h->OB, nPts = h->nPts;
+  const size_t NN = (size_t) N * N;
+  for (int b0 = 0; b0 < nO; b0 += OB)
+  {
+    const int nb = std::min(OB, nO - b0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradMap, gmaps + NN * (size_t) b0, sizeof(double) * NN * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, bioem_grad_gather_launch(h->stream, h->dPts, nPts, h->dAngles, o0 + b0, h->isQuat, N, h->pixelSize, h->shiftX,
+                                          h->shiftY, h->dGradMap, nb, h->dGradU, h->dGradVS, h->dGradPart));
+    HIP_CHECK(h, hipMemcpyAsync(u_out + (size_t) b0 * nPts, h->dGradU, sizeof(double) * (size_t) nb * nPts, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
   return 0;
 }
 

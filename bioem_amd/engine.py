@@ -23,6 +23,8 @@ ORIENT_OCC_DTYPE = np.dtype([("occ", "<f8"), ("occ2", "<f8"), ("wmax", "<f8"), (
                              ("hard", "<f8")])
 WINDOW_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4")])
 SCAN_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("shiftX", "<i4"), ("shiftY", "<i4")])
+GRAD_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4"), ("shiftX", "<i4"), ("shiftY", "<i4")])
+GRAD_POINT_DTYPE = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("sumw", "<f8"), ("count", "<i8")])
 MIN_PROB = -999999.0
 
 
@@ -98,6 +100,10 @@ def load_library():
     if hasattr(L, "bioem_hip_ctf_scan"):
         L.bioem_hip_ctf_scan.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp, vp, vp]
         L.bioem_hip_debug_ctf_scan.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]
+    if hasattr(L, "bioem_hip_model_gradient"):
+        L.bioem_hip_model_gradient.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp]
+        L.bioem_hip_debug_grad_image.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp]
+        L.bioem_hip_debug_grad_gather.argtypes = [vp, vp, ci, ci, vp]
     if hasattr(L, "bioem_hip_orientation_sums"):
         L.bioem_hip_orientation_sums.argtypes = [vp, vp, ci, ci, ci, vp]
         L.bioem_hip_merge_orient_sums_host.argtypes = [ci, ci, C.POINTER(vp), vp]
@@ -168,6 +174,7 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_ctf_table", "bioem_hip_ring_count", "bioem_hip_best_match_rings", "bioem_hip_debug_ring_sums",
            "bioem_hip_window_count", "bioem_hip_window_offsets", "bioem_hip_window_posterior", "bioem_hip_debug_window",
            "bioem_hip_ctf_scan", "bioem_hip_debug_ctf_scan",
+           "bioem_hip_model_gradient", "bioem_hip_debug_grad_image", "bioem_hip_debug_grad_gather",
            "bioem_hip_orientation_sums", "bioem_hip_merge_orient_sums_host", "bioem_hip_debug_orient_sums",
            "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy",
            "bioem_hip_view_sums", "bioem_hip_view_averages", "bioem_hip_debug_view_sums",
@@ -679,6 +686,82 @@ class Engine:
         if rc:
             self._scan_raise("debug_ctf_scan", rc)
         return logp, cc, par
+
+    def model_gradient(self, requests, weights=None, own=False, want_grad=True, want_params=False):
+        """the derivative of the log posterior of each request (particle, orient, conv, shiftX, shiftY) of
+        GRAD_REQUEST_DTYPE [n] (or an [n, 5] integer array) with respect to the density of every model point
+        (include/bioem_hip.h).  Returns a dict: "points" GRAD_POINT_DTYPE [nPts], the sums over the requests
+        in request order with the weights float64 [n] (None: all 1); "coef" float64 [n, 4] = (a, b, g, m); with want_grad
+        "grad" float64 [n, nPts]; with want_params "params" PARAM5_DTYPE [n], the linearisation point.  orient indexes the
+        shared list, with own=True the list of the request's particle.  Outside a run; a refusal raises RuntimeError
+        with .rc == 2."""
+        r = np.asarray(requests)
+        if r.dtype != GRAD_REQUEST_DTYPE:
+            r = np.asarray(r, dtype=np.int32).reshape(-1, 5)
+            q = np.zeros(len(r), dtype=GRAD_REQUEST_DTYPE)
+            for i, f in enumerate(GRAD_REQUEST_DTYPE.names):
+                q[f] = r[:, i]
+            r = q
+        r = np.ascontiguousarray(r.reshape(-1))
+        n, nPts = len(r), getattr(self, "_nPts", 0)   # (no model: the entry refuses)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            assert w.shape == (n,), w.shape
+        out = {"points": np.zeros(nPts, dtype=GRAD_POINT_DTYPE), "coef": np.zeros((n, 4), dtype=np.float64)}
+        if want_grad:
+            out["grad"] = np.zeros((n, nPts), dtype=np.float64)
+        if want_params:
+            out["params"] = np.zeros(n, dtype=PARAM5_DTYPE)
+        rc = self.L.bioem_hip_model_gradient(self.h, _p(r) if n else None, _p(w), n, int(bool(own)), _p(out.get("grad")),
+                                             _p(out["points"]), _p(out.get("params")), _p(out["coef"]))
+        if rc:
+            self._scan_raise("model_gradient", rc)
+        return out
+
+    def best_match_gradient(self, pmap, p0=0, p1=None, own=False, weights=None, want_grad=True, want_params=False):
+        """model_gradient of the best record (orient, conv, cent_x, cent_y) of particles [p0, p1) of a probability block's
+        map entries (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
+        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
+        assert pmap.shape == (self.nMaps,)
+        p1 = self.nMaps if p1 is None else int(p1)
+        req = np.zeros(max(0, p1 - int(p0)), dtype=GRAD_REQUEST_DTYPE)
+        req["particle"] = np.arange(int(p0), p1)
+        req["orient"], req["conv"] = pmap["orient"][int(p0):p1], pmap["conv"][int(p0):p1]
+        req["shiftX"], req["shiftY"] = pmap["cent_x"][int(p0):p1], pmap["cent_y"][int(p0):p1]
+        return self.model_gradient(req, weights=weights, own=own, want_grad=want_grad, want_params=want_params)
+
+    def debug_grad_image(self, specConv, specRef, kernels, params, sumRef, sumsqRef, shifts):
+        """test hook: a, b, g and the gradient image G_P of n records from conv spectra, particle spectra and kernels handed
+        in, float32 [n, N, H, 2] each (or complex64 [n, N, H]), params PARAM5_DTYPE [n], the particles' sums float32 [n]
+        and the shifts int [n, 2].  Needs only the handle's parameters.  Returns (gmap float64 [n, N, N], coef float64
+        [n, 3]); a refusal raises with .rc == 2."""
+        specConv, specRef, kernels = self._spectra(specConv), self._spectra(specRef), self._spectra(kernels)
+        n = len(specConv)
+        params = np.ascontiguousarray(params, dtype=PARAM5_DTYPE)
+        sumRef = np.ascontiguousarray(sumRef, dtype=np.float32)
+        sumsqRef = np.ascontiguousarray(sumsqRef, dtype=np.float32)
+        shifts = np.ascontiguousarray(shifts, dtype=np.int32)
+        assert specConv.shape == (n, self.N, self.H, 2) and specRef.shape == specConv.shape and kernels.shape == specConv.shape
+        assert params.shape == (n,) and sumRef.shape == (n,) and sumsqRef.shape == (n,) and shifts.shape == (n, 2)
+        gmap = np.zeros((n, self.N, self.N), dtype=np.float64)
+        coef = np.zeros((n, 3), dtype=np.float64)
+        rc = self.L.bioem_hip_debug_grad_image(self.h, _p(specConv), _p(specRef), _p(kernels), _p(params), _p(sumRef),
+                                               _p(sumsqRef), _p(shifts), n, _p(gmap), _p(coef))
+        if rc:
+            self._scan_raise("debug_grad_image", rc)
+        return gmap, coef
+
+    def debug_grad_gather(self, gmaps, o0=0):
+        """test hook: u_k of every model point from the maps float64 [nO, N, N] at the orientations [o0, o0 + nO) of the
+        shared list.  Returns float64 [nO, nPts]; a refusal raises with .rc == 2."""
+        gmaps = np.ascontiguousarray(gmaps, dtype=np.float64)
+        assert gmaps.ndim == 3 and gmaps.shape[1:] == (self.N, self.N), gmaps.shape
+        u = np.zeros((len(gmaps), self._nPts), dtype=np.float64)
+        rc = self.L.bioem_hip_debug_grad_gather(self.h, _p(gmaps), int(o0), len(gmaps), _p(u))
+        if rc:
+            self._scan_raise("debug_grad_gather", rc)
+        return u
 
     def orientation_sums(self, prior=None, p0=0, p1=None, own=False):
         """the orientation posterior of particles [p0, p1) reduced where the angle table lives: ORIENT_SUMS_DTYPE

@@ -175,6 +175,15 @@ CtfScanStats ctf_scan_stats(const double *logp, const float *triples, const int 
 std::string write_ctf_scan(const char *file, const double *logp, const float *triples, const int counts[3], int nMaps,
                            const int *orient, const int *shiftX, const int *shiftY, bool usepsf, float elecwavel,
                            const double *numconst);
+// --ModelGradient (modelgrad.cpp): the text file of the sums acc[nPts] of bioem_hip_model_gradient over the particles'
+// best records.  After the HEADER:: NOTATION bar, one notation line and the bar again, per model point
+//  POINT k x y z radius density sum mean z count
+// (sum = sum_r g_rk, mean = sum / sumw or 0 where no request saw the point, z = sum / sqrt(sumsq) or 0) and one line
+//  DATASET rho_dot_sum norm nonfinite
+// (sum_k rho_k sum_k, which the normalisation of the projection makes 0 analytically; the Euclidean norm of sum; the
+// requests whose coefficients were not finite).  17 significant digits.  Returns the empty string, or the error.
+std::string write_model_gradient(const char *file, const bioem_hip_model_point *points, const bioem_hip_grad_point *acc, int nPts,
+                                 int nonfinite);
 // --OrientStats (orientstats.cpp): the text file of the sums sums[nMaps] of bioem_hip_orientation_sums.  After the
 // HEADER:: NOTATION bar, one notation line (it carries the constant as NumericalConst) and the bar again, per particle
 //  ORIENT p count logZ omax A pTop entropy nEff meanq1 meanq2 meanq3 meanq4 spreadDeg
@@ -308,6 +317,7 @@ public:
   // FILE_Round2); k = 4 is a conventional choice, not a tuned one
   std::string ctfScanFile;
   int ctfScanFactor = 4;
+  std::string modelGradFile;   // --ModelGradient: the density gradient of the best matches per model point (FILE, FILE_Round2)
   std::string orientStatsFile; // --OrientStats: summaries of every particle's orientation posterior (WRITE_PROB_ANGLES)
   std::string orientOccFile;   // --OrientOccupancy: occupancy of every orientation over the data set (WRITE_PROB_ANGLES)
   int fitOrientPrior = 0;      // --FitOrientPrior N: N EM iterations of the orientation prior, FILE_prior
@@ -363,6 +373,9 @@ private:
   // chunks of candidates, written by write_ctf_scan; voluPerMap as for writeProbabilities
   void writeCtfScan(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
                     const bioem_hip_param_device &pd, const float *voluPerMap = nullptr);
+  // --ModelGradient: the records' gradient per model point from handle h (bioem_hip_model_gradient), written by
+  // write_model_gradient
+  void writeModelGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
   // --OrientStats: the shards' orientation sums (bioem_hip_orientation_sums) merged on the host, written by
   // write_orient_stats; numconst: the constant of ANG_PROB
   void writeOrientStats(const std::string &file, double numconst);

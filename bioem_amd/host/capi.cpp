@@ -64,6 +64,18 @@ int bioem_host_write_ctf_scan(const char *file, const double *logp, const float 
   return 1;
 }
 
+// the --ModelGradient text of acc[nPts] (write_model_gradient, bioem_host.h); 0, or 1 with the text in err[cap]
+int bioem_host_write_model_gradient(const char *file, const bioem_hip_model_point *points, const bioem_hip_grad_point *acc,
+                                    int nPts, int nonfinite, char *err, int cap)
+{
+  const std::string e = bioem_host::write_model_gradient(file, points, acc, nPts, nonfinite);
+  if (e.empty())
+    return 0;
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return 1;
+}
+
 // == volume element (param.cpp:1600-1607)
 float bioem_host_volume_element(float voluang, int gridSpaceCenter, int maxDisplaceCenter, float pixelSize, int nAmp,
                                 float gridEnvelop, float gridPhase, float sigB, float sigDef, float sigAmp)

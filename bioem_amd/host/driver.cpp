@@ -77,6 +77,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"BestWindow", required_argument, 0, 0},
                                        {"CTFScan", required_argument, 0, 0},
                                        {"CTFScanFactor", required_argument, 0, 0},
+                                       {"ModelGradient", required_argument, 0, 0},
                                        {"OrientStats", required_argument, 0, 0},
                                        {"OrientOccupancy", required_argument, 0, 0},
                                        {"FitOrientPrior", required_argument, 0, 0},
@@ -123,6 +124,9 @@ int Driver::readOptions(int ac, char **av)
     printf("                         also arg_Round2)\n");
     printf("  --CTFScanFactor arg    (Optional) With --CTFScan: every CTF axis with more than one point is refined arg-fold;\n");
     printf("                         1, 2, 4, 8 or 16 (default 4)\n");
+    printf("  --ModelGradient arg    (Optional) Write per model point the gradient of the log posterior of the particles' best\n");
+    printf("                         matches with respect to its density (which part of the model do the data argue against?\n");
+    printf("                         with --RefineOrientations also arg_Round2)\n");
     printf("  --OrientStats arg      (Optional) Write per particle the summaries of its orientation posterior (entropy, effective\n");
     printf("                         number of orientations, mean orientation, spread; needs WRITE_PROB_ANGLES)\n");
     printf("  --OrientOccupancy arg  (Optional) Write per orientation its occupancy over the data set (which views are in it, how\n");
@@ -254,6 +258,11 @@ int Driver::readOptions(int ac, char **av)
       }
       ctfScanFactor = (int) k;
     }
+    else if (name == "ModelGradient")
+    {
+      std::cout << "Writing the density gradient of the best matches per model point to: " << optarg << "\n";
+      modelGradFile = optarg;
+    }
     else if (name == "OrientStats")
     {
       std::cout << "Writing the summaries of the orientation posteriors to: " << optarg << "\n";
@@ -328,9 +337,10 @@ int Driver::readOptions(int ac, char **av)
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
     if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty() || !bestWindowFile.empty() ||
-        !ctfScanFile.empty() || !orientStatsFile.empty() || !orientOccFile.empty() || !viewAvgFile.empty())
+        !ctfScanFile.empty() || !orientStatsFile.empty() || !orientOccFile.empty() || !viewAvgFile.empty() ||
+        !modelGradFile.empty())
       fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow, --CTFScan, --OrientStats, --OrientOccupancy, "
-            "--ViewAverages and --RefineOrientations");
+            "--ViewAverages, --ModelGradient and --RefineOrientations");
     const std::string err = read_best_parameters(bestParamFile.c_str(), best);
     if (!err.empty())
       fatal("%s", err.c_str());
@@ -800,6 +810,38 @@ void Driver::writeCtfScan(const std::string &file, bioem_hip_handle h, const bio
             << "\n";
 }
 
+// --ModelGradient: the gradient of the log posterior of every record (orientation, CTF set, shift) from handle h with
+// respect to the density of every model point, summed over the particles with weight 1 (bioem_hip_model_gradient), then
+// the text file (write_model_gradient).  A particle no run compared has no record: a warning, and it adds nothing.
+void Driver::writeModelGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists)
+{
+  const int nMaps = particles.ntot;
+  std::vector<bioem_hip_grad_request> req;
+  for (int p = 0; p < nMaps; p++)
+  {
+    const bioem_hip_prob_map &r = pmap[p];
+    if (r.Total == 0.0 && r.Constoadd == -999999.)
+    {
+      warn("Density gradient of RefMap %d not computed: no run compared it", p);
+      continue;
+    }
+    req.push_back({p, r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y});
+  }
+  std::vector<bioem_hip_grad_point> acc(model.points.size(), bioem_hip_grad_point{0., 0., 0., 0});
+  std::vector<double> coef(4 * req.size());
+  if (!req.empty())
+    check(h, bioem_hip_model_gradient(h, req.data(), nullptr, (int) req.size(), ownLists, nullptr, acc.data(), nullptr, coef.data()),
+          "model gradient");
+  int nonfinite = 0;
+  for (size_t i = 0; i < req.size(); i++)
+    nonfinite += !(std::isfinite(coef[4 * i]) && std::isfinite(coef[4 * i + 1]) && std::isfinite(coef[4 * i + 2]));
+  const std::string err = write_model_gradient(file.c_str(), model.points.data(), acc.data(), (int) model.points.size(), nonfinite);
+  if (!err.empty())
+    fatal("--ModelGradient: %s", err.c_str());
+  std::cout << "Density gradient of " << req.size() << " particles' best matches over " << model.points.size()
+            << " model points written to: " << file << "\n";
+}
+
 // --OrientStats: every shard's sums over the orientations it owns (bioem_hip_orientation_sums), merged on the host in
 // shard order, then the text file (write_orient_stats)
 void Driver::writeOrientStats(const std::string &file, double numconst)
@@ -1111,6 +1153,8 @@ int Driver::run()
     writeBestWindow(bestWindowFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0, param.pd);
   if (!ctfScanFile.empty())
     writeCtfScan(ctfScanFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0, param.pd);
+  if (!modelGradFile.empty())
+    writeModelGradient(modelGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!viewAvgFile.empty())
     writeViewAverages(viewAvgFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
   if (!refineFile.empty())
@@ -1189,6 +1233,8 @@ void Driver::runRound2()
     writeBestWindow(bestWindowFile + "_Round2", h, pm.data(), 1, pd2);
   if (!ctfScanFile.empty())
     writeCtfScan(ctfScanFile + "_Round2", h, pm.data(), 1, pd2);
+  if (!modelGradFile.empty())
+    writeModelGradient(modelGradFile + "_Round2", h, pm.data(), 1);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), (size_t) G);
   bioem_hip_destroy(h);
@@ -1288,6 +1334,8 @@ void Driver::runRound2Seeds()
     writeBestWindow(bestWindowFile + "_Round2", h, pm.data(), 1, pd2, volu.data());
   if (!ctfScanFile.empty())
     writeCtfScan(ctfScanFile + "_Round2", h, pm.data(), 1, pd2, volu.data());
+  if (!modelGradFile.empty())
+    writeModelGradient(modelGradFile + "_Round2", h, pm.data(), 1);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), 0, offsets.data(),
                  volu.data());

@@ -395,3 +395,17 @@ def write_ctf_scan(path, logp, triples, counts, orient, shiftX, shiftY, numconst
                                    sx.ctypes.data, sy.ctypes.data, int(bool(usepsf)), float(elecwavel), nc.ctypes.data, err,
                                    512):
         raise ValueError(err.value.decode())
+
+
+def write_model_gradient(path, points, acc, nonfinite=0):
+    """the --ModelGradient text file of the sums acc (GRAD_POINT_DTYPE [nPts], Engine.model_gradient's "points") over the
+    model's points (POINT_DTYPE [nPts]): the writer the CLI uses; bioem_amd.model_gradient.parse reads it back"""
+    L = load_host_library()
+    vp = C.c_void_p
+    L.bioem_host_write_model_gradient.argtypes = [C.c_char_p, vp, vp, C.c_int, C.c_int, C.c_char_p, C.c_int]
+    p = np.ascontiguousarray(points)
+    a = np.ascontiguousarray(acc)
+    assert p.dtype.itemsize == 24 and a.dtype.itemsize == 32 and p.shape == a.shape and p.ndim == 1
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_model_gradient(path.encode(), p.ctypes.data, a.ctypes.data, len(p), int(nonfinite), err, 512):
+        raise ValueError(err.value.decode())

@@ -465,6 +465,54 @@ int bioem_hip_debug_ctf_scan(bioem_hip_handle h, const float *specP, const float
                              const float *ctfParam3, int G, double *logp_out, float *cc_out,
                              bioem_hip_param5 *params_out);
 
+/* ---- Density gradient of the log posterior per model point (no reference counterpart) ----
+ * For request (p, o, c, X, Y) the derivative of the log posterior of that match with respect to the density rho_k of every
+ * model point.  N = NumberPixels, Nt = N N.  Projection (createProjection): U = sum_k v_k rho_k s_k placed at the point's
+ * pixel, T = sum_k v_k rho_k sigma_k, P = (NormDen / T) U; s_k the footprint of point k at unit density (a single 1 for
+ * radius <= pixelSize), sigma_k its sum, v_k = 0 where the reference skips the point.
+ *   Linearisation point: sumC, sumsquareC and cc as the CTF scan above delivers them for (p, o, X, Y) with the handle's
+ *       own set c as candidate (same bits); sumref, sumsquareref the particle's.  All widened to double:
+ *       F  = ssq Nt - s s,   fe = Nt (ssr ssq - cc cc) + 2 sr s cc - ssr s s - sr sr ssq,
+ *       a = dL/ds   = (3 - Nt)/2 (2 sr cc - 2 ssr s) / fe + (Nt/2 - 2) (-2 s) / F,
+ *       b = dL/dssq = (3 - Nt)/2 (Nt ssr - sr sr) / fe + (Nt/2 - 2) Nt / F,
+ *       g = dL/dcc  = (3 - Nt)/2 (-2 Nt cc + 2 sr s) / fe          (the CTF priors are constants);
+ *   G^_P[k] = (a Nt [k = 0] + 2 b conv[k] + g F_p[k] exp(-2 pi i ((kx dx + ky dy) mod N) / N)) K_c[k], dx = -X, dy = -Y,
+ *       conv = P^ conj(K_c) the float expression of the convolution; G_P = c2r(G^_P) / Nt by two exact-DFT passes in
+ *       double, the Hermitian part taken in the self-conjugate columns;
+ *   u_k = v_k sum_{di,dj} s_k[di][dj] G_P[i_k + di][j_k + dj] on the pixels and under the skip rules of the projection,
+ *   m = sum_k rho_k u_k,   dL/drho_k = (NormDen / T) (u_k - v_k sigma_k m / T), T summed in double from the same s_k.
+ * This is the exact derivative of the double closed form at the device's linearisation point.  The float roundings of
+ * the pipeline (the map narrowed to float, float spectra, cc rounded once, the density inside the float numerator of a
+ * sphere's weight) are not differentiated.  a s + 2 b ssq + g cc = -1 and sum_k rho_k dL/drho_k = 0 hold analytically.
+ * A request whose fe or F is not positive and finite gives what the formulas give (sumsq shows it).
+ * points_out[k], over the requests in request order with w_r = weights[r] (1 where weights is null), g_rk the gradient:
+ *   sum = sum_r w_r g_rk,  sumsq = sum_r (w_r g_rk)^2,  sumw = sum_r w_r v_rk,  count = sum_r v_rk.
+ * A row of grad_out depends on its request alone; the sums depend on the requests and their order alone: the same bits
+ * for any batch size, batch boundary and run.  Calling rules and refusals of the CTF scan (2, the request named, the
+ * handle usable); also refused: conv outside [0, nCTF), CTF kernels not uploaded, grad_out and points_out both null, a
+ * weight that is not finite.  Staging is allocated at the first call (1 when the memory is not there).  Requests go in
+ * batches of maxOrientations; one launch of the CTF scan serves up to 16 of them (as that entry does).  Phase records: per
+ * batch 0 the projection and 1 the scan's preparation; per launch of the scan one more record of phase 1, the
+ * linearisation and a, b, g (iOrientBegin / iOrientEnd the requests of the launch); then per batch 2 the gradient
+ * spectrum and the inverse transform, 3 the gather and the fold. */
+typedef struct { int particle, orient, conv, shiftX, shiftY; } bioem_hip_grad_request;   /* 20 bytes */
+typedef struct { double sum, sumsq, sumw; long long count; } bioem_hip_grad_point;       /* 32 bytes */
+int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *req, const double *weights /* [n] or NULL */,
+                             int n, int ownLists, double *grad_out /* [n][nPts] or NULL */,
+                             bioem_hip_grad_point *points_out /* [nPts] or NULL */,
+                             bioem_hip_param5 *params_out /* [n] or NULL */,
+                             double *coef_out /* [n][4] {a, b, g, m} or NULL */);
+/* test hook: a, b, g and G_P from conv spectra, particle spectra and kernels handed in ([n][N][H] (re, im) each, reference
+ * layout), the parameters {.., sumC, sumsquareC} and the particles' sums per record; cc is the scan's double sum of the
+ * record.  Needs only the handle's parameters. */
+int bioem_hip_debug_grad_image(bioem_hip_handle h, const float *specConv, const float *specRef, const float *kernels,
+                               const bioem_hip_param5 *params, const float *sumRef, const float *sumsqRef,
+                               const int *shiftXY /* [n][2] */, int n, double *gmap_out /* [n][N][N] */,
+                               double *coef_out /* [n][3] {a, b, g} */);
+/* test hook: u_k of the model's points from maps handed in, at the orientations [o0, o0 + nO) of the shared list */
+int bioem_hip_debug_grad_gather(bioem_hip_handle h, const double *gmaps /* [nO][N][N] */, int o0, int nO,
+                                double *u_out /* [nO][nPts] */);
+
 /* ---- Summaries of the orientation posterior of every particle (WRITE_PROB_ANGLES; no reference counterpart) ----
  * The [orientations][nMaps] table of bioem_hip_prob_angle stays on the device; this entry reduces it there.  Let
  * F = forAngles, C = ConstAngle of entry (o, p).  Only entries with F > 0 count (entries never compared, or beyond a
