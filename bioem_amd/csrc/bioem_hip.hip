@@ -2690,6 +2690,261 @@ int bioem_hip_merge(bioem_hip_handle *handles, int n, void *pProbMaps_host, int 
   return 0;
 }
 
+} // extern "C" (closed around the helpers below: Staging::get is a template, as dev_alloc is)
+
+// ---- what the analysis entries below share: refusals, validation, staging buffers, the batch step ----
+namespace
+{
+// a refusal of an entry: "<entry>: <why>" as the handle's message, return 2
+struct Refuse
+{
+  bioem_hip_ctx *h;
+  const char *entry;
+  int operator()(const std::string &why) const
+  {
+    h->err = std::string(entry) + ": " + why;
+    return 2;
+  }
+};
+
+// What is queued ahead of an entry: rows staged through the reference-compatible entry go first (call order), and nothing
+// queued may still use buffer set 0.  voidSlot0: the entry writes buffer set 0 itself
+int begin_analysis(bioem_hip_ctx *h, bool voidSlot0)
+{
+  if (compat_flush(h))
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
+  if (voidSlot0)
+    void_slot(h->slot[0]);
+  return 0;
+}
+
+// the first of the uploads an entry needs that the handle lacks, in the order every entry names them; nullptr: none
+enum
+{
+  NEED_MODEL = 1,
+  NEED_CTF = 2,
+  NEED_ORIENT = 4,
+  NEED_PARTICLES = 8,
+  NEED_ALL = 15
+};
+const char *missing_state(const bioem_hip_ctx *h, int needs, int ownLists)
+{
+  if ((needs & NEED_MODEL) && (!h->dPts || h->nPts < 1))
+    return "model not uploaded";
+  if ((needs & NEED_CTF) && !h->ctfUp)
+    return "CTF kernels not uploaded";
+  if ((needs & NEED_ORIENT) && (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1))
+    return ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
+                    : "orientations not uploaded";
+  if ((needs & NEED_PARTICLES) && !h->refUp)
+    return "particles not uploaded";
+  return nullptr;
+}
+
+// the list a particle's orientation index runs over: its first entry in the list the batch reads, and its length
+void orient_span(const bioem_hip_ctx *h, int ownLists, int particle, int &first, int &len)
+{
+  first = ownLists ? h->ownOff[(size_t) particle] : 0;
+  len = ownLists ? h->ownOff[(size_t) particle + 1] - first : h->nAnglesUp;
+}
+
+// a shift outside (-N, N) on either axis would index outside the twiddle table
+bool shift_outside(int N, int x, int y) { return x <= -N || x >= N || y <= -N || y >= N; }
+
+// what is wrong with the CTF set or the displacement of a best-match record; nullptr: nothing
+const char *bad_match_place(const bioem_hip_ctx *h, const bioem_hip_prob_map &r)
+{
+  if (r.max_prob_conv < 0 || r.max_prob_conv >= h->nCTF)
+    return "max_prob_conv outside [0, nCTF)";
+  if (shift_outside(h->N, r.max_prob_cent_x, r.max_prob_cent_y))
+    return "displacement of N pixels or more";
+  return nullptr;
+}
+
+// the best-match records of the particles [p0, p1) as the kernels read them; 0, or the refusal of the first bad one
+int match_records(const bioem_hip_ctx *h, const Refuse &refuse, const bioem_hip_prob_map *records, int ownLists, int p0, int p1,
+                  std::vector<RenderRecord> &recs)
+{
+  recs.resize((size_t) (p1 - p0));
+  for (int p = p0; p < p1; p++)
+  {
+    const bioem_hip_prob_map &r = records[p];
+    int first, len;
+    orient_span(h, ownLists, p, first, len);
+    const char *why = r.max_prob_orient < 0 || r.max_prob_orient >= len ? "max_prob_orient outside its orientation list"
+                                                                        : bad_match_place(h, r);
+    if (why)
+    {
+      char buf[256];
+      snprintf(buf, sizeof(buf), "particle %d: %s (orient %d of %d, conv %d, cent %d %d)", p, why, r.max_prob_orient, len,
+               r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y);
+      return refuse(buf);
+    }
+    recs[(size_t) (p - p0)] = {first + r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y, r.max_prob_norm,
+                               r.max_prob_mu};
+  }
+  return 0;
+}
+
+// A request (particle, orientation and, where the entry has them, CTF set and shift; a field it lacks is 0): what is wrong
+// with it, or nullptr.  first / len: the list of its particle (orient_span), 0 while the particle itself is out of range
+enum
+{
+  REQ_CONV = 1,
+  REQ_SHIFT = 2
+};
+const char *bad_request(const bioem_hip_ctx *h, const bioem_hip_grad_request &r, int fields, int ownLists, int &first, int &len)
+{
+  first = len = 0;
+  if (r.particle < 0 || r.particle >= h->nMaps)
+    return "particle outside [0, nMaps)";
+  orient_span(h, ownLists, r.particle, first, len);
+  if (r.orient < 0 || r.orient >= len)
+    return "orient outside its orientation list";
+  if ((fields & REQ_CONV) && (r.conv < 0 || r.conv >= h->nCTF))
+    return "conv outside [0, nCTF)";
+  if ((fields & REQ_SHIFT) && shift_outside(h->N, r.shiftX, r.shiftY))
+    return "shift outside (-N, N)";
+  return nullptr;
+}
+
+// the refusal of request i: the reason, then the fields the entry has against their ranges
+std::string request_refusal(const bioem_hip_ctx *h, int i, const char *why, const bioem_hip_grad_request &r, int fields, int len)
+{
+  char buf[256];
+  int at = snprintf(buf, sizeof(buf), "request %d: %s (particle %d of %d, orient %d of %d", i, why, r.particle, h->nMaps,
+                    r.orient, len);
+  if (fields & REQ_CONV)
+    at += snprintf(buf + at, sizeof(buf) - at, ", conv %d of %d", r.conv, h->nCTF);
+  if (fields & REQ_SHIFT)
+    at += snprintf(buf + at, sizeof(buf) - at, ", shift %d %d, N %d", r.shiftX, r.shiftY, h->N);
+  return std::string(buf) + ")";
+}
+
+// the shifts (x, y) of the n records handed to a debug hook; 0, or the refusal of the first outside (-N, N)
+int debug_shifts_refused(const bioem_hip_ctx *h, const Refuse &refuse, const int *shiftXY, int n)
+{
+  for (int i = 0; i < n; i++)
+    if (shift_outside(h->N, shiftXY[2 * i], shiftXY[2 * i + 1]))
+    {
+      char buf[160];
+      snprintf(buf, sizeof(buf), "record %d: shift outside (-N, N) (shift %d %d, N %d)", i, shiftXY[2 * i], shiftXY[2 * i + 1],
+               h->N);
+      return refuse(buf);
+    }
+  return 0;
+}
+
+// Device buffers an entry obtains together, for fields of the handle: either all of them, and commit() hands them to the
+// fields (releasing what a field held: a group that grows), or the handle stays exactly as it was and commit() returns 1.
+struct Staging
+{
+  bioem_hip_ctx *h;
+  struct Item
+  {
+    void *field, *fresh;                                           // a T *& of the handle, the T * obtained for it
+    void (*take)(bioem_hip_ctx *h, void *field, void *fresh); // the field takes it, as a T * again
+  };
+  std::vector<Item> items;
+  bool failed = false;
+
+  // n elements for a field of the handle
+  template <class T>
+  T *get(T *&field, size_t n)
+  {
+    T *p = nullptr;
+    failed = failed || dev_alloc(h, p, n);
+    items.push_back({&field, p, [](bioem_hip_ctx *h_, void *f, void *fresh) {
+                       T *&dst = *static_cast<T **>(f);
+                       dev_release(h_, dst);
+                       dst = static_cast<T *>(fresh);
+                     }});
+    return p;
+  }
+  // an upload that belongs to the transaction (dst: what get() returned)
+  void fill(void *dst, const void *src, size_t bytes)
+  {
+    failed = failed || hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess;
+  }
+  int commit()
+  {
+    for (Item &it : items)
+      if (failed)
+        dev_release(h, it.fresh);
+      else
+        it.take(h, it.field, it.fresh);
+    if (failed)
+      (void) hipGetLastError();
+    return failed;
+  }
+};
+
+// the orientations the n records on the device name, gathered from src into the contiguous list dAngles
+// (records: RenderRecord or BioemWindowRecord, the same 24 bytes with src first)
+int gather_matches(bioem_hip_ctx *h, const OrientList &src, const void *dRec, int n, float4 *dAngles)
+{
+  hipLaunchKernelGGL(k_render_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, src.d,
+                     static_cast<const RenderRecord *>(dRec), n, dAngles);
+  HIP_CHECK(h, hipGetLastError());
+  return 0;
+}
+
+// the projections of the gathered orientations [o0, o0 + n) into buffer set 0: phase 0 of the records [i0, i0 + n)
+int project_matches(bioem_hip_ctx *h, const OrientList &src, const float4 *dAngles, int o0, int n, int i0)
+{
+  const OrientList L = {dAngles, src.isQuat, src.quatNormDev};
+  return phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, i0, i0 + n, 0, 0) ||
+         project_batch(h, h->slot[0], h->stream, L, o0, n) || phase_end(h, h->stream);
+}
+
+// a batch of n records (the records [i0, i0 + n) of the call) to the device, their orientations gathered, their projections
+// in buffer set 0
+int stage_matches(bioem_hip_ctx *h, const OrientList &src, void *dRec, float4 *dAngles, const void *hostRecs, int n, int i0)
+{
+  HIP_CHECK(h, hipMemcpyAsync(dRec, hostRecs, sizeof(RenderRecord) * n, hipMemcpyHostToDevice, h->stream));
+  return gather_matches(h, src, dRec, n, dAngles) || project_matches(h, src, dAngles, 0, n, i0);
+}
+
+// the spectra of the particles of nb records back in reference layout, dst[i] for record i: one launch per run of
+// consecutive particles
+int unreorder_runs(bioem_hip_ctx *h, const BioemWindowRecord *recs, int nb, float2 *dst)
+{
+  for (int i = 0; i < nb;)
+  {
+    int j = i + 1;
+    while (j < nb && recs[j].particle == recs[j - 1].particle + 1)
+      j++;
+    hipLaunchKernelGGL(k_unreorder, dim3(std::min(1024, 16 * (j - i))), dim3(256), 0, h->stream,
+                       h->dRef + h->Mc * (size_t) recs[i].particle, dst + (size_t) h->M * i, j - i, h->N, h->H, h->plan.halfR,
+                       h->plan.N1, h->Hp);
+    HIP_CHECK(h, hipGetLastError());
+    i = j;
+  }
+  return 0;
+}
+
+// (the attribute belongs to the kernels, not the handle: images beyond 2 048 pixels need more than 64 KiB)
+int render_lds_attr(bioem_hip_ctx *h, size_t lds)
+{
+  HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_cols), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+  HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+  return 0;
+}
+
+// a launch failed inside an open phase: the phase is dropped, its events go back to the pool
+void drop_open_phase(bioem_hip_ctx *h)
+{
+  if (!h->phaseTiming || h->phasePending.empty())
+    return;
+  h->evPool.push_back(h->phasePending.back().a);
+  h->evPool.push_back(h->phasePending.back().b);
+  h->phasePending.pop_back();
+}
+} // namespace
+
+extern "C" {
+
 // ---- the calculated image of the best-match records (bioem::printModel, bioem.cpp:624-657, 1925-2085) ----
 int bioem_hip_render_best_maps(bioem_hip_handle h, const bioem_hip_prob_map *records, int ownLists, int iMapBegin,
                                int iMapEnd, float *maps_out)
@@ -2697,83 +2952,38 @@ int bioem_hip_render_best_maps(bioem_hip_handle h, const bioem_hip_prob_map *rec
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  char buf[256];
-  auto refuse = [&](const char *why) {
-    h->err = std::string("render_best_maps: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "render_best_maps"};
   if (!records || !maps_out)
     return refuse("null argument");
   if (iMapBegin < 0 || iMapEnd > h->nMaps || iMapBegin >= iMapEnd)
     return refuse("particle range empty, reversed or outside [0, nMaps)");
-  if (!h->dPts || h->nPts < 1)
-    return refuse("model not uploaded");
-  if (!h->ctfUp)
-    return refuse("CTF kernels not uploaded");
-  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
-    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
-                           : "orientations not uploaded");
+  if (const char *why = missing_state(h, NEED_MODEL | NEED_CTF | NEED_ORIENT, ownLists))
+    return refuse(why);
+  std::vector<RenderRecord> recs;
+  if (const int rc = match_records(h, refuse, records, ownLists, iMapBegin, iMapEnd, recs))
+    return rc;
   const int N = h->N, H = h->H;
-  std::vector<RenderRecord> recs((size_t) (iMapEnd - iMapBegin));
-  for (int p = iMapBegin; p < iMapEnd; p++)
-  {
-    const bioem_hip_prob_map &r = records[p];
-    const int first = ownLists ? h->ownOff[p] : 0, len = ownLists ? h->ownOff[p + 1] - h->ownOff[p] : h->nAnglesUp;
-    const char *why = nullptr;
-    if (r.max_prob_orient < 0 || r.max_prob_orient >= len)
-      why = "max_prob_orient outside its orientation list";
-    else if (r.max_prob_conv < 0 || r.max_prob_conv >= h->nCTF)
-      why = "max_prob_conv outside [0, nCTF)";
-    else if (r.max_prob_cent_x <= -N || r.max_prob_cent_x >= N || r.max_prob_cent_y <= -N || r.max_prob_cent_y >= N)
-      why = "displacement of N pixels or more";
-    if (why)
-    {
-      snprintf(buf, sizeof(buf), "particle %d: %s (orient %d of %d, conv %d, cent %d %d)", p, why, r.max_prob_orient, len,
-               r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y);
-      return refuse(buf);
-    }
-    recs[(size_t) (p - iMapBegin)] = {first + r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y,
-                                      r.max_prob_norm, r.max_prob_mu};
-  }
   const int OB = h->OB; // maxOrientations of bioem_hip_max_batch; slot 0 holds at least that many images
   const size_t NN = (size_t) N * N, lds = sizeof(double2) * 2 * (size_t) N;
   if (!h->dRenderOut)
-  { // a failed allocation (return 1) leaves the handle as it was
-    RenderRecord *rec = nullptr;
-    float4 *ang = nullptr;
-    float *out = nullptr;
-    if (dev_alloc(h, rec, (size_t) OB) || dev_alloc(h, ang, (size_t) OB) || dev_alloc(h, out, (size_t) OB * NN))
-    {
-      dev_release(h, rec);
-      dev_release(h, ang);
-      dev_release(h, out);
-      (void) hipGetLastError();
+  {
+    Staging st = {h};
+    st.get(h->dRenderRec, (size_t) OB);
+    st.get(h->dRenderAngles, (size_t) OB);
+    st.get(h->dRenderOut, (size_t) OB * NN);
+    if (st.commit())
       return 1;
-    }
-    h->dRenderRec = rec;
-    h->dRenderAngles = ang;
-    h->dRenderOut = out;
   }
-  // (the attribute belongs to the kernel, not the handle: images beyond 2 048 pixels need more than 64 KiB)
-  HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_cols), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-  HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
+  if (render_lds_attr(h, lds) || begin_analysis(h, true))
     return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
   bioem_hip_ctx::Slot &s0 = h->slot[0];
-  void_slot(s0);
   const OrientList src = ownLists ? own_list(h) : shared_list(h);
-  const OrientList L = {h->dRenderAngles, src.isQuat, src.quatNormDev};
   int A, B;
   dft_split(N, A, B);
   for (size_t b0 = 0; b0 < recs.size(); b0 += (size_t) OB)
   {
     const int n = (int) std::min<size_t>((size_t) OB, recs.size() - b0);
-    HIP_CHECK(h, hipMemcpyAsync(h->dRenderRec, recs.data() + b0, sizeof(RenderRecord) * n, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_render_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, src.d, h->dRenderRec, n, h->dRenderAngles);
-    HIP_CHECK(h, hipGetLastError());
-    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, (int) b0, (int) b0 + n, 0, 0) ||
-        project_batch(h, s0, h->stream, L, 0, n) || phase_end(h, h->stream))
+    if (stage_matches(h, src, h->dRenderRec, h->dRenderAngles, recs.data() + b0, n, (int) b0))
       return 1;
     if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, (int) b0, (int) b0 + n, 0, 0))
       return 1;
@@ -2805,28 +3015,13 @@ int ring_staging(bioem_hip_ctx *h)
   if (h->dRingOut)
     return 0;
   const size_t OB = (size_t) h->OB;
-  RenderRecord *rec = nullptr;
-  float4 *ang = nullptr;
-  float2 *ref = nullptr;
-  double *scr = nullptr;
-  bioem_hip_ring_sums *out = nullptr;
-  if (dev_alloc(h, rec, OB) || dev_alloc(h, ang, OB) || dev_alloc(h, ref, OB * (size_t) h->M) ||
-      dev_alloc(h, scr, bioem_ring_scratch(h->N, h->OB)) || dev_alloc(h, out, OB * (size_t) bioem_ring_count(h->N)))
-  {
-    dev_release(h, rec);
-    dev_release(h, ang);
-    dev_release(h, ref);
-    dev_release(h, scr);
-    dev_release(h, out);
-    (void) hipGetLastError();
-    return 1;
-  }
-  h->dRingRec = rec;
-  h->dRingAngles = ang;
-  h->dRingRef = ref;
-  h->dRingScratch = scr;
-  h->dRingOut = out;
-  return 0;
+  Staging st = {h};
+  st.get(h->dRingRec, OB);
+  st.get(h->dRingAngles, OB);
+  st.get(h->dRingRef, OB * (size_t) h->M);
+  st.get(h->dRingScratch, bioem_ring_scratch(h->N, h->OB));
+  st.get(h->dRingOut, OB * (size_t) bioem_ring_count(h->N));
+  return st.commit();
 }
 
 // the ring pass of n staged images (records in dRingRec, particle spectra in dRingRef, projections in slot 0) and
@@ -2850,65 +3045,25 @@ int bioem_hip_best_match_rings(bioem_hip_handle h, const bioem_hip_prob_map *rec
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  char buf[256];
-  auto refuse = [&](const char *why) {
-    h->err = std::string("best_match_rings: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "best_match_rings"};
   if (!records || !out)
     return refuse("null argument");
   if (iMapBegin < 0 || iMapEnd > h->nMaps || iMapBegin >= iMapEnd)
     return refuse("particle range empty, reversed or outside [0, nMaps)");
-  if (!h->dPts || h->nPts < 1)
-    return refuse("model not uploaded");
-  if (!h->ctfUp)
-    return refuse("CTF kernels not uploaded");
-  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
-    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
-                           : "orientations not uploaded");
-  if (!h->refUp)
-    return refuse("particles not uploaded");
-  const int N = h->N;
-  std::vector<RenderRecord> recs((size_t) (iMapEnd - iMapBegin));
-  for (int p = iMapBegin; p < iMapEnd; p++)
-  {
-    const bioem_hip_prob_map &r = records[p];
-    const int first = ownLists ? h->ownOff[p] : 0, len = ownLists ? h->ownOff[p + 1] - h->ownOff[p] : h->nAnglesUp;
-    const char *why = nullptr;
-    if (r.max_prob_orient < 0 || r.max_prob_orient >= len)
-      why = "max_prob_orient outside its orientation list";
-    else if (r.max_prob_conv < 0 || r.max_prob_conv >= h->nCTF)
-      why = "max_prob_conv outside [0, nCTF)";
-    else if (r.max_prob_cent_x <= -N || r.max_prob_cent_x >= N || r.max_prob_cent_y <= -N || r.max_prob_cent_y >= N)
-      why = "displacement of N pixels or more";
-    if (why)
-    {
-      snprintf(buf, sizeof(buf), "particle %d: %s (orient %d of %d, conv %d, cent %d %d)", p, why, r.max_prob_orient, len,
-               r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y);
-      return refuse(buf);
-    }
-    recs[(size_t) (p - iMapBegin)] = {first + r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y,
-                                      r.max_prob_norm, r.max_prob_mu};
-  }
-  if (ring_staging(h))
+  if (const char *why = missing_state(h, NEED_ALL, ownLists))
+    return refuse(why);
+  std::vector<RenderRecord> recs;
+  if (const int rc = match_records(h, refuse, records, ownLists, iMapBegin, iMapEnd, recs))
+    return rc;
+  if (ring_staging(h) || begin_analysis(h, true))
     return 1;
-  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
-  bioem_hip_ctx::Slot &s0 = h->slot[0];
-  void_slot(s0);
   const OrientList src = ownLists ? own_list(h) : shared_list(h);
-  const OrientList L = {h->dRingAngles, src.isQuat, src.quatNormDev};
-  const int OB = h->OB;
+  const int N = h->N, OB = h->OB;
   const size_t nRings = (size_t) bioem_ring_count(N);
   for (size_t b0 = 0; b0 < recs.size(); b0 += (size_t) OB)
   {
     const int n = (int) std::min<size_t>((size_t) OB, recs.size() - b0);
-    HIP_CHECK(h, hipMemcpyAsync(h->dRingRec, recs.data() + b0, sizeof(RenderRecord) * n, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_render_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, src.d, h->dRingRec, n, h->dRingAngles);
-    HIP_CHECK(h, hipGetLastError());
-    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, (int) b0, (int) b0 + n, 0, 0) ||
-        project_batch(h, s0, h->stream, L, 0, n) || phase_end(h, h->stream))
+    if (stage_matches(h, src, h->dRingRec, h->dRingAngles, recs.data() + b0, n, (int) b0))
       return 1;
     if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, (int) b0, (int) b0 + n, 0, 0))
       return 1;
@@ -2929,21 +3084,17 @@ int bioem_hip_debug_ring_sums(bioem_hip_handle h, const float *specR, const floa
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  auto refuse = [&](const char *why) {
-    h->err = std::string("debug_ring_sums: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "debug_ring_sums"};
   if (!specR || !specP || !records || !out || n < 1)
     return refuse("null argument or no images");
-  if (!h->ctfUp)
-    return refuse("CTF kernels not uploaded");
+  if (const char *why = missing_state(h, NEED_CTF, 0))
+    return refuse(why);
   const int N = h->N;
   std::vector<RenderRecord> recs((size_t) n);
   for (int p = 0; p < n; p++)
   {
     const bioem_hip_prob_map &r = records[p];
-    if (r.max_prob_conv < 0 || r.max_prob_conv >= h->nCTF || r.max_prob_cent_x <= -N || r.max_prob_cent_x >= N ||
-        r.max_prob_cent_y <= -N || r.max_prob_cent_y >= N)
+    if (bad_match_place(h, r))
     {
       char buf[160];
       snprintf(buf, sizeof(buf), "image %d: max_prob_conv outside [0, nCTF) or a displacement of N pixels or more (conv %d, cent %d %d)",
@@ -2952,13 +3103,9 @@ int bioem_hip_debug_ring_sums(bioem_hip_handle h, const float *specR, const floa
     }
     recs[(size_t) p] = {0, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y, r.max_prob_norm, r.max_prob_mu};
   }
-  if (ring_staging(h))
+  if (ring_staging(h) || begin_analysis(h, true))
     return 1;
-  if (compat_flush(h))
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
   bioem_hip_ctx::Slot &s0 = h->slot[0];
-  void_slot(s0);
   const size_t M = (size_t) h->M, nRings = (size_t) bioem_ring_count(N);
   for (int b0 = 0; b0 < n; b0 += h->OB)
   {
@@ -2982,41 +3129,22 @@ int view_staging(bioem_hip_ctx *h, bool maps)
   const size_t OB = (size_t) h->OB, M = (size_t) h->M;
   if (!h->dViewNum)
   {
-    double2 *num = nullptr;
-    double *den = nullptr, *tau = nullptr;
-    BioemViewMember *mem = nullptr;
-    int *off = nullptr;
-    float2 *unit = nullptr;
     const std::vector<float2> ones(M, make_float2(1.f, 0.f));
-    if (dev_alloc(h, num, OB * M) || dev_alloc(h, den, OB * M) || dev_alloc(h, tau, OB) || dev_alloc(h, mem, OB) ||
-        dev_alloc(h, off, OB + 1) || dev_alloc(h, unit, M) ||
-        hipMemcpy(unit, ones.data(), sizeof(float2) * M, hipMemcpyHostToDevice) != hipSuccess)
-    {
-      dev_release(h, num);
-      dev_release(h, den);
-      dev_release(h, tau);
-      dev_release(h, mem);
-      dev_release(h, off);
-      dev_release(h, unit);
-      (void) hipGetLastError();
+    Staging st = {h};
+    st.get(h->dViewNum, OB * M);
+    st.get(h->dViewDen, OB * M);
+    st.get(h->dViewTau, OB);
+    st.get(h->dViewMem, OB);
+    st.get(h->dViewOff, OB + 1);
+    st.fill(st.get(h->dViewUnit, M), ones.data(), sizeof(float2) * M);
+    if (st.commit())
       return 1;
-    }
-    h->dViewNum = num;
-    h->dViewDen = den;
-    h->dViewTau = tau;
-    h->dViewMem = mem;
-    h->dViewOff = off;
-    h->dViewUnit = unit;
   }
   if (maps && !h->dViewMaps)
   {
-    float *out = nullptr;
-    if (dev_alloc(h, out, OB * (size_t) h->N * h->N))
-    {
-      (void) hipGetLastError();
-      return 1;
-    }
-    h->dViewMaps = out;
+    Staging st = {h};
+    st.get(h->dViewMaps, OB * (size_t) h->N * h->N);
+    return st.commit();
   }
   return 0;
 }
@@ -3027,14 +3155,11 @@ int view_members(bioem_hip_ctx *h, const char *what, const bioem_hip_prob_map *r
                  const int *groupOf, int nP, int nGroups, int g0, int g1, std::vector<BioemViewMember> &mem)
 {
   char buf[256];
-  auto refuse = [&](const char *why) {
-    h->err = std::string(what) + ": " + why;
-    return 2;
-  };
+  const Refuse refuse = {h, what};
   if (nGroups < 1 || g0 < 0 || g1 > nGroups || g0 >= g1)
     return refuse("group range empty, reversed or outside [0, nGroups)");
-  if (!h->ctfUp)
-    return refuse("CTF kernels not uploaded");
+  if (const char *why = missing_state(h, NEED_CTF, 0))
+    return refuse(why);
   const int N = h->N;
   mem.assign((size_t) nP, BioemViewMember{});
   for (int p = 0; p < nP; p++)
@@ -3049,10 +3174,8 @@ int view_members(bioem_hip_ctx *h, const char *what, const bioem_hip_prob_map *r
       why = "group outside [0, nGroups) and not -1";
     else if (!(w >= 0.) || !std::isfinite(w))
       why = "weight negative or not finite";
-    else if (r.max_prob_conv < 0 || r.max_prob_conv >= h->nCTF)
-      why = "max_prob_conv outside [0, nCTF)";
-    else if (r.max_prob_cent_x <= -N || r.max_prob_cent_x >= N || r.max_prob_cent_y <= -N || r.max_prob_cent_y >= N)
-      why = "displacement of N pixels or more";
+    else
+      why = bad_match_place(h, r);
     if (why)
     {
       snprintf(buf, sizeof(buf), "particle %d: %s (group %d of %d, weight %g, conv %d, cent %d %d)", p, why, g, nGroups, w,
@@ -3130,11 +3253,8 @@ int view_accumulate_chunk(bioem_hip_ctx *h, const float *specHost, const std::ve
 int view_sums_run(bioem_hip_ctx *h, const float *specHost, const std::vector<BioemViewMember> &mem, const double *weights,
                   const int *groupOf, int nP, int g0, int g1, double *num_out, double *den_out, double *stats_out)
 {
-  if (ring_staging(h) || view_staging(h, false))
+  if (ring_staging(h) || view_staging(h, false) || begin_analysis(h, false)) // (buffer set 0 is not written)
     return 1;
-  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
   const size_t M = (size_t) h->M;
   for (int ga = g0; ga < g1; ga += h->OB)
   {
@@ -3166,19 +3286,14 @@ int bioem_hip_view_sums(bioem_hip_handle h, const bioem_hip_prob_map *records, c
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "view_sums"};
   if (!records || !groupOf || !num_out || !den_out || !stats_out)
-  {
-    h->err = "view_sums: null argument";
-    return 2;
-  }
+    return refuse("null argument");
   std::vector<BioemViewMember> mem;
   if (const int rc = view_members(h, "view_sums", records, weights, groupOf, h->nMaps, nGroups, g0, g1, mem))
     return rc;
-  if (!h->refUp)
-  {
-    h->err = "view_sums: particles not uploaded";
-    return 2;
-  }
+  if (const char *why = missing_state(h, NEED_PARTICLES, 0))
+    return refuse(why);
   return view_sums_run(h, nullptr, mem, weights, groupOf, h->nMaps, g0, g1, num_out, den_out, stats_out);
 }
 
@@ -3189,10 +3304,7 @@ int bioem_hip_debug_view_sums(bioem_hip_handle h, const float *specR, const bioe
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
   if (!specR || !records || !groupOf || !num_out || !den_out || !stats_out || n < 1)
-  {
-    h->err = "debug_view_sums: null argument or no images";
-    return 2;
-  }
+    return Refuse{h, "debug_view_sums"}("null argument or no images");
   std::vector<BioemViewMember> mem;
   if (const int rc = view_members(h, "debug_view_sums", records, weights, groupOf, n, nGroups, 0, nGroups, mem))
     return rc;
@@ -3207,23 +3319,16 @@ int bioem_hip_view_averages(bioem_hip_handle h, const bioem_hip_prob_map *record
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
   char buf[160];
-  auto refuse = [&](const char *why) {
-    h->err = std::string("view_averages: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "view_averages"};
   if (!records || !groupOf || !groupOrient || !rings_out)
     return refuse("null argument");
   if (!(wiener >= 0.) || !std::isfinite(wiener))
     return refuse("wiener negative or not finite");
-  std::vector<BioemViewMember> mem;
+  std::vector<BioemViewMember> mem; // (the members' CTF sets are checked against the CTF kernels, so those come first here)
   if (const int rc = view_members(h, "view_averages", records, weights, groupOf, h->nMaps, nGroups, g0, g1, mem))
     return rc;
-  if (!h->dPts || h->nPts < 1)
-    return refuse("model not uploaded");
-  if (h->nAnglesUp < 1)
-    return refuse("orientations not uploaded");
-  if (!h->refUp)
-    return refuse("particles not uploaded");
+  if (const char *why = missing_state(h, NEED_MODEL | NEED_ORIENT | NEED_PARTICLES, 0))
+    return refuse(why);
   for (int g = g0; g < g1; g++)
     if (groupOrient[g] < -1 || groupOrient[g] >= h->nAnglesUp)
     {
@@ -3238,18 +3343,9 @@ int bioem_hip_view_averages(bioem_hip_handle h, const bioem_hip_prob_map *record
   const size_t lds = sizeof(double2) * 2 * (size_t) N;
   int A, B;
   dft_split(N, A, B);
-  if (maps)
-  {
-    HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_cols), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_render_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-  }
-  if (compat_flush(h))
+  if ((maps && render_lds_attr(h, lds)) || begin_analysis(h, true))
     return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
   bioem_hip_ctx::Slot &s0 = h->slot[0];
-  void_slot(s0);
-  const OrientList src = shared_list(h);
-  const OrientList L = {h->dRingAngles, src.isQuat, src.quatNormDev};
   std::vector<RenderRecord> recs;
   for (int ga = g0; ga < g1; ga += OB)
   {
@@ -3262,11 +3358,7 @@ int bioem_hip_view_averages(bioem_hip_handle h, const bioem_hip_prob_map *record
     recs.assign((size_t) nG, RenderRecord{0, 0, 0, 0, 1.f, 0.f});
     for (int g = ga; g < gb; g++)
       recs[(size_t) (g - ga)].src = std::max(0, groupOrient[g]);
-    HIP_CHECK(h, hipMemcpyAsync(h->dRingRec, recs.data(), sizeof(RenderRecord) * nG, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_render_gather, dim3((nG + 255) / 256), dim3(256), 0, h->stream, src.d, h->dRingRec, nG, h->dRingAngles);
-    HIP_CHECK(h, hipGetLastError());
-    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, ga, gb, 0, 0) || project_batch(h, s0, h->stream, L, 0, nG) ||
-        phase_end(h, h->stream))
+    if (stage_matches(h, shared_list(h), h->dRingRec, h->dRingAngles, recs.data(), nG, ga))
       return 1;
     bioem_hip_ring_sums *ro = rings_out + nRings * (size_t) (ga - g0);
     HIP_CHECK(h, bioem_ring_sums_launch(h->stream, h->dRingRef, s0.specRef, h->dViewUnit,
@@ -3328,48 +3420,21 @@ int window_staging(bioem_hip_ctx *h)
   std::vector<int> X;
   window_shifts(h->plan, X);
   const size_t nd = X.size();
-  BioemWindowRecord *rec = nullptr;
-  float4 *ang = nullptr;
-  float2 *ref = nullptr, *conv = nullptr;
-  float *terms = nullptr, *sums = nullptr, *cc = nullptr;
-  bioem_hip_param5 *par = nullptr;
-  double2 *postc = nullptr, *T = nullptr;
-  int *shifts = nullptr;
-  double *logp = nullptr;
-  if (dev_alloc(h, rec, OB) || dev_alloc(h, ang, OB) || dev_alloc(h, ref, OB * M) || dev_alloc(h, conv, OB * M) ||
-      dev_alloc(h, terms, OB * M4) || dev_alloc(h, sums, 2 * OB) || dev_alloc(h, cc, OB * nd * nd) ||
-      dev_alloc(h, par, OB) || dev_alloc(h, postc, OB) || dev_alloc(h, T, bioem_window_scratch(h->N, (int) nd, h->OB)) ||
-      dev_alloc(h, shifts, nd) || dev_alloc(h, logp, OB * nd * nd) ||
-      hipMemcpy(shifts, X.data(), sizeof(int) * nd, hipMemcpyHostToDevice) != hipSuccess)
-  {
-    dev_release(h, rec);
-    dev_release(h, ang);
-    dev_release(h, ref);
-    dev_release(h, conv);
-    dev_release(h, terms);
-    dev_release(h, sums);
-    dev_release(h, cc);
-    dev_release(h, par);
-    dev_release(h, postc);
-    dev_release(h, T);
-    dev_release(h, shifts);
-    dev_release(h, logp);
-    (void) hipGetLastError();
-    return 1;
-  }
-  h->dWinRec = rec;
-  h->dWinAngles = ang;
-  h->dWinRef = ref;
-  h->dWinConv = conv;
-  h->dWinTerms = terms;
-  h->dWinSums = sums;
-  h->dWinCc = cc;
-  h->dWinParams = par;
-  h->dWinPostc = postc;
-  h->dWinT = T;
-  h->dWinShifts = shifts;
-  h->dWinLogp = logp;
-  return 0;
+  Staging st = {h};
+  st.get(h->dWinRec, OB);
+  st.get(h->dWinAngles, OB);
+  st.get(h->dWinRef, OB * M);
+  st.get(h->dWinConv, OB * M);
+  st.get(h->dWinTerms, OB * M4);
+  st.get(h->dWinSums, 2 * OB);
+  st.get(h->dWinCc, OB * nd * nd);
+  st.get(h->dWinParams, OB);
+  st.get(h->dWinPostc, OB);
+  st.get(h->dWinT, bioem_window_scratch(h->N, (int) nd, h->OB));
+  int *shifts = st.get(h->dWinShifts, nd);
+  st.get(h->dWinLogp, OB * nd * nd);
+  st.fill(shifts, X.data(), sizeof(int) * nd);
+  return st.commit();
 }
 
 // the window pass of n staged records (records in dWinRec, conv spectra in dWinConv, particle spectra in dWinRef,
@@ -3411,68 +3476,31 @@ int bioem_hip_window_posterior(bioem_hip_handle h, const bioem_hip_window_reques
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  char buf[256];
-  auto refuse = [&](const char *why) {
-    h->err = std::string("window_posterior: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "window_posterior"};
   if (!req || !logp_out || n < 1)
     return refuse("null argument or no requests");
-  if (!h->dPts || h->nPts < 1)
-    return refuse("model not uploaded");
-  if (!h->ctfUp)
-    return refuse("CTF kernels not uploaded");
-  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
-    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
-                           : "orientations not uploaded");
-  if (!h->refUp)
-    return refuse("particles not uploaded");
+  if (const char *why = missing_state(h, NEED_ALL, ownLists))
+    return refuse(why);
   std::vector<BioemWindowRecord> recs((size_t) n);
   for (int i = 0; i < n; i++)
   {
-    const bioem_hip_window_request &r = req[i];
-    const char *why = nullptr;
-    int first = 0, len = 0;
-    if (r.particle < 0 || r.particle >= h->nMaps)
-      why = "particle outside [0, nMaps)";
-    else
-    {
-      first = ownLists ? h->ownOff[(size_t) r.particle] : 0;
-      len = ownLists ? h->ownOff[(size_t) r.particle + 1] - first : h->nAnglesUp;
-      if (r.orient < 0 || r.orient >= len)
-        why = "orient outside its orientation list";
-      else if (r.conv < 0 || r.conv >= h->nCTF)
-        why = "conv outside [0, nCTF)";
-    }
-    if (why)
-    {
-      snprintf(buf, sizeof(buf), "request %d: %s (particle %d of %d, orient %d of %d, conv %d of %d)", i, why, r.particle,
-               h->nMaps, r.orient, len, r.conv, h->nCTF);
-      return refuse(buf);
-    }
+    const bioem_hip_grad_request r = {req[i].particle, req[i].orient, req[i].conv, 0, 0};
+    int first, len;
+    if (const char *why = bad_request(h, r, REQ_CONV, ownLists, first, len))
+      return refuse(request_refusal(h, i, why, r, REQ_CONV, len));
     recs[(size_t) i] = {first + r.orient, r.conv, r.particle, 0, {0.f, 0.f}};
   }
-  if (window_staging(h))
+  if (window_staging(h) || begin_analysis(h, true))
     return 1;
-  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
   bioem_hip_ctx::Slot &s0 = h->slot[0];
-  void_slot(s0);
   const OrientList src = ownLists ? own_list(h) : shared_list(h);
-  const OrientList L = {h->dWinAngles, src.isQuat, src.quatNormDev};
   const int N = h->N, OB = h->OB;
   const size_t M = (size_t) h->M, cells = (size_t) h->plan.nd * h->plan.nd;
   const int M4 = (int) ((M + 3) & ~(size_t) 3);
   for (int b0 = 0; b0 < n; b0 += OB)
   {
     const int nb = std::min(OB, n - b0);
-    HIP_CHECK(h, hipMemcpyAsync(h->dWinRec, recs.data() + b0, sizeof(BioemWindowRecord) * nb, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_render_gather, dim3((nb + 255) / 256), dim3(256), 0, h->stream, src.d,
-                       reinterpret_cast<const RenderRecord *>(h->dWinRec), nb, h->dWinAngles);
-    HIP_CHECK(h, hipGetLastError());
-    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, b0, b0 + nb, 0, 0) ||
-        project_batch(h, s0, h->stream, L, 0, nb) || phase_end(h, h->stream))
+    if (stage_matches(h, src, h->dWinRec, h->dWinAngles, recs.data() + b0, nb, b0))
       return 1;
     if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, b0, b0 + nb, 0, 0))
       return 1;
@@ -3483,19 +3511,8 @@ int bioem_hip_window_posterior(bioem_hip_handle h, const bioem_hip_window_reques
     HIP_CHECK(h, hipGetLastError());
     if (phase_end(h, h->stream) || phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, b0, b0 + nb, 0, 0))
       return 1;
-    // the particles' spectra back in reference layout: one launch per run of consecutive particles
-    for (int i = 0; i < nb;)
-    {
-      int j = i + 1;
-      while (j < nb && recs[(size_t) (b0 + j)].particle == recs[(size_t) (b0 + j - 1)].particle + 1)
-        j++;
-      hipLaunchKernelGGL(k_unreorder, dim3(std::min(1024, 16 * (j - i))), dim3(256), 0, h->stream,
-                         h->dRef + h->Mc * (size_t) recs[(size_t) (b0 + i)].particle, h->dWinRef + M * (size_t) i, j - i, N, h->H,
-                         h->plan.halfR, h->plan.N1, h->Hp);
-      HIP_CHECK(h, hipGetLastError());
-      i = j;
-    }
-    if (window_batch(h, nb, h->dSumRef, h->dSumsqRef, logp_out + cells * (size_t) b0, cc_out ? cc_out + cells * (size_t) b0 : nullptr))
+    if (unreorder_runs(h, recs.data() + b0, nb, h->dWinRef) ||
+        window_batch(h, nb, h->dSumRef, h->dSumsqRef, logp_out + cells * (size_t) b0, cc_out ? cc_out + cells * (size_t) b0 : nullptr))
       return 1;
     if (params_out)
       HIP_CHECK(h, hipMemcpyAsync(params_out + b0, h->dWinParams, sizeof(bioem_hip_param5) * nb, hipMemcpyDeviceToHost, h->stream));
@@ -3514,15 +3531,9 @@ int bioem_hip_debug_window(bioem_hip_handle h, const float *specConv, const floa
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
   if (!specConv || !specRef || !params || !sumRef || !sumsqRef || !logp_out || n < 1)
-  {
-    h->err = "debug_window: null argument or no records";
-    return 2;
-  }
-  if (window_staging(h))
+    return Refuse{h, "debug_window"}("null argument or no records");
+  if (window_staging(h) || begin_analysis(h, false)) // (buffer set 0 is not written)
     return 1;
-  if (compat_flush(h))
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
   const size_t M = (size_t) h->M, cells = (size_t) h->plan.nd * h->plan.nd;
   std::vector<BioemWindowRecord> recs((size_t) std::min(n, h->OB));
   for (size_t i = 0; i < recs.size(); i++)
@@ -3566,58 +3577,27 @@ int scan_staging(bioem_hip_ctx *h, int G)
   const size_t OB = (size_t) h->OB, M = (size_t) h->M, cap = (size_t) scan_capacity(h);
   if (!h->dScanZ)
   {
-    BioemScanShift *sh = nullptr;
-    BioemWindowRecord *rec = nullptr;
-    float2 *pw = nullptr, *raw = nullptr;
-    double2 *z = nullptr;
-    float *sums = nullptr;
-    if (dev_alloc(h, sh, OB) || dev_alloc(h, rec, cap) || dev_alloc(h, pw, cap * M) ||
-        dev_alloc(h, raw, (size_t) kScanLanes * M) || dev_alloc(h, z, cap * M) || dev_alloc(h, sums, 2 * cap))
-    {
-      dev_release(h, sh);
-      dev_release(h, rec);
-      dev_release(h, pw);
-      dev_release(h, raw);
-      dev_release(h, z);
-      dev_release(h, sums);
-      (void) hipGetLastError();
+    Staging st = {h};
+    st.get(h->dScanShift, OB);
+    st.get(h->dScanRec, cap);
+    st.get(h->dScanPw, cap * M);
+    st.get(h->dScanRaw, (size_t) kScanLanes * M);
+    st.get(h->dScanZ, cap * M);
+    st.get(h->dScanSums, 2 * cap);
+    if (st.commit())
       return 1;
-    }
-    h->dScanShift = sh;
-    h->dScanRec = rec;
-    h->dScanPw = pw;
-    h->dScanRaw = raw;
-    h->dScanZ = z;
-    h->dScanSums = sums;
   }
   if (G <= h->scanCapG)
     return 0;
   const size_t chunks = ((size_t) G + kScanLanes - 1) / kScanLanes;
-  float2 *packed = nullptr;
-  float *ctf = nullptr, *cc = nullptr;
-  double *logp = nullptr;
-  bioem_hip_param5 *par = nullptr;
-  if (dev_alloc(h, packed, chunks * kScanLanes * M) || dev_alloc(h, ctf, 3 * (size_t) G) || dev_alloc(h, cc, cap * G) ||
-      dev_alloc(h, logp, cap * G) || dev_alloc(h, par, cap * G))
-  {
-    dev_release(h, packed);
-    dev_release(h, ctf);
-    dev_release(h, cc);
-    dev_release(h, logp);
-    dev_release(h, par);
-    (void) hipGetLastError();
+  Staging st = {h}; // the group that grows with G: what it held goes once the larger buffers are all there
+  st.get(h->dScanPacked, chunks * kScanLanes * M);
+  st.get(h->dScanCtf, 3 * (size_t) G);
+  st.get(h->dScanCc, cap * G);
+  st.get(h->dScanLogp, cap * G);
+  st.get(h->dScanParams, cap * G);
+  if (st.commit())
     return 1;
-  }
-  dev_release(h, h->dScanPacked);
-  dev_release(h, h->dScanCtf);
-  dev_release(h, h->dScanCc);
-  dev_release(h, h->dScanLogp);
-  dev_release(h, h->dScanParams);
-  h->dScanPacked = packed;
-  h->dScanCtf = ctf;
-  h->dScanCc = cc;
-  h->dScanLogp = logp;
-  h->dScanParams = par;
   h->scanCapG = G;
   return 0;
 }
@@ -3674,94 +3654,45 @@ int bioem_hip_ctf_scan(bioem_hip_handle h, const bioem_hip_scan_request *req, in
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  char buf[256];
-  auto refuse = [&](const char *why) {
-    h->err = std::string("ctf_scan: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "ctf_scan"};
   if (!req || !logp_out || n < 1)
     return refuse("null argument or no requests");
   if (G < 1)
-  {
-    snprintf(buf, sizeof(buf), "no candidates (G = %d)", G);
-    return refuse(buf);
-  }
+    return refuse("no candidates (G = " + std::to_string(G) + ")");
   if (!kernels || !ctfParam3)
     return refuse("null candidate kernels or parameters");
-  if (!h->dPts || h->nPts < 1)
-    return refuse("model not uploaded");
-  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
-    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
-                           : "orientations not uploaded");
-  if (!h->refUp)
-    return refuse("particles not uploaded");
-  const int N = h->N, OB = h->OB;
+  if (const char *why = missing_state(h, NEED_MODEL | NEED_ORIENT | NEED_PARTICLES, ownLists)) // (the CTF sets are handed in)
+    return refuse(why);
+  const int OB = h->OB;
   std::vector<BioemWindowRecord> recs((size_t) n);
   std::vector<BioemScanShift> shifts((size_t) n);
   for (int i = 0; i < n; i++)
   {
-    const bioem_hip_scan_request &r = req[i];
-    const char *why = nullptr;
-    int first = 0, len = 0;
-    if (r.particle < 0 || r.particle >= h->nMaps)
-      why = "particle outside [0, nMaps)";
-    else
-    {
-      first = ownLists ? h->ownOff[(size_t) r.particle] : 0;
-      len = ownLists ? h->ownOff[(size_t) r.particle + 1] - first : h->nAnglesUp;
-      if (r.orient < 0 || r.orient >= len)
-        why = "orient outside its orientation list";
-      else if (r.shiftX <= -N || r.shiftX >= N || r.shiftY <= -N || r.shiftY >= N)
-        why = "shift outside (-N, N)";
-    }
-    if (why)
-    {
-      snprintf(buf, sizeof(buf), "request %d: %s (particle %d of %d, orient %d of %d, shift %d %d, N %d)", i, why, r.particle,
-               h->nMaps, r.orient, len, r.shiftX, r.shiftY, N);
-      return refuse(buf);
-    }
+    const bioem_hip_grad_request r = {req[i].particle, req[i].orient, 0, req[i].shiftX, req[i].shiftY};
+    int first, len;
+    if (const char *why = bad_request(h, r, REQ_SHIFT, ownLists, first, len))
+      return refuse(request_refusal(h, i, why, r, REQ_SHIFT, len));
     recs[(size_t) i] = {first + r.orient, 0, r.particle, 0, {0.f, 0.f}};
     shifts[(size_t) i] = {r.shiftX, r.shiftY};
   }
-  if (scan_staging(h, G))
+  if (scan_staging(h, G) || begin_analysis(h, true))
     return 1;
-  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
   bioem_hip_ctx::Slot &s0 = h->slot[0];
-  void_slot(s0);
   const OrientList src = ownLists ? own_list(h) : shared_list(h);
-  const OrientList L = {h->dWinAngles, src.isQuat, src.quatNormDev};
-  const size_t M = (size_t) h->M;
   const int cap = scan_capacity(h);
   for (int b0 = 0, r0 = 0; b0 < n; b0 += OB) // r0: the first request of the launch being gathered
   {
     const int nb = std::min(OB, n - b0);
+    // (stage_matches with the shifts' copy between its records' copy and its gather, as it always was enqueued)
     HIP_CHECK(h, hipMemcpyAsync(h->dWinRec, recs.data() + b0, sizeof(BioemWindowRecord) * nb, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shifts.data() + b0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_render_gather, dim3((nb + 255) / 256), dim3(256), 0, h->stream, src.d,
-                       reinterpret_cast<const RenderRecord *>(h->dWinRec), nb, h->dWinAngles);
-    HIP_CHECK(h, hipGetLastError());
-    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, b0, b0 + nb, 0, 0) ||
-        project_batch(h, s0, h->stream, L, 0, nb) || phase_end(h, h->stream))
+    if (gather_matches(h, src, h->dWinRec, nb, h->dWinAngles) || project_matches(h, src, h->dWinAngles, 0, nb, b0))
       return 1;
     if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, b0, b0 + nb, 0, 0))
       return 1;
     if (b0 == 0 && scan_candidates(h, kernels, ctfParam3, G)) // (part of the first batch's preparation)
       return 1;
-    // the particles' spectra back in reference layout: one launch per run of consecutive particles
-    for (int i = 0; i < nb;)
-    {
-      int j = i + 1;
-      while (j < nb && recs[(size_t) (b0 + j)].particle == recs[(size_t) (b0 + j - 1)].particle + 1)
-        j++;
-      hipLaunchKernelGGL(k_unreorder, dim3(std::min(1024, 16 * (j - i))), dim3(256), 0, h->stream,
-                         h->dRef + h->Mc * (size_t) recs[(size_t) (b0 + i)].particle, h->dWinRef + M * (size_t) i, j - i, N, h->H,
-                         h->plan.halfR, h->plan.N1, h->Hp);
-      HIP_CHECK(h, hipGetLastError());
-      i = j;
-    }
-    if (scan_prepare(h, b0 - r0, nb, s0.specRef, recs.data() + b0))
+    if (unreorder_runs(h, recs.data() + b0, nb, h->dWinRef) || scan_prepare(h, b0 - r0, nb, s0.specRef, recs.data() + b0))
       return 1;
     if (b0 + nb - r0 + OB > cap || b0 + nb == n)
     { // no room for another batch, or the last one: one launch over what is gathered
@@ -3783,26 +3714,14 @@ int bioem_hip_debug_ctf_scan(bioem_hip_handle h, const float *specP, const float
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  char buf[160];
+  const Refuse refuse = {h, "debug_ctf_scan"};
   if (!specP || !specRef || !sumRef || !sumsqRef || !shiftXY || !kernels || !ctfParam3 || !logp_out || n < 1 || G < 1)
-  {
-    h->err = "debug_ctf_scan: null argument, no records or no candidates";
-    return 2;
-  }
-  const int N = h->N, OB = h->OB;
-  for (int i = 0; i < n; i++)
-    if (shiftXY[2 * i] <= -N || shiftXY[2 * i] >= N || shiftXY[2 * i + 1] <= -N || shiftXY[2 * i + 1] >= N)
-    {
-      snprintf(buf, sizeof(buf), "debug_ctf_scan: record %d: shift outside (-N, N) (shift %d %d, N %d)", i, shiftXY[2 * i],
-               shiftXY[2 * i + 1], N);
-      h->err = buf;
-      return 2;
-    }
-  if (scan_staging(h, G))
+    return refuse("null argument, no records or no candidates");
+  if (const int rc = debug_shifts_refused(h, refuse, shiftXY, n))
+    return rc;
+  if (scan_staging(h, G) || begin_analysis(h, false)) // (buffer set 0 is not written)
     return 1;
-  if (compat_flush(h))
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
+  const int OB = h->OB;
   const size_t M = (size_t) h->M;
   const int cap = scan_capacity(h);
   std::vector<BioemWindowRecord> recs((size_t) std::min(n, cap)); // a record's sums lie at its place in the launch
@@ -3847,60 +3766,29 @@ int grad_staging(bioem_hip_ctx *h, int G, int nPts)
   const size_t OB = (size_t) h->OB, M = (size_t) h->M, NN = (size_t) h->N * h->N, cap = (size_t) scan_capacity(h);
   if (!h->dGradMap)
   { // per record of a launch of the scan: records, coefficients, weights, parameters, orientations; the rest per batch
-    BioemGradRecord *rec = nullptr;
-    double *coef = nullptr, *w = nullptr, *mT = nullptr, *map = nullptr;
-    bioem_hip_param5 *par = nullptr;
-    double2 *spec = nullptr;
-    float4 *ang = nullptr;
-    if (dev_alloc(h, rec, cap) || dev_alloc(h, coef, 4 * cap) || dev_alloc(h, w, cap) || dev_alloc(h, mT, 2 * OB) ||
-        dev_alloc(h, map, OB * NN) || dev_alloc(h, par, cap) || dev_alloc(h, spec, OB * M) || dev_alloc(h, ang, cap))
-    {
-      dev_release(h, ang);
-      dev_release(h, rec);
-      dev_release(h, coef);
-      dev_release(h, w);
-      dev_release(h, mT);
-      dev_release(h, map);
-      dev_release(h, par);
-      dev_release(h, spec);
-      (void) hipGetLastError();
+    Staging st = {h};
+    st.get(h->dGradRec, cap);
+    st.get(h->dGradCoef, 4 * cap);
+    st.get(h->dGradW, cap);
+    st.get(h->dGradMT, 2 * OB);
+    st.get(h->dGradMap, OB * NN);
+    st.get(h->dGradParams, cap);
+    st.get(h->dGradSpec, OB * M);
+    st.get(h->dGradAngles, cap);
+    if (st.commit())
       return 1;
-    }
-    h->dGradRec = rec;
-    h->dGradCoef = coef;
-    h->dGradW = w;
-    h->dGradMT = mT;
-    h->dGradMap = map;
-    h->dGradParams = par;
-    h->dGradSpec = spec;
-    h->dGradAngles = ang;
   }
   if (nPts <= h->gradCapPts)
     return 0;
   const size_t P = (size_t) nPts, tiles = (size_t) bioem_grad_tiles(nPts);
-  double *u = nullptr, *vs = nullptr, *part = nullptr, *rows = nullptr;
-  bioem_hip_grad_point *acc = nullptr;
-  if (dev_alloc(h, u, OB * P) || dev_alloc(h, vs, OB * P) || dev_alloc(h, part, 2 * OB * tiles) || dev_alloc(h, rows, OB * P) ||
-      dev_alloc(h, acc, P))
-  {
-    dev_release(h, u);
-    dev_release(h, vs);
-    dev_release(h, part);
-    dev_release(h, rows);
-    dev_release(h, acc);
-    (void) hipGetLastError();
+  Staging st = {h}; // the group that grows with the model: what it held goes once the larger buffers are all there
+  st.get(h->dGradU, OB * P);
+  st.get(h->dGradVS, OB * P);
+  st.get(h->dGradPart, 2 * OB * tiles);
+  st.get(h->dGradRows, OB * P);
+  st.get(h->dGradAcc, P);
+  if (st.commit())
     return 1;
-  }
-  dev_release(h, h->dGradU);
-  dev_release(h, h->dGradVS);
-  dev_release(h, h->dGradPart);
-  dev_release(h, h->dGradRows);
-  dev_release(h, h->dGradAcc);
-  h->dGradU = u;
-  h->dGradVS = vs;
-  h->dGradPart = part;
-  h->dGradRows = rows;
-  h->dGradAcc = acc;
   h->gradCapPts = nPts;
   return 0;
 }
@@ -3924,24 +3812,13 @@ int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *r
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  char buf[256];
-  auto refuse = [&](const char *why) {
-    h->err = std::string("model_gradient: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "model_gradient"};
   if (!req || n < 1)
     return refuse("null argument or no requests");
   if (!grad_out && !points_out)
     return refuse("grad_out and points_out both null");
-  if (!h->dPts || h->nPts < 1)
-    return refuse("model not uploaded");
-  if (!h->ctfUp)
-    return refuse("CTF kernels not uploaded");
-  if (ownLists ? (!h->dOwnAngles || h->ownOff.empty()) : h->nAnglesUp < 1)
-    return refuse(ownLists ? "no per-particle orientation lists (bioem_hip_upload_particle_orientation_lists)"
-                           : "orientations not uploaded");
-  if (!h->refUp)
-    return refuse("particles not uploaded");
+  if (const char *why = missing_state(h, NEED_ALL, ownLists))
+    return refuse(why);
   const int N = h->N, OB = h->OB, G = h->nCTF, nPts = h->nPts;
   const int cap = scan_capacity(h); // records one launch of the scan serves: whole batches
   std::vector<BioemWindowRecord> recs((size_t) n);
@@ -3951,44 +3828,22 @@ int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *r
   for (int i = 0; i < n; i++)
   {
     const bioem_hip_grad_request &r = req[i];
-    const char *why = nullptr;
-    int first = 0, len = 0;
-    if (r.particle < 0 || r.particle >= h->nMaps)
-      why = "particle outside [0, nMaps)";
-    else
-    {
-      first = ownLists ? h->ownOff[(size_t) r.particle] : 0;
-      len = ownLists ? h->ownOff[(size_t) r.particle + 1] - first : h->nAnglesUp;
-      if (r.orient < 0 || r.orient >= len)
-        why = "orient outside its orientation list";
-      else if (r.conv < 0 || r.conv >= G)
-        why = "conv outside [0, nCTF)";
-      else if (r.shiftX <= -N || r.shiftX >= N || r.shiftY <= -N || r.shiftY >= N)
-        why = "shift outside (-N, N)";
-      else if (weights && !std::isfinite(weights[i]))
-        why = "weight not finite";
-    }
+    int first, len;
+    const char *why = bad_request(h, r, REQ_CONV | REQ_SHIFT, ownLists, first, len);
+    if (!why && weights && !std::isfinite(weights[i]))
+      why = "weight not finite";
     if (why)
-    {
-      snprintf(buf, sizeof(buf), "request %d: %s (particle %d of %d, orient %d of %d, conv %d of %d, shift %d %d, N %d)", i, why,
-               r.particle, h->nMaps, r.orient, len, r.conv, G, r.shiftX, r.shiftY, N);
-      return refuse(buf);
-    }
+      return refuse(request_refusal(h, i, why, r, REQ_CONV | REQ_SHIFT, len));
     recs[(size_t) i] = {first + r.orient, r.conv, r.particle, 0, {0.f, 0.f}};
     shifts[(size_t) i] = {r.shiftX, r.shiftY};
     grecs[(size_t) i] = {r.conv, r.particle, (i % cap) * G + r.conv, 0};
     if (weights)
       ws[(size_t) i] = weights[i];
   }
-  if (grad_staging(h, G, nPts))
+  if (grad_staging(h, G, nPts) || begin_analysis(h, true))
     return 1;
-  if (compat_flush(h)) // rows staged through the reference-compatible entry go first (call order)
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream)); // nothing queued may still use buffer set 0
   bioem_hip_ctx::Slot &s0 = h->slot[0];
-  void_slot(s0);
   const OrientList src = ownLists ? own_list(h) : shared_list(h);
-  const OrientList L = {h->dGradAngles, src.isQuat, src.quatNormDev};
   const size_t M = (size_t) h->M;
   int A, B;
   dft_split(N, A, B);
@@ -3999,33 +3854,21 @@ int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *r
     HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(h, hipMemcpyAsync(h->dGradRec, grecs.data() + g0, sizeof(BioemGradRecord) * ng, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(h, hipMemcpyAsync(h->dGradW, ws.data() + g0, sizeof(double) * ng, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_render_gather, dim3((ng + 255) / 256), dim3(256), 0, h->stream, src.d,
-                       reinterpret_cast<const RenderRecord *>(h->dScanRec), ng, h->dGradAngles);
-    HIP_CHECK(h, hipGetLastError());
+    if (gather_matches(h, src, h->dScanRec, ng, h->dGradAngles)) // (once per launch of the scan: phase 3 reads them again)
+      return 1;
     // per batch: the projection and the scan's preparation of its records, into their places of the launch
     for (int b0 = 0; b0 < ng; b0 += OB)
     {
       const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
       HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shifts.data() + r0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
-      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, r0, r0 + nb, 0, 0) ||
-          project_batch(h, s0, h->stream, L, b0, nb) || phase_end(h, h->stream))
+      if (project_matches(h, src, h->dGradAngles, b0, nb, r0))
         return 1;
       if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, r0, r0 + nb, 0, 0))
         return 1;
       if (r0 == 0 && grad_candidates(h)) // (part of the first batch's preparation)
         return 1;
-      // the particles' spectra back in reference layout: one launch per run of consecutive particles
-      for (int i = 0; i < nb;)
-      {
-        int j = i + 1;
-        while (j < nb && recs[(size_t) (r0 + j)].particle == recs[(size_t) (r0 + j - 1)].particle + 1)
-          j++;
-        hipLaunchKernelGGL(k_unreorder, dim3(std::min(1024, 16 * (j - i))), dim3(256), 0, h->stream,
-                           h->dRef + h->Mc * (size_t) recs[(size_t) (r0 + i)].particle, h->dWinRef + M * (size_t) i, j - i, N, h->H,
-                           h->plan.halfR, h->plan.N1, h->Hp);
-        HIP_CHECK(h, hipGetLastError());
-        i = j;
-      }
+      if (unreorder_runs(h, recs.data() + r0, nb, h->dWinRef))
+        return 1;
       HIP_CHECK(h, bioem_scan_prep_launch(h->stream, s0.specRef, h->dWinRef, h->dScanShift, nb, N, h->dTwD,
                                           h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0));
       if (phase_end(h, h->stream))
@@ -4051,7 +3894,7 @@ int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *r
       HIP_CHECK(h, bioem_grad_inverse_launch(h->stream, h->dGradSpec, nb, N, A, B, h->dTwD, s0.rowSpec, h->dGradMap));
       if (phase_end(h, h->stream) || phase_begin(h, h->stream, 3, r0, r0 + nb, 0, 0))
         return 1;
-      HIP_CHECK(h, bioem_grad_gather_launch(h->stream, h->dPts, nPts, h->dGradAngles, b0, L.isQuat, N, h->pixelSize, h->shiftX,
+      HIP_CHECK(h, bioem_grad_gather_launch(h->stream, h->dPts, nPts, h->dGradAngles, b0, src.isQuat, N, h->pixelSize, h->shiftX,
                                             h->shiftY, h->dGradMap, nb, h->dGradU, h->dGradVS, h->dGradPart));
       HIP_CHECK(h, bioem_grad_fold_launch(h->stream, h->dGradU, h->dGradVS, h->dGradPart, h->dGradW + b0, nb, nPts, h->NormDen,
                                           h->dGradMT, h->dGradCoef + 4 * (size_t) b0, grad_out ? h->dGradRows : nullptr,
@@ -4084,28 +3927,15 @@ int bioem_hip_debug_grad_image(bioem_hip_handle h, const float *specConv, const 
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  char buf[160];
+  const Refuse refuse = {h, "debug_grad_image"};
   if (!specConv || !specRef || !kernels || !params || !sumRef || !sumsqRef || !shiftXY || !gmap_out || !coef_out || n < 1)
-  {
-    h->err = "debug_grad_image: null argument or no records";
-    return 2;
-  }
-  const int N = h->N, OB = h->OB;
-  for (int i = 0; i < n; i++)
-    if (shiftXY[2 * i] <= -N || shiftXY[2 * i] >= N || shiftXY[2 * i + 1] <= -N || shiftXY[2 * i + 1] >= N)
-    {
-      snprintf(buf, sizeof(buf), "debug_grad_image: record %d: shift outside (-N, N) (shift %d %d, N %d)", i, shiftXY[2 * i],
-               shiftXY[2 * i + 1], N);
-      h->err = buf;
-      return 2;
-    }
-  if (grad_staging(h, 1, std::max(1, h->nPts)))
+    return refuse("null argument or no records");
+  if (const int rc = debug_shifts_refused(h, refuse, shiftXY, n))
+    return rc;
+  if (grad_staging(h, 1, std::max(1, h->nPts)) || begin_analysis(h, true))
     return 1;
-  if (compat_flush(h))
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
   bioem_hip_ctx::Slot &s0 = h->slot[0];
-  void_slot(s0);
+  const int N = h->N, OB = h->OB;
   const size_t M = (size_t) h->M, NN = (size_t) N * N;
   int A, B;
   dft_split(N, A, B);
@@ -4159,21 +3989,13 @@ int bioem_hip_debug_grad_gather(bioem_hip_handle h, const double *gmaps, int o0,
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "debug_grad_gather"};
   if (!gmaps || !u_out || nO < 1 || o0 < 0 || o0 + nO > h->nAnglesUp)
-  {
-    h->err = "debug_grad_gather: null argument, or orientations empty or outside the uploaded list";
-    return 2;
-  }
-  if (!h->dPts || h->nPts < 1)
-  {
-    h->err = "debug_grad_gather: model not uploaded";
-    return 2;
-  }
-  if (grad_staging(h, 1, h->nPts))
+    return refuse("null argument, or orientations empty or outside the uploaded list");
+  if (const char *why = missing_state(h, NEED_MODEL, 0))
+    return refuse(why);
+  if (grad_staging(h, 1, h->nPts) || begin_analysis(h, false)) // (buffer set 0 is not written)
     return 1;
-  if (compat_flush(h))
-    return 1;
-  HIP_CHECK(h, hipStreamSynchronize(h->prepStream));
   const int N = h->N, OB = h->OB, nPts = h->nPts;
   const size_t NN = (size_t) N * N;
   for (int b0 = 0; b0 < nO; b0 += OB)
@@ -4195,10 +4017,7 @@ int bioem_hip_orientation_sums(bioem_hip_handle h, const double *logPrior, int i
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  auto refuse = [&](const char *why) {
-    h->err = std::string("orientation_sums: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "orientation_sums"};
   if (!h->pd.writeAngles)
     return refuse("handle was created without WRITE_PROB_ANGLES");
   if (!out)
@@ -4216,22 +4035,13 @@ int bioem_hip_orientation_sums(bioem_hip_handle h, const double *logPrior, int i
   const int nO = h->angO1 - h->angO0, np = iMapEnd - iMapBegin;
   if (!h->dOrientOut)
   {
-    double *scr = nullptr, *qq = nullptr, *pri = nullptr;
-    bioem_hip_orient_sums *res = nullptr;
-    if (dev_alloc(h, scr, bioem_orient_scratch(nO, h->nMaps)) || dev_alloc(h, qq, (size_t) nO * 10) ||
-        dev_alloc(h, pri, (size_t) nO) || dev_alloc(h, res, (size_t) h->nMaps))
-    {
-      dev_release(h, scr);
-      dev_release(h, qq);
-      dev_release(h, pri);
-      dev_release(h, res);
-      (void) hipGetLastError();
+    Staging st = {h};
+    st.get(h->dOrientScratch, bioem_orient_scratch(nO, h->nMaps));
+    st.get(h->dOrientQQ, (size_t) nO * 10);
+    st.get(h->dOrientPrior, (size_t) nO);
+    st.get(h->dOrientOut, (size_t) h->nMaps);
+    if (st.commit())
       return 1;
-    }
-    h->dOrientScratch = scr;
-    h->dOrientQQ = qq;
-    h->dOrientPrior = pri;
-    h->dOrientOut = res;
   }
   if (logPrior)
     HIP_CHECK(h, hipMemcpyAsync(h->dOrientPrior, logPrior + h->angO0, sizeof(double) * (size_t) nO, hipMemcpyHostToDevice, h->stream));
@@ -4249,13 +4059,8 @@ int bioem_hip_orientation_sums(bioem_hip_handle h, const double *logPrior, int i
                                   ownLists ? h->dOwnAngles : nullptr, ownLists ? h->dOwnOff : nullptr, h->ownIsQuat,
                                   h->dOrientScratch, h->dOrientOut);
   if (le != hipSuccess || phase_end(h, h->stream))
-  { // a launch failed: the phase that was opened is dropped, its events go back to the pool
-    if (h->phaseTiming && !h->phasePending.empty())
-    {
-      h->evPool.push_back(h->phasePending.back().a);
-      h->evPool.push_back(h->phasePending.back().b);
-      h->phasePending.pop_back();
-    }
+  {
+    drop_open_phase(h);
     if (le != hipSuccess)
       h->err = std::string("orientation_sums: launch failed: ") + hipGetErrorString(le);
     return 1;
@@ -4337,10 +4142,7 @@ int debug_orient(bioem_hip_ctx *h, const char *what, const bioem_hip_prob_angle 
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  auto refuse = [&](const char *why) {
-    h->err = std::string(what) + ": " + why;
-    return 2;
-  };
+  const Refuse refuse = {h, what};
   if (!table || !out || nO < 1 || nMaps < 1 || (offsets && !angles4))
     return refuse("null argument or an empty table");
   std::vector<int> off;
@@ -4428,10 +4230,7 @@ int bioem_hip_orientation_occupancy(bioem_hip_handle h, const double *logPrior, 
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  auto refuse = [&](const char *why) {
-    h->err = std::string("orientation_occupancy: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "orientation_occupancy"};
   if (!h->pd.writeAngles)
     return refuse("handle was created without WRITE_PROB_ANGLES");
   if (!sums || !out)
@@ -4447,25 +4246,14 @@ int bioem_hip_orientation_occupancy(bioem_hip_handle h, const double *logPrior, 
   const int nO = h->angO1 - h->angO0, np = iMapEnd - iMapBegin;
   if (!h->dOccOut)
   {
-    double *m = nullptr, *rs = nullptr, *pri = nullptr;
-    int *om = nullptr;
-    bioem_hip_orient_occ *res = nullptr;
-    if (dev_alloc(h, m, (size_t) h->nMaps) || dev_alloc(h, rs, (size_t) h->nMaps) || dev_alloc(h, pri, (size_t) nO) ||
-        dev_alloc(h, om, (size_t) h->nMaps) || dev_alloc(h, res, (size_t) nO))
-    {
-      dev_release(h, m);
-      dev_release(h, rs);
-      dev_release(h, pri);
-      dev_release(h, om);
-      dev_release(h, res);
-      (void) hipGetLastError();
+    Staging st = {h};
+    st.get(h->dOccM, (size_t) h->nMaps);
+    st.get(h->dOccRS0, (size_t) h->nMaps);
+    st.get(h->dOccPrior, (size_t) nO);
+    st.get(h->dOccOmax, (size_t) h->nMaps);
+    st.get(h->dOccOut, (size_t) nO);
+    if (st.commit())
       return 1;
-    }
-    h->dOccM = m;
-    h->dOccRS0 = rs;
-    h->dOccPrior = pri;
-    h->dOccOmax = om;
-    h->dOccOut = res;
   }
   const OccNormalisers N(sums, np);
   // the copies below read N and the caller's buffers asynchronously: whichever way this call ends, the stream is drained
@@ -4487,13 +4275,8 @@ int bioem_hip_orientation_occupancy(bioem_hip_handle h, const double *logPrior, 
   const hipError_t le = bioem_orient_occ_launch(h->stream, pang, nO, h->nMaps, iMapBegin, np, h->angO0,
                                                 logPrior ? h->dOccPrior : nullptr, h->dOccM, h->dOccRS0, h->dOccOmax, h->dOccOut);
   if (le != hipSuccess || phase_end(h, h->stream))
-  { // the launch failed: the phase that was opened is dropped, its events go back to the pool
-    if (h->phaseTiming && !h->phasePending.empty())
-    {
-      h->evPool.push_back(h->phasePending.back().a);
-      h->evPool.push_back(h->phasePending.back().b);
-      h->phasePending.pop_back();
-    }
+  {
+    drop_open_phase(h);
     if (le != hipSuccess)
       h->err = std::string("orientation_occupancy: launch failed: ") + hipGetErrorString(le);
     return 1;
@@ -4510,10 +4293,7 @@ int bioem_hip_debug_orient_occupancy(bioem_hip_handle h, const bioem_hip_prob_an
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
-  auto refuse = [&](const char *why) {
-    h->err = std::string("debug_orient_occupancy: ") + why;
-    return 2;
-  };
+  const Refuse refuse = {h, "debug_orient_occupancy"};
   if (!table || !sums || !out || nO < 1 || nMaps < 1)
     return refuse("null argument or an empty table");
   if (p0 < 0 || p1 > nMaps || p0 >= p1)
