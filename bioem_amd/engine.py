@@ -185,6 +185,63 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _spectra(a):
+    """spectra float32 [..., 2], or complex [...] viewed as such"""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "c":
+        a = np.ascontiguousarray(a.astype(np.complex64)).view(np.float32).reshape(a.shape + (2,))
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _pmap(pmap, n):
+    """the map entries of a probability block: PROB_MAP_DTYPE [n], contiguous"""
+    pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
+    assert pmap.shape == (n,)
+    return pmap
+
+
+def _vector(v, n):
+    """an optional prior or weight vector: None, or float64 [n], contiguous"""
+    if v is None:
+        return None
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    assert v.shape == (n,), v.shape
+    return v
+
+
+def _requests(requests, dtype):
+    """requests of a request dtype as a contiguous [n] array of it: such an array itself, or an [n, k] integer array (a
+    list of tuples) with the columns in the order of dtype.names"""
+    r = np.asarray(requests)
+    if r.dtype != dtype:
+        r = np.asarray(r, dtype=np.int32)
+        if r.ndim == 2 and r.shape[1] != len(dtype.names):
+            raise ValueError("%d columns for the requests (%s)" % (r.shape[1], ", ".join(dtype.names)))
+        r = r.reshape(-1, len(dtype.names))
+        q = np.zeros(len(r), dtype=dtype)
+        for i, f in enumerate(dtype.names):
+            q[f] = r[:, i]
+        r = q
+    return np.ascontiguousarray(r.reshape(-1))
+
+
+def _match_requests(pmap, p0, p1, dtype):
+    """the requests of a request dtype for the best records of particles [p0, p1) of pmap (PROB_MAP_DTYPE): every field the
+    dtype has from the record's orient, conv, cent_x (shiftX) and cent_y (shiftY)"""
+    p0, p1 = int(p0), int(p1)
+    req = np.zeros(max(0, p1 - p0), dtype=dtype)
+    req["particle"] = np.arange(p0, p1)
+    for f in dtype.names[1:]:
+        req[f] = pmap[{"shiftX": "cent_x", "shiftY": "cent_y"}.get(f, f)][p0:p1]
+    return req
+
+
+def _first_or_tuple(first, *extras):
+    """first alone, or the tuple of it and the extras that were asked for (those not None)"""
+    out = (first,) + tuple(e for e in extras if e is not None)
+    return out[0] if len(out) == 1 else out
+
+
 def ring_count(N):
     """rings of an N x N image (bioem_hip_ring_count): the rounded radius of the corner coefficient plus one; no device"""
     return int(load_library().bioem_hip_ring_count(int(N)))
@@ -243,7 +300,9 @@ class Engine:
 
     def _chk(self, rc, what):
         if rc:
-            raise RuntimeError("%s: %s" % (what, self.L.bioem_hip_last_error(self.h).decode()))
+            e = RuntimeError("%s: %s" % (what, self.L.bioem_hip_last_error(self.h).decode()))
+            e.rc = rc
+            raise e
 
     def close(self):
         if self.h:
@@ -416,15 +475,10 @@ class Engine:
         out[p, (k + X) mod N, (j + Y) mod N] = conv[k, j] / N^2 * norm + mu for the record (orient, conv, X, Y, norm, mu) of
         pmap (PROB_MAP_DTYPE [nMaps], global particle indices: the block of finish_run or a merged one); own: orient
         indexes the particle's own list.  Call outside a run.  A refused record raises RuntimeError with .rc == 2."""
-        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
-        assert pmap.shape == (self.nMaps,)
+        pmap = _pmap(pmap, self.nMaps)
         p1 = self.nMaps if p1 is None else int(p1)
         out = np.empty((max(0, p1 - int(p0)), self.N, self.N), dtype=np.float32)
-        rc = self.L.bioem_hip_render_best_maps(self.h, _p(pmap), int(bool(own)), int(p0), p1, _p(out))
-        if rc:
-            e = RuntimeError("render_best_maps: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(self.L.bioem_hip_render_best_maps(self.h, _p(pmap), int(bool(own)), int(p0), p1, _p(out)), "render_best_maps")
         return out
 
     def best_match_rings(self, pmap, p0=0, p1=None, own=False):
@@ -433,51 +487,28 @@ class Engine:
         particle's spectrum, M the spectrum of the image render_best_maps writes for the record, w the weight of the
         Hermitian partner; include/bioem_hip.h).  pmap, own and the calling rules as render_best_maps; needs the
         particles.  A refused record raises RuntimeError with .rc == 2."""
-        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
-        assert pmap.shape == (self.nMaps,)
+        pmap = _pmap(pmap, self.nMaps)
         p1 = self.nMaps if p1 is None else int(p1)
         out = np.zeros((max(0, p1 - int(p0)), ring_count(self.N)), dtype=RING_SUMS_DTYPE)
-        rc = self.L.bioem_hip_best_match_rings(self.h, _p(pmap), int(bool(own)), int(p0), p1, _p(out))
-        if rc:
-            e = RuntimeError("best_match_rings: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(self.L.bioem_hip_best_match_rings(self.h, _p(pmap), int(bool(own)), int(p0), p1, _p(out)), "best_match_rings")
         return out
 
     def debug_ring_sums(self, specR, specP, records):
         """test hook: the ring kernel of best_match_rings on n spectrum pairs handed in, float32 [n, N, H, 2] each (or
         complex64 [n, N, H]); records: PROB_MAP_DTYPE [n], of which conv, cent_x, cent_y, norm and mu are used.  Needs
         the CTF kernels only.  Returns RING_SUMS_DTYPE [n, ring_count(N)]; a refusal raises with .rc == 2."""
-        def spec(a):
-            a = np.ascontiguousarray(a)
-            if a.dtype.kind == "c":
-                a = np.ascontiguousarray(a.astype(np.complex64)).view(np.float32).reshape(a.shape + (2,))
-            return np.ascontiguousarray(a, dtype=np.float32)
-        specR, specP = spec(specR), spec(specP)
+        specR, specP = _spectra(specR), _spectra(specP)
         records = np.ascontiguousarray(records, dtype=PROB_MAP_DTYPE)
         n = len(records)
         assert specR.shape == (n, self.N, self.H, 2) and specP.shape == specR.shape
         out = np.zeros((n, ring_count(self.N)), dtype=RING_SUMS_DTYPE)
-        rc = self.L.bioem_hip_debug_ring_sums(self.h, _p(specR), _p(specP), _p(records), n, _p(out))
-        if rc:
-            e = RuntimeError("debug_ring_sums: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(self.L.bioem_hip_debug_ring_sums(self.h, _p(specR), _p(specP), _p(records), n, _p(out)), "debug_ring_sums")
         return out
 
     def _view_args(self, pmap, group_of, weights, n):
-        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
         group_of = np.ascontiguousarray(group_of, dtype=np.int32)
-        if weights is not None:
-            weights = np.ascontiguousarray(weights, dtype=np.float64)
-            assert weights.shape == (n,)
-        assert pmap.shape == (n,) and group_of.shape == (n,)
-        return pmap, group_of, weights
-
-    def _view_raise(self, what, rc):
-        e = RuntimeError("%s: %s" % (what, self.L.bioem_hip_last_error(self.h).decode()))
-        e.rc = rc
-        raise e
+        assert group_of.shape == (n,)
+        return _pmap(pmap, n), group_of, _vector(weights, n)
 
     def view_sums(self, pmap, group_of, weights=None, g0=0, g1=None, n_groups=None):
         """the normal equations of the aligned average of every group in [g0, g1) (include/bioem_hip.h): returns
@@ -492,10 +523,8 @@ class Engine:
         num = np.zeros((n, self.N, self.H), dtype=np.complex128)
         den = np.zeros((n, self.N, self.H), dtype=np.float64)
         stats = np.zeros((n, 2), dtype=np.float64)
-        rc = self.L.bioem_hip_view_sums(self.h, _p(pmap), _p(weights), _p(group_of), nG, int(g0), g1, _p(num), _p(den),
-                                        _p(stats))
-        if rc:
-            self._view_raise("view_sums", rc)
+        self._chk(self.L.bioem_hip_view_sums(self.h, _p(pmap), _p(weights), _p(group_of), nG, int(g0), g1, _p(num), _p(den),
+                                             _p(stats)), "view_sums")
         return num, den, stats
 
     def view_averages(self, pmap, group_of, group_orient, weights=None, wiener=0.1, g0=0, g1=None, maps=True):
@@ -511,20 +540,15 @@ class Engine:
         rings = np.zeros((n, ring_count(self.N)), dtype=RING_SUMS_DTYPE)
         avg = np.zeros((n, self.N, self.N), dtype=np.float32) if maps else None
         proj = np.zeros((n, self.N, self.N), dtype=np.float32) if maps else None
-        rc = self.L.bioem_hip_view_averages(self.h, _p(pmap), _p(weights), _p(group_of), _p(group_orient), nG, float(wiener),
-                                            int(g0), g1, _p(rings), _p(avg), _p(proj))
-        if rc:
-            self._view_raise("view_averages", rc)
+        self._chk(self.L.bioem_hip_view_averages(self.h, _p(pmap), _p(weights), _p(group_of), _p(group_orient), nG,
+                                                 float(wiener), int(g0), g1, _p(rings), _p(avg), _p(proj)), "view_averages")
         return rings, avg, proj
 
     def debug_view_sums(self, specR, pmap, group_of, weights=None, n_groups=None):
         """test hook: the accumulation kernel of view_sums on n spectra handed in, float32 [n, N, H, 2] or complex64
         [n, N, H] in reference layout; pmap, group_of, weights run over the n spectra.  Needs the CTF kernels only.
         Returns (num, den, stats) for all groups as view_sums does."""
-        specR = np.ascontiguousarray(specR)
-        if specR.dtype.kind == "c":
-            specR = np.ascontiguousarray(specR.astype(np.complex64)).view(np.float32).reshape(specR.shape + (2,))
-        specR = np.ascontiguousarray(specR, dtype=np.float32)
+        specR = _spectra(specR)
         n = len(specR)
         assert specR.shape == (n, self.N, self.H, 2)
         pmap, group_of, weights = self._view_args(pmap, group_of, weights, n)
@@ -532,10 +556,8 @@ class Engine:
         num = np.zeros((max(nG, 0), self.N, self.H), dtype=np.complex128)
         den = np.zeros((max(nG, 0), self.N, self.H), dtype=np.float64)
         stats = np.zeros((max(nG, 0), 2), dtype=np.float64)
-        rc = self.L.bioem_hip_debug_view_sums(self.h, _p(specR), _p(pmap), _p(weights), _p(group_of), n, nG, _p(num),
-                                              _p(den), _p(stats))
-        if rc:
-            self._view_raise("debug_view_sums", rc)
+        self._chk(self.L.bioem_hip_debug_view_sums(self.h, _p(specR), _p(pmap), _p(weights), _p(group_of), n, nG, _p(num),
+                                                   _p(den), _p(stats)), "debug_view_sums")
         return num, den, stats
 
     def window_shifts(self):
@@ -549,46 +571,26 @@ class Engine:
         the request's particle.  Requests are independent and may repeat particles in any order.  want_cc adds the
         float32 cross-correlation values [n, nd, nd], want_params the PARAM5_DTYPE [n] of the requests' (orient, conv)
         pairs; the result is then a tuple in that order.  Outside a run; a refusal raises RuntimeError with .rc == 2."""
-        r = np.asarray(requests)
-        if r.dtype != WINDOW_REQUEST_DTYPE:
-            r = np.asarray(r, dtype=np.int32).reshape(-1, 3)
-            q = np.zeros(len(r), dtype=WINDOW_REQUEST_DTYPE)
-            q["particle"], q["orient"], q["conv"] = r[:, 0], r[:, 1], r[:, 2]
-            r = q
-        r = np.ascontiguousarray(r.reshape(-1))
+        r = _requests(requests, WINDOW_REQUEST_DTYPE)
         n, nd = len(r), len(self.window_shifts())
         logp = np.zeros((n, nd, nd), dtype=np.float64)
         cc = np.zeros((n, nd, nd), dtype=np.float32) if want_cc else None
         par = np.zeros(n, dtype=PARAM5_DTYPE) if want_params else None
-        rc = self.L.bioem_hip_window_posterior(self.h, _p(r) if n else None, n, int(bool(own)), _p(logp), _p(cc), _p(par))
-        if rc:
-            e = RuntimeError("window_posterior: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
-        out = (logp,) + ((cc,) if want_cc else ()) + ((par,) if want_params else ())
-        return out[0] if len(out) == 1 else out
+        self._chk(self.L.bioem_hip_window_posterior(self.h, _p(r) if n else None, n, int(bool(own)), _p(logp), _p(cc), _p(par)),
+                  "window_posterior")
+        return _first_or_tuple(logp, cc, par)
 
     def best_match_window(self, pmap, p0=0, p1=None, own=False, want_cc=False, want_params=False):
         """window_posterior of the best record (orient, conv) of particles [p0, p1) of a probability block's map
         entries (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
-        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
-        assert pmap.shape == (self.nMaps,)
-        p1 = self.nMaps if p1 is None else int(p1)
-        req = np.zeros(max(0, p1 - int(p0)), dtype=WINDOW_REQUEST_DTYPE)
-        req["particle"] = np.arange(int(p0), p1)
-        req["orient"], req["conv"] = pmap["orient"][int(p0):p1], pmap["conv"][int(p0):p1]
+        req = _match_requests(_pmap(pmap, self.nMaps), p0, self.nMaps if p1 is None else p1, WINDOW_REQUEST_DTYPE)
         return self.window_posterior(req, own=own, want_cc=want_cc, want_params=want_params)
 
     def debug_window(self, specConv, specRef, params, sumRef, sumsqRef):
         """test hook: the window kernels of window_posterior on n spectrum pairs handed in, float32 [n, N, H, 2] each (or
         complex64 [n, N, H]), with params PARAM5_DTYPE [n] and the particles' sums float32 [n].  Needs only the handle's
         parameters.  Returns (logp float64 [n, nd, nd], cc float32 [n, nd, nd]); a refusal raises with .rc == 2."""
-        def spec(a):
-            a = np.ascontiguousarray(a)
-            if a.dtype.kind == "c":
-                a = np.ascontiguousarray(a.astype(np.complex64)).view(np.float32).reshape(a.shape + (2,))
-            return np.ascontiguousarray(a, dtype=np.float32)
-        specConv, specRef = spec(specConv), spec(specRef)
+        specConv, specRef = _spectra(specConv), _spectra(specRef)
         params = np.ascontiguousarray(params, dtype=PARAM5_DTYPE)
         n, nd = len(params), len(self.window_shifts())
         sumRef = np.ascontiguousarray(sumRef, dtype=np.float32)
@@ -597,32 +599,16 @@ class Engine:
         assert sumRef.shape == (n,) and sumsqRef.shape == (n,)
         logp = np.zeros((n, nd, nd), dtype=np.float64)
         cc = np.zeros((n, nd, nd), dtype=np.float32)
-        rc = self.L.bioem_hip_debug_window(self.h, _p(specConv), _p(specRef), _p(params), _p(sumRef), _p(sumsqRef), n,
-                                           _p(logp), _p(cc))
-        if rc:
-            e = RuntimeError("debug_window: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(self.L.bioem_hip_debug_window(self.h, _p(specConv), _p(specRef), _p(params), _p(sumRef), _p(sumsqRef), n,
+                                                _p(logp), _p(cc)), "debug_window")
         return logp, cc
 
-    @staticmethod
-    def _spectra(a):
-        a = np.ascontiguousarray(a)
-        if a.dtype.kind == "c":
-            a = np.ascontiguousarray(a.astype(np.complex64)).view(np.float32).reshape(a.shape + (2,))
-        return np.ascontiguousarray(a, dtype=np.float32)
-
     def _scan_candidates(self, kernels, ctf_params):
-        kernels = self._spectra(kernels)
+        kernels = _spectra(kernels)
         ctf_params = np.ascontiguousarray(ctf_params, dtype=np.float32)
         assert kernels.ndim == 4 and kernels.shape[1:] == (self.N, self.H, 2), kernels.shape
         assert ctf_params.shape == (len(kernels), 3), ctf_params.shape
         return kernels, ctf_params
-
-    def _scan_raise(self, name, rc):
-        e = RuntimeError("%s: %s" % (name, self.L.bioem_hip_last_error(self.h).decode()))
-        e.rc = rc
-        raise e
 
     def ctf_scan(self, requests, kernels, ctf_params, own=False, want_cc=False, want_params=False):
         """the log posterior of each request (particle, orient, shiftX, shiftY) of SCAN_REQUEST_DTYPE [n] (or an [n, 4]
@@ -633,35 +619,20 @@ class Engine:
         list of the request's particle.  want_cc adds the float32 cross-correlation values [n, G], want_params the
         PARAM5_DTYPE [n, G] of the (request, candidate) pairs; the result is then a tuple in that order.  Outside a run;
         a refusal raises RuntimeError with .rc == 2."""
-        r = np.asarray(requests)
-        if r.dtype != SCAN_REQUEST_DTYPE:
-            r = np.asarray(r, dtype=np.int32).reshape(-1, 4)
-            q = np.zeros(len(r), dtype=SCAN_REQUEST_DTYPE)
-            q["particle"], q["orient"], q["shiftX"], q["shiftY"] = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
-            r = q
-        r = np.ascontiguousarray(r.reshape(-1))
+        r = _requests(requests, SCAN_REQUEST_DTYPE)
         kernels, ctf_params = self._scan_candidates(kernels, ctf_params)
         n, G = len(r), len(kernels)
         logp = np.zeros((n, G), dtype=np.float64)
         cc = np.zeros((n, G), dtype=np.float32) if want_cc else None
         par = np.zeros((n, G), dtype=PARAM5_DTYPE) if want_params else None
-        rc = self.L.bioem_hip_ctf_scan(self.h, _p(r) if n else None, n, int(bool(own)), _p(kernels) if G else None,
-                                       _p(ctf_params) if G else None, G, _p(logp), _p(cc), _p(par))
-        if rc:
-            self._scan_raise("ctf_scan", rc)
-        out = (logp,) + ((cc,) if want_cc else ()) + ((par,) if want_params else ())
-        return out[0] if len(out) == 1 else out
+        self._chk(self.L.bioem_hip_ctf_scan(self.h, _p(r) if n else None, n, int(bool(own)), _p(kernels) if G else None,
+                                            _p(ctf_params) if G else None, G, _p(logp), _p(cc), _p(par)), "ctf_scan")
+        return _first_or_tuple(logp, cc, par)
 
     def best_match_ctf_scan(self, pmap, kernels, ctf_params, p0=0, p1=None, own=False, want_cc=False, want_params=False):
         """ctf_scan of the best record (orient, cent_x, cent_y) of particles [p0, p1) of a probability block's map entries
         (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
-        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
-        assert pmap.shape == (self.nMaps,)
-        p1 = self.nMaps if p1 is None else int(p1)
-        req = np.zeros(max(0, p1 - int(p0)), dtype=SCAN_REQUEST_DTYPE)
-        req["particle"] = np.arange(int(p0), p1)
-        req["orient"] = pmap["orient"][int(p0):p1]
-        req["shiftX"], req["shiftY"] = pmap["cent_x"][int(p0):p1], pmap["cent_y"][int(p0):p1]
+        req = _match_requests(_pmap(pmap, self.nMaps), p0, self.nMaps if p1 is None else p1, SCAN_REQUEST_DTYPE)
         return self.ctf_scan(req, kernels, ctf_params, own=own, want_cc=want_cc, want_params=want_params)
 
     def debug_ctf_scan(self, specP, specRef, sumRef, sumsqRef, shifts, kernels, ctf_params):
@@ -669,7 +640,7 @@ class Engine:
         (or complex64 [n, N, H]), with the particles' sums float32 [n] and the shifts int [n, 2].  Needs only the handle's
         parameters.  Returns (logp float64 [n, G], cc float32 [n, G], params PARAM5_DTYPE [n, G]); a refusal raises with
         .rc == 2."""
-        specP, specRef = self._spectra(specP), self._spectra(specRef)
+        specP, specRef = _spectra(specP), _spectra(specRef)
         kernels, ctf_params = self._scan_candidates(kernels, ctf_params)
         n, G = len(specP), len(kernels)
         sumRef = np.ascontiguousarray(sumRef, dtype=np.float32)
@@ -680,11 +651,9 @@ class Engine:
         logp = np.zeros((n, G), dtype=np.float64)
         cc = np.zeros((n, G), dtype=np.float32)
         par = np.zeros((n, G), dtype=PARAM5_DTYPE)
-        rc = self.L.bioem_hip_debug_ctf_scan(self.h, _p(specP), _p(specRef), _p(sumRef), _p(sumsqRef), _p(shifts), n,
-                                             _p(kernels) if G else None, _p(ctf_params) if G else None, G, _p(logp), _p(cc),
-                                             _p(par))
-        if rc:
-            self._scan_raise("debug_ctf_scan", rc)
+        self._chk(self.L.bioem_hip_debug_ctf_scan(self.h, _p(specP), _p(specRef), _p(sumRef), _p(sumsqRef), _p(shifts), n,
+                                                  _p(kernels) if G else None, _p(ctf_params) if G else None, G, _p(logp),
+                                                  _p(cc), _p(par)), "debug_ctf_scan")
         return logp, cc, par
 
     def model_gradient(self, requests, weights=None, own=False, want_grad=True, want_params=False):
@@ -695,40 +664,22 @@ class Engine:
         "grad" float64 [n, nPts]; with want_params "params" PARAM5_DTYPE [n], the linearisation point.  orient indexes the
         shared list, with own=True the list of the request's particle.  Outside a run; a refusal raises RuntimeError
         with .rc == 2."""
-        r = np.asarray(requests)
-        if r.dtype != GRAD_REQUEST_DTYPE:
-            r = np.asarray(r, dtype=np.int32).reshape(-1, 5)
-            q = np.zeros(len(r), dtype=GRAD_REQUEST_DTYPE)
-            for i, f in enumerate(GRAD_REQUEST_DTYPE.names):
-                q[f] = r[:, i]
-            r = q
-        r = np.ascontiguousarray(r.reshape(-1))
+        r = _requests(requests, GRAD_REQUEST_DTYPE)
         n, nPts = len(r), getattr(self, "_nPts", 0)   # (no model: the entry refuses)
-        w = None
-        if weights is not None:
-            w = np.ascontiguousarray(weights, dtype=np.float64)
-            assert w.shape == (n,), w.shape
+        w = _vector(weights, n)
         out = {"points": np.zeros(nPts, dtype=GRAD_POINT_DTYPE), "coef": np.zeros((n, 4), dtype=np.float64)}
         if want_grad:
             out["grad"] = np.zeros((n, nPts), dtype=np.float64)
         if want_params:
             out["params"] = np.zeros(n, dtype=PARAM5_DTYPE)
-        rc = self.L.bioem_hip_model_gradient(self.h, _p(r) if n else None, _p(w), n, int(bool(own)), _p(out.get("grad")),
-                                             _p(out["points"]), _p(out.get("params")), _p(out["coef"]))
-        if rc:
-            self._scan_raise("model_gradient", rc)
+        self._chk(self.L.bioem_hip_model_gradient(self.h, _p(r) if n else None, _p(w), n, int(bool(own)), _p(out.get("grad")),
+                                                  _p(out["points"]), _p(out.get("params")), _p(out["coef"])), "model_gradient")
         return out
 
     def best_match_gradient(self, pmap, p0=0, p1=None, own=False, weights=None, want_grad=True, want_params=False):
         """model_gradient of the best record (orient, conv, cent_x, cent_y) of particles [p0, p1) of a probability block's
         map entries (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
-        pmap = np.ascontiguousarray(pmap, dtype=PROB_MAP_DTYPE)
-        assert pmap.shape == (self.nMaps,)
-        p1 = self.nMaps if p1 is None else int(p1)
-        req = np.zeros(max(0, p1 - int(p0)), dtype=GRAD_REQUEST_DTYPE)
-        req["particle"] = np.arange(int(p0), p1)
-        req["orient"], req["conv"] = pmap["orient"][int(p0):p1], pmap["conv"][int(p0):p1]
-        req["shiftX"], req["shiftY"] = pmap["cent_x"][int(p0):p1], pmap["cent_y"][int(p0):p1]
+        req = _match_requests(_pmap(pmap, self.nMaps), p0, self.nMaps if p1 is None else p1, GRAD_REQUEST_DTYPE)
         return self.model_gradient(req, weights=weights, own=own, want_grad=want_grad, want_params=want_params)
 
     def debug_grad_image(self, specConv, specRef, kernels, params, sumRef, sumsqRef, shifts):
@@ -736,7 +687,7 @@ class Engine:
         in, float32 [n, N, H, 2] each (or complex64 [n, N, H]), params PARAM5_DTYPE [n], the particles' sums float32 [n]
         and the shifts int [n, 2].  Needs only the handle's parameters.  Returns (gmap float64 [n, N, N], coef float64
         [n, 3]); a refusal raises with .rc == 2."""
-        specConv, specRef, kernels = self._spectra(specConv), self._spectra(specRef), self._spectra(kernels)
+        specConv, specRef, kernels = _spectra(specConv), _spectra(specRef), _spectra(kernels)
         n = len(specConv)
         params = np.ascontiguousarray(params, dtype=PARAM5_DTYPE)
         sumRef = np.ascontiguousarray(sumRef, dtype=np.float32)
@@ -746,10 +697,8 @@ class Engine:
         assert params.shape == (n,) and sumRef.shape == (n,) and sumsqRef.shape == (n,) and shifts.shape == (n, 2)
         gmap = np.zeros((n, self.N, self.N), dtype=np.float64)
         coef = np.zeros((n, 3), dtype=np.float64)
-        rc = self.L.bioem_hip_debug_grad_image(self.h, _p(specConv), _p(specRef), _p(kernels), _p(params), _p(sumRef),
-                                               _p(sumsqRef), _p(shifts), n, _p(gmap), _p(coef))
-        if rc:
-            self._scan_raise("debug_grad_image", rc)
+        self._chk(self.L.bioem_hip_debug_grad_image(self.h, _p(specConv), _p(specRef), _p(kernels), _p(params), _p(sumRef),
+                                                    _p(sumsqRef), _p(shifts), n, _p(gmap), _p(coef)), "debug_grad_image")
         return gmap, coef
 
     def debug_grad_gather(self, gmaps, o0=0):
@@ -758,9 +707,7 @@ class Engine:
         gmaps = np.ascontiguousarray(gmaps, dtype=np.float64)
         assert gmaps.ndim == 3 and gmaps.shape[1:] == (self.N, self.N), gmaps.shape
         u = np.zeros((len(gmaps), self._nPts), dtype=np.float64)
-        rc = self.L.bioem_hip_debug_grad_gather(self.h, _p(gmaps), int(o0), len(gmaps), _p(u))
-        if rc:
-            self._scan_raise("debug_grad_gather", rc)
+        self._chk(self.L.bioem_hip_debug_grad_gather(self.h, _p(gmaps), int(o0), len(gmaps), _p(u)), "debug_grad_gather")
         return u
 
     def orientation_sums(self, prior=None, p0=0, p1=None, own=False):
@@ -771,15 +718,9 @@ class Engine:
         prior: None, or nAngles log priors by global orientation index (not with own lists).  Call after finish_run on a
         handle with WRITE_PROB_ANGLES; a shard sums over its own block.  A refusal raises RuntimeError with .rc == 2."""
         p1 = self.nMaps if p1 is None else int(p1)
-        if prior is not None:
-            prior = np.ascontiguousarray(prior, dtype=np.float64)
-            assert prior.shape == (self.nAngles,)
+        prior = _vector(prior, self.nAngles)
         out = np.zeros(max(0, p1 - int(p0)), dtype=ORIENT_SUMS_DTYPE)
-        rc = self.L.bioem_hip_orientation_sums(self.h, _p(prior), int(p0), p1, int(bool(own)), _p(out))
-        if rc:
-            e = RuntimeError("orientation_sums: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(self.L.bioem_hip_orientation_sums(self.h, _p(prior), int(p0), p1, int(bool(own)), _p(out)), "orientation_sums")
         return out
 
     def debug_orient_sums(self, table, angles=None, isQuat=True, prior=None, offsets=None):
@@ -793,20 +734,14 @@ class Engine:
         out = np.zeros(nMaps, dtype=ORIENT_SUMS_DTYPE)
         if offsets is None:
             assert angles is None or len(angles) == nO
-            if prior is not None:
-                prior = np.ascontiguousarray(prior, dtype=np.float64)
-                assert prior.shape == (nO,)
-            rc = self.L.bioem_hip_debug_orient_sums(self.h, _p(table), nO, nMaps, _p(angles), int(bool(isQuat)), _p(prior),
-                                                    _p(out))
+            rc = self.L.bioem_hip_debug_orient_sums(self.h, _p(table), nO, nMaps, _p(angles), int(bool(isQuat)),
+                                                    _p(_vector(prior, nO)), _p(out))
         else:
             offsets = np.ascontiguousarray(offsets, dtype=np.int64)
             assert offsets.shape == (nMaps + 1,) and prior is None and angles is not None and len(angles) >= offsets[-1]
             rc = self.L.bioem_hip_debug_orient_sums_own(self.h, _p(table), nO, nMaps, _p(angles), _p(offsets),
                                                         int(bool(isQuat)), _p(out))
-        if rc:
-            e = RuntimeError("debug_orient_sums: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(rc, "debug_orient_sums")
         return out
 
     def orientation_occupancy(self, sums, prior=None, p0=0, p1=None):
@@ -822,16 +757,11 @@ class Engine:
         assert sums.ndim == 1
         if 0 <= int(p0) < p1 <= self.nMaps:              # (a range the entry refuses reads no sums)
             assert len(sums) == p1 - int(p0)
-        if prior is not None:
-            prior = np.ascontiguousarray(prior, dtype=np.float64)
-            assert prior.shape == (self.nAngles,)
+        prior = _vector(prior, self.nAngles)
         o0, o1 = self.shard if self.shard is not None else (0, self.nAngles)
         out = np.zeros(o1 - o0, dtype=ORIENT_OCC_DTYPE)
-        rc = self.L.bioem_hip_orientation_occupancy(self.h, _p(prior), _p(sums) if sums.size else None, int(p0), p1, _p(out))
-        if rc:
-            e = RuntimeError("orientation_occupancy: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(self.L.bioem_hip_orientation_occupancy(self.h, _p(prior), _p(sums) if sums.size else None, int(p0), p1,
+                                                         _p(out)), "orientation_occupancy")
         return out
 
     def debug_orient_occupancy(self, table, sums, prior=None, p0=0, p1=None, o0=0):
@@ -843,37 +773,23 @@ class Engine:
         p1 = nMaps if p1 is None else int(p1)
         sums = np.ascontiguousarray(sums, dtype=ORIENT_SUMS_DTYPE)
         assert sums.shape == (p1 - int(p0),)
-        if prior is not None:
-            prior = np.ascontiguousarray(prior, dtype=np.float64)
-            assert prior.shape == (nO,)
+        prior = _vector(prior, nO)
         out = np.zeros(nO, dtype=ORIENT_OCC_DTYPE)
-        rc = self.L.bioem_hip_debug_orient_occupancy(self.h, _p(table), nO, nMaps, _p(prior), _p(sums), int(p0), p1, int(o0),
-                                                     _p(out))
-        if rc:
-            e = RuntimeError("debug_orient_occupancy: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(self.L.bioem_hip_debug_orient_occupancy(self.h, _p(table), nO, nMaps, _p(prior), _p(sums), int(p0), p1,
+                                                          int(o0), _p(out)), "debug_orient_occupancy")
         return out
 
     def enable_ctf_table(self, on=True):
         """keep the posterior per (CTF set, particle) beside the particle entries, from the next start_run on; call it
         outside a run (inside one it raises, .rc == 2)"""
-        rc = self.L.bioem_hip_enable_ctf_table(self.h, int(bool(on)))
-        if rc:
-            e = RuntimeError("enable_ctf_table: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(self.L.bioem_hip_enable_ctf_table(self.h, int(bool(on))), "enable_ctf_table")
 
     def ctf_table(self):
         """[nCTF, nMaps] PROB_MAP_DTYPE: entry (c, p) is what particle p's entry would be had the run compared CTF set c
         only (conv == c; orient / cent_x / cent_y / norm / mu of the best match under that CTF set).  Flushes and
         synchronises.  Without enable_ctf_table it raises with .rc == 2."""
         out = np.zeros((self.nCTF, self.nMaps), dtype=PROB_MAP_DTYPE)
-        rc = self.L.bioem_hip_ctf_table(self.h, _p(out))
-        if rc:
-            e = RuntimeError("ctf_table: %s" % self.L.bioem_hip_last_error(self.h).decode())
-            e.rc = rc
-            raise e
+        self._chk(self.L.bioem_hip_ctf_table(self.h, _p(out)), "ctf_table")
         return out
 
     def synchronize(self):
@@ -897,24 +813,18 @@ class Engine:
         td = np.zeros(max(nO, 0), dtype=np.float64)
         spec = np.zeros((max(nO, 0), self.N, self.H, 2), dtype=np.float32) if want_spec else None
         info = np.zeros(6, dtype=np.int32)
-        rc = self.L.bioem_hip_debug_projection_maps(self.h, int(o0), nO, int(self.PROJECTION_PATHS.get(path, path)),
-                                                    _p(maps), _p(td), _p(spec), _p(info))
-        if rc:
-            self._view_raise("debug_projection_maps", rc)
+        self._chk(self.L.bioem_hip_debug_projection_maps(self.h, int(o0), nO, int(self.PROJECTION_PATHS.get(path, path)),
+                                                         _p(maps), _p(td), _p(spec), _p(info)), "debug_projection_maps")
         return maps, td, spec, dict(zip(("path", "boxLo", "boxSide", "compact", "TR", "iradMax"), map(int, info)))
 
     def debug_stamps(self):
         """the footprint table of the uploaded model (bioem_hip_debug_stamps): (stamps float64 [nPts, S, S], iradMax),
         S = 2 iradMax + 1; raises with .rc == 2 where the model has none"""
         irad = C.c_int()
-        rc = self.L.bioem_hip_debug_stamps(self.h, None, C.byref(irad))
-        if rc:
-            self._view_raise("debug_stamps", rc)
+        self._chk(self.L.bioem_hip_debug_stamps(self.h, None, C.byref(irad)), "debug_stamps")
         S = 2 * irad.value + 1
         out = np.zeros((self._nPts, S, S), dtype=np.float64)
-        rc = self.L.bioem_hip_debug_stamps(self.h, _p(out), C.byref(irad))
-        if rc:
-            self._view_raise("debug_stamps", rc)
+        self._chk(self.L.bioem_hip_debug_stamps(self.h, _p(out), C.byref(irad)), "debug_stamps")
         return out, irad.value
 
     def debug_convolution(self, iOrient, iConv):

@@ -25,6 +25,9 @@ namespace bioem_host
 [[noreturn]] void fatal(const char *fmt, ...);
 void warn(const char *fmt, ...);
 
+// a map entry some run compared: no longer as the initialisation of a probability block left it
+inline bool has_record(const bioem_hip_prob_map &r) { return !(r.Total == 0.0 && r.Constoadd == -999999.); }
+
 struct InputParams
 {
   // parameter-file content (param.cpp:64-627)
@@ -379,6 +382,8 @@ private:
   // --OrientStats: the shards' orientation sums (bioem_hip_orientation_sums) merged on the host, written by
   // write_orient_stats; numconst: the constant of ANG_PROB
   void writeOrientStats(const std::string &file, double numconst);
+  // every shard's orientation sums under logPrior (null: none), merged on the host in shard order
+  void shardOrientSums(const double *logPrior, std::vector<bioem_hip_orient_sums> &sums);
   // --OrientOccupancy / --FitOrientPrior: every shard's sums merged on the host, every shard's occupancy block under the
   // merged sums, written by write_orient_occupancy; nIter EM iterations of the prior, written by write_orient_prior
   void writeOrientOccupancy(const std::string &file, int nIter);

@@ -6,6 +6,7 @@
 // shards are merged with the log-sum-exp rule of bioem.cpp:909-1044.
 #include <getopt.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -50,6 +51,53 @@ void check(bioem_hip_handle h, int rc, const char *what)
 {
   if (rc)
     fatal("%s: %s", what, bioem_hip_last_error(h));
+}
+
+// the constant of a LogProb line for the volume element volu (the arguments stay float: log(volu) as the sites wrote it)
+double numconst_of(float Ntotpi, float volu)
+{
+  return 0.5 * log(M_PI) + (1 - Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(volu);
+}
+
+// the handle's batch (bioem_hip_max_batch), at least 1 and at most `most`
+int batch_size(bioem_hip_handle h, int most = INT_MAX)
+{
+  int batch = 1;
+  bioem_hip_max_batch(h, &batch, nullptr);
+  return std::max(1, std::min(batch, most));
+}
+
+// call(p0, p1) of a best-match entry for one batch; where it refuses a record (returns 2) the batch is retried record by
+// record and refused(p) warns and zero-fills each one still refused.  A device error (1) ends the run.
+template <class Call, class Refused>
+void batch_or_each_record(bioem_hip_handle h, int p0, int p1, const char *what, Call call, Refused refused)
+{
+  int rc = call(p0, p1);
+  if (rc == 2)
+  {
+    for (int p = p0; p < p1 && rc != 1; p++)
+    {
+      rc = call(p, p + 1);
+      if (rc == 2)
+        refused(p);
+    }
+    rc = rc == 1 ? 1 : 0;
+  }
+  check(h, rc, what);
+}
+
+// the records pmap[nMaps] in order: push(p, record) for each one a run compared, the warning noMatch (a format that takes
+// the particle's index) for the others
+template <class Push>
+void for_each_match(const bioem_hip_prob_map *pmap, int nMaps, const char *noMatch, Push push)
+{
+  for (int p = 0; p < nMaps; p++)
+  {
+    if (has_record(pmap[p]))
+      push(p, pmap[p]);
+    else
+      warn(noMatch, p);
+  }
 }
 } // namespace
 
@@ -586,9 +634,7 @@ void Driver::print_phase_report()
 void Driver::writeBestMaps(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists)
 {
   const int nMaps = particles.ntot, N = param.N;
-  int batch = 1;
-  bioem_hip_max_batch(h, &batch, nullptr);
-  batch = std::max(1, std::min(batch, nMaps));
+  const int batch = batch_size(h, nMaps);
   const size_t NN = (size_t) N * N;
   std::vector<float> buf((size_t) batch * NN);
   MrcStackWriter w;
@@ -597,21 +643,14 @@ void Driver::writeBestMaps(const std::string &file, bioem_hip_handle h, const bi
   for (int p0 = 0; p0 < nMaps; p0 += batch)
   {
     const int p1 = std::min(nMaps, p0 + batch);
-    int rc = bioem_hip_render_best_maps(h, pmap, ownLists, p0, p1, buf.data());
-    if (rc == 2)
-    { // a record without an image (a particle the round never compared): its section is zero, the others are rendered
-      for (int p = p0; p < p1 && rc != 1; p++)
-      {
-        rc = bioem_hip_render_best_maps(h, pmap, ownLists, p, p + 1, buf.data() + (size_t) (p - p0) * NN);
-        if (rc == 2)
-        {
+    // a record without an image (a particle the round never compared): its section is zero, the others are rendered
+    batch_or_each_record(
+        h, p0, p1, "render best maps",
+        [&](int a, int b) { return bioem_hip_render_best_maps(h, pmap, ownLists, a, b, buf.data() + (size_t) (a - p0) * NN); },
+        [&](int p) {
           warn("best map of RefMap %d not rendered: %s", p, bioem_hip_last_error(h));
           std::fill(buf.begin() + (size_t) (p - p0) * NN, buf.begin() + (size_t) (p - p0 + 1) * NN, 0.f);
-        }
-      }
-      rc = rc == 1 ? 1 : 0;
-    }
-    check(h, rc, "render best maps");
+        });
     if (!w.append(buf.data(), p1 - p0))
       fatal("Writing %s", file.c_str());
   }
@@ -625,29 +664,18 @@ void Driver::writeBestFrc(const std::string &file, bioem_hip_handle h, const bio
 {
   const int nMaps = particles.ntot, N = param.N;
   const size_t nRings = (size_t) bioem_hip_ring_count(N);
-  int batch = 1;
-  bioem_hip_max_batch(h, &batch, nullptr);
-  batch = std::max(1, std::min(batch, nMaps));
+  const int batch = batch_size(h, nMaps);
   std::vector<bioem_hip_ring_sums> sums((size_t) nMaps * nRings);
   const bioem_hip_ring_sums zero = {0., 0., 0.};
   for (int p0 = 0; p0 < nMaps; p0 += batch)
-  {
-    const int p1 = std::min(nMaps, p0 + batch);
-    int rc = bioem_hip_best_match_rings(h, pmap, ownLists, p0, p1, sums.data() + (size_t) p0 * nRings);
-    if (rc == 2)
-    { // a record without a best match (a particle the round never compared): its sums are zero, the others are computed
-      for (int p = p0; p < p1 && rc != 1; p++)
-      {
-        rc = bioem_hip_best_match_rings(h, pmap, ownLists, p, p + 1, sums.data() + (size_t) p * nRings);
-        if (rc == 2)
-        {
+  { // a record without a best match (a particle the round never compared): its sums are zero, the others are computed
+    batch_or_each_record(
+        h, p0, std::min(nMaps, p0 + batch), "best match rings",
+        [&](int a, int b) { return bioem_hip_best_match_rings(h, pmap, ownLists, a, b, sums.data() + (size_t) a * nRings); },
+        [&](int p) {
           warn("ring sums of RefMap %d not computed: %s", p, bioem_hip_last_error(h));
           std::fill(sums.begin() + (size_t) p * nRings, sums.begin() + (size_t) (p + 1) * nRings, zero);
-        }
-      }
-      rc = rc == 1 ? 1 : 0;
-    }
-    check(h, rc, "best match rings");
+        });
   }
   const std::string err = write_best_frc(file.c_str(), sums.data(), nMaps, N, param.pixelSize);
   if (!err.empty())
@@ -669,9 +697,7 @@ void Driver::writeViewAverages(const std::string &file, bioem_hip_handle h, cons
       counts[(size_t) groupOf[(size_t) p]]++;
   if (nViews < 1)
     warn("--ViewAverages: no orientation has %d particles or more; the files hold no view", viewMinParticles);
-  int batch = 1;
-  bioem_hip_max_batch(h, &batch, nullptr);
-  batch = std::max(1, batch);
+  const int batch = batch_size(h);
   std::vector<bioem_hip_ring_sums> rings((size_t) nViews * nRings);
   std::vector<float> avg((size_t) batch * NN), proj((size_t) batch * NN);
   const std::string avgFile = file + "_avg.mrc", projFile = file + "_proj.mrc";
@@ -709,9 +735,7 @@ void Driver::writeBestWindow(const std::string &file, bioem_hip_handle h, const 
   std::vector<int> shifts((size_t) nd);
   bioem_hip_window_offsets(pd.NumberPixels, pd.maxDisplaceCenter, pd.GridSpaceCenter, algo, shifts.data(), nd);
   const size_t cells = (size_t) nd * nd;
-  int batch = 1;
-  bioem_hip_max_batch(h, &batch, nullptr);
-  batch = std::max(1, batch);
+  const int batch = batch_size(h);
   std::vector<double> logp(cells * (size_t) nMaps, 0.), table(cells * (size_t) batch), numconst((size_t) nMaps);
   std::vector<int> orient((size_t) nMaps, -1), conv((size_t) nMaps, 0), who;
   std::vector<bioem_hip_window_request> req;
@@ -726,22 +750,15 @@ void Driver::writeBestWindow(const std::string &file, bioem_hip_handle h, const 
     who.clear();
   };
   for (int p = 0; p < nMaps; p++)
-  {
-    numconst[(size_t) p] =
-        0.5 * log(M_PI) + (1 - pd.Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(voluPerMap ? voluPerMap[p] : pd.volu);
-    const bioem_hip_prob_map &r = pmap[p];
-    if (r.Total == 0.0 && r.Constoadd == -999999.)
-    {
-      warn("window of RefMap %d not computed: no run compared it", p);
-      continue;
-    }
+    numconst[(size_t) p] = numconst_of(pd.Ntotpi, voluPerMap ? voluPerMap[p] : pd.volu);
+  for_each_match(pmap, nMaps, "window of RefMap %d not computed: no run compared it", [&](int p, const bioem_hip_prob_map &r) {
     orient[(size_t) p] = r.max_prob_orient;
     conv[(size_t) p] = r.max_prob_conv;
     req.push_back({p, r.max_prob_orient, r.max_prob_conv});
     who.push_back(p);
     if ((int) req.size() == batch)
       flush();
-  }
+  });
   flush();
   const std::string err = write_best_window(file.c_str(), logp.data(), shifts.data(), nd, nMaps, orient.data(), conv.data(),
                                             param.ctfParam.data(), param.usepsf, param.elecwavel, numconst.data());
@@ -771,21 +788,14 @@ void Driver::writeCtfScan(const std::string &file, bioem_hip_handle h, const bio
   std::vector<int> orient((size_t) nMaps, -1), shiftX((size_t) nMaps, 0), shiftY((size_t) nMaps, 0), who;
   std::vector<bioem_hip_scan_request> req;
   for (int p = 0; p < nMaps; p++)
-  {
-    numconst[(size_t) p] =
-        0.5 * log(M_PI) + (1 - pd.Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(voluPerMap ? voluPerMap[p] : pd.volu);
-    const bioem_hip_prob_map &r = pmap[p];
-    if (r.Total == 0.0 && r.Constoadd == -999999.)
-    {
-      warn("CTF scan of RefMap %d not computed: no run compared it", p);
-      continue;
-    }
+    numconst[(size_t) p] = numconst_of(pd.Ntotpi, voluPerMap ? voluPerMap[p] : pd.volu);
+  for_each_match(pmap, nMaps, "CTF scan of RefMap %d not computed: no run compared it", [&](int p, const bioem_hip_prob_map &r) {
     orient[(size_t) p] = r.max_prob_orient;
     shiftX[(size_t) p] = r.max_prob_cent_x;
     shiftY[(size_t) p] = r.max_prob_cent_y;
     req.push_back({p, r.max_prob_orient, r.max_prob_cent_x, r.max_prob_cent_y});
     who.push_back(p);
-  }
+  });
   const int chunk = 256;
   const size_t M = (size_t) N * (N / 2 + 1);
   std::vector<float> kernels(2 * M * (size_t) std::min(chunk, G));
@@ -817,16 +827,10 @@ void Driver::writeModelGradient(const std::string &file, bioem_hip_handle h, con
 {
   const int nMaps = particles.ntot;
   std::vector<bioem_hip_grad_request> req;
-  for (int p = 0; p < nMaps; p++)
-  {
-    const bioem_hip_prob_map &r = pmap[p];
-    if (r.Total == 0.0 && r.Constoadd == -999999.)
-    {
-      warn("Density gradient of RefMap %d not computed: no run compared it", p);
-      continue;
-    }
-    req.push_back({p, r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y});
-  }
+  for_each_match(pmap, nMaps, "Density gradient of RefMap %d not computed: no run compared it",
+                 [&](int p, const bioem_hip_prob_map &r) {
+                   req.push_back({p, r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y});
+                 });
   std::vector<bioem_hip_grad_point> acc(model.points.size(), bioem_hip_grad_point{0., 0., 0., 0});
   std::vector<double> coef(4 * req.size());
   if (!req.empty())
@@ -842,37 +846,11 @@ void Driver::writeModelGradient(const std::string &file, bioem_hip_handle h, con
             << " model points written to: " << file << "\n";
 }
 
-// --OrientStats: every shard's sums over the orientations it owns (bioem_hip_orientation_sums), merged on the host in
-// shard order, then the text file (write_orient_stats)
-void Driver::writeOrientStats(const std::string &file, double numconst)
+// every shard's sums over the orientations it owns under logPrior (bioem_hip_orientation_sums), merged on the host in
+// shard order
+void Driver::shardOrientSums(const double *logPrior, std::vector<bioem_hip_orient_sums> &sums)
 {
   const int nMaps = particles.ntot, nShards = (int) shards.size();
-  std::vector<double> prior;
-  if (param.yespriorAngles)
-    prior.assign(param.angprior.begin(), param.angprior.end());
-  std::vector<std::vector<bioem_hip_orient_sums>> part((size_t) nShards);
-  std::vector<const bioem_hip_orient_sums *> ptrs((size_t) nShards);
-  for (int g = 0; g < nShards; g++)
-  {
-    part[(size_t) g].resize((size_t) nMaps);
-    check(shards[g].h, bioem_hip_orientation_sums(shards[g].h, prior.empty() ? nullptr : prior.data(), 0, nMaps, 0,
-                                                  part[(size_t) g].data()), "orientation sums");
-    ptrs[(size_t) g] = part[(size_t) g].data();
-  }
-  std::vector<bioem_hip_orient_sums> sums((size_t) nMaps);
-  if (bioem_hip_merge_orient_sums_host(nShards, nMaps, ptrs.data(), sums.data()))
-    fatal("merge failed");
-  const std::string err = write_orient_stats(file.c_str(), sums.data(), nMaps, param.angles.data(), nullptr, param.doquater, numconst);
-  if (!err.empty())
-    fatal("--OrientStats: %s", err.c_str());
-  std::cout << "Orientation posterior summaries of " << nMaps << " particles written to: " << file << "\n";
-}
-
-// one pass of --OrientOccupancy under logPrior: every shard's sums over the orientations it owns merged on the host in
-// shard order (as --OrientStats does), then every shard's occupancy block under the merged sums, in block order
-void Driver::orientOccupancyPass(const double *logPrior, std::vector<bioem_hip_orient_sums> &sums, std::vector<bioem_hip_orient_occ> &occ)
-{
-  const int nMaps = particles.ntot, nShards = (int) shards.size(), nO = param.nTotGridAngles;
   std::vector<std::vector<bioem_hip_orient_sums>> part((size_t) nShards);
   std::vector<const bioem_hip_orient_sums *> ptrs((size_t) nShards);
   for (int g = 0; g < nShards; g++)
@@ -884,6 +862,29 @@ void Driver::orientOccupancyPass(const double *logPrior, std::vector<bioem_hip_o
   sums.resize((size_t) nMaps);
   if (bioem_hip_merge_orient_sums_host(nShards, nMaps, ptrs.data(), sums.data()))
     fatal("merge failed");
+}
+
+// --OrientStats: the shards' merged sums (shardOrientSums), then the text file (write_orient_stats)
+void Driver::writeOrientStats(const std::string &file, double numconst)
+{
+  const int nMaps = particles.ntot;
+  std::vector<double> prior;
+  if (param.yespriorAngles)
+    prior.assign(param.angprior.begin(), param.angprior.end());
+  std::vector<bioem_hip_orient_sums> sums;
+  shardOrientSums(prior.empty() ? nullptr : prior.data(), sums);
+  const std::string err = write_orient_stats(file.c_str(), sums.data(), nMaps, param.angles.data(), nullptr, param.doquater, numconst);
+  if (!err.empty())
+    fatal("--OrientStats: %s", err.c_str());
+  std::cout << "Orientation posterior summaries of " << nMaps << " particles written to: " << file << "\n";
+}
+
+// one pass of --OrientOccupancy under logPrior: every shard's sums over the orientations it owns merged on the host in
+// shard order (as --OrientStats does), then every shard's occupancy block under the merged sums, in block order
+void Driver::orientOccupancyPass(const double *logPrior, std::vector<bioem_hip_orient_sums> &sums, std::vector<bioem_hip_orient_occ> &occ)
+{
+  const int nMaps = particles.ntot, nShards = (int) shards.size(), nO = param.nTotGridAngles;
+  shardOrientSums(logPrior, sums);
   occ.assign((size_t) nO, bioem_hip_orient_occ());
   for (int g = 0; g < nShards; g++)
   {
@@ -992,7 +993,7 @@ int Driver::run()
   const int nMaps = particles.ntot, nAngles = param.nTotGridAngles, nC = param.nTotCTFs;
   const int nShards = (int) shards.size();
   const int K = param.pd.writeAngles;
-  const double numconst = 0.5 * log(M_PI) + (1 - param.pd.Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(param.pd.volu);
+  const double numconst = numconst_of(param.pd.Ntotpi, param.pd.volu);
   // per shard: the host block start_run / finish_run move -- map entries only for orientation-block shards, map
   // entries + the (tiny) full angle table when the CTF grid is split
   const size_t bytes = splitCTF ? bioem_hip_prob_size(nMaps, nAngles, K) : bioem_hip_prob_size(nMaps, 0, 0);
@@ -1353,7 +1354,7 @@ std::string write_ctf_prob(const char *file, const bioem_hip_prob_map *tab, int 
     for (int c = 0; c < nCTF; c++)
     {
       const bioem_hip_prob_map &e = tab[(size_t) c * nMaps + i];
-      if (e.Total == 0.0 && e.Constoadd == -999999.)
+      if (!has_record(e))
       {
         snprintf(buf, sizeof(buf), "RefMap %d has no comparison under CTF set %d: its entry of the CTF table is untouched", i, c);
         return buf;
@@ -1373,7 +1374,7 @@ std::string write_ctf_prob(const char *file, const bioem_hip_prob_map *tab, int 
   for (int i = 0; i < nMaps; i++)
   {
     // the constant of this map's LogProb line (Driver::writeProbabilities), by the same expressions
-    const double numconst = 0.5 * log(M_PI) + (1 - Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(voluPerMap ? voluPerMap[i] : volu);
+    const double numconst = numconst_of(Ntotpi, voluPerMap ? voluPerMap[i] : volu);
     const float *A = angles + 4 * (angleOffsets ? (size_t) angleOffsets[i] : anglesPerMap * (size_t) i); // this map's list
     for (int c = 0; c < nCTF; c++)
     {
@@ -1450,7 +1451,7 @@ void Driver::writeProbabilities(const std::string &file, const bioem_hip_prob_ma
 {
   const int nMaps = particles.ntot;
   const bool writeAng = angProb && pd.writeAngles;
-  const double numconst = 0.5 * log(M_PI) + (1 - pd.Ntotpi * 0.5) * (log(2 * M_PI) + 1) + log(pd.volu);
+  const double numconst = numconst_of(pd.Ntotpi, pd.volu);
   const char *bar = "************************* HEADER:: NOTATION *******************************************\n";
   const float *K = param.ctfParam.data();
 

@@ -21,7 +21,7 @@ int view_groups_by_orientation(const bioem_hip_prob_map *pmap, int nMaps, int nO
   std::vector<int> count((size_t) nOrient, 0), group((size_t) nOrient, -1);
   auto compared = [&](int p) { // a particle no run compared has no arg-max
     const bioem_hip_prob_map &r = pmap[p];
-    return !(r.Total == 0.0 && r.Constoadd == -999999.) && r.max_prob_orient >= 0 && r.max_prob_orient < nOrient;
+    return has_record(r) && r.max_prob_orient >= 0 && r.max_prob_orient < nOrient;
   };
   for (int p = 0; p < nMaps; p++)
     if (compared(p))

@@ -331,3 +331,15 @@ def test_an_index_beyond_an_own_list_names_that_list():
         ref = joined(J.good(entry, E, own=True)())
         check(J, E, entry, call, want, own=True, ref=ref)
     E.close()
+
+
+def test_a_run_entry_raises_with_its_return_code():
+    """the run entries raise as the analysis entries do: the message they always had, and the entry's return code as .rc"""
+    I = inputs()
+    E = I.sc.engine  # (shared orientations only)
+    with pytest.raises(RuntimeError) as e:
+        E.compare_own_orientations(0, 1)
+    assert str(e.value) == ("compare_own_orientations: compare_own_orientations: no per-particle orientation lists "
+                            "(bioem_hip_upload_particle_orientations)")
+    assert e.value.rc == 2
+    assert joined(I.good("render_best_maps", E)()) == I.ref["render_best_maps"]
