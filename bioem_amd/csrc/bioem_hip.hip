@@ -62,6 +62,9 @@
 //   grad_kernels.hpp     k_grad_coef, k_grad_spectrum, k_grad_cols, k_grad_rows, k_grad_gather, k_grad_norm, k_grad_fold
 //                          bioem_hip_model_gradient: the derivative of a request's log posterior with respect to the
 //                          density of every model point (kernels_grad.hip; declarations only here)
+//   recon_kernels.hpp    k_recon_matrices, k_recon_insert, k_recon_tau_part, k_recon_tau, k_recon_estimate, k_recon_axis0,
+//                          k_recon_correct  bioem_hip_reconstruct: the view sums gathered into a 3D Fourier volume, its
+//                          estimate and real-space volume (kernels_recon.hip; declarations only here)
 //   orient_kernels.hpp   k_orient_max, k_orient_sums, k_orient_fold, k_orient_products  bioem_hip_orientation_sums: the
 //                          orientation posterior of every particle reduced where the angle table lives
 //                          (kernels_orient.hip; declarations only here); k_orient_occ  bioem_hip_orientation_occupancy:
@@ -136,6 +139,7 @@ struct HipErr
 #include "window_kernels.hpp"
 #include "scan_kernels.hpp"
 #include "grad_kernels.hpp"
+#include "recon_kernels.hpp"
 #include "orient_kernels.hpp"
 
 struct bioem_hip_ctx
@@ -240,6 +244,13 @@ struct bioem_hip_ctx
   int *dViewOff = nullptr;
   float2 *dViewUnit = nullptr;
   float *dViewMaps = nullptr;
+  // bioem_hip_reconstruct / bioem_hip_debug_reconstruct: numV (then V^, then the column pass), denV (then the float
+  // volume), the axis-0 pass (then the planes), the slots, orientations, angles and matrices of a chunk of views, the
+  // partial sums of the mean, tau and the sinc^2 table (allocated at the first call)
+  double2 *dReconNum = nullptr, *dReconWork = nullptr;
+  double *dReconDen = nullptr, *dReconR = nullptr, *dReconPart = nullptr, *dReconTau = nullptr, *dReconSinc = nullptr;
+  int *dReconSlot = nullptr, *dReconOrient = nullptr;
+  float4 *dReconAngles = nullptr;
   // bioem_hip_window_posterior / bioem_hip_debug_window: a batch's records, gathered orientations, particle and conv
   // spectra in reference layout, Parseval terms, parameters, particle sums handed in, the scratch T of the window pass,
   // the window's shifts in ascending order and the results (allocated at the first call)
@@ -3389,6 +3400,233 @@ int bioem_hip_view_averages(bioem_hip_handle h, const bioem_hip_prob_map *record
   }
   drain_phases(h);
   return 0;
+}
+
+// ---- the 3D density the view sums support (recon_kernels.hpp) ----
+namespace
+{
+// the buffers of the reconstruction; a failed allocation (return 1) leaves the handle as it was.  dReconWork holds N
+// planes of [N][N] doubles after the inverse (16 N^2 H >= 8 N^3 bytes), dReconDen the float volume (8 N^2 H >= 4 N^3)
+int recon_staging(bioem_hip_ctx *h)
+{
+  if (h->dReconNum)
+    return 0;
+  const size_t OB = (size_t) h->OB, N = (size_t) h->N, V = N * (size_t) h->M;
+  std::vector<double> sinc2(N);
+  for (size_t x = 0; x < N; x++)
+  { // the transform of the tent about the origin voxel o = (N + 1) / 2
+    const double t = M_PI * ((double) x - (double) ((N + 1) / 2)) / (double) N;
+    const double s = t == 0. ? 1. : sin(t) / t;
+    sinc2[x] = s * s;
+  }
+  Staging st = {h};
+  st.get(h->dReconNum, V);
+  st.get(h->dReconDen, V);
+  st.get(h->dReconWork, V);
+  st.get(h->dReconR, 9 * OB);
+  st.get(h->dReconPart, (size_t) kReconTauBlocks);
+  st.get(h->dReconTau, 1);
+  st.get(h->dReconSlot, OB);
+  st.get(h->dReconOrient, OB);
+  st.get(h->dReconAngles, OB);
+  st.fill(st.get(h->dReconSinc, N), sinc2.data(), sizeof(double) * N);
+  return st.commit();
+}
+
+bool recon_flags_known(int flags) { return (flags & ~(BIOEM_HIP_RECON_CORRECT | BIOEM_HIP_RECON_NO_CULL)) == 0; }
+
+int recon_begin(bioem_hip_ctx *h)
+{
+  const size_t V = (size_t) h->N * h->M;
+  HIP_CHECK(h, hipMemsetAsync(h->dReconNum, 0, sizeof(double2) * V, h->stream));
+  HIP_CHECK(h, hipMemsetAsync(h->dReconDen, 0, sizeof(double) * V, h->stream));
+  return 0;
+}
+
+// n views of dViewNum / dViewDen into the volume, in the order of slots[]: their matrices from the orientations orient[]
+// of `list`, or (orient null) from the n angles in dReconAngles.  The stream is drained: the caller's lists are free.
+int recon_insert_chunk(bioem_hip_ctx *h, const OrientList &list, const int *slots, const int *orient, int n, int flags, int g0)
+{
+  if (n < 1)
+    return 0;
+  HIP_CHECK(h, hipMemcpyAsync(h->dReconSlot, slots, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+  if (orient)
+    HIP_CHECK(h, hipMemcpyAsync(h->dReconOrient, orient, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+  if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, g0, g0 + n, 0, 0))
+    return 1;
+  HIP_CHECK(h, bioem_recon_matrices_launch(h->stream, list.d, orient ? h->dReconOrient : nullptr, list.isQuat, n, h->dReconR));
+  HIP_CHECK(h, bioem_recon_insert_launch(h->stream, h->dViewNum, h->dViewDen, h->dReconSlot, h->dReconR, n, h->N, h->dTwD,
+                                         (flags & BIOEM_HIP_RECON_NO_CULL) ? 0 : 1, h->dReconNum, h->dReconDen));
+  if (phase_end(h, h->stream))
+    return 1;
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// numV / denV as they stand to the host where asked for, then V^, then the volume; tau to *tau_out.  The phase records
+// hold the kernels, not the copies to the host.
+int recon_finish(bioem_hip_ctx *h, double wiener, int flags, float *vol_out, double *spec_out, double *numV_out,
+                 double *denV_out, double *tau_out)
+{
+  const int N = h->N;
+  const size_t V = (size_t) N * h->M, N3 = (size_t) N * N * N;
+  if (numV_out)
+    HIP_CHECK(h, hipMemcpyAsync(numV_out, h->dReconNum, sizeof(double2) * V, hipMemcpyDeviceToHost, h->stream));
+  if (denV_out)
+    HIP_CHECK(h, hipMemcpyAsync(denV_out, h->dReconDen, sizeof(double) * V, hipMemcpyDeviceToHost, h->stream));
+  if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, 0, 1, 0, 0))
+    return 1;
+  HIP_CHECK(h, bioem_recon_estimate_launch(h->stream, h->dReconNum, h->dReconDen, N, wiener, h->dTwD, h->dReconPart,
+                                           h->dReconTau));
+  if (phase_end(h, h->stream))
+    return 1;
+  if (spec_out)
+    HIP_CHECK(h, hipMemcpyAsync(spec_out, h->dReconNum, sizeof(double2) * V, hipMemcpyDeviceToHost, h->stream));
+  if (tau_out)
+    HIP_CHECK(h, hipMemcpyAsync(tau_out, h->dReconTau, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (vol_out)
+  {
+    int A, B;
+    dft_split(N, A, B);
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, 1, 2, 0, 0))
+      return 1;
+    // axis 0: V^ -> work; the planes: work -> columns (over V^) -> maps (over work); the float volume over denV
+    HIP_CHECK(h, bioem_recon_axis0_launch(h->stream, h->dReconNum, N, h->dTwD, h->dReconWork));
+    HIP_CHECK(h, bioem_grad_inverse_launch(h->stream, h->dReconWork, N, N, A, B, h->dTwD, h->dReconNum,
+                                           reinterpret_cast<double *>(h->dReconWork)));
+    float *dVol = reinterpret_cast<float *>(h->dReconDen);
+    HIP_CHECK(h, bioem_recon_correct_launch(h->stream, reinterpret_cast<const double *>(h->dReconWork), N, h->dReconSinc,
+                                            (flags & BIOEM_HIP_RECON_CORRECT) ? 1 : 0, dVol));
+    if (phase_end(h, h->stream))
+      return 1;
+    HIP_CHECK(h, hipMemcpyAsync(vol_out, dVol, sizeof(float) * N3, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  drain_phases(h);
+  return 0;
+}
+} // namespace
+
+int bioem_hip_reconstruct(bioem_hip_handle h, const bioem_hip_prob_map *records, const double *weights, const int *groupOf,
+                          const int *groupOrient, int nGroups, double wiener, int flags, float *vol_out, double *spec_out,
+                          double *den_out, double *stats_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[160];
+  const Refuse refuse = {h, "reconstruct"};
+  if (!records || !groupOf || !groupOrient)
+    return refuse("null argument");
+  if (!vol_out && !spec_out && !den_out && !stats_out)
+    return refuse("every output is null");
+  if (!recon_flags_known(flags))
+    return refuse("unknown flag bits");
+  if (!(wiener >= 0.) || !std::isfinite(wiener))
+    return refuse("wiener negative or not finite");
+  std::vector<BioemViewMember> mem;
+  if (const int rc = view_members(h, "reconstruct", records, weights, groupOf, h->nMaps, nGroups, 0, nGroups, mem))
+    return rc;
+  if (const char *why = missing_state(h, NEED_ORIENT | NEED_PARTICLES, 0))
+    return refuse(why);
+  for (int g = 0; g < nGroups; g++)
+    if (groupOrient[g] < -1 || groupOrient[g] >= h->nAnglesUp)
+    {
+      snprintf(buf, sizeof(buf), "group %d: orientation %d outside the list of %d and not -1", g, groupOrient[g], h->nAnglesUp);
+      return refuse(buf);
+    }
+  if (ring_staging(h) || view_staging(h, false) || recon_staging(h) || begin_analysis(h, false)) // (set 0 is not written)
+    return 1;
+  // The views of the call: the groups with an orientation and a member, in ascending order, numbered densely so that
+  // every chunk but the last is full -- nothing is accumulated for a group that is not inserted, and the volume is read
+  // and written once per maxOrientations views.  viewOf[p]: the view of particle p, or -1.
+  std::vector<int> count((size_t) nGroups, 0), view((size_t) nGroups, -1), orient, viewOf((size_t) h->nMaps, -1);
+  double stats[4] = {0., 0., 0., 0.};
+  for (int p = 0; p < h->nMaps; p++)
+    if (groupOf[p] >= 0)
+      count[(size_t) groupOf[p]]++;
+  for (int g = 0; g < nGroups; g++)
+    if (groupOrient[g] >= 0 && count[(size_t) g] > 0)
+    {
+      view[(size_t) g] = (int) orient.size();
+      orient.push_back(groupOrient[g]);
+    }
+  for (int p = 0; p < h->nMaps; p++)
+    if (groupOf[p] >= 0 && view[(size_t) groupOf[p]] >= 0)
+    {
+      viewOf[(size_t) p] = view[(size_t) groupOf[p]];
+      stats[1] += 1.;
+      stats[2] += weights ? weights[p] : 1.;
+    }
+  const int nViews = (int) orient.size();
+  stats[0] = (double) nViews;
+  if (recon_begin(h))
+    return 1;
+  std::vector<int> slots((size_t) h->OB);
+  for (int i = 0; i < h->OB; i++)
+    slots[(size_t) i] = i;
+  for (int va = 0; va < nViews; va += h->OB)
+  {
+    const int vb = std::min(nViews, va + h->OB);
+    if (view_accumulate_chunk(h, nullptr, mem, viewOf.data(), h->nMaps, va, vb) ||
+        recon_insert_chunk(h, shared_list(h), slots.data(), orient.data() + va, vb - va, flags, va))
+      return 1;
+  }
+  if (recon_finish(h, wiener, flags, vol_out, spec_out, nullptr, den_out, &stats[3]))
+    return 1;
+  if (stats_out)
+    memcpy(stats_out, stats, sizeof(stats));
+  return 0;
+}
+
+int bioem_hip_debug_reconstruct(bioem_hip_handle h, const double *num, const double *den, const float *angles4, int isQuat,
+                                int nViews, double wiener, int flags, float *vol_out, double *spec_out, double *numV_out,
+                                double *denV_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[160];
+  const Refuse refuse = {h, "debug_reconstruct"};
+  if (!num || !den || !angles4)
+    return refuse("null argument");
+  if (!vol_out && !spec_out && !numV_out && !denV_out)
+    return refuse("every output is null");
+  if (!recon_flags_known(flags))
+    return refuse("unknown flag bits");
+  if (nViews < 1)
+    return refuse("no views");
+  if (!(wiener >= 0.) || !std::isfinite(wiener))
+    return refuse("wiener negative or not finite");
+  for (int v = 0; v < nViews; v++)
+    for (int c = 0; c < (isQuat ? 4 : 3); c++)
+      if (!std::isfinite(angles4[4 * (size_t) v + c]))
+      {
+        snprintf(buf, sizeof(buf), "view %d: orientation not finite", v);
+        return refuse(buf);
+      }
+  if (view_staging(h, false) || recon_staging(h) || begin_analysis(h, false)) // (buffer set 0 is not written)
+    return 1;
+  if (recon_begin(h))
+    return 1;
+  const size_t M = (size_t) h->M;
+  const OrientList list = {h->dReconAngles, isQuat ? 1 : 0, 0.};
+  std::vector<int> slots;
+  for (int va = 0; va < nViews; va += h->OB)
+  {
+    const int n = std::min(h->OB, nViews - va);
+    slots.resize((size_t) n);
+    for (int i = 0; i < n; i++)
+      slots[(size_t) i] = i;
+    HIP_CHECK(h, hipMemcpyAsync(h->dViewNum, num + 2 * M * (size_t) va, sizeof(double2) * M * n, hipMemcpyHostToDevice,
+                                h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dViewDen, den + M * (size_t) va, sizeof(double) * M * n, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dReconAngles, angles4 + 4 * (size_t) va, sizeof(float4) * n, hipMemcpyHostToDevice,
+                                h->stream));
+    if (recon_insert_chunk(h, list, slots.data(), nullptr, n, flags, va))
+      return 1;
+  }
+  return recon_finish(h, wiener, flags, vol_out, spec_out, numV_out, denV_out, nullptr);
 }
 
 // ---- log posterior of every cell of the displacement window of a request (window_kernels.hpp) ----

@@ -26,6 +26,7 @@ SCAN_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("shiftX"
 GRAD_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4"), ("shiftX", "<i4"), ("shiftY", "<i4")])
 GRAD_POINT_DTYPE = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("sumw", "<f8"), ("count", "<i8")])
 MIN_PROB = -999999.0
+RECON_CORRECT, RECON_NO_CULL = 1, 2   # BIOEM_HIP_RECON_* of include/bioem_hip.h
 
 
 class ParamDevice(C.Structure):
@@ -116,6 +117,9 @@ def load_library():
         L.bioem_hip_view_sums.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]
         L.bioem_hip_view_averages.argtypes = [vp, vp, vp, vp, vp, ci, C.c_double, ci, ci, vp, vp, vp]
         L.bioem_hip_debug_view_sums.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp]
+    if hasattr(L, "bioem_hip_reconstruct"):
+        L.bioem_hip_reconstruct.argtypes = [vp, vp, vp, vp, vp, ci, C.c_double, ci, vp, vp, vp, vp]
+        L.bioem_hip_debug_reconstruct.argtypes = [vp, vp, vp, vp, ci, ci, C.c_double, ci, vp, vp, vp, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -178,6 +182,7 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_orientation_sums", "bioem_hip_merge_orient_sums_host", "bioem_hip_debug_orient_sums",
            "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy",
            "bioem_hip_view_sums", "bioem_hip_view_averages", "bioem_hip_debug_view_sums",
+           "bioem_hip_reconstruct", "bioem_hip_debug_reconstruct",
            "bioem_hip_set_compare_variant", "bioem_hip_debug_projection_maps", "bioem_hip_debug_stamps"]
 
 
@@ -559,6 +564,58 @@ class Engine:
         self._chk(self.L.bioem_hip_debug_view_sums(self.h, _p(specR), _p(pmap), _p(weights), _p(group_of), n, nG, _p(num),
                                                    _p(den), _p(stats)), "debug_view_sums")
         return num, den, stats
+
+    def reconstruct(self, pmap, group_of, group_orient, weights=None, wiener=0.1, correct=True, want_spec=False,
+                    want_vol=True, cull=True):
+        """the 3D density the aligned view sums of the groups support under their orientations (include/bioem_hip.h, DESIGN
+        2.20).  Arguments as view_averages; groups with group_orient -1 or no member are skipped.  Returns a dict: "vol"
+        float32 [N, N, N] with its origin at voxel (o, o, o), o = (N + 1) // 2 (unless want_vol=False); "stats" float64 [4]
+        = views used, particles used, the sum of their weights, tau; with want_spec "spec" complex128 [N, N, H] = V^ and
+        "den" float64 [N, N, H] = denV.  correct: divide by the transform of the interpolation kernel; cull=False: the
+        test switch BIOEM_HIP_RECON_NO_CULL (same bits).  A refusal raises RuntimeError with .rc == 2."""
+        pmap, group_of, weights = self._view_args(pmap, group_of, weights, self.nMaps)
+        group_orient = np.ascontiguousarray(group_orient, dtype=np.int32)
+        shape = (self.N, self.N, self.H)
+        out = {"stats": np.zeros(4, dtype=np.float64)}
+        if want_vol:
+            out["vol"] = np.zeros((self.N,) * 3, dtype=np.float32)
+        if want_spec:
+            out["spec"] = np.zeros(shape, dtype=np.complex128)
+            out["den"] = np.zeros(shape, dtype=np.float64)
+        flags = (RECON_CORRECT if correct else 0) | (0 if cull else RECON_NO_CULL)
+        self._chk(self.L.bioem_hip_reconstruct(self.h, _p(pmap), _p(weights), _p(group_of), _p(group_orient),
+                                               len(group_orient), float(wiener), flags, _p(out.get("vol")),
+                                               _p(out.get("spec")), _p(out.get("den")), _p(out["stats"])), "reconstruct")
+        return out
+
+    def debug_reconstruct(self, num, den, angles, isQuat=True, wiener=0.1, correct=True, cull=True, want_vol=True,
+                          want_spec=True, want_sums=True, flags=None):
+        """test hook: the kernels of reconstruct alone on the sums of n views handed in, num complex128 [n, N, H] and den
+        float64 [n, N, H] as view_sums delivers them, under the orientations angles float32 [n, 4].  Needs only the
+        handle's parameters.  Returns a dict with "vol" float32 [N, N, N], "spec" complex128 [N, N, H] = V^, "numV"
+        complex128 and "denV" float64 [N, N, H], each where asked for; flags overrides correct / cull with raw flag bits.
+        A refusal raises with .rc == 2."""
+        num = np.ascontiguousarray(num, dtype=np.complex128)
+        den = np.ascontiguousarray(den, dtype=np.float64)
+        angles = np.ascontiguousarray(angles, dtype=np.float32)
+        n = len(angles)
+        assert angles.shape == (n, 4) and num.shape == (n, self.N, self.H) and den.shape == num.shape
+        shape = (self.N, self.N, self.H)
+        out = {}
+        if want_vol:
+            out["vol"] = np.zeros((self.N,) * 3, dtype=np.float32)
+        if want_spec:
+            out["spec"] = np.zeros(shape, dtype=np.complex128)
+        if want_sums:
+            out["numV"] = np.zeros(shape, dtype=np.complex128)
+            out["denV"] = np.zeros(shape, dtype=np.float64)
+        if flags is None:
+            flags = (RECON_CORRECT if correct else 0) | (0 if cull else RECON_NO_CULL)
+        self._chk(self.L.bioem_hip_debug_reconstruct(self.h, _p(num) if n else None, _p(den) if n else None,
+                                                     _p(angles) if n else None, int(bool(isQuat)), n, float(wiener),
+                                                     int(flags), _p(out.get("vol")), _p(out.get("spec")), _p(out.get("numV")),
+                                                     _p(out.get("denV"))), "debug_reconstruct")
+        return out
 
     def window_shifts(self):
         """the cell coordinates of this handle's window tables (window_offsets of its parameters)"""

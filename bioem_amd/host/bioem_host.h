@@ -259,6 +259,24 @@ int view_groups_by_orientation(const bioem_hip_prob_map *pmap, int nMaps, int nO
 std::string write_view_averages(const char *file, const bioem_hip_ring_sums *rings, int nViews, const int *groupOrient,
                                 const int *counts, const float *angles4, bool doquater, int N, float pixelSize, int minCount,
                                 double wiener);
+// --Reconstruct (reconstruct.cpp).  recon_shell_sums: per shell of the rounded |kappa| of the stored half spectra specA, specB
+// [N][N][H] (re, im) the number of coefficients of the full spectrum and the sums cross = sum w Re(A conj(B)), powA, powB
+// with the Hermitian weights 2 and 1 of the ring sums (the weights add up to N^3).  write_reconstruction: after the HEADER::
+// NOTATION bar, one notation line and the bar again, one line per shell s >= 0
+//  SHELL s resolution weight FSC cross powHalf1 powHalf2
+// (resolution = N pixelSize / s in Angstrom, 0 for shell 0; FSC = cross / sqrt(powHalf1 powHalf2), 0 where the product is 0)
+// and one line
+//  DATASET views particles tau res05 res0143
+// (res05 / res0143: the resolution of the first shell s >= 1 with FSC < 0.5 / < 0.143, -1 when none).  write_mrc_volume: the
+// volume [N][N][N] (origin at voxel (N + 1) / 2) as a mode-2 MRC file that --ReadModelMRC reads back with every point where
+// the reconstruction has it: file[e] = vol[(e + 1) mod N] on every axis, stated in the file's label.  Each returns the empty
+// string, or the error.
+void recon_shell_sums(const double *specA, const double *specB, int N, std::vector<double> &weight, std::vector<double> &cross,
+                      std::vector<double> &powA, std::vector<double> &powB);
+std::string write_reconstruction(const char *file, const std::vector<double> &weight, const std::vector<double> &cross,
+                                 const std::vector<double> &powA, const std::vector<double> &powB, int N, float pixelSize,
+                                 double wiener, long long views, long long particles, double tau);
+std::string write_mrc_volume(const char *file, const float *vol, int N, float pixelSize);
 // MRC mode-2 stack nx = ny = N, nz = nMaps in the storage order the --ReadMRC reader expects, written batch by batch
 struct MrcStackWriter
 {
@@ -330,6 +348,11 @@ public:
   std::string viewAvgFile;
   int viewMinParticles = 2;
   double viewWiener = 0.1;
+  // --Reconstruct FILE: the 3D density of the particles under their arg-max orientations (FILE.mrc, FILE_half1.mrc,
+  // FILE_half2.mrc) and the shell correlation of the halves (FILE); --ReconstructWiener t: tau = t * mean denV, a
+  // conventional default, not a tuned one
+  std::string reconFile;
+  double reconWiener = 0.1;
   std::string bestParamFile; // --PrintBestCalMap: the reference's one-record mode, no particles, writes BESTMAP
   BestParams best;
   int printBestCalMap();     // bioem::printModel (bioem.cpp:624-657, 1925-2085)
@@ -368,6 +391,9 @@ private:
   // --ViewAverages: the records grouped by orientation, the chain on handle h (bioem_hip_view_averages) in chunks of
   // views, written by write_view_averages and two MRC stacks
   void writeViewAverages(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap);
+  // --Reconstruct: the records grouped by orientation (at least one member), the chain on handle h (bioem_hip_reconstruct)
+  // for all particles and for the even and the odd ones, written by write_mrc_volume and write_reconstruction
+  void writeReconstruction(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap);
   // --BestWindow: the window tables of the records' (orientation, CTF) pairs from handle h (bioem_hip_window_posterior),
   // written by write_best_window; voluPerMap as for writeProbabilities
   void writeBestWindow(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,

@@ -378,4 +378,25 @@ int bioem_host_write_mrc_stack(const char *file, const float *maps, int nMaps, i
       return 1;
   return w.close() ? 0 : 1;
 }
+
+// the --Reconstruct text of the shell sums of two half spectra [N][N][H] (recon_shell_sums, write_reconstruction) and the
+// MRC volume (write_mrc_volume); 0, or 1 with the text in err[cap]
+int bioem_host_write_reconstruction(const char *file, const double *specA, const double *specB, int N, float pixelSize,
+                                    double wiener, long long views, long long particles, double tau, char *err, int cap)
+{
+  std::vector<double> w, c, pa, pb;
+  bioem_host::recon_shell_sums(specA, specB, N, w, c, pa, pb);
+  const std::string e = bioem_host::write_reconstruction(file, w, c, pa, pb, N, pixelSize, wiener, views, particles, tau);
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return e.empty() ? 0 : 1;
+}
+
+int bioem_host_write_mrc_volume(const char *file, const float *vol, int N, float pixelSize, char *err, int cap)
+{
+  const std::string e = bioem_host::write_mrc_volume(file, vol, N, pixelSize);
+  if (err && cap > 0)
+    snprintf(err, (size_t) cap, "%s", e.c_str());
+  return e.empty() ? 0 : 1;
+}
 }

@@ -113,7 +113,7 @@ Driver::~Driver() { cleanup(); }
 int Driver::readOptions(int ac, char **av)
 {
   std::string infile, modelfile, mapfile, anglefile;
-  bool viewOptions = false, scanOptions = false;
+  bool viewOptions = false, scanOptions = false, reconOptions = false;
   std::cout << " ++++++++++++ FROM COMMAND LINE +++++++++++\n\n";
   static const struct option opts[] = {{"Modelfile", required_argument, 0, 0},
                                        {"Particlesfile", required_argument, 0, 0},
@@ -132,6 +132,8 @@ int Driver::readOptions(int ac, char **av)
                                        {"ViewAverages", required_argument, 0, 0},
                                        {"ViewMinParticles", required_argument, 0, 0},
                                        {"ViewWiener", required_argument, 0, 0},
+                                       {"Reconstruct", required_argument, 0, 0},
+                                       {"ReconstructWiener", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
                                        {"RefineSeeds", required_argument, 0, 0},
@@ -185,6 +187,11 @@ int Driver::readOptions(int ac, char **av)
     printf("                         against the model's projection: ring correlation in arg, stacks arg_avg.mrc and arg_proj.mrc\n");
     printf("  --ViewMinParticles arg (Optional) With --ViewAverages: views with fewer particles are left out (default 2)\n");
     printf("  --ViewWiener arg       (Optional) With --ViewAverages: the Wiener constant as a fraction of the mean weight (default 0.1)\n");
+    printf("  --Reconstruct arg      (Optional) Write the 3D density the particles support under their best orientations: arg.mrc,\n");
+    printf("                         the half sets arg_half1.mrc / arg_half2.mrc and their shell correlation in arg; read back\n");
+    printf("                         with --ReadModelMRC the volume lies where it was reconstructed (odd NUMBER_PIXELS: half a\n");
+    printf("                         pixel beyond it on every axis)\n");
+    printf("  --ReconstructWiener arg (Optional) With --Reconstruct: the Wiener constant as a fraction of the mean weight (default 0.1)\n");
     printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
@@ -346,6 +353,18 @@ int Driver::readOptions(int ac, char **av)
       if (!(viewWiener >= 0.) || !std::isfinite(viewWiener))
         fatal("--ViewWiener needs a non-negative number");
     }
+    else if (name == "Reconstruct")
+    {
+      std::cout << "Writing the reconstruction to: " << optarg << "\n";
+      reconFile = optarg;
+    }
+    else if (name == "ReconstructWiener")
+    {
+      reconWiener = atof(optarg);
+      reconOptions = true;
+      if (!(reconWiener >= 0.) || !std::isfinite(reconWiener))
+        fatal("--ReconstructWiener needs a non-negative number");
+    }
     else if (name == "PrintBestCalMap")
     {
       std::cout << "Reading best parameters from file: " << optarg << "\n";
@@ -386,9 +405,9 @@ int Driver::readOptions(int ac, char **av)
     // one CTF / PSF kernel, no particles, no grids
     if (!bestMapsFile.empty() || !refineFile.empty() || !probCtfFile.empty() || !bestFrcFile.empty() || !bestWindowFile.empty() ||
         !ctfScanFile.empty() || !orientStatsFile.empty() || !orientOccFile.empty() || !viewAvgFile.empty() ||
-        !modelGradFile.empty())
+        !modelGradFile.empty() || !reconFile.empty())
       fatal("--PrintBestCalMap goes without --BestMaps, --ProbCTF, --BestFRC, --BestWindow, --CTFScan, --OrientStats, --OrientOccupancy, "
-            "--ViewAverages, --ModelGradient and --RefineOrientations");
+            "--ViewAverages, --ModelGradient, --Reconstruct and --RefineOrientations");
     const std::string err = read_best_parameters(bestParamFile.c_str(), best);
     if (!err.empty())
       fatal("%s", err.c_str());
@@ -442,6 +461,10 @@ int Driver::readOptions(int ac, char **av)
     fatal("--ViewMinParticles / --ViewWiener go with --ViewAverages");
   if (!viewAvgFile.empty() && !refineFile.empty()) // the views are orientations of the shared list
     fatal("--ViewAverages is not valid with --RefineOrientations (own lists share no orientation index)");
+  if (reconOptions && reconFile.empty())
+    fatal("--ReconstructWiener goes with --Reconstruct");
+  if (!reconFile.empty() && !refineFile.empty()) // the views are orientations of the shared list
+    fatal("--Reconstruct is not valid with --RefineOrientations (own lists share no orientation index)");
   if (fitOrientPrior && orientOccFile.empty())
     fatal("--FitOrientPrior is only valid with --OrientOccupancy");
   if (!orientOccFile.empty())
@@ -721,6 +744,43 @@ void Driver::writeViewAverages(const std::string &file, bioem_hip_handle h, cons
   if (!err.empty())
     fatal("--ViewAverages: %s", err.c_str());
   std::cout << "Averages of " << nViews << " views written to: " << file << ", " << avgFile << ", " << projFile << "\n";
+}
+
+// --Reconstruct: the merged records grouped by their arg-max orientation (one member is enough), the chain on handle h
+// three times through weights -- all particles, the even and the odd ones -- then the volumes (write_mrc_volume) and the
+// shell correlation of the two halves (write_reconstruction)
+void Driver::writeReconstruction(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap)
+{
+  const int nMaps = particles.ntot, N = param.N, H = N / 2 + 1;
+  const size_t N3 = (size_t) N * N * N, V = (size_t) N * N * H;
+  std::vector<int> groupOf, groupOrient;
+  const int nViews = view_groups_by_orientation(pmap, nMaps, param.nTotGridAngles, 1, groupOf, groupOrient);
+  if (nViews < 1)
+    fatal("--Reconstruct: no particle has a record to reconstruct from");
+  std::vector<float> vol(N3);
+  std::vector<double> spec[2] = {std::vector<double>(2 * V), std::vector<double>(2 * V)}, w((size_t) nMaps);
+  double stats[4] = {0., 0., 0., 0.}, half[4];
+  const std::string names[3] = {file + ".mrc", file + "_half1.mrc", file + "_half2.mrc"};
+  for (int k = 0; k < 3; k++)
+  { // k = 0: every particle; 1, 2: the even and the odd ones
+    for (int p = 0; p < nMaps; p++)
+      w[(size_t) p] = (k == 0 || p % 2 == k - 1) ? 1. : 0.;
+    check(h, bioem_hip_reconstruct(h, pmap, w.data(), groupOf.data(), groupOrient.data(), nViews, reconWiener,
+                                   BIOEM_HIP_RECON_CORRECT, vol.data(), k ? spec[k - 1].data() : nullptr, nullptr,
+                                   k ? half : stats),
+          "reconstruction");
+    const std::string err = write_mrc_volume(names[k].c_str(), vol.data(), N, param.pixelSize);
+    if (!err.empty())
+      fatal("--Reconstruct: %s", err.c_str());
+  }
+  std::vector<double> weight, cross, pa, pb;
+  recon_shell_sums(spec[0].data(), spec[1].data(), N, weight, cross, pa, pb);
+  const std::string err = write_reconstruction(file.c_str(), weight, cross, pa, pb, N, param.pixelSize, reconWiener,
+                                               (long long) stats[0], (long long) stats[1], stats[3]);
+  if (!err.empty())
+    fatal("--Reconstruct: %s", err.c_str());
+  std::cout << "Reconstruction from " << (long long) stats[1] << " particles in " << (long long) stats[0]
+            << " views written to: " << file << ", " << names[0] << ", " << names[1] << ", " << names[2] << "\n";
 }
 
 // --BestWindow: the window table of every record's (orientation, CTF) pair from handle h, batch by batch, then the text
@@ -1158,6 +1218,8 @@ int Driver::run()
     writeModelGradient(modelGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!viewAvgFile.empty())
     writeViewAverages(viewAvgFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
+  if (!reconFile.empty())
+    writeReconstruction(reconFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
   if (!refineFile.empty())
   {
     if (refineSeeds >= 2)

@@ -227,6 +227,33 @@ def write_view_averages(path, rings, group_orient, counts, angles, doquater, N, 
         raise ValueError(err.value.decode())
 
 
+def write_reconstruction(path, specA, specB, N, pixelSize, wiener=0.1, views=0, particles=0, tau=0.0):
+    """the --Reconstruct text file from the two half-set spectra complex128 [N, N, H] (Engine.reconstruct): the shell sums and
+    the writer the CLI uses; bioem_amd.reconstruct.parse reads it back"""
+    L = load_host_library()
+    L.bioem_host_write_reconstruction.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_double,
+                                                  C.c_longlong, C.c_longlong, C.c_double, C.c_char_p, C.c_int]
+    A = np.ascontiguousarray(specA, dtype=np.complex128)
+    B = np.ascontiguousarray(specB, dtype=np.complex128)
+    assert A.shape == B.shape == (N, N, N // 2 + 1)
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_reconstruction(path.encode(), A.ctypes.data, B.ctypes.data, int(N), float(pixelSize), float(wiener),
+                                         int(views), int(particles), float(tau), err, 512):
+        raise ValueError(err.value.decode())
+
+
+def write_mrc_volume(path, vol, pixelSize):
+    """a volume float32 [N, N, N] as the MRC file of --Reconstruct (the writer the CLI uses): read_model(isMRC=True) places
+    every point where the reconstruction has it; bioem_amd.reconstruct.read_mrc reads the volume back"""
+    L = load_host_library()
+    L.bioem_host_write_mrc_volume.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_float, C.c_char_p, C.c_int]
+    v = np.ascontiguousarray(vol, dtype=np.float32)
+    assert v.ndim == 3 and v.shape == (v.shape[0],) * 3
+    err = C.create_string_buffer(512)
+    if L.bioem_host_write_mrc_volume(path.encode(), v.ctypes.data, v.shape[0], float(pixelSize), err, 512):
+        raise ValueError(err.value.decode())
+
+
 def write_best_window(path, logp, shifts, orient, conv, ctfParam, numconst, usepsf=False, elecwavel=0.019866):
     """the --BestWindow text file of window tables [nMaps, nd, nd] (Engine.best_match_window) at the shifts [nd]: the
     writer the CLI uses; bioem_amd.best_window.parse reads it back.  orient, conv [nMaps]: the records' pair (orient < 0:

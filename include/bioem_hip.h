@@ -634,6 +634,47 @@ int bioem_hip_view_averages(bioem_hip_handle h, const bioem_hip_prob_map *record
 int bioem_hip_debug_view_sums(bioem_hip_handle h, const float *specR, const bioem_hip_prob_map *records, const double *weights,
                               const int *groupOf, int n, int nGroups, double *num_out, double *den_out, double *stats_out);
 
+/* ---- The 3D density the aligned view sums support (no reference counterpart) ----
+ * The views' sums num_g, den_g above are put together by the Fourier-slice theorem under the orientations the run
+ * assigned.  o = (N + 1) / 2 is the pixel the projection puts the model's origin on, M = (N - 1) / 2, a centred frequency
+ * kappa stands for index kappa mod N, everything in double:
+ *   S_g(a, b) = num_g[a mod N][b] tw[(o (a + b)) mod N] for b >= 0, conj(S_g(-a, -b)) for b < 0; D_g(a, b) likewise from
+ *               den_g (real); both 0 outside |a|, |b| <= M (N even: the Nyquist row and column are left out)
+ *   R_g       = the float rotation matrix the projection builds for the orientation, widened
+ *   q_i       = (R[i][0] k0 + R[i][1] k1) + R[i][2] k2 for the stored voxel (k0, k1, k2): index i <= N / 2 stands for
+ *               kappa = i, a larger one for i - N, on axes 0 and 1; 0 <= k2 < H
+ *   numV[k]  += wz w_t S_g(tap), denV[k] += wz w_t D_g(tap) with wz = max(0, 1 - |q2|) and the taps (a, b), (a + 1, b),
+ *               (a, b + 1), (a + 1, b + 1) about a = floor(q0), b = floor(q1) of weights (1 - f0)(1 - f1), f0 (1 - f1),
+ *               (1 - f0) f1, f0 f1; views in ascending order, taps in this order, weight = wz * (w_t) rounded as written
+ *   V^[k]     = numV / (denV + tau) tw[(-o (k0 + k1 + k2)) mod N], tau = wiener * mean_k denV[k], 0 where denV + tau is 0
+ *   vol       = c2r3(V^) / N^3: the inverse along axis 0, then every plane through the passes of the gradient image;
+ *               with BIOEM_HIP_RECON_CORRECT divided by prod_d sinc^2(pi (x_d - o) / N); rounded to float.  The origin
+ *               of the volume is voxel (o, o, o), axes as the model's (x, y, z).
+ * A voxel is owned by one lane that adds its views one after the other: no atomics, the bits of a voxel depend on the
+ * views alone -- not on the chunks of groups, the other voxels, BIOEM_HIP_RECON_NO_CULL or the run.
+ * Outputs, each may be NULL but not all: vol_out [N][N][N] float, spec_out [N][N][H] (re, im) doubles = V^, den_out /
+ * denV_out [N][N][H] doubles, numV_out [N][N][H] (re, im) doubles.  The volume buffers (about 40 N^2 H bytes) are allocated
+ * at the first call: 1 when the memory is not there.  Phase records: phase 2 per particle batch of the accumulation, phase
+ * 1 per chunk of views inserted, phase 0 with iOrientBegin 0 over the estimate and with iOrientBegin 1 over the inverse. */
+#define BIOEM_HIP_RECON_CORRECT 1 /* divide the volume by the transform of the interpolation kernel */
+#define BIOEM_HIP_RECON_NO_CULL 2 /* test switch: no view is left out for a whole brick of voxels (same bits) */
+/* The chain: the accumulation of bioem_hip_view_sums in chunks of at most maxOrientations groups, each chunk inserted while
+ * it is on the device.  groupOrient[g] indexes the shared orientation list; groups with groupOrient[g] = -1 or without
+ * members are skipped.  stats_out {views used, particles used, sum of their weights, tau}.  Calling rules, handle kinds and
+ * refusals as bioem_hip_view_averages (the model is not needed; a negative wiener is refused as there), and refused with 2 as
+ * well: all outputs NULL, unknown flag bits, a non-finite wiener.  The views are numbered densely before they are chunked:
+ * nothing is accumulated for a skipped group. */
+int bioem_hip_reconstruct(bioem_hip_handle h, const bioem_hip_prob_map *records, const double *weights, const int *groupOf,
+                          const int *groupOrient, int nGroups, double wiener, int flags, float *vol_out, double *spec_out,
+                          double *den_out, double *stats_out);
+/* test hook: the kernels alone on nViews sums handed in (num [v][N][H] (re, im), den [v][N][H]) under the orientations
+ * angles4 [v][4] (quaternions, or Euler angles with isQuat 0); needs no particles, model or CTF.  Refused with 2, the view
+ * named: a null input, all outputs NULL, unknown flag bits, nViews < 1, a non-finite orientation, a negative or non-finite
+ * wiener. */
+int bioem_hip_debug_reconstruct(bioem_hip_handle h, const double *num, const double *den, const float *angles4, int isQuat,
+                                int nViews, double wiener, int flags, float *vol_out, double *spec_out, double *numV_out,
+                                double *denV_out);
+
 #ifdef __cplusplus
 }
 #endif
