@@ -1210,7 +1210,8 @@ int compat_flush(bioem_hip_ctx *h)
 }
 
 // conv spectra of CTFs [c0, c0 + nC) of the nO projected orientations, row ob * nC + (c - c0)
-int convolve_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, int nO, int c0, int nC, bool own = false)
+// which of the two convolution paths a batch takes (read per call; bioem_hip_debug_convolve_batch reports it)
+bool convolve_fused(const bioem_hip_ctx *h, bool own)
 {
   // few particles: the preparation is the longer half of the pipeline and the fused kernel shortens it; many particles:
   // it hides behind the comparison either way, and the one-wave blocks of k_parseval_ordered take less from the
@@ -1219,7 +1220,12 @@ int convolve_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t 
   const char *fe = getenv("BIOEM_CONVOLVE_FUSED");
   // (the own-list pass: a conv spectrum meets one particle, the preparation is the long pole whatever nMaps is, and its
   // batches hold no buffer for the ordered sums of the two-kernel path -- always fused)
-  if (own || (fe ? atoi(fe) != 0 : h->nMaps <= 256))
+  return own || (fe ? atoi(fe) != 0 : h->nMaps <= 256);
+}
+
+int convolve_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t st, int nO, int c0, int nC, bool own = false)
+{
+  if (convolve_fused(h, own))
   {
     // chains on the lanes of the adding wave: 4 orientations x up to 4 CTFs, 3 x 5, or 3 x 6 per block (16, 15, 18
     // products per producing thread and tile: more, and the producers -- ~25 vector instructions per product -- take
@@ -4663,6 +4669,54 @@ int bioem_hip_debug_convolution(bioem_hip_handle h, int iOrient, int iConv, floa
   HIP_CHECK(h, hipStreamSynchronize(h->stream));
   *sumC = q.sumC;
   *sumsquareC = q.sumsquareC;
+  return 0;
+}
+
+int bioem_hip_debug_convolve_batch(bioem_hip_handle h, const float *specP, int nO, int c0, int nC, float *conv_out,
+                                   bioem_hip_param5 *params_out, float *raw_out, int *info_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "debug_convolve_batch"};
+  if (!specP || !conv_out || !params_out || !info_out)
+    return refuse("null argument");
+  if (const char *why = missing_state(h, NEED_CTF, 0))
+    return refuse(why);
+  if (nO < 1 || nO > h->OB)
+    return refuse("between 1 and maxOrientations (" + std::to_string(h->OB) + ") orientations per call");
+  if (c0 < 0 || nC < 1 || c0 > h->nCTF - nC)
+    return refuse("CTF range empty or outside [0, nCTF)");
+  const size_t rows = (size_t) nO * nC; // (at most maxOrientations x nCTF)
+  if (rows + 1 > h->slotRows)
+    return refuse("the conv rows of a batch (" + std::to_string(h->slotRows) + ") do not hold " + std::to_string(rows) +
+                  " rows and a guard row");
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  const bool fused = convolve_fused(h, false);
+  if (!fused && (!s0.scratch || rows > (size_t) ((h->maxOC + 31) & ~31)))
+    return refuse("the two-kernel path is selected and the batch has no buffer for the ordered sums of " +
+                  std::to_string(rows) + " rows");
+  if (begin_analysis(h, true))
+    return 1;
+  const size_t M = (size_t) h->M;
+  OrientDebugBufs B;
+  float2 *tmp = nullptr; // the rows and the guard row in reference layout
+  HIP_CHECK(h, B.get(&tmp, nullptr, sizeof(float2) * M * (rows + 1)));
+  HIP_CHECK(h, hipMemcpyAsync(s0.specRef, specP, sizeof(float2) * M * nO, hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(h, hipMemsetAsync(s0.conv, 0xFF, sizeof(float2) * h->Mc * (rows + 1), h->stream));
+  HIP_CHECK(h, hipMemsetAsync(s0.params, 0xFF, sizeof(bioem_hip_param5) * (rows + 1), h->stream));
+  if (convolve_batch(h, s0, h->stream, nO, c0, nC))
+    return 1;
+  hipLaunchKernelGGL(k_unreorder, dim3((unsigned) std::min<size_t>(1024, 16 * (rows + 1))), dim3(256), 0, h->stream, s0.conv,
+                     tmp, (int) (rows + 1), h->N, h->H, h->plan.halfR, h->plan.N1, h->Hp);
+  HIP_CHECK(h, hipGetLastError());
+  HIP_CHECK(h, hipMemcpyAsync(conv_out, tmp, sizeof(float2) * M * (rows + 1), hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipMemcpyAsync(params_out, s0.params, sizeof(bioem_hip_param5) * (rows + 1), hipMemcpyDeviceToHost, h->stream));
+  if (raw_out)
+    HIP_CHECK(h, hipMemcpyAsync(raw_out, s0.conv, sizeof(float2) * h->Mc * rows, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  const int info[6] = {fused ? 1 : 0, h->plan.halfR, h->plan.N1, h->Hp, (int) rows, 1};
+  std::copy(info, info + 6, info_out);
   return 0;
 }
 

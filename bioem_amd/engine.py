@@ -145,6 +145,8 @@ def load_library():
         L.bioem_hip_debug_projection_maps.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp]
         L.bioem_hip_debug_stamps.argtypes = [vp, vp, C.POINTER(ci)]
     L.bioem_hip_debug_convolution.argtypes = [vp, ci, ci, vp, C.POINTER(cf), C.POINTER(cf)]
+    if hasattr(L, "bioem_hip_debug_convolve_batch"):
+        L.bioem_hip_debug_convolve_batch.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp]
     L.bioem_hip_debug_particles.argtypes = [vp, vp, vp, vp]
     L.bioem_hip_kernel_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.bioem_hip_reset_kernel_stats.argtypes = [vp]
@@ -183,7 +185,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy",
            "bioem_hip_view_sums", "bioem_hip_view_averages", "bioem_hip_debug_view_sums",
            "bioem_hip_reconstruct", "bioem_hip_debug_reconstruct",
-           "bioem_hip_set_compare_variant", "bioem_hip_debug_projection_maps", "bioem_hip_debug_stamps"]
+           "bioem_hip_set_compare_variant", "bioem_hip_debug_projection_maps", "bioem_hip_debug_stamps",
+           "bioem_hip_debug_convolve_batch"]
 
 
 def _p(a):
@@ -890,6 +893,29 @@ class Engine:
         self._chk(self.L.bioem_hip_debug_convolution(self.h, iOrient, iConv, _p(out), C.byref(s), C.byref(s2)),
                   "debug_convolution")
         return out, np.float32(s.value), np.float32(s2.value)
+
+    def debug_convolve_batch(self, specP, c0, nC, want_raw=False):
+        """one convolution batch as a run launches it (bioem_hip_debug_convolve_batch), from the projection spectra specP
+        float32 [nO, N, H, 2] and the handle's CTF sets [c0, c0 + nC): (conv float32 [nO nC + 1, N, H, 2] in reference
+        layout, params PARAM5_DTYPE [nO nC + 1], raw float32 [nO nC, N Hp, 2] or None, info).  The last conv row and the
+        last params entry are the guard: 0xFF bytes no kernel may have touched.  info: dict fused / fast / N1 / Hp / rows /
+        guard.  BIOEM_CONVOLVE_FUSED is read at the call.  Invalid arguments raise with .rc == 2; the handle stays usable."""
+        specP = _spectra(specP)
+        assert specP.ndim == 4 and specP.shape[1:] == (self.N, self.H, 2), specP.shape
+        nO, c0, nC = len(specP), int(c0), int(nC)
+        rows = max(nO * nC, 0)
+        conv = np.zeros((rows + 1, self.N, self.H, 2), dtype=np.float32)
+        params = np.zeros(rows + 1, dtype=PARAM5_DTYPE)
+        info = np.zeros(6, dtype=np.int32)
+        raw = None
+        if want_raw:    # (Hp, the pitch of a row pair, is the handle's and comes back in info: at most H + 15)
+            raw = np.zeros((rows, self.N * (self.H + 15), 2), dtype=np.float32)
+        self._chk(self.L.bioem_hip_debug_convolve_batch(self.h, _p(specP), nO, c0, nC, _p(conv), _p(params), _p(raw),
+                                                        _p(info)), "debug_convolve_batch")
+        info = dict(zip(("fused", "fast", "N1", "Hp", "rows", "guard"), map(int, info)))
+        if raw is not None:
+            raw = raw.reshape(-1)[:rows * self.N * info["Hp"] * 2].reshape(rows, self.N * info["Hp"], 2).copy()
+        return conv, params, raw, info
 
     def debug_particles(self):
         spec = np.empty((self.nMaps, self.N, self.H, 2), dtype=np.float32)

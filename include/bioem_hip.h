@@ -328,6 +328,19 @@ int bioem_hip_debug_stamps(bioem_hip_handle h, double *stamps_out, int *iradMax_
 /* conv spectrum + {sumC, sumsquareC} of (iOrient, iConv) in reference layout */
 int bioem_hip_debug_convolution(bioem_hip_handle h, int iOrient, int iConv, float *spec_out, float *sumC,
                                 float *sumsquareC);
+/* One whole convolution batch as a run launches it, from projection spectra the caller hands in (outside a run): buffer
+ * set 0 takes specP [nO][N][N/2+1][2] (reference layout) as its projection spectra, its conv rows [0, nO nC + 1) and the
+ * same entries of its parameter list are filled with 0xFF bytes, and the convolution of the nO orientations with the
+ * handle's CTF sets [c0, c0 + nC) (bioem_hip_upload_ctf) is launched exactly as a run launches it -- the fused kernel or the
+ * two kernels, BIOEM_CONVOLVE_FUSED read at this call.  conv_out [nO nC + 1][N][N/2+1][2]: row o nC + c in reference
+ * layout, the last one the guard row no kernel may have written; params_out [nO nC + 1] likewise; raw_out NULL or the
+ * nO nC rows as they lie in the comparison layout, [nO nC][N Hp][2] float; info_out [6] int = {fused path (1 / 0), R / 2
+ * of the comparison layout (0: reference layout), N1, Hp, rows handed out, guard row present}.  Refused with 2 and a
+ * message, the handle usable afterwards: a null argument (raw_out may be), CTF sets not uploaded, nO outside
+ * [1, maxOrientations], a CTF range empty or outside [0, nCTF), nO nC + 1 rows more than a batch holds, the two-kernel
+ * path selected without a buffer for the ordered sums of nO nC rows. */
+int bioem_hip_debug_convolve_batch(bioem_hip_handle h, const float *specP, int nO, int c0, int nC, float *conv_out,
+                                   bioem_hip_param5 *params_out, float *raw_out, int *info_out);
 /* download device-side particle precompute (reference layout) */
 int bioem_hip_debug_particles(bioem_hip_handle h, float *refFFT_out, float *sum_out, float *sumsq_out);
 /* accumulated HIP-event time of the comparison kernel on the engine's stream since the last reset:
