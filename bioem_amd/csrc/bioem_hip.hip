@@ -65,6 +65,9 @@
 //   recon_kernels.hpp    k_recon_matrices, k_recon_insert, k_recon_tau_part, k_recon_tau, k_recon_estimate, k_recon_axis0,
 //                          k_recon_correct  bioem_hip_reconstruct: the view sums gathered into a 3D Fourier volume, its
 //                          estimate and real-space volume (kernels_recon.hip; declarations only here)
+//   soft_kernels.hpp     k_soft_cols, k_soft_rows, k_soft_accumulate  bioem_hip_view_sums_soft / _reconstruct_soft: the view
+//                          sums under a table of weighted shifts per (particle, group, CTF set) (kernels_soft.hip;
+//                          declarations only here)
 //   orient_kernels.hpp   k_orient_max, k_orient_sums, k_orient_fold, k_orient_products  bioem_hip_orientation_sums: the
 //                          orientation posterior of every particle reduced where the angle table lives
 //                          (kernels_orient.hip; declarations only here); k_orient_occ  bioem_hip_orientation_occupancy:
@@ -140,6 +143,7 @@ struct HipErr
 #include "scan_kernels.hpp"
 #include "grad_kernels.hpp"
 #include "recon_kernels.hpp"
+#include "soft_kernels.hpp"
 #include "orient_kernels.hpp"
 
 struct bioem_hip_ctx
@@ -251,6 +255,14 @@ struct bioem_hip_ctx
   double *dReconDen = nullptr, *dReconR = nullptr, *dReconPart = nullptr, *dReconTau = nullptr, *dReconSinc = nullptr;
   int *dReconSlot = nullptr, *dReconOrient = nullptr;
   float4 *dReconAngles = nullptr;
+  // bioem_hip_view_sums_soft / _debug_view_sums_soft / _reconstruct_soft: the tables, U, W and members of a launch of at
+  // most maxOrientations members, the shifts mod N and the twiddles, exact at the multiples of a quarter turn (allocated at
+  // the first call, grown with the tables: softNd)
+  double *dSoftCells = nullptr;
+  double2 *dSoftU = nullptr, *dSoftW = nullptr, *dSoftTw = nullptr;
+  BioemSoftMember *dSoftMem = nullptr;
+  int *dSoftXm = nullptr;
+  int softNd = 0;
   // bioem_hip_window_posterior / bioem_hip_debug_window: a batch's records, gathered orientations, particle and conv
   // spectra in reference layout, Parseval terms, parameters, particle sums handed in, the scratch T of the window pass,
   // the window's shifts in ascending order and the results (allocated at the first call)
@@ -3635,6 +3647,329 @@ int bioem_hip_debug_reconstruct(bioem_hip_handle h, const double *num, const dou
   return recon_finish(h, wiener, flags, vol_out, spec_out, numV_out, denV_out, nullptr);
 }
 
+// ---- posterior-weighted view sums and their density (soft_kernels.hpp) ----
+static_assert(sizeof(bioem_hip_soft_member) == 40, "member layout");
+
+namespace
+{
+// the buffers of the soft entries for tables of nd x nd cells; a failed allocation (return 1) leaves the handle as it was
+int soft_staging(bioem_hip_ctx *h, int nd)
+{
+  if (h->dSoftW && nd <= h->softNd)
+    return 0;
+  const size_t OB = (size_t) h->OB, T = (size_t) nd * nd;
+  // tw[j] = exp(+2 pi i j / N) as dTwD holds it, but 0 and +-1 where 4 j is a multiple of N: the correctly rounded values
+  // there (cos(pi / 2) of the library is 6e-17), so a table of whole shifts of a quarter image multiplies exactly
+  const int N = h->N;
+  std::vector<double2> tw((size_t) N);
+  for (int j = 0; j < N; j++)
+  {
+    tw[(size_t) j] = twiddle_d(j, N);
+    if ((4 * j) % N == 0)
+    {
+      const int q = 4 * j / N; // quarter turns
+      tw[(size_t) j] = make_double2(q == 0 ? 1. : q == 2 ? -1. : 0., q == 1 ? 1. : q == 3 ? -1. : 0.);
+    }
+  }
+  Staging st = {h};
+  st.fill(st.get(h->dSoftTw, (size_t) N), tw.data(), sizeof(double2) * N);
+  st.get(h->dSoftCells, OB * T);
+  st.get(h->dSoftU, OB * (size_t) nd * h->H);
+  st.get(h->dSoftW, OB * (size_t) h->M);
+  st.get(h->dSoftMem, OB);
+  st.get(h->dSoftXm, (size_t) h->N);
+  if (st.commit())
+    return 1;
+  h->softNd = nd;
+  return 0;
+}
+
+// The arguments every soft entry checks.  order: the members with a group by ascending (particle, position in the list),
+// the order of a group's additions; xm: the shifts mod N.  Returns 0, or 2 with the handle's message set.
+int soft_members(bioem_hip_ctx *h, const char *what, const bioem_hip_soft_member *members, const double *cells, int n,
+                 const int *shifts, int nd, int nGroups, int g0, int g1, int nParticles, std::vector<int> &order,
+                 std::vector<int> &xm)
+{
+  char buf[320];
+  const Refuse refuse = {h, what};
+  const int N = h->N;
+  if (nd < 1 || nd > N)
+  {
+    snprintf(buf, sizeof(buf), "nd %d outside [1, N] (N %d)", nd, N);
+    return refuse(buf);
+  }
+  xm.resize((size_t) nd);
+  for (int i = 0; i < nd; i++)
+  {
+    if (shifts[i] <= -N || shifts[i] >= N)
+    {
+      snprintf(buf, sizeof(buf), "shift %d: %d outside (-N, N) (N %d)", i, shifts[i], N);
+      return refuse(buf);
+    }
+    xm[(size_t) i] = (shifts[i] % N + N) % N;
+  }
+  if (nGroups < 1 || g0 < 0 || g1 > nGroups || g0 >= g1)
+    return refuse("group range empty, reversed or outside [0, nGroups)");
+  if (const char *why = missing_state(h, NEED_CTF, 0))
+    return refuse(why);
+  const size_t T = (size_t) nd * nd;
+  order.clear();
+  for (int r = 0; r < n; r++)
+  {
+    const bioem_hip_soft_member &m = members[r];
+    if (m.group == -1)
+      continue;
+    const char *why = nullptr;
+    if (m.group < -1 || m.group >= nGroups)
+      why = "group outside [0, nGroups) and not -1";
+    else if (m.particle < 0 || m.particle >= nParticles)
+      why = "particle out of range";
+    else if (m.conv < 0 || m.conv >= h->nCTF)
+      why = "conv outside [0, nCTF)";
+    else if (!std::isfinite(m.s2) || !std::isfinite(m.b) || !std::isfinite(m.mass))
+      why = "s2, b or mass not finite";
+    else if (m.s2 < 0. || m.mass < 0.)
+      why = "s2 or mass negative";
+    else
+      for (size_t c = 0; c < T && !why; c++)
+        if (!std::isfinite(cells[(size_t) r * T + c]))
+          why = "a cell of the table not finite";
+    if (why)
+    {
+      snprintf(buf, sizeof(buf), "member %d: %s (particle %d of %d, group %d of %d, conv %d of %d, s2 %g, b %g, mass %g)", r, why,
+               m.particle, nParticles, m.group, nGroups, m.conv, h->nCTF, m.s2, m.b, m.mass);
+      return refuse(buf);
+    }
+    order.push_back(r);
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return members[a].particle < members[b].particle; });
+  return 0;
+}
+
+// num / den of the groups [ga, gb) (at most maxOrientations of them) into dViewNum / dViewDen, as view_accumulate_chunk:
+// zeroed, then per batch of maxOrientations particles the members of `order` whose groupOf[] lies in the range, at most
+// maxOrientations of them per launch of the three kernels, on the handle's stream.  specHost: the spectra of the caller.
+int soft_accumulate_chunk(bioem_hip_ctx *h, const float *specHost, const bioem_hip_soft_member *members, const int *groupOf,
+                          const double *cells, const std::vector<int> &order, int nd, int nP, int ga, int gb)
+{
+  const int nG = gb - ga, OB = h->OB, N = h->N;
+  const size_t M = (size_t) h->M, T = (size_t) nd * nd;
+  const double NN = (double) N * (double) N;
+  HIP_CHECK(h, hipMemsetAsync(h->dViewNum, 0, sizeof(double2) * M * nG, h->stream));
+  HIP_CHECK(h, hipMemsetAsync(h->dViewDen, 0, sizeof(double) * M * nG, h->stream));
+  std::vector<int> off((size_t) nG + 1), cur((size_t) nG), sel;
+  std::vector<BioemSoftMember> bm;
+  std::vector<double> bc;
+  size_t at = 0;
+  for (int b0 = 0; b0 < nP; b0 += OB)
+  {
+    const int nb = std::min(OB, nP - b0);
+    sel.clear();
+    for (; at < order.size() && members[order[at]].particle < b0 + nb; at++)
+      if (groupOf[order[at]] >= ga && groupOf[order[at]] < gb)
+        sel.push_back(order[at]);
+    if (sel.empty())
+      continue;
+    if (specHost)
+      HIP_CHECK(h, hipMemcpyAsync(h->dRingRef, specHost + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice,
+                                  h->stream));
+    else
+    {
+      hipLaunchKernelGGL(k_unreorder, dim3(1024), dim3(256), 0, h->stream, h->dRef + h->Mc * (size_t) b0, h->dRingRef, nb, N,
+                         h->H, h->plan.halfR, h->plan.N1, h->Hp);
+      HIP_CHECK(h, hipGetLastError());
+    }
+    for (size_t s0 = 0; s0 < sel.size(); s0 += (size_t) OB)
+    {
+      const int ns = (int) std::min((size_t) OB, sel.size() - s0);
+      std::fill(off.begin(), off.end(), 0);
+      for (int i = 0; i < ns; i++)
+        off[(size_t) (groupOf[sel[s0 + i]] - ga) + 1]++;
+      for (int g = 0; g < nG; g++)
+      {
+        cur[(size_t) g] = off[(size_t) g];
+        off[(size_t) g + 1] += off[(size_t) g];
+      }
+      bm.resize((size_t) ns);
+      bc.resize((size_t) ns * T);
+      for (int i = 0; i < ns; i++) // ascending within every group
+      {
+        const int r = sel[s0 + i];
+        const bioem_hip_soft_member &m = members[r];
+        bm[(size_t) cur[(size_t) (groupOf[r] - ga)]++] = {m.particle - b0, m.conv, i, 0, m.s2, m.b * NN};
+        memcpy(bc.data() + (size_t) i * T, cells + (size_t) r * T, sizeof(double) * T);
+      }
+      HIP_CHECK(h, hipMemcpyAsync(h->dSoftMem, bm.data(), sizeof(BioemSoftMember) * bm.size(), hipMemcpyHostToDevice, h->stream));
+      HIP_CHECK(h, hipMemcpyAsync(h->dViewOff, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, h->stream));
+      HIP_CHECK(h, hipMemcpyAsync(h->dSoftCells, bc.data(), sizeof(double) * bc.size(), hipMemcpyHostToDevice, h->stream));
+      // phase 0: the column pass, 1: the row pass, 2: the accumulation; iConvEnd = nd tells them from the chain's records
+      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_PROJECTION, b0, b0 + nb, 0, nd))
+        return 1;
+      HIP_CHECK(h, bioem_soft_cols_launch(h->stream, h->dSoftCells, h->dSoftXm, ns, nd, N, h->dSoftTw, h->dSoftU));
+      if (phase_end(h, h->stream) || phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, b0, b0 + nb, 0, nd))
+        return 1;
+      HIP_CHECK(h, bioem_soft_rows_launch(h->stream, h->dSoftU, h->dSoftXm, ns, nd, N, h->dSoftTw, h->dSoftW));
+      if (phase_end(h, h->stream) || phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, b0, b0 + nb, 0, nd))
+        return 1;
+      HIP_CHECK(h, bioem_soft_accumulate_launch(h->stream, h->dRingRef, h->dCTF, h->dSoftMem, h->dViewOff, nG, N, h->dSoftW,
+                                                h->dViewNum, h->dViewDen));
+      if (phase_end(h, h->stream))
+        return 1;
+      HIP_CHECK(h, hipStreamSynchronize(h->stream)); // bm, off and bc are rewritten for the next launch
+    }
+  }
+  return 0;
+}
+
+// staging of every soft entry and the shifts of the call on the device
+int soft_begin(bioem_hip_ctx *h, const std::vector<int> &xm, bool recon)
+{
+  if (ring_staging(h) || view_staging(h, false) || soft_staging(h, (int) xm.size()) || (recon && recon_staging(h)) ||
+      begin_analysis(h, false)) // (buffer set 0 is not written)
+    return 1;
+  HIP_CHECK(h, hipMemcpyAsync(h->dSoftXm, xm.data(), sizeof(int) * xm.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// the sums of the groups [g0, g1) to the host, chunk by chunk; stats on the host in the order of the additions
+int soft_sums_run(bioem_hip_ctx *h, const float *specHost, const bioem_hip_soft_member *members, const double *cells, int n,
+                  const std::vector<int> &order, const std::vector<int> &xm, int nP, int g0, int g1, double *num_out,
+                  double *den_out, double *stats_out)
+{
+  if (soft_begin(h, xm, false))
+    return 1;
+  const size_t M = (size_t) h->M;
+  std::vector<int> groupOf((size_t) n);
+  for (int r = 0; r < n; r++)
+    groupOf[(size_t) r] = members[r].group;
+  for (int ga = g0; ga < g1; ga += h->OB)
+  {
+    const int gb = std::min(g1, ga + h->OB);
+    if (soft_accumulate_chunk(h, specHost, members, groupOf.data(), cells, order, (int) xm.size(), nP, ga, gb))
+      return 1;
+    HIP_CHECK(h, hipMemcpyAsync(num_out + 2 * M * (size_t) (ga - g0), h->dViewNum, sizeof(double2) * M * (gb - ga),
+                                hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(den_out + M * (size_t) (ga - g0), h->dViewDen, sizeof(double) * M * (gb - ga),
+                                hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  drain_phases(h);
+  for (int g = g0; g < g1; g++)
+    stats_out[2 * (size_t) (g - g0)] = stats_out[2 * (size_t) (g - g0) + 1] = 0.;
+  for (int r : order)
+    if (members[r].group >= g0 && members[r].group < g1)
+    {
+      stats_out[2 * (size_t) (members[r].group - g0)] += 1.;
+      stats_out[2 * (size_t) (members[r].group - g0) + 1] += members[r].mass;
+    }
+  return 0;
+}
+} // namespace
+
+int bioem_hip_view_sums_soft(bioem_hip_handle h, const bioem_hip_soft_member *members, const double *cells, int n,
+                             const int *shifts, int nd, int nGroups, int g0, int g1, double *num_out, double *den_out,
+                             double *stats_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "view_sums_soft"};
+  if (!members || !cells || !shifts || !num_out || !den_out || !stats_out || n < 1)
+    return refuse("null argument or no members");
+  std::vector<int> order, xm;
+  if (const int rc = soft_members(h, "view_sums_soft", members, cells, n, shifts, nd, nGroups, g0, g1, h->nMaps, order, xm))
+    return rc;
+  if (const char *why = missing_state(h, NEED_PARTICLES, 0))
+    return refuse(why);
+  return soft_sums_run(h, nullptr, members, cells, n, order, xm, h->nMaps, g0, g1, num_out, den_out, stats_out);
+}
+
+int bioem_hip_debug_view_sums_soft(bioem_hip_handle h, const float *specR, int nSpec, const bioem_hip_soft_member *members,
+                                   const double *cells, int n, const int *shifts, int nd, int nGroups, double *num_out,
+                                   double *den_out, double *stats_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (!specR || !members || !cells || !shifts || !num_out || !den_out || !stats_out || n < 1 || nSpec < 1)
+    return Refuse{h, "debug_view_sums_soft"}("null argument, no members or no images");
+  std::vector<int> order, xm;
+  if (const int rc = soft_members(h, "debug_view_sums_soft", members, cells, n, shifts, nd, nGroups, 0, nGroups, nSpec, order, xm))
+    return rc;
+  return soft_sums_run(h, specR, members, cells, n, order, xm, nSpec, 0, nGroups, num_out, den_out, stats_out);
+}
+
+int bioem_hip_reconstruct_soft(bioem_hip_handle h, const bioem_hip_soft_member *members, const double *cells, int n,
+                               const int *shifts, int nd, const int *groupOrient, int nGroups, double wiener, int flags,
+                               float *vol_out, double *spec_out, double *den_out, double *stats_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  char buf[160];
+  const Refuse refuse = {h, "reconstruct_soft"};
+  if (!members || !cells || !shifts || !groupOrient || n < 1)
+    return refuse("null argument or no members");
+  if (!vol_out && !spec_out && !den_out && !stats_out)
+    return refuse("every output is null");
+  if (!recon_flags_known(flags))
+    return refuse("unknown flag bits");
+  if (!(wiener >= 0.) || !std::isfinite(wiener))
+    return refuse("wiener negative or not finite");
+  std::vector<int> order, xm;
+  if (const int rc = soft_members(h, "reconstruct_soft", members, cells, n, shifts, nd, nGroups, 0, nGroups, h->nMaps, order, xm))
+    return rc;
+  if (const char *why = missing_state(h, NEED_ORIENT | NEED_PARTICLES, 0))
+    return refuse(why);
+  for (int g = 0; g < nGroups; g++)
+    if (groupOrient[g] < -1 || groupOrient[g] >= h->nAnglesUp)
+    {
+      snprintf(buf, sizeof(buf), "group %d: orientation %d outside the list of %d and not -1", g, groupOrient[g], h->nAnglesUp);
+      return refuse(buf);
+    }
+  if (soft_begin(h, xm, true))
+    return 1;
+  // the views of the call as in bioem_hip_reconstruct: the groups with an orientation and a member, numbered densely;
+  // viewOf[r]: the view of member r, or -1
+  std::vector<int> count((size_t) nGroups, 0), view((size_t) nGroups, -1), orient, viewOf((size_t) n, -1);
+  double stats[4] = {0., 0., 0., 0.};
+  for (int r : order)
+    count[(size_t) members[r].group]++;
+  for (int g = 0; g < nGroups; g++)
+    if (groupOrient[g] >= 0 && count[(size_t) g] > 0)
+    {
+      view[(size_t) g] = (int) orient.size();
+      orient.push_back(groupOrient[g]);
+    }
+  for (int r : order)
+    if (view[(size_t) members[r].group] >= 0)
+    {
+      viewOf[(size_t) r] = view[(size_t) members[r].group];
+      stats[1] += 1.;
+      stats[2] += members[r].mass;
+    }
+  const int nViews = (int) orient.size();
+  stats[0] = (double) nViews;
+  if (recon_begin(h))
+    return 1;
+  std::vector<int> slots((size_t) h->OB);
+  for (int i = 0; i < h->OB; i++)
+    slots[(size_t) i] = i;
+  for (int va = 0; va < nViews; va += h->OB)
+  {
+    const int vb = std::min(nViews, va + h->OB);
+    if (soft_accumulate_chunk(h, nullptr, members, viewOf.data(), cells, order, nd, h->nMaps, va, vb) ||
+        recon_insert_chunk(h, shared_list(h), slots.data(), orient.data() + va, vb - va, flags, va))
+      return 1;
+  }
+  if (recon_finish(h, wiener, flags, vol_out, spec_out, nullptr, den_out, &stats[3]))
+    return 1;
+  if (stats_out)
+    memcpy(stats_out, stats, sizeof(stats));
+  return 0;
+}
+
 // ---- log posterior of every cell of the displacement window of a request (window_kernels.hpp) ----
 static_assert(sizeof(BioemWindowRecord) == sizeof(RenderRecord) && sizeof(bioem_hip_window_request) == 12,
               "record / request layout");
@@ -4726,7 +5061,7 @@ int bioem_hip_debug_particles(bioem_hip_handle h, float *refFFT_out, float *sum_
   const size_t M = (size_t) h->M;
   bioem_hip_ctx::Slot &s0 = h->slot[0];
   void_slot(s0);
-  for (int b = 0; b < h->nMaps; b += h->chunkB)
+  for (int b = 0; refFFT_out && b < h->nMaps; b += h->chunkB)
   {
     const int n = std::min(h->chunkB, h->nMaps - b);
     hipLaunchKernelGGL(k_unreorder, dim3(1024), dim3(256), 0, h->stream, h->dRef + h->Mc * (size_t) b, s0.specRef, n, h->N,

@@ -24,6 +24,8 @@ ORIENT_OCC_DTYPE = np.dtype([("occ", "<f8"), ("occ2", "<f8"), ("wmax", "<f8"), (
 WINDOW_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4")])
 SCAN_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("shiftX", "<i4"), ("shiftY", "<i4")])
 GRAD_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4"), ("shiftX", "<i4"), ("shiftY", "<i4")])
+SOFT_MEMBER_DTYPE = np.dtype([("particle", "<i4"), ("group", "<i4"), ("conv", "<i4"), ("pad", "<i4"), ("s2", "<f8"),
+                              ("b", "<f8"), ("mass", "<f8")])
 GRAD_POINT_DTYPE = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("sumw", "<f8"), ("count", "<i8")])
 MIN_PROB = -999999.0
 RECON_CORRECT, RECON_NO_CULL = 1, 2   # BIOEM_HIP_RECON_* of include/bioem_hip.h
@@ -120,6 +122,10 @@ def load_library():
     if hasattr(L, "bioem_hip_reconstruct"):
         L.bioem_hip_reconstruct.argtypes = [vp, vp, vp, vp, vp, ci, C.c_double, ci, vp, vp, vp, vp]
         L.bioem_hip_debug_reconstruct.argtypes = [vp, vp, vp, vp, ci, ci, C.c_double, ci, vp, vp, vp, vp]
+    if hasattr(L, "bioem_hip_view_sums_soft"):
+        L.bioem_hip_view_sums_soft.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp]
+        L.bioem_hip_debug_view_sums_soft.argtypes = [vp, vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp]
+        L.bioem_hip_reconstruct_soft.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, C.c_double, ci, vp, vp, vp, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -185,6 +191,7 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_debug_orient_sums_own", "bioem_hip_orientation_occupancy", "bioem_hip_debug_orient_occupancy",
            "bioem_hip_view_sums", "bioem_hip_view_averages", "bioem_hip_debug_view_sums",
            "bioem_hip_reconstruct", "bioem_hip_debug_reconstruct",
+           "bioem_hip_view_sums_soft", "bioem_hip_debug_view_sums_soft", "bioem_hip_reconstruct_soft",
            "bioem_hip_set_compare_variant", "bioem_hip_debug_projection_maps", "bioem_hip_debug_stamps",
            "bioem_hip_debug_convolve_batch"]
 
@@ -619,6 +626,102 @@ class Engine:
                                                      int(flags), _p(out.get("vol")), _p(out.get("spec")), _p(out.get("numV")),
                                                      _p(out.get("denV"))), "debug_reconstruct")
         return out
+
+    def _soft_args(self, members, cells, shifts):
+        members = np.ascontiguousarray(members, dtype=SOFT_MEMBER_DTYPE).reshape(-1)
+        shifts = np.ascontiguousarray(self.window_shifts() if shifts is None else shifts, dtype=np.int32).reshape(-1)
+        cells = np.ascontiguousarray(cells, dtype=np.float64)
+        assert cells.shape == (len(members), len(shifts), len(shifts)), cells.shape
+        return members, cells, shifts
+
+    @staticmethod
+    def _soft_groups(members, n_groups):
+        return (int(members["group"].max()) + 1 if len(members) else 0) if n_groups is None else int(n_groups)
+
+    def view_sums_soft(self, members, cells, shifts=None, g0=0, g1=None, n_groups=None):
+        """the normal equations of view_sums under tables of weighted shifts (include/bioem_hip.h): members
+        SOFT_MEMBER_DTYPE [n] = one (particle, group, conv) each with its s2, b, mass (group -1 = left out), cells float64
+        [n, nd, nd] with cell [i, j] = a at the shift (shifts[i], shifts[j]); shifts: int [nd], window_shifts() unless
+        given; n_groups: max group + 1 unless given.  Returns (num, den, stats) for the groups [g0, g1) as view_sums does,
+        stats = number of members, sum of mass.  bioem_amd/soft_views.py builds members from a posterior.  A refusal
+        raises RuntimeError with .rc == 2."""
+        members, cells, shifts = self._soft_args(members, cells, shifts)
+        nG = self._soft_groups(members, n_groups)
+        g1 = nG if g1 is None else int(g1)
+        n = max(0, g1 - int(g0))
+        num = np.zeros((n, self.N, self.H), dtype=np.complex128)
+        den = np.zeros((n, self.N, self.H), dtype=np.float64)
+        stats = np.zeros((n, 2), dtype=np.float64)
+        self._chk(self.L.bioem_hip_view_sums_soft(self.h, _p(members), _p(cells), len(members), _p(shifts), len(shifts), nG,
+                                                  int(g0), g1, _p(num), _p(den), _p(stats)), "view_sums_soft")
+        return num, den, stats
+
+    def debug_view_sums_soft(self, specR, members, cells, shifts=None, n_groups=None):
+        """test hook: the kernels of view_sums_soft on spectra handed in, float32 [nSpec, N, H, 2] or complex64 [nSpec, N, H]
+        in reference layout; `particle` of a member indexes them.  Needs the CTF kernels only.  Returns (num, den, stats)
+        for all groups."""
+        specR = _spectra(specR)
+        assert specR.shape[1:] == (self.N, self.H, 2)
+        members, cells, shifts = self._soft_args(members, cells, shifts)
+        nG = self._soft_groups(members, n_groups)
+        num = np.zeros((max(nG, 0), self.N, self.H), dtype=np.complex128)
+        den = np.zeros((max(nG, 0), self.N, self.H), dtype=np.float64)
+        stats = np.zeros((max(nG, 0), 2), dtype=np.float64)
+        self._chk(self.L.bioem_hip_debug_view_sums_soft(self.h, _p(specR), len(specR), _p(members), _p(cells), len(members),
+                                                        _p(shifts), len(shifts), nG, _p(num), _p(den), _p(stats)),
+                  "debug_view_sums_soft")
+        return num, den, stats
+
+    def reconstruct_soft(self, members, cells, group_orient, shifts=None, wiener=0.1, correct=True, want_spec=False,
+                         want_vol=True, cull=True):
+        """reconstruct with the accumulation of view_sums_soft in place of the hard one: members, cells and shifts as
+        there, group_orient int [nGroups] into the shared orientation list (-1 = skipped).  Returns the dict of
+        reconstruct; "stats" = views used, members used, the sum of their mass, tau."""
+        members, cells, shifts = self._soft_args(members, cells, shifts)
+        group_orient = np.ascontiguousarray(group_orient, dtype=np.int32)
+        shape = (self.N, self.N, self.H)
+        out = {"stats": np.zeros(4, dtype=np.float64)}
+        if want_vol:
+            out["vol"] = np.zeros((self.N,) * 3, dtype=np.float32)
+        if want_spec:
+            out["spec"] = np.zeros(shape, dtype=np.complex128)
+            out["den"] = np.zeros(shape, dtype=np.float64)
+        flags = (RECON_CORRECT if correct else 0) | (0 if cull else RECON_NO_CULL)
+        self._chk(self.L.bioem_hip_reconstruct_soft(self.h, _p(members), _p(cells), len(members), _p(shifts), len(shifts),
+                                                    _p(group_orient), len(group_orient), float(wiener), flags,
+                                                    _p(out.get("vol")), _p(out.get("spec")), _p(out.get("den")),
+                                                    _p(out["stats"])), "reconstruct_soft")
+        return out
+
+    def soft_members(self, pmap, K=1, topk=None, sum_ref=None, own=False, weights=None, log_prior=None, batch=4096,
+                     want_weights=False):
+        """the members of view_sums_soft / reconstruct_soft from the posterior of a finished run (bioem_amd/soft_views.py):
+        K = 1: every CTF set and every window cell at the arg-max orientation of each particle of pmap (PROB_MAP_DTYPE
+        [nMaps]); K >= 2: at the first K orientations of topk (CANDIDATE_DTYPE [nMaps, >= K], topk_angles or a merged
+        ranking).  group = orientation.  window_posterior runs over the requests `batch` at a time.  sum_ref: the
+        particles' sums float32 [nMaps] (debug_particles unless given); weights: float64 [nMaps] or None; log_prior:
+        float64 [nAngles] or None.  Returns (members, cells, requests), with want_weights the posterior weights float64
+        [n, nd, nd] as well."""
+        from . import soft_views
+        pmap = _pmap(pmap, self.nMaps)
+        if int(K) <= 1:
+            req, group = soft_views.requests_best(pmap, self.nCTF)
+        else:
+            if topk is None:
+                raise ValueError("soft_members: K >= 2 needs the candidates of topk_angles")
+            req, group = soft_views.requests_topk(topk, int(K), self.nCTF)
+        nd = len(self.window_shifts())
+        logp = np.zeros((len(req), nd, nd), dtype=np.float64)
+        cc = np.zeros((len(req), nd, nd), dtype=np.float32)
+        par = np.zeros(len(req), dtype=PARAM5_DTYPE)
+        for i0 in range(0, len(req), int(batch)):
+            i1 = min(len(req), i0 + int(batch))
+            logp[i0:i1], cc[i0:i1], par[i0:i1] = self.window_posterior(req[i0:i1], own=own, want_cc=True, want_params=True)
+        if sum_ref is None:
+            sum_ref = self.debug_particles()[1]
+        out = soft_views.members(req, group, logp, cc, par, sum_ref, self.N, weights=weights, log_prior=log_prior,
+                                 want_weights=want_weights)
+        return out[:2] + (req,) + out[2:]
 
     def window_shifts(self):
         """the cell coordinates of this handle's window tables (window_offsets of its parameters)"""

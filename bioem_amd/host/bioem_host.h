@@ -277,6 +277,15 @@ std::string write_reconstruction(const char *file, const std::vector<double> &we
                                  const std::vector<double> &powA, const std::vector<double> &powB, int N, float pixelSize,
                                  double wiener, long long views, long long particles, double tau);
 std::string write_mrc_volume(const char *file, const float *vol, int N, float pixelSize);
+// --ReconstructSoft: appends to the text file of write_reconstruction per particle p one line
+//  SOFT p requests n_eff mass_argmax
+// (requests: its (orientation, CTF set) pairs; n_eff = 1 / sum w^2 over (orientation, CTF set, cell), 0 without a weight;
+// mass_argmax: the largest w) and per shell of the two soft half maps one line
+//  SOFTSHELL s resolution weight FSC cross powHalf1 powHalf2
+// in the columns of the SHELL lines (bioem_amd/soft_views.py parses both).  Returns the empty string, or the error.
+std::string append_reconstruction_soft(const char *file, const int *requests, const double *nEff, const double *massArgmax,
+                                       int nMaps, const std::vector<double> &weight, const std::vector<double> &cross,
+                                       const std::vector<double> &powA, const std::vector<double> &powB, int N, float pixelSize);
 // MRC mode-2 stack nx = ny = N, nz = nMaps in the storage order the --ReadMRC reader expects, written batch by batch
 struct MrcStackWriter
 {
@@ -353,6 +362,9 @@ public:
   // conventional default, not a tuned one
   std::string reconFile;
   double reconWiener = 0.1;
+  // --ReconstructSoft K with --Reconstruct: the density under the posterior over (K best orientations, CTF set, window
+  // cell) of every particle (FILE_soft.mrc, FILE_soft_half1.mrc, FILE_soft_half2.mrc, SOFT / SOFTSHELL lines in FILE); 0: off
+  int reconSoftK = 0;
   std::string bestParamFile; // --PrintBestCalMap: the reference's one-record mode, no particles, writes BESTMAP
   BestParams best;
   int printBestCalMap();     // bioem::printModel (bioem.cpp:624-657, 1925-2085)
@@ -394,6 +406,10 @@ private:
   // --Reconstruct: the records grouped by orientation (at least one member), the chain on handle h (bioem_hip_reconstruct)
   // for all particles and for the even and the odd ones, written by write_mrc_volume and write_reconstruction
   void writeReconstruction(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap);
+  // --ReconstructSoft: the members of the posterior over the window tables from handle h (bioem_hip_window_posterior), the
+  // chain on it (bioem_hip_reconstruct_soft) for all particles and the two halves, written by write_mrc_volume and
+  // append_reconstruction_soft
+  void writeReconstructionSoft(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap);
   // --BestWindow: the window tables of the records' (orientation, CTF) pairs from handle h (bioem_hip_window_posterior),
   // written by write_best_window; voluPerMap as for writeProbabilities
   void writeBestWindow(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,

@@ -134,6 +134,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"ViewWiener", required_argument, 0, 0},
                                        {"Reconstruct", required_argument, 0, 0},
                                        {"ReconstructWiener", required_argument, 0, 0},
+                                       {"ReconstructSoft", required_argument, 0, 0},
                                        {"ReadOrientation", required_argument, 0, 0},
                                        {"RefineOrientations", required_argument, 0, 0},
                                        {"RefineSeeds", required_argument, 0, 0},
@@ -192,6 +193,11 @@ int Driver::readOptions(int ac, char **av)
     printf("                         with --ReadModelMRC the volume lies where it was reconstructed (odd NUMBER_PIXELS: half a\n");
     printf("                         pixel beyond it on every axis)\n");
     printf("  --ReconstructWiener arg (Optional) With --Reconstruct: the Wiener constant as a fraction of the mean weight (default 0.1)\n");
+    printf("  --ReconstructSoft arg  (Optional) With --Reconstruct: the same density under the posterior instead of its arg-max:\n");
+    printf("                         every particle enters with every CTF set and every cell of the displacement window at its\n");
+    printf("                         arg best orientations (1: the best one; 2 or more: of the ANG_PROB ranking, needs\n");
+    printf("                         WRITE_PROB_ANGLES >= arg), weighted by the posterior: arg_soft.mrc, arg_soft_half1.mrc,\n");
+    printf("                         arg_soft_half2.mrc of --Reconstruct and SOFT / SOFTSHELL lines in its text file\n");
     printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
@@ -365,6 +371,12 @@ int Driver::readOptions(int ac, char **av)
       if (!(reconWiener >= 0.) || !std::isfinite(reconWiener))
         fatal("--ReconstructWiener needs a non-negative number");
     }
+    else if (name == "ReconstructSoft")
+    {
+      reconSoftK = atoi(optarg);
+      if (reconSoftK < 1)
+        fatal("--ReconstructSoft needs a positive number of orientations");
+    }
     else if (name == "PrintBestCalMap")
     {
       std::cout << "Reading best parameters from file: " << optarg << "\n";
@@ -463,8 +475,13 @@ int Driver::readOptions(int ac, char **av)
     fatal("--ViewAverages is not valid with --RefineOrientations (own lists share no orientation index)");
   if (reconOptions && reconFile.empty())
     fatal("--ReconstructWiener goes with --Reconstruct");
+  if (reconSoftK && reconFile.empty())
+    fatal("--ReconstructSoft goes with --Reconstruct");
   if (!reconFile.empty() && !refineFile.empty()) // the views are orientations of the shared list
     fatal("--Reconstruct is not valid with --RefineOrientations (own lists share no orientation index)");
+  if (reconSoftK >= 2 && param.pd.writeAngles < reconSoftK) // the orientations beyond the best come from the ANG_PROB ranking
+    fatal("--ReconstructSoft %d needs WRITE_PROB_ANGLES %d or more in the parameter file: the orientations are the first of "
+          "the ANG_PROB ranking", reconSoftK, reconSoftK);
   if (fitOrientPrior && orientOccFile.empty())
     fatal("--FitOrientPrior is only valid with --OrientOccupancy");
   if (!orientOccFile.empty())
@@ -781,6 +798,136 @@ void Driver::writeReconstruction(const std::string &file, bioem_hip_handle h, co
     fatal("--Reconstruct: %s", err.c_str());
   std::cout << "Reconstruction from " << (long long) stats[1] << " particles in " << (long long) stats[0]
             << " views written to: " << file << ", " << names[0] << ", " << names[1] << ", " << names[2] << "\n";
+}
+
+// --ReconstructSoft K: per particle with a record the requests (its K best orientations) x (every CTF set), their window
+// tables from handle h batch by batch (bioem_hip_window_posterior), the weight, norm and mu of every cell as
+// bioem_amd/soft_views.py states them, the members and tables of bioem_hip_reconstruct_soft, the chain three times -- all
+// particles, the even and the odd ones -- then the volumes FILE_soft*.mrc and the lines append_reconstruction_soft adds
+void Driver::writeReconstructionSoft(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap)
+{
+  const int nMaps = particles.ntot, N = param.N, H = N / 2 + 1, nC = param.nTotCTFs, K = reconSoftK;
+  const int Kang = param.pd.writeAngles, nA = param.nTotGridAngles;
+  const size_t N3 = (size_t) N * N * N, V = (size_t) N * N * H;
+  const int nd = bioem_hip_window_count(N, param.pd.maxDisplaceCenter, param.pd.GridSpaceCenter, algo);
+  if (nd < 1)
+    fatal("--ReconstructSoft: no displacement window for these parameters");
+  std::vector<int> shifts((size_t) nd);
+  bioem_hip_window_offsets(N, param.pd.maxDisplaceCenter, param.pd.GridSpaceCenter, algo, shifts.data(), nd);
+  const size_t T = (size_t) nd * nd;
+  std::vector<bioem_hip_window_request> req;
+  for_each_match(pmap, nMaps, "RefMap %d has no member in the soft reconstruction: no run compared it",
+                 [&](int p, const bioem_hip_prob_map &r) {
+                   for (int k = 0; k < K; k++)
+                   {
+                     const int o = K == 1 ? r.max_prob_orient : cand[(size_t) p * Kang + k].orient;
+                     for (int c = 0; c < nC && o >= 0 && o < nA; c++)
+                       req.push_back({p, o, c});
+                   }
+                 });
+  if (req.empty())
+    fatal("--ReconstructSoft: no particle has a record to reconstruct from");
+  const size_t n = req.size();
+  std::vector<float> sumRef((size_t) nMaps), sumsqRef((size_t) nMaps);
+  check(h, bioem_hip_debug_particles(h, nullptr, sumRef.data(), sumsqRef.data()), "particle sums");
+  // t = logp + log prior, norm and mu of every cell; a cell where one of them is not finite has t = -inf
+  std::vector<double> t(n * T), norm(n * T), mu(n * T);
+  {
+    const int batch = batch_size(h);
+    std::vector<float> cc((size_t) batch * T);
+    std::vector<bioem_hip_param5> par((size_t) batch);
+    const double Ntotpi = (double) param.pd.Ntotpi;
+    for (size_t i0 = 0; i0 < n; i0 += (size_t) batch)
+    {
+      const int nb = (int) std::min((size_t) batch, n - i0);
+      check(h, bioem_hip_window_posterior(h, req.data() + i0, nb, 0, t.data() + i0 * T, cc.data(), par.data()), "window posterior");
+      for (int i = 0; i < nb; i++)
+      {
+        const bioem_hip_window_request &q = req[i0 + (size_t) i];
+        const double sumC = (double) par[(size_t) i].sumC, sumsqC = (double) par[(size_t) i].sumsquareC;
+        const double sumref = (double) sumRef[(size_t) q.particle], d = sumC * sumC - sumsqC * Ntotpi;
+        const double prior = param.yespriorAngles ? (double) param.angprior[(size_t) q.orient] : 0.;
+        for (size_t c = 0; c < T; c++)
+        {
+          const size_t e = (i0 + (size_t) i) * T + c;
+          const double value = (double) cc[(size_t) i * T + c];
+          norm[e] = -(-sumC * sumref + Ntotpi * value) / d;
+          mu[e] = -(-sumC * value + sumsqC * sumref) / d;
+          t[e] += prior;
+          if (!std::isfinite(t[e]) || !std::isfinite(norm[e]) || !std::isfinite(mu[e]))
+            t[e] = -INFINITY;
+        }
+      }
+    }
+  }
+  // per particle (its requests are consecutive): the weights over all cells of all its requests, the members, the summary
+  std::vector<bioem_hip_soft_member> members(n);
+  std::vector<double> cells(n * T, 0.), nEff((size_t) nMaps, 0.), wMax((size_t) nMaps, 0.);
+  std::vector<int> nReq((size_t) nMaps, 0);
+  for (size_t r0 = 0; r0 < n;)
+  {
+    size_t r1 = r0;
+    while (r1 < n && req[r1].particle == req[r0].particle)
+      r1++;
+    const int p = req[r0].particle;
+    double top = -INFINITY, Z = 0., s2w = 0.;
+    for (size_t e = r0 * T; e < r1 * T; e++)
+      top = std::max(top, t[e]);
+    for (size_t e = r0 * T; e < r1 * T && top > -INFINITY; e++)
+      Z += t[e] > -INFINITY ? std::exp(t[e] - top) : 0.;
+    for (size_t r = r0; r < r1; r++)
+    {
+      bioem_hip_soft_member m = {p, top > -INFINITY ? req[r].orient : -1, req[r].conv, 0, 0., 0., 0.};
+      for (size_t e = r * T; e < (r + 1) * T && top > -INFINITY; e++)
+      {
+        const double w = t[e] > -INFINITY ? std::exp(t[e] - top) / Z : 0.;
+        if (w > 0.)
+        {
+          cells[e] = w * norm[e];
+          m.s2 += w * norm[e] * norm[e];
+          m.b += w * norm[e] * mu[e];
+          m.mass += w;
+          s2w += w * w;
+          wMax[(size_t) p] = std::max(wMax[(size_t) p], w);
+        }
+      }
+      members[r] = m;
+    }
+    nReq[(size_t) p] = (int) (r1 - r0);
+    nEff[(size_t) p] = s2w > 0. ? 1. / s2w : 0.;
+    r0 = r1;
+  }
+  std::vector<int> groupOrient((size_t) nA);
+  for (int o = 0; o < nA; o++)
+    groupOrient[(size_t) o] = o;
+  std::vector<float> vol(N3);
+  std::vector<double> spec[2] = {std::vector<double>(2 * V), std::vector<double>(2 * V)};
+  std::vector<bioem_hip_soft_member> half;
+  double stats[4] = {0., 0., 0., 0.}, hs[4];
+  const std::string names[3] = {file + "_soft.mrc", file + "_soft_half1.mrc", file + "_soft_half2.mrc"};
+  for (int k = 0; k < 3; k++)
+  { // k = 0: every particle; 1, 2: the even and the odd ones (the others are left out)
+    half = members;
+    for (size_t r = 0; r < n && k; r++)
+      if (half[r].particle % 2 != k - 1)
+        half[r].group = -1;
+    check(h, bioem_hip_reconstruct_soft(h, half.data(), cells.data(), (int) n, shifts.data(), nd, groupOrient.data(), nA,
+                                        reconWiener, BIOEM_HIP_RECON_CORRECT, vol.data(), k ? spec[k - 1].data() : nullptr, nullptr,
+                                        k ? hs : stats),
+          "soft reconstruction");
+    const std::string err = write_mrc_volume(names[k].c_str(), vol.data(), N, param.pixelSize);
+    if (!err.empty())
+      fatal("--ReconstructSoft: %s", err.c_str());
+  }
+  std::vector<double> weight, cross, pa, pb;
+  recon_shell_sums(spec[0].data(), spec[1].data(), N, weight, cross, pa, pb);
+  const std::string err = append_reconstruction_soft(file.c_str(), nReq.data(), nEff.data(), wMax.data(), nMaps, weight, cross,
+                                                     pa, pb, N, param.pixelSize);
+  if (!err.empty())
+    fatal("--ReconstructSoft: %s", err.c_str());
+  std::cout << "Soft reconstruction (" << K << " orientation" << (K > 1 ? "s" : "") << " per particle) from " << (long long) stats[1]
+            << " members in " << (long long) stats[0] << " views written to: " << file << ", " << names[0] << ", " << names[1]
+            << ", " << names[2] << "\n";
 }
 
 // --BestWindow: the window table of every record's (orientation, CTF) pair from handle h, batch by batch, then the text
@@ -1220,6 +1367,8 @@ int Driver::run()
     writeViewAverages(viewAvgFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
   if (!reconFile.empty())
     writeReconstruction(reconFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
+  if (!reconFile.empty() && reconSoftK)
+    writeReconstructionSoft(reconFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
   if (!refineFile.empty())
   {
     if (refineSeeds >= 2)

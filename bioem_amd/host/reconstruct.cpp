@@ -1,6 +1,6 @@
 // reconstruct.cpp -- the host side of --Reconstruct: the Fourier shell correlation of the two half-set reconstructions the
-// device delivers (bioem_hip_reconstruct), the text file of the shells and the MRC volume a run reads back with
-// --ReadModelMRC.  No reference counterpart.  Nothing here needs a device; bioem_amd/reconstruct.py states the same in numpy.
+// device delivers (bioem_hip_reconstruct), the text file of the shells, the lines --ReconstructSoft adds to it and the MRC
+// volume a run reads back with --ReadModelMRC.  No reference counterpart.  Nothing here needs a device; bioem_amd/reconstruct.py states the same in numpy.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -75,6 +75,27 @@ std::string write_reconstruction(const char *file, const std::vector<double> &we
             cross[(size_t) s], powA[(size_t) s], powB[(size_t) s]);
   }
   fprintf(f, "DATASET %lld %lld %.15e %.15e %.15e\n", views, particles, tau, r05, r0143);
+  const bool bad = ferror(f) != 0;
+  return (fclose(f) != 0 || bad) ? std::string("Writing ") + file : std::string();
+}
+
+std::string append_reconstruction_soft(const char *file, const int *requests, const double *nEff, const double *massArgmax,
+                                       int nMaps, const std::vector<double> &weight, const std::vector<double> &cross,
+                                       const std::vector<double> &powA, const std::vector<double> &powB, int N, float pixelSize)
+{
+  const int nShells = (int) weight.size();
+  if (nShells < 1 || cross.size() != weight.size() || powA.size() != weight.size() || powB.size() != weight.size())
+    return "no shells to write";
+  FILE *f = fopen(file, "a");
+  if (!f)
+    return std::string("Opening ") + file;
+  for (int p = 0; p < nMaps; p++)
+    fprintf(f, "SOFT %d %d %.15e %.15e\n", p, requests[p], nEff[p], massArgmax[p]);
+  const double size = (double) N * (double) pixelSize;
+  for (int s = 0; s < nShells; s++)
+    fprintf(f, "SOFTSHELL %d %.15e %.15e %.15e %.15e %.15e %.15e\n", s, s ? size / s : 0., weight[(size_t) s],
+            shell_quotient(cross[(size_t) s], powA[(size_t) s], powB[(size_t) s]), cross[(size_t) s], powA[(size_t) s],
+            powB[(size_t) s]);
   const bool bad = ferror(f) != 0;
   return (fclose(f) != 0 || bad) ? std::string("Writing ") + file : std::string();
 }

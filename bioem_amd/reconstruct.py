@@ -135,6 +135,8 @@ def parse(path):
         if not ln.strip():
             continue
         t = ln.split()
+        if t[0].startswith("SOFT"):   # the lines --ReconstructSoft adds (bioem_amd/soft_views.py)
+            continue
         if t[0] == "SHELL" and len(t) == 8:
             shells.append((int(t[1]),) + tuple(float(x) for x in t[2:]))
         elif t[0] == "DATASET" and len(t) == 6:

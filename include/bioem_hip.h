@@ -341,7 +341,7 @@ int bioem_hip_debug_convolution(bioem_hip_handle h, int iOrient, int iConv, floa
  * path selected without a buffer for the ordered sums of nO nC rows. */
 int bioem_hip_debug_convolve_batch(bioem_hip_handle h, const float *specP, int nO, int c0, int nC, float *conv_out,
                                    bioem_hip_param5 *params_out, float *raw_out, int *info_out);
-/* download device-side particle precompute (reference layout) */
+/* download device-side particle precompute (reference layout); refFFT_out may be NULL: the sums alone */
 int bioem_hip_debug_particles(bioem_hip_handle h, float *refFFT_out, float *sum_out, float *sumsq_out);
 /* accumulated HIP-event time of the comparison kernel on the engine's stream since the last reset:
  * total ms, launches, comparisons processed */
@@ -687,6 +687,54 @@ int bioem_hip_reconstruct(bioem_hip_handle h, const bioem_hip_prob_map *records,
 int bioem_hip_debug_reconstruct(bioem_hip_handle h, const double *num, const double *den, const float *angles4, int isQuat,
                                 int nViews, double wiener, int flags, float *vol_out, double *spec_out, double *numV_out,
                                 double *denV_out);
+
+/* ---- Posterior-weighted view sums and their density (no reference counterpart) ----
+ * The sums above align a particle by one record at weight 1.  Here a *member* r is one (particle p, group g, CTF set c)
+ * and carries a table a_r[i][j] of doubles over the cells of a shift list X_0 ... X_{nd - 1} handed in -- cell [i][j] is
+ * the shift (X_i, X_j), cent_x first, as in bioem_hip_window_posterior -- and three scalars s2_r, b_r, mass_r.  With R_p,
+ * K~_c and tw as above, everything in double:
+ *   W_r[k1][k2] = sum_i sum_j a_r[i][j] tw[(k1 X_i + k2 X_j) mod N]
+ *   num_g[k]   += K~_c[k] (R_p[k] W_r[k] - [k = 0] b_r N^2)
+ *   den_g[k]   += s2_r |K~_c[k]|^2
+ *   stats_g     = { number of members, sum mass_r }
+ * the hard-assignment sum averaged over the cells, each cell with its own least-squares norm and mu under the weight w
+ * of the cell: a = w norm, s2 = sum_cells w norm^2, b = sum_cells w norm mu, mass = sum_cells w.  A member whose table
+ * has one non-zero cell a = w norm at (X, Y), with s2 = a norm and b = a mu, is a member of the hard sums; a may have
+ * either sign.  This is a profile-likelihood convention, not the exact M-step: the posterior the reference integrates
+ * marginalises norm and mu analytically, while each cell enters here with its arg-max norm and mu.
+ * Summation order: W is separable, U_r[i][k2] = sum_j a_r[i][j] tw[(k2 X_j) mod N] with j ascending, then W_r[k1][k2] =
+ * sum_i tw[(k1 X_i) mod N] U_r[i][k2] with i ascending; twiddle indices are reduced in integers, every product and sum
+ * rounds once.  The table tw of these entries holds 0 and +-1 exactly where 4 j is a multiple of N (the correctly rounded
+ * values), so tables over whole shifts of a quarter image multiply exactly.  A lane owns its (group, coefficient) and
+ * adds the group's members in ascending (particle, position in the member list); accumulators of a group that spans particle batches continue in device memory.  No atomics: the bits of a
+ * group depend on its own members alone -- not on the batch size, the batch boundaries, the other groups, the range
+ * [g0, g1) or the run.  Every handle kind gives the same bytes.
+ * Calling rules and outputs as for the hard sums.  Refused with 2, the member or group named and the handle usable: a
+ * null argument or n < 1, nd < 1 or nd > N, a shift of N pixels or more, an empty or reversed group range, a group outside
+ * [0, nGroups) that is not -1 (-1 leaves the member out; nothing else of it is read), particle or conv out of range, a
+ * non-finite cell, s2, b or mass, a negative s2 or mass, and CTF kernels or particles not uploaded.  Phase records per
+ * launch of at most maxOrientations members, all with iConvEnd = nd (which tells them from the chain's own records):
+ * phase 0 over the column pass, phase 1 over the row pass, phase 2 over the accumulation, iOrientBegin / iOrientEnd the
+ * particle batch. */
+typedef struct { int particle, group, conv, pad; double s2, b, mass; } bioem_hip_soft_member;   /* 40 bytes */
+/* members [n], cells [n][nd][nd], shifts [nd]; out for the groups [g0, g1) as the hard sums deliver them.  Needs the
+ * particles and the CTF kernels. */
+int bioem_hip_view_sums_soft(bioem_hip_handle h, const bioem_hip_soft_member *members, const double *cells, int n,
+                             const int *shifts, int nd, int nGroups, int g0, int g1, double *num_out, double *den_out,
+                             double *stats_out);
+/* test hook: the same kernels on nSpec spectra handed in (specR [nSpec][N][H] (re, im), reference layout) for all nGroups
+ * groups; `particle` indexes specR; needs the CTF kernels only */
+int bioem_hip_debug_view_sums_soft(bioem_hip_handle h, const float *specR, int nSpec, const bioem_hip_soft_member *members,
+                                   const double *cells, int n, const int *shifts, int nd, int nGroups, double *num_out,
+                                   double *den_out, double *stats_out);
+/* The chain of the hard reconstruction with this accumulation in place of the hard one: groups with groupOrient[g] = -1 or
+ * without members are skipped, the others numbered densely, accumulated chunk by chunk and inserted while on the device.
+ * stats_out {views used, members used, sum of their mass, tau}.  Outputs, flags and the further refusals (all outputs
+ * NULL, unknown flag bits, a negative or non-finite wiener, groupOrient outside the orientation list, orientations not
+ * uploaded) as there. */
+int bioem_hip_reconstruct_soft(bioem_hip_handle h, const bioem_hip_soft_member *members, const double *cells, int n,
+                               const int *shifts, int nd, const int *groupOrient, int nGroups, double wiener, int flags,
+                               float *vol_out, double *spec_out, double *den_out, double *stats_out);
 
 #ifdef __cplusplus
 }
