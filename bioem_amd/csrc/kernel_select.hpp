@@ -554,9 +554,17 @@ KernelPlan plan_kernels(int N, int maxD, int grid, int algo)
   {
     static const int tileRows[3] = {21, 27, 31};
     static const double tileCost[3] = {6.05, 6.5, 6.7};
+    // A tile breaks a tie between bit-equal maxima by its own ascending rows (its local list is sorted), and
+    // k_merge_tiles by the visiting rank.  ALGO 2 visits the rows in ascending order, so the two agree.  ALGO 1 visits
+    // 0 .. mD before -mD .. -1: a tile that holds the rows -1 and 0 prefers a negative row to row 0.  Wherever it takes
+    // no more tiles, the rows -mD .. -1 and 0 .. mD of an ALGO 1 window are therefore tiled apart, the last tile of
+    // either side masked by ndx / ndy (tests/test_compare_cells_gpu.py, the flat window).  Where it would take one tile
+    // more per axis (3^2 -> 4^2 launches and the like) the window keeps the plain tiling and that tie rule: DESIGN 2.23.
+    auto tiles_of = [&](int t) { return (P.nd + t - 1) / t; };
+    auto tiles_apart = [&](int t) { return (mD + t - 1) / t + (mD + t) / t; };
     int order[3] = {0, 1, 2};
     std::sort(order, order + 3, [&](int x, int y) {
-      const int nx = (P.nd + tileRows[x] - 1) / tileRows[x], ny = (P.nd + tileRows[y] - 1) / tileRows[y];
+      const int nx = tiles_of(tileRows[x]), ny = tiles_of(tileRows[y]);
       return nx * nx * tileCost[x] < ny * ny * tileCost[y];
     });
     for (int k : order)
@@ -566,12 +574,22 @@ KernelPlan plan_kernels(int N, int maxD, int grid, int algo)
       if (!plan_window_kernel(Q, N, H, (t - 1) / 2, false))
         continue;
       Q.tileT = t;
-      Q.tilesPerAxis = (P.nd + t - 1) / t;
-      for (int i = 0; i < Q.tilesPerAxis; i++)
+      Q.tilesPerAxis = tiles_of(t);
+      const bool apart = algo == 1 && tiles_apart(t) == Q.tilesPerAxis;
+      auto side = [&](int first, int rows) { // tiles over the window rows [first, first + rows)
+        for (int i = 0; i * t < rows; i++)
+        {
+          Q.tileCenter.push_back(first + i * t + Q.winD);  // centre row of the tile
+          Q.tileValid.push_back(std::min(t, rows - i * t)); // its rows inside [first, first + rows)
+        }
+      };
+      if (apart)
       {
-        Q.tileCenter.push_back(-mD + i * t + Q.winD);       // centre row of tile i
-        Q.tileValid.push_back(std::min(t, P.nd - i * t));   // rows of tile i inside the window
+        side(-mD, mD);
+        side(0, mD + 1);
       }
+      else
+        side(-mD, P.nd);
       return Q;
     }
   }
