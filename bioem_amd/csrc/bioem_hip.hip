@@ -65,6 +65,9 @@
 //   recon_kernels.hpp    k_recon_matrices, k_recon_insert, k_recon_tau_part, k_recon_tau, k_recon_estimate, k_recon_axis0,
 //                          k_recon_correct  bioem_hip_reconstruct: the view sums gathered into a 3D Fourier volume, its
 //                          estimate and real-space volume (kernels_recon.hip; declarations only here)
+//   slice_kernels.hpp    k_slice_axis, k_slice_centre, k_slice_project  a volume as the model: its padded, centred spectrum
+//                          and the central slices that stand in for projection + r2c (kernels_slice.hip; declarations
+//                          only here)
 //   soft_kernels.hpp     k_soft_cols, k_soft_rows, k_soft_accumulate  bioem_hip_view_sums_soft / _reconstruct_soft: the view
 //                          sums under a table of weighted shifts per (particle, group, CTF set) (kernels_soft.hip;
 //                          declarations only here)
@@ -143,6 +146,7 @@ struct HipErr
 #include "scan_kernels.hpp"
 #include "grad_kernels.hpp"
 #include "recon_kernels.hpp"
+#include "slice_kernels.hpp"
 #include "soft_kernels.hpp"
 #include "orient_kernels.hpp"
 
@@ -178,6 +182,14 @@ struct bioem_hip_ctx
   int nPts = 0;
   float NormDen = 0, pixelSize = 0;
   int shiftX = 0, shiftY = 0;
+  // a volume as the model (bioem_hip_upload_model_volume / _spectrum; slice_kernels.hpp): the centred spectrum C
+  // [PN][PN][PH], PN = volPad N; null with a point model -- a handle holds one kind, an upload replaces the other
+  double2 *dVolC = nullptr;
+  int volPad = 0;
+  // bioem_hip_debug_slices: angles, matrices and slices of a chunk of maxOrientations (allocated at the first call)
+  float4 *dSliceAngles = nullptr;
+  double *dSliceR = nullptr;
+  double2 *dSliceOut = nullptr;
   int iradMax = 0; // widest sphere footprint of the model, pixels (k_project_bands)
   // BIOEM_CC_DIRECT=1 (BASELINE config 4): real-space particles, real-space conv maps of a launch, column pass of the c2r
   bool direct = false;
@@ -1057,6 +1069,9 @@ struct OrientList
   int isQuat;
   double quatNormDev;
 };
+// a model of either kind: points, or a volume
+bool has_model(const bioem_hip_ctx *h) { return h->dPts || h->dVolC; }
+
 OrientList shared_list(const bioem_hip_ctx *h) { return {h->dAngles, h->isQuat, h->quatNormDev}; }
 OrientList own_list(const bioem_hip_ctx *h) { return {h->dOwnAngles, h->ownIsQuat, h->ownQuatNormDev}; }
 
@@ -1120,6 +1135,15 @@ int project_batch(bioem_hip_ctx *h, const bioem_hip_ctx::Slot &bb, hipStream_t s
                   int force = kProjectAuto, ProjectPlan *taken = nullptr)
 {
   const int N = h->N;
+  if (h->dVolC)
+  { // a volume model: the slices of its spectrum stand where the r2c stores its result; the matrices borrow the row-pass
+    // buffer of the r2c that does not run (9 doubles per image of N H double2)
+    double *R = reinterpret_cast<double *>(bb.rowSpec);
+    HIP_CHECK(h, bioem_recon_matrices_launch(st, L.d + o0, nullptr, L.isQuat, nO, R));
+    HIP_CHECK(h, bioem_slice_project_launch(st, h->dVolC, h->volPad, R, nO, N, h->dTwD, h->shiftX, h->shiftY,
+                                            (double) h->NormDen, bb.specRef, nullptr, bb.tempDen));
+    return 0;
+  }
   const ProjectPlan P = project_plan(h, L, force);
   if (taken)
     *taken = P;
@@ -1763,6 +1787,14 @@ int bioem_hip_upload_model(bioem_hip_handle h, const bioem_hip_model_point *pts,
                            float pixelSize, int shiftX, int shiftY)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
+  if (h->dVolC)
+  { // the points replace a volume model: nothing queued may still read it
+    HIP_CHECK(h, hipDeviceSynchronize());
+    dev_release(h, h->dVolC);
+    h->volPad = 0;
+    void_slot(h->slot[0]); // (what a slot holds staged are slices of the volume)
+    void_slot(h->slot[1]);
+  }
   dev_release(h, h->dPts);
   if (upload(h, h->dPts, pts, (size_t) nPts))
     return 1;
@@ -2057,7 +2089,7 @@ int bioem_hip_compare_own_orientations(bioem_hip_handle h, int iMapBegin, int iM
     h->err = "compare_own_orientations: no per-particle orientation lists (bioem_hip_upload_particle_orientations)";
     return 2;
   }
-  if (!h->dPts || iMapBegin < 0 || iMapEnd > h->nMaps || iMapBegin > iMapEnd)
+  if (!has_model(h) || iMapBegin < 0 || iMapEnd > h->nMaps || iMapBegin > iMapEnd)
   {
     h->err = "compare_own_orientations: model not uploaded or particle range invalid";
     return 2;
@@ -2221,7 +2253,7 @@ int bioem_hip_project_convolve_compare_ctf(bioem_hip_handle h, int iOrientBegin,
                                            int iConvEnd)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
-  if (!h->dPts || iOrientBegin < 0 || iOrientEnd > h->nAnglesUp || iOrientBegin > iOrientEnd || iConvBegin < 0 ||
+  if (!has_model(h) || iOrientBegin < 0 || iOrientEnd > h->nAnglesUp || iOrientBegin > iOrientEnd || iConvBegin < 0 ||
       iConvEnd > h->nCTF || iConvBegin >= iConvEnd)
   {
     h->err = "project_convolve_compare: model/orientations not uploaded or range invalid";
@@ -2264,7 +2296,7 @@ int bioem_hip_project(bioem_hip_handle h, int iPipeline, int iOrientBegin, int i
 {
   HIP_CHECK(h, hipSetDevice(h->device));
   const int nO = iOrientEnd - iOrientBegin;
-  if (!h->dPts || iOrientBegin < 0 || iOrientEnd > h->nAnglesUp || nO < 1)
+  if (!has_model(h) || iOrientBegin < 0 || iOrientEnd > h->nAnglesUp || nO < 1)
   {
     h->err = "bioem_hip_project: model/orientations not uploaded or range invalid";
     return 2;
@@ -2759,7 +2791,7 @@ enum
 };
 const char *missing_state(const bioem_hip_ctx *h, int needs, int ownLists)
 {
-  if ((needs & NEED_MODEL) && (!h->dPts || h->nPts < 1))
+  if ((needs & NEED_MODEL) && !h->dVolC && (!h->dPts || h->nPts < 1))
     return "model not uploaded";
   if ((needs & NEED_CTF) && !h->ctfUp)
     return "CTF kernels not uploaded";
@@ -4392,6 +4424,8 @@ int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *r
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
   const Refuse refuse = {h, "model_gradient"};
+  if (h->dVolC)
+    return refuse("the model is a volume");
   if (!req || n < 1)
     return refuse("null argument or no requests");
   if (!grad_out && !points_out)
@@ -4569,6 +4603,8 @@ int bioem_hip_debug_grad_gather(bioem_hip_handle h, const double *gmaps, int o0,
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
   const Refuse refuse = {h, "debug_grad_gather"};
+  if (h->dVolC)
+    return refuse("the model is a volume");
   if (!gmaps || !u_out || nO < 1 || o0 < 0 || o0 + nO > h->nAnglesUp)
     return refuse("null argument, or orientations empty or outside the uploaded list");
   if (const char *why = missing_state(h, NEED_MODEL, 0))
@@ -4899,6 +4935,241 @@ int bioem_hip_debug_orient_occupancy(bioem_hip_handle h, const bioem_hip_prob_an
   return 0;
 }
 
+} // extern "C" (closed around the helpers of the volume model)
+
+// ---- a volume as the model (slice_kernels.hpp) ----
+namespace
+{
+// exp(+2 pi i k c / PN) for the stored index i of an axis of PN entries (i <= PN / 2 stands for k = i, a larger one for i -
+// PN): made on the host with libm, as the sinc^2 table of the reconstruction
+void centre_table(int PN, double c, double2 *e)
+{
+  for (int i = 0; i < PN; i++)
+  {
+    const int k = i <= PN / 2 ? i : i - PN;
+    const double ang = 2.0 * M_PI * ((double) k * c) / (double) PN;
+    e[i] = c == 0. ? make_double2(1., 0.) : make_double2(cos(ang), sin(ang));
+  }
+}
+
+// spec on the device ([PN][PN][PH], un-centred; owned by the caller, not yet a field of the handle) becomes the handle's
+// model: centred, Re C(0) checked, and only then the model it replaces goes.  dSpec is released on every failure.
+int volume_commit(bioem_hip_ctx *h, const Refuse &refuse, double2 *dSpec, int pad, const double *centre, int shiftX, int shiftY)
+{
+  const int N = h->N, PN = pad * N, o = (N + 1) / 2;
+  std::vector<double2> tab((size_t) 4 * PN);
+  for (int j = 0; j < PN; j++)
+    tab[(size_t) j] = twiddle_d(j, PN);
+  for (int d = 0; d < 3; d++)
+    centre_table(PN, centre ? centre[d] : 0., tab.data() + (size_t) (d + 1) * PN);
+  double2 *dTab = nullptr;
+  double2 c0 = make_double2(0., 0.);
+  int rc = upload(h, dTab, tab.data(), tab.size());
+  if (!rc)
+  {
+    hipError_t e = bioem_slice_centre_launch(h->stream, dSpec, PN, o, dTab, dTab + PN);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(&c0, dSpec, sizeof(double2), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess)
+      e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess)
+    {
+      h->err = std::string("upload of a volume model failed: ") + hipGetErrorString(e);
+      rc = 1;
+    }
+  }
+  dev_release(h, dTab);
+  if (rc)
+  {
+    dev_release(h, dSpec);
+    return rc;
+  }
+  if (!(c0.x > 0.) || !std::isfinite(c0.x))
+  {
+    dev_release(h, dSpec);
+    char buf[128];
+    snprintf(buf, sizeof(buf), "the total density Re C(0) = %g is not positive", c0.x);
+    return refuse(buf);
+  }
+  // nothing queued may still read the model that goes
+  if (const hipError_t e = hipDeviceSynchronize())
+  {
+    dev_release(h, dSpec);
+    h->err = std::string("upload of a volume model failed: ") + hipGetErrorString(e);
+    return 1;
+  }
+  dev_release(h, h->dVolC);
+  dev_release(h, h->dPts);
+  dev_release(h, h->dStamp);
+  h->nPts = 0;
+  h->iradMax = 0;
+  h->modelRadius = 0.;
+  h->dVolC = dSpec;
+  h->volPad = pad;
+  h->NormDen = (float) c0.x;
+  h->shiftX = shiftX;
+  h->shiftY = shiftY;
+  void_slot(h->slot[0]);
+  void_slot(h->slot[1]);
+  return 0;
+}
+
+const char *volume_args(int pad, const void *data, const double *centre)
+{
+  if (pad != 1 && pad != 2)
+    return "pad must be 1 or 2";
+  if (!data)
+    return "null argument";
+  if (centre && (!std::isfinite(centre[0]) || !std::isfinite(centre[1]) || !std::isfinite(centre[2])))
+    return "centre not finite";
+  return nullptr;
+}
+} // namespace
+
+extern "C" {
+
+int bioem_hip_upload_model_spectrum(bioem_hip_handle h, const double *spec, int pad, const double *centre, int shiftX,
+                                    int shiftY)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "upload_model_spectrum"};
+  if (const char *why = volume_args(pad, spec, centre))
+    return refuse(why);
+  const size_t PN = (size_t) pad * h->N, V = PN * PN * (PN / 2 + 1);
+  for (size_t e = 0; e < 2 * V; e++)
+    if (!std::isfinite(spec[e]))
+      return refuse("spectrum not finite at coefficient " + std::to_string(e / 2));
+  if (begin_analysis(h, false))
+    return 1;
+  double2 *dSpec = nullptr;
+  if (upload(h, dSpec, reinterpret_cast<const double2 *>(spec), V))
+  {
+    dev_release(h, dSpec);
+    (void) hipGetLastError();
+    return 1;
+  }
+  return volume_commit(h, refuse, dSpec, pad, centre, shiftX, shiftY);
+}
+
+int bioem_hip_upload_model_volume(bioem_hip_handle h, const float *vol, int pad, int flags, const double *centre, int shiftX,
+                                  int shiftY)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "upload_model_volume"};
+  if (const char *why = volume_args(pad, vol, centre))
+    return refuse(why);
+  if (flags & ~BIOEM_HIP_VOLUME_PRECORRECT)
+    return refuse("unknown flag bits");
+  const size_t N = (size_t) h->N, PN = (size_t) pad * N, PH = PN / 2 + 1, NNN = N * N * N;
+  for (size_t e = 0; e < NNN; e++)
+    if (!std::isfinite(vol[e]))
+      return refuse("volume not finite at voxel " + std::to_string(e));
+  // the density in double, divided by the transform of the trilinear kernel on the padded grid where asked for
+  std::vector<double> sinc2(N, 1.);
+  if (flags & BIOEM_HIP_VOLUME_PRECORRECT)
+    for (size_t x = 0; x < N; x++)
+    {
+      const double t = M_PI * ((double) x - (double) ((N + 1) / 2)) / (double) PN;
+      const double s = t == 0. ? 1. : sin(t) / t;
+      sinc2[x] = s * s;
+    }
+  std::vector<double2> in(NNN);
+  for (size_t x0 = 0, e = 0; x0 < N; x0++)
+    for (size_t x1 = 0; x1 < N; x1++)
+      for (size_t x2 = 0; x2 < N; x2++, e++)
+      {
+        double v = (double) vol[e];
+        if (flags & BIOEM_HIP_VOLUME_PRECORRECT)
+          v = v / ((sinc2[x0] * sinc2[x1]) * sinc2[x2]);
+        in[e] = make_double2(v, 0.);
+      }
+  std::vector<double2> twP(PN);
+  for (size_t j = 0; j < PN; j++)
+    twP[j] = twiddle_d((long long) j, (int) PN);
+  if (begin_analysis(h, false))
+    return 1;
+  // axis 2: [N][N][N] -> [N][N][PH]; axis 1: -> [N][PN][PH]; axis 0: -> [PN][PN][PH]
+  double2 *dA = nullptr, *dB = nullptr, *dSpec = nullptr, *dTw = nullptr;
+  int rc = dev_alloc(h, dA, std::max(NNN, N * PN * PH)) || dev_alloc(h, dB, N * N * PH) || dev_alloc(h, dSpec, PN * PN * PH) ||
+           dev_alloc(h, dTw, PN);
+  if (!rc)
+  {
+    hipError_t e = hipMemcpyAsync(dA, in.data(), sizeof(double2) * NNN, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(dTw, twP.data(), sizeof(double2) * PN, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess)
+      e = bioem_slice_axis_launch(h->stream, dA, N * N, (int) N, (int) PH, 1, (int) PN, dTw, dB);
+    if (e == hipSuccess)
+      e = bioem_slice_axis_launch(h->stream, dB, N, (int) N, (int) PN, PH, (int) PN, dTw, dA);
+    if (e == hipSuccess)
+      e = bioem_slice_axis_launch(h->stream, dA, 1, (int) N, (int) PN, PN * PH, (int) PN, dTw, dSpec);
+    if (e == hipSuccess)
+      e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess)
+    {
+      h->err = std::string("upload_model_volume failed: ") + hipGetErrorString(e);
+      rc = 1;
+    }
+  }
+  else
+    (void) hipGetLastError();
+  dev_release(h, dA);
+  dev_release(h, dB);
+  dev_release(h, dTw);
+  if (rc)
+  {
+    dev_release(h, dSpec);
+    return 1;
+  }
+  return volume_commit(h, refuse, dSpec, pad, centre, shiftX, shiftY);
+}
+
+int bioem_hip_debug_slices(bioem_hip_handle h, const float *angles4, int n, int isQuat, double *out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "debug_slices"};
+  if (!angles4 || !out || n < 1)
+    return refuse("null argument or no orientations");
+  if (!h->dVolC)
+    return refuse("the model is not a volume");
+  const size_t M = (size_t) h->M, OB = (size_t) h->OB;
+  if (!h->dSliceOut)
+  {
+    Staging st = {h};
+    st.get(h->dSliceAngles, OB);
+    st.get(h->dSliceR, 9 * OB);
+    st.get(h->dSliceOut, OB * M);
+    if (st.commit())
+    {
+      h->err = "debug_slices: device memory";
+      return 1;
+    }
+  }
+  if (begin_analysis(h, false))
+    return 1;
+  for (int g0 = 0; g0 < n; g0 += h->OB)
+  {
+    const int nb = std::min(h->OB, n - g0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dSliceAngles, angles4 + 4 * (size_t) g0, sizeof(float4) * nb, hipMemcpyHostToDevice,
+                                h->stream));
+    // (poisoned: a bin the kernel leaves unwritten reads back as a NaN)
+    HIP_CHECK(h, hipMemsetAsync(h->dSliceOut, 0xff, sizeof(double2) * M * nb, h->stream));
+    HIP_CHECK(h, bioem_recon_matrices_launch(h->stream, h->dSliceAngles, nullptr, isQuat ? 1 : 0, nb, h->dSliceR));
+    HIP_CHECK(h, bioem_slice_project_launch(h->stream, h->dVolC, h->volPad, h->dSliceR, nb, h->N, h->dTwD, h->shiftX,
+                                            h->shiftY, (double) h->NormDen, nullptr, h->dSliceOut, nullptr));
+    HIP_CHECK(h, hipMemcpyAsync(out + 2 * M * (size_t) g0, h->dSliceOut, sizeof(double2) * M * nb, hipMemcpyDeviceToHost,
+                                h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
 int bioem_hip_debug_projection(bioem_hip_handle h, int iOrient, float *spec_out)
 {
   HIP_CHECK(h, hipSetDevice(h->device));
@@ -4923,6 +5194,8 @@ int bioem_hip_debug_projection_maps(bioem_hip_handle h, int o0, int nO, int path
   };
   if (!maps_out || !tempden_out || !info_out)
     return refuse("null argument");
+  if (h->dVolC)
+    return refuse("the model is a volume");
   if (!h->dPts || h->nAnglesUp < 1)
     return refuse("model or orientations not uploaded");
   if (path < kProjectAuto || path > kProjectAtomics)
@@ -4971,6 +5244,11 @@ int bioem_hip_debug_stamps(bioem_hip_handle h, double *stamps_out, int *iradMax_
   if (!h)
     return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
+  if (h->dVolC)
+  {
+    h->err = "debug_stamps: the model is a volume";
+    return 2;
+  }
   if (!iradMax_out || !h->dStamp)
   {
     h->err = !h->dStamp ? "debug_stamps: the model has no footprint table" : "debug_stamps: null argument";

@@ -29,6 +29,7 @@ SOFT_MEMBER_DTYPE = np.dtype([("particle", "<i4"), ("group", "<i4"), ("conv", "<
 GRAD_POINT_DTYPE = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("sumw", "<f8"), ("count", "<i8")])
 MIN_PROB = -999999.0
 RECON_CORRECT, RECON_NO_CULL = 1, 2   # BIOEM_HIP_RECON_* of include/bioem_hip.h
+VOLUME_PRECORRECT = 1                 # BIOEM_HIP_VOLUME_PRECORRECT
 
 
 class ParamDevice(C.Structure):
@@ -126,6 +127,10 @@ def load_library():
         L.bioem_hip_view_sums_soft.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp]
         L.bioem_hip_debug_view_sums_soft.argtypes = [vp, vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp]
         L.bioem_hip_reconstruct_soft.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, C.c_double, ci, vp, vp, vp, vp]
+    if hasattr(L, "bioem_hip_upload_model_volume"):
+        L.bioem_hip_upload_model_spectrum.argtypes = [vp, vp, ci, vp, ci, ci]
+        L.bioem_hip_upload_model_volume.argtypes = [vp, vp, ci, ci, vp, ci, ci]
+        L.bioem_hip_debug_slices.argtypes = [vp, vp, ci, ci, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -193,7 +198,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_reconstruct", "bioem_hip_debug_reconstruct",
            "bioem_hip_view_sums_soft", "bioem_hip_debug_view_sums_soft", "bioem_hip_reconstruct_soft",
            "bioem_hip_set_compare_variant", "bioem_hip_debug_projection_maps", "bioem_hip_debug_stamps",
-           "bioem_hip_debug_convolve_batch"]
+           "bioem_hip_debug_convolve_batch",
+           "bioem_hip_upload_model_spectrum", "bioem_hip_upload_model_volume", "bioem_hip_debug_slices"]
 
 
 def _p(a):
@@ -384,6 +390,52 @@ class Engine:
         self._chk(self.L.bioem_hip_upload_model(self.h, _p(points), len(points), float(NormDen), float(pixelSize),
                                                 int(shiftX), int(shiftY)), "upload_model")
         self._nPts = len(points)
+
+    @staticmethod
+    def _centre(centre):
+        if centre is None:
+            return None
+        centre = np.ascontiguousarray(centre, dtype=np.float64)
+        assert centre.shape == (3,)
+        return centre
+
+    def upload_model_volume(self, vol, pad=2, precorrect=True, centre=None, shiftX=0, shiftY=0):
+        """a volume as the model (bioem_hip_upload_model_volume): vol float32 [N, N, N] with its origin at
+        voxel (o, o, o), o = (N + 1) // 2, as reconstruct delivers it; replaces a point model.  Projections are then
+        central slices of its spectrum on a grid padded by pad (1 or 2), interpolated trilinearly.  precorrect: divide by
+        the transform of the trilinear kernel first; centre: float64 [3], the density is moved by -centre pixels
+        (volume_model.centre_of_mass); shiftX, shiftY as upload_model.  A refusal raises RuntimeError with .rc == 2 and
+        leaves the model as it was."""
+        if vol is not None:
+            vol = np.ascontiguousarray(vol, dtype=np.float32)
+            assert vol.shape == (self.N,) * 3, vol.shape
+        centre = self._centre(centre)
+        flags = VOLUME_PRECORRECT if precorrect else 0
+        self._chk(self.L.bioem_hip_upload_model_volume(self.h, _p(vol), int(pad), flags, _p(centre), int(shiftX),
+                                                       int(shiftY)), "upload_model_volume")
+        self._nPts = 0
+
+    def upload_model_spectrum(self, spec, pad=1, centre=None, shiftX=0, shiftY=0):
+        """the same from the spectrum itself: spec complex128 [PN, PN, PH], PN = pad N, PH = PN // 2 + 1, un-centred, in
+        the layout and sign convention of reconstruct's "spec" at pad = 1 (volume_model.pad_spectrum states it)"""
+        if spec is not None:
+            spec = np.ascontiguousarray(spec, dtype=np.complex128)
+            if pad in (1, 2):
+                PN = int(pad) * self.N
+                assert spec.shape == (PN, PN, PN // 2 + 1), spec.shape
+        centre = self._centre(centre)
+        self._chk(self.L.bioem_hip_upload_model_spectrum(self.h, _p(spec), int(pad), _p(centre), int(shiftX), int(shiftY)),
+                  "upload_model_spectrum")
+        self._nPts = 0
+
+    def debug_slices(self, angles, isQuat=True):
+        """test hook: the slice kernel alone under the orientations angles float32 [n, 4]; complex128 [n, N, H], the
+        slices of the volume model as they stand before the rounding to float"""
+        angles = np.ascontiguousarray(angles, dtype=np.float32).reshape(-1, 4)
+        out = np.zeros((len(angles), self.N, self.H), dtype=np.complex128)
+        self._chk(self.L.bioem_hip_debug_slices(self.h, _p(angles) if len(angles) else None, len(angles), int(bool(isQuat)),
+                                                _p(out)), "debug_slices")
+        return out
 
     def upload_orientations(self, angles, isQuat):
         angles = np.ascontiguousarray(angles, dtype=np.float32)

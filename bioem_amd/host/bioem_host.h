@@ -302,6 +302,16 @@ struct Model
   std::vector<bioem_hip_model_point> points;
   float NormDen = 0;
   bool readPDB = false, readModelMRC = false;
+  // --ModelVolume: the MRC density itself is the model (bioem_hip_upload_model_volume), not a point per voxel.  volume
+  // [N][N][N] with its origin at voxel (N + 1) / 2, the cyclic one-voxel shift of write_mrc_volume undone; centre: its
+  // centre of mass in voxels relative to the origin (0 with NO_CENTEROFMASS); no points
+  bool readVolume = false;
+  int volumePad = 2;
+  std::vector<float> volume;
+  double centre[3] = {0., 0., 0.};
+  void readVolumeFile(const InputParams &p, const char *file);
+  // the model of either kind into handle h; the library's return code
+  int upload(bioem_hip_handle h, const InputParams &p) const;
   void readModel(const InputParams &p, const char *file); // model.cpp:674-710
   void readTextFile(const InputParams &p, const char *file);
   void readPDBFile(const char *file);

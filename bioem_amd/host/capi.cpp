@@ -163,6 +163,22 @@ int bioem_host_read_model(const char *file, int isPDB, int nocentermass, float p
   return (int) m.points.size();
 }
 
+// the reader of --ModelVolume: vol [N][N][N] with its origin at voxel (N + 1) / 2, the centre of mass in voxels relative to
+// it (0 with nocentermass) and the total density; returns N^3
+int bioem_host_read_model_volume(const char *file, int N, int nocentermass, float *vol, double *centre, float *normden)
+{
+  bioem_host::InputParams P;
+  P.nocentermass = nocentermass;
+  P.N = N;
+  bioem_host::Model m;
+  m.readVolume = true;
+  m.readModel(P, file);
+  std::copy(m.volume.begin(), m.volume.end(), vol);
+  std::copy(m.centre, m.centre + 3, centre);
+  *normden = m.NormDen;
+  return (int) m.volume.size();
+}
+
 // particle readers: mode 0 text, 1 single MRC, 2 list of MRCs; returns the number of images
 int bioem_host_read_particles(const char *file, int mode, int N, int notnormmap, float *maps, int cap)
 {

@@ -113,7 +113,7 @@ Driver::~Driver() { cleanup(); }
 int Driver::readOptions(int ac, char **av)
 {
   std::string infile, modelfile, mapfile, anglefile;
-  bool viewOptions = false, scanOptions = false, reconOptions = false;
+  bool viewOptions = false, scanOptions = false, reconOptions = false, volumeOptions = false;
   std::cout << " ++++++++++++ FROM COMMAND LINE +++++++++++\n\n";
   static const struct option opts[] = {{"Modelfile", required_argument, 0, 0},
                                        {"Particlesfile", required_argument, 0, 0},
@@ -141,6 +141,8 @@ int Driver::readOptions(int ac, char **av)
                                        {"RefineLogWindow", required_argument, 0, 0},
                                        {"ReadPDB", no_argument, 0, 0},
                                        {"ReadModelMRC", no_argument, 0, 0},
+                                       {"ModelVolume", no_argument, 0, 0},
+                                       {"ModelVolumePad", required_argument, 0, 0},
                                        {"ReadMRC", no_argument, 0, 0},
                                        {"ReadMultipleMRC", no_argument, 0, 0},
                                        {"DumpMaps", no_argument, 0, 0},
@@ -201,6 +203,9 @@ int Driver::readOptions(int ac, char **av)
     printf("  --PrintBestCalMap arg  (Optional) Only print best calculated map (file of BEST_ parameters). NO BioEM!\n");
     printf("  --ReadPDB              (Optional) If reading model file in PDB format\n");
     printf("  --ReadModelMRC         (Optional) If reading model file in MRC format\n");
+    printf("  --ModelVolume          (Optional) The model file is an MRC density (mode 2, cubic, side NUMBER_PIXELS, as --Reconstruct\n");
+    printf("                         writes it) used as a volume: projections are central slices of its spectrum\n");
+    printf("  --ModelVolumePad arg   (Optional) With --ModelVolume: padding of the spectrum, 1 or 2 (default 2)\n");
     printf("  --ReadMRC              (Optional) If reading particle file in MRC format\n");
     printf("  --ReadMultipleMRC      (Optional) If reading multiple MRCs\n");
     printf("  --OutputFile arg       (Optional) For changing the outputfile name\n");
@@ -255,6 +260,18 @@ int Driver::readOptions(int ac, char **av)
     {
       std::cout << "Reading model file in MRC format.\n";
       model.readModelMRC = true;
+    }
+    else if (name == "ModelVolume")
+    {
+      std::cout << "Reading model file as an MRC density volume.\n";
+      model.readVolume = true;
+    }
+    else if (name == "ModelVolumePad")
+    {
+      model.volumePad = atoi(optarg);
+      volumeOptions = true;
+      if (model.volumePad != 1 && model.volumePad != 2)
+        fatal("--ModelVolumePad needs 1 or 2");
     }
     else if (name == "ReadOrientation")
     {
@@ -412,6 +429,19 @@ int Driver::readOptions(int ac, char **av)
   }
   if (particles.readMultMRC && !particles.readMRC)
     fatal("For multiple MRCs command --ReadMRC is necessary too");
+  if (volumeOptions && !model.readVolume)
+    fatal("--ModelVolumePad goes with --ModelVolume");
+  if (model.readVolume)
+  { // the density itself is the model: nothing that reads or needs points goes with it
+    if (model.readPDB)
+      fatal("--ModelVolume is not valid with --ReadPDB (a PDB file holds atoms, not a density volume)");
+    if (model.readModelMRC)
+      fatal("--ModelVolume is not valid with --ReadModelMRC (which turns every voxel into a point; choose one)");
+    if (!modelGradFile.empty())
+      fatal("--ModelVolume is not valid with --ModelGradient (the gradient is per model point; a volume has none)");
+    if (!bestParamFile.empty())
+      fatal("--ModelVolume is not valid with --PrintBestCalMap (its one-record mode reads the model as points)");
+  }
   if (!bestParamFile.empty())
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
@@ -590,8 +620,7 @@ int Driver::configure(int ac, char **av)
     check(h, rc, "bioem_hip_create");
     check(h, bioem_hip_upload_particle_maps(h, particles.maps.data()), "upload particles");
     check(h, bioem_hip_upload_ctf(h, param.refCTF.data(), param.ctfParam.data()), "upload CTF");
-    check(h, bioem_hip_upload_model(h, model.points.data(), (int) model.points.size(), model.NormDen, param.pixelSize,
-                                    param.shiftX, param.shiftY),
+    check(h, model.upload(h, param),
           "upload model");
     check(h, bioem_hip_upload_orientations(h, param.angles.data(), nA, param.doquater ? 1 : 0), "upload orientations");
     if (!probCtfFile.empty())
@@ -1167,8 +1196,7 @@ int Driver::printBestCalMap()
   bioem_hip_handle h = nullptr;
   check(h, bioem_hip_create(&h, firstDev, &param.pd, 1, 1, 1, algo), "bioem_hip_create");
   check(h, bioem_hip_upload_ctf(h, param.refCTF.data(), param.ctfParam.data()), "upload CTF");
-  check(h, bioem_hip_upload_model(h, model.points.data(), (int) model.points.size(), model.NormDen, param.pixelSize,
-                                  param.shiftX, param.shiftY),
+  check(h, model.upload(h, param),
         "upload model");
   check(h, bioem_hip_upload_orientations(h, param.angles.data(), 1, param.doquater ? 1 : 0), "upload orientations");
   bioem_hip_prob_map rec;
@@ -1421,8 +1449,7 @@ void Driver::runRound2()
   check(h, bioem_hip_create(&h, firstDev, &pd2, nMaps, G, nC, algo), "bioem_hip_create (second round)");
   check(h, bioem_hip_upload_particle_maps(h, particles.maps.data()), "upload particles");
   check(h, bioem_hip_upload_ctf(h, param.refCTF.data(), param.ctfParam.data()), "upload CTF");
-  check(h, bioem_hip_upload_model(h, model.points.data(), (int) model.points.size(), model.NormDen, param.pixelSize,
-                                  param.shiftX, param.shiftY),
+  check(h, model.upload(h, param),
         "upload model");
   check(h, bioem_hip_upload_particle_orientations(h, lists.data(), G, 1), "upload particle orientations");
   if (!probCtfFile.empty())
@@ -1522,8 +1549,7 @@ void Driver::runRound2Seeds()
   check(h, bioem_hip_create(&h, firstDev, &pd2, nMaps, std::max(1, longest), nC, algo), "bioem_hip_create (second round)");
   check(h, bioem_hip_upload_particle_maps(h, particles.maps.data()), "upload particles");
   check(h, bioem_hip_upload_ctf(h, param.refCTF.data(), param.ctfParam.data()), "upload CTF");
-  check(h, bioem_hip_upload_model(h, model.points.data(), (int) model.points.size(), model.NormDen, param.pixelSize,
-                                  param.shiftX, param.shiftY),
+  check(h, model.upload(h, param),
         "upload model");
   check(h, bioem_hip_upload_particle_orientation_lists(h, lists.data(), offsets.data(), 1), "upload particle orientation lists");
   if (!probCtfFile.empty())

@@ -187,6 +187,64 @@ void Model::readMRCFile(const InputParams &p, const char *file)
   std::cout << "Protein structure read from MRC\n";
 }
 
+// --ModelVolume: a cubic mode-2 MRC of side NUMBER_PIXELS as the density itself.  write_mrc_volume stores file[e] =
+// vol[(e + 1) mod N] on every axis; undone here, vol[(e + 1) mod N] = file[e], so that for even N the density sits where
+// --ReadModelMRC puts it.  The centre of mass is summed in double.
+void Model::readVolumeFile(const InputParams &p, const char *file)
+{
+  const std::string name(file);
+  if (name.find(".mrc") > name.find_last_not_of(" \t"))
+    warn("MRC extension NOT detected in file name: %s. Are you sure you want to read an MRC?", file);
+  const MrcHeader h = mrc_read_header(file);
+  if (h.mode != 2)
+    fatal("MRC mode: %d. Currently mode 2 is the only one allowed", h.mode);
+  const int N = p.N;
+  if (h.nc != N || h.nr != N || h.ns != N)
+    fatal("--ModelVolume: the MRC is %d x %d x %d, it must be cubic of side NUMBER_PIXELS = %d", h.nc, h.nr, h.ns, N);
+  const size_t total = (size_t) N * N * N;
+  FILE *f = fopen(file, "rb");
+  if (!f)
+    fatal("Opening MRC: %s", file);
+  if (fseek(f, 1024 + (long) h.nsymbt, SEEK_SET) != 0)
+    fatal("Converting Data: %s", file);
+  std::vector<unsigned int> raw(total);
+  if (fread(raw.data(), 4, total, f) != total)
+    fatal("Converting Data: %s", file);
+  fclose(f);
+  points.clear();
+  volume.assign(total, 0.f);
+  double sum = 0., r[3] = {0., 0., 0.};
+  const int o = (N + 1) / 2;
+  size_t e = 0;
+  for (int e0 = 0; e0 < N; e0++)
+    for (int e1 = 0; e1 < N; e1++)
+      for (int e2 = 0; e2 < N; e2++, e++)
+      {
+        unsigned int v = raw[e];
+        if (h.swap)
+          v = mrc_bswap32(v);
+        float c;
+        memcpy(&c, &v, 4);
+        const int x0 = (e0 + 1) % N, x1 = (e1 + 1) % N, x2 = (e2 + 1) % N;
+        volume[((size_t) x0 * N + x1) * N + x2] = c;
+        sum += (double) c;
+        r[0] += (double) c * (x0 - o);
+        r[1] += (double) c * (x1 - o);
+        r[2] += (double) c * (x2 - o);
+      }
+  NormDen = (float) sum;
+  for (int k = 0; k < 3; k++)
+    centre[k] = p.nocentermass || sum == 0. ? 0. : r[k] / sum;
+  std::cout << "Protein density read from MRC as a volume\n";
+}
+
+int Model::upload(bioem_hip_handle h, const InputParams &p) const
+{
+  if (readVolume)
+    return bioem_hip_upload_model_volume(h, volume.data(), volumePad, BIOEM_HIP_VOLUME_PRECORRECT, centre, p.shiftX, p.shiftY);
+  return bioem_hip_upload_model(h, points.data(), (int) points.size(), NormDen, p.pixelSize, p.shiftX, p.shiftY);
+}
+
 void Model::centerDensityMass()
 {
   float r[3] = {0.f, 0.f, 0.f};
@@ -202,6 +260,14 @@ void Model::centerDensityMass()
 
 void Model::readModel(const InputParams &p, const char *file)
 {
+  if (readVolume)
+  {
+    readVolumeFile(p, file);
+    std::cout << "Total Number of Voxels " << volume.size();
+    std::cout << "\nTotal Number of Electrons " << NormDen;
+    std::cout << "\n+++++++++++++++++++++++++++++++++++++++++ \n";
+    return;
+  }
   if (readPDB)
     readPDBFile(file);
   else if (readModelMRC)

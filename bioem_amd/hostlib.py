@@ -108,6 +108,22 @@ def read_model(path, isPDB=False, nocentermass=False, cap=1 << 20, isMRC=False, 
     return pts[:n].copy(), np.float32(nd.value)
 
 
+def read_model_volume(path, N, nocentermass=False):
+    """the reader of --ModelVolume: an MRC density (mode 2, cubic, side N) as (vol float32 [N, N, N] with its origin at
+    voxel (N + 1) // 2 -- the cyclic one-voxel shift of write_mrc_volume undone --, centre float64 [3], its centre of mass in
+    voxels relative to the origin (0 with nocentermass), NormDen); any other file ends the process with the reader's fatal"""
+    L = load_host_library()
+    L.bioem_host_read_model_volume.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.bioem_host_read_model_volume.restype = C.c_int
+    vol = np.zeros((N, N, N), dtype=np.float32)
+    centre = np.zeros(3, dtype=np.float64)
+    nd = C.c_float()
+    n = L.bioem_host_read_model_volume(path.encode(), int(N), int(nocentermass), vol.ctypes.data, centre.ctypes.data,
+                                       C.byref(nd))
+    assert n == N ** 3
+    return vol, centre, np.float32(nd.value)
+
+
 def read_particles(path, N, mode=0, notnormmap=False, cap=4096):
     L = load_host_library()
     L.bioem_host_read_particles.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]

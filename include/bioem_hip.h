@@ -736,6 +736,39 @@ int bioem_hip_reconstruct_soft(bioem_hip_handle h, const bioem_hip_soft_member *
                                const int *shifts, int nd, const int *groupOrient, int nGroups, double wiener, int flags,
                                float *vol_out, double *spec_out, double *den_out, double *stats_out);
 
+/* ---- A volume as the model: projections as central slices of its spectrum (no reference counterpart) ----
+ * A handle holds either a point model (bioem_hip_upload_model) or a volume model; uploading one replaces the other.  With
+ * N, H, o, M, tw as above, the padding P = pad in {1, 2}, PN = P N, PH = PN / 2 + 1, M_P = (PN - 1) / 2, axes the model's
+ * (x, y, z), the volume's origin at voxel (o, o, o), everything in double:
+ *   spec[k]  = sum_x vol[x] exp(-2 pi i k.x / PN) over the N^3 box in the first octant of the PN^3 box, [PN][PN][PH]
+ *              (re, im), un-centred: bioem_hip_reconstruct's spec_out at pad = 1
+ *   C(k')    = spec[k' mod PN] exp(+2 pi i (k'0 + k'1 + k'2) o / PN) exp(+2 pi i k'.centre / PN): the spectrum about the
+ *              origin voxel of the density moved by -centre pixels (NULL: 0), what the handle keeps ([PN][PN][PH] double2,
+ *              wrapped indices on axes 0 and 1).  NormDen := Re C(0).
+ *   slice    : stored coefficient (a mod N, b), |a| <= N / 2, 0 <= b < H, under the orientation's float matrix R, widened:
+ *              0 + 0i where a^2 + b^2 > M^2; else k_j = (a R[0][j]) + (b R[1][j]), k' = P k, trilinear about floor(k'):
+ *              the taps t = 4 d0 + 2 d1 + d2 ascending with weights ((w0 w1) w2), w_d = d_d ? f_d : 1 - f_d; a tap with a
+ *              negative third index reads conj C(-k'), a tap outside |k'_d| <= M_P (or a NaN coordinate) adds nothing; the
+ *              sum times tw[(-o (a + b) + shiftX a + shiftY b) mod N], rounded once to float2 where the r2c of a point
+ *              model's projection stores its result.  No NormDen / tempden factor: nothing is skipped.
+ * The slice moves the origin to the pixel floor(x / px + N / 2 + 0.5) - shift of the real-space projection.  Every run
+ * entry, own-list pass and analysis entry projects through it.  A lane owns its coefficient: the same bits for any batch
+ * size, position in the list, handle kind and run.  The entries that need points -- bioem_hip_model_gradient,
+ * bioem_hip_debug_grad_gather, bioem_hip_debug_projection_maps, bioem_hip_debug_stamps -- return 2, "the model is a volume".
+ * Refused with 2, the cause named and the handle usable with the model it had: pad outside {1, 2}, a null array, unknown
+ * flag bits, a non-finite value in spec, vol or centre, Re C(0) <= 0.  1: device memory (C takes 16 PN^2 PH bytes, 722 MB
+ * at 224^2 with pad = 2; the volume entry twice that while it runs). */
+#define BIOEM_HIP_VOLUME_PRECORRECT 1 /* divide vol by prod_d sinc^2(pi (x_d - o) / PN), the transform of the trilinear kernel */
+int bioem_hip_upload_model_spectrum(bioem_hip_handle h, const double *spec, int pad, const double *centre, int shiftX,
+                                    int shiftY);
+/* vol [N][N][N]; the spectrum is formed on the device by three passes of direct summation (a lane owns its output, fixed
+ * order, no atomics), then handled as above */
+int bioem_hip_upload_model_volume(bioem_hip_handle h, const float *vol, int pad, int flags, const double *centre, int shiftX,
+                                  int shiftY);
+/* test hook: the slice kernel alone on n orientations handed in (angles4 [n][4]); out [n][N][H] (re, im) doubles, the
+ * slices as they stand before the rounding to float.  Refused with 2: a null argument, n < 1, the model is not a volume. */
+int bioem_hip_debug_slices(bioem_hip_handle h, const float *angles4, int n, int isQuat, double *out);
+
 #ifdef __cplusplus
 }
 #endif
