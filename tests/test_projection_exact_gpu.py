@@ -388,20 +388,34 @@ def test_invalid_arguments_are_refused():
 
 
 # ---- (c) the r2c from double maps ----
-def spectrum_from_maps(maps, td):
+def scaled_maps(maps, td):
     """what the transform behind the projection is given: the double map scaled by NormDen / tempden in float
-    (bioem.cpp:1808-1818), transformed in double"""
+    (bioem.cpp:1808-1818)"""
     ratio = f32(NORM_DEN) / td.astype(f32)
     img = maps.astype(f32) * ratio[:, None, None]
     assert img.dtype == f32
-    return np.fft.rfft2(img.astype(np.float64))
+    return img
+
+
+def spectrum_from_maps(maps, td):
+    """... transformed in double"""
+    return np.fft.rfft2(scaled_maps(maps, td).astype(np.float64))
 
 
 def check_spectrum(c, path="auto"):
+    import os
+    import r2c_reference as rr
     maps, td, spec, info = c.E.debug_projection_maps(0, len(c.angles), path, want_spec=True)
     want = spectrum_from_maps(maps, td)
     got = spec[..., 0].astype(np.float64) + 1j * spec[..., 1]
     assert np.abs(got - want).max() <= 1.5e-7 * np.abs(want).max()
+    # word by word against the exact transform of the same float images (tests/r2c_reference.py, DESIGN 2.25)
+    img = scaled_maps(maps, td)
+    re, im = rr.exact_r2c(img)
+    m = rr.m_of(c.N, os.environ.get("BIOEM_R2C") == "dft")
+    v = rr.verdict(spec, re, im, np.abs(img.astype(np.float64)).sum(axis=(1, 2)), m)
+    print("N %d box [%d, +%d): m %d  %s" % (c.N, info["boxLo"], info["boxSide"], m, v))
+    assert v.bad == 0 and v.share <= 1.0, (str(v), v.first_bad)
     return spec, info
 
 
