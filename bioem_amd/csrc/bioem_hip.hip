@@ -2494,47 +2494,68 @@ int bioem_hip_merge_host(int nShards, int nMaps, int nAngles, int writeAngles, c
 
 
 // ---- WRITE_PROB_ANGLES: K best orientations per particle, selected where the table lives ----
-static int topk_device(bioem_hip_ctx *h, int K, double numconst)
+// W slots per particle: K (the K best alone) or 2K - 1 (with the tie candidates a merge of shards needs)
+static int topk_device(bioem_hip_ctx *h, int K, int W, double numconst)
 {
   if (!h->pd.writeAngles || K < 1)
   {
     h->err = "topk_angles: handle was created without WRITE_PROB_ANGLES or K < 1";
     return 2;
   }
-  if (h->candK != K)
+  if (h->candK != W)
   {
     dev_release(h, h->dCand);
     h->candK = 0;
-    if (dev_alloc(h, h->dCand, (size_t) h->nMaps * K))
+    if (dev_alloc(h, h->dCand, (size_t) h->nMaps * W))
       return 1;
-    h->candK = K;
+    h->candK = W;
   }
   const bioem_hip_prob_angle *pang =
       reinterpret_cast<const bioem_hip_prob_angle *>(h->dProb + sizeof(bioem_hip_prob_map) * h->nMaps);
   hipLaunchKernelGGL(k_topk_angles, dim3((h->nMaps + 63) / 64), dim3(64), 0, h->stream, pang, h->angO1 - h->angO0, h->nMaps,
-                     h->angO0, K, numconst, h->dCand);
+                     h->angO0, K, W, numconst, h->dCand);
   HIP_CHECK(h, hipGetLastError());
   return 0;
 }
 
-int bioem_hip_topk_angles(bioem_hip_handle h, int K, double numconst, bioem_hip_angle_candidate *out)
+static int topk_to_host(bioem_hip_ctx *h, int K, int W, double numconst, bioem_hip_angle_candidate *out)
 {
+  if (!h)
+    return 2;
   HIP_CHECK(h, hipSetDevice(h->device));
+  if (!out)
+  {
+    h->err = "topk_angles: null output";
+    return 2;
+  }
   if (compat_flush(h))
     return 1;
-  if (const int rc = topk_device(h, K, numconst))
+  if (const int rc = topk_device(h, K, W, numconst))
     return rc;
-  HIP_CHECK(h, hipMemcpyAsync(out, h->dCand, sizeof(bioem_hip_angle_candidate) * (size_t) h->nMaps * K, hipMemcpyDeviceToHost,
+  HIP_CHECK(h, hipMemcpyAsync(out, h->dCand, sizeof(bioem_hip_angle_candidate) * (size_t) h->nMaps * W, hipMemcpyDeviceToHost,
                               h->stream));
   HIP_CHECK(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
-int bioem_hip_merge_topk_host(int nShards, int nMaps, int K, const bioem_hip_angle_candidate *const *cands,
-                              bioem_hip_angle_candidate *out)
+int bioem_hip_topk_angles(bioem_hip_handle h, int K, double numconst, bioem_hip_angle_candidate *out)
 {
-  if (nShards < 1 || K < 1)
+  return topk_to_host(h, K, K, numconst, out);
+}
+
+int bioem_hip_merge_candidates(bioem_hip_handle h, int K, double numconst, bioem_hip_angle_candidate *out)
+{
+  return topk_to_host(h, K, 2 * K - 1, numconst, out);
+}
+
+int bioem_hip_merge_topk_host_wide(int nShards, int nMaps, int K, int W, const bioem_hip_angle_candidate *const *cands,
+                                   bioem_hip_angle_candidate *out)
+{
+  if (nShards < 1 || K < 1 || W < K || nMaps < 0 || !cands || (nMaps > 0 && !out))
     return 2;
+  for (int s = 0; s < nShards; s++)
+    if (!cands[s] && nMaps > 0)
+      return 2;
   typedef std::pair<double, int> Item; // (logp, index into `all`): the reference's heap item with the orientation
                                        // replaced by a position that is monotone in it
   std::vector<bioem_hip_angle_candidate> all;
@@ -2542,9 +2563,9 @@ int bioem_hip_merge_topk_host(int nShards, int nMaps, int K, const bioem_hip_ang
   {
     all.clear();
     for (int s = 0; s < nShards; s++)
-      for (int k = 0; k < K; k++)
-        if (cands[s][(size_t) i * K + k].orient >= 0)
-          all.push_back(cands[s][(size_t) i * K + k]);
+      for (int k = 0; k < W; k++)
+        if (cands[s][(size_t) i * W + k].orient >= 0)
+          all.push_back(cands[s][(size_t) i * W + k]);
     // the writer walks the orientations in ascending order (bioem.cpp:1257)
     std::sort(all.begin(), all.end(),
               [](const bioem_hip_angle_candidate &a, const bioem_hip_angle_candidate &b) { return a.orient < b.orient; });
@@ -2576,6 +2597,12 @@ int bioem_hip_merge_topk_host(int nShards, int nMaps, int K, const bioem_hip_ang
     }
   }
   return 0;
+}
+
+int bioem_hip_merge_topk_host(int nShards, int nMaps, int K, const bioem_hip_angle_candidate *const *cands,
+                              bioem_hip_angle_candidate *out)
+{
+  return bioem_hip_merge_topk_host_wide(nShards, nMaps, K, K, cands, out);
 }
 
 // ---- RCCL merge (one process, n GPUs): librccl is large, so it is loaded when the first merge asks for it ----
@@ -2636,6 +2663,81 @@ const char *rccl_load()
     }                                                                                                              \
   } while (0)
 
+// what follows the all-gather: h0->dRecv holds n payloads of `payload` bytes each (nMaps map entries, then with K > 0
+// nMaps lists of 2K - 1 candidates).  The map entries fold on the device, the lists merge on the host; h0's stream is
+// idle on return.
+static int merge_gathered(bioem_hip_ctx *h0, int n, int K, size_t payload, void *pProbMaps_host,
+                          bioem_hip_angle_candidate *cand_host)
+{
+  const int nMaps = h0->nMaps;
+  const size_t mapBytes = sizeof(bioem_hip_prob_map) * (size_t) nMaps;
+  HIP_CHECK(h0, hipSetDevice(h0->device));
+  if (!h0->dMerged && dev_alloc(h0, h0->dMerged, nMaps))
+    return 1;
+  hipLaunchKernelGGL(k_merge_shards, dim3((nMaps + 127) / 128), dim3(128), 0, h0->stream, h0->dRecv, n, payload, nMaps,
+                     h0->dMerged);
+  HIP_CHECK(h0, hipGetLastError());
+  HIP_CHECK(h0, hipMemcpyAsync(pProbMaps_host, h0->dMerged, mapBytes, hipMemcpyDeviceToHost, h0->stream));
+  std::vector<std::vector<bioem_hip_angle_candidate>> gathered;
+  if (K > 0)
+  {
+    gathered.resize(n);
+    for (int s = 0; s < n; s++)
+    {
+      gathered[s].resize((size_t) nMaps * (2 * K - 1));
+      HIP_CHECK(h0, hipMemcpyAsync(gathered[s].data(), h0->dRecv + (size_t) s * payload + mapBytes, payload - mapBytes,
+                                   hipMemcpyDeviceToHost, h0->stream));
+    }
+  }
+  HIP_CHECK(h0, hipStreamSynchronize(h0->stream));
+  if (K > 0)
+  {
+    std::vector<const bioem_hip_angle_candidate *> ptrs(n);
+    for (int s = 0; s < n; s++)
+      ptrs[s] = gathered[s].data();
+    return bioem_hip_merge_topk_host_wide(n, nMaps, K, 2 * K - 1, ptrs.data(), cand_host);
+  }
+  return 0;
+}
+
+static size_t merge_payload(int nMaps, int K)
+{
+  return sizeof(bioem_hip_prob_map) * (size_t) nMaps + (K > 0 ? sizeof(bioem_hip_angle_candidate) * (size_t) nMaps * (2 * K - 1) : 0);
+}
+
+static int merge_recv_buffer(bioem_hip_ctx *h, size_t bytes)
+{
+  if (h->recvBytes < bytes)
+  {
+    dev_release(h, h->dRecv);
+    h->recvBytes = 0;
+    if (dev_alloc(h, h->dRecv, bytes))
+      return 1;
+    h->recvBytes = bytes;
+  }
+  return 0;
+}
+
+int bioem_hip_debug_merge_gathered(bioem_hip_handle h, const void *gathered, int nShards, int K, void *maps_out,
+                                   bioem_hip_angle_candidate *cand_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  if (!gathered || !maps_out || nShards < 1 || K < 0 || (K > 0 && !cand_out))
+  {
+    h->err = "debug_merge_gathered: null argument, nShards < 1 or K < 0";
+    return 2;
+  }
+  if (compat_flush(h))
+    return 1;
+  const size_t payload = merge_payload(h->nMaps, K);
+  if (merge_recv_buffer(h, payload * nShards))
+    return 1;
+  HIP_CHECK(h, hipMemcpyAsync(h->dRecv, gathered, payload * nShards, hipMemcpyHostToDevice, h->stream));
+  return merge_gathered(h, nShards, K, payload, maps_out, cand_out);
+}
+
 int bioem_hip_merge(bioem_hip_handle *handles, int n, void *pProbMaps_host, int K, double numconst,
                     bioem_hip_angle_candidate *cand_host)
 {
@@ -2676,8 +2778,8 @@ int bioem_hip_merge(bioem_hip_handle *handles, int n, void *pProbMaps_host, int 
   }
   const std::vector<ncclComm_t> &comm = it->second;
   const size_t mapBytes = sizeof(bioem_hip_prob_map) * (size_t) nMaps;
-  const size_t payload = mapBytes + (K > 0 ? sizeof(bioem_hip_angle_candidate) * (size_t) nMaps * K : 0);
-  // stage every shard's contribution: its map entries (already on the device) and its K best orientations
+  const size_t payload = merge_payload(nMaps, K);
+  // stage every shard's contribution: its map entries (already on the device) and its list of 2K - 1 candidates
   for (int i = 0; i < n; i++)
   {
     bioem_hip_ctx *h = handles[i];
@@ -2692,18 +2794,12 @@ int bioem_hip_merge(bioem_hip_handle *handles, int n, void *pProbMaps_host, int 
         return 1;
       h->sendBytes = payload;
     }
-    if (h->recvBytes < payload * n)
-    {
-      dev_release(h, h->dRecv);
-      h->recvBytes = 0;
-      if (dev_alloc(h, h->dRecv, payload * n))
-        return 1;
-      h->recvBytes = payload * n;
-    }
+    if (merge_recv_buffer(h, payload * n))
+      return 1;
     HIP_CHECK(h, hipMemcpyAsync(h->dSend, h->dProb, mapBytes, hipMemcpyDeviceToDevice, h->stream));
     if (K > 0)
     {
-      if (const int rc = topk_device(h, K, numconst))
+      if (const int rc = topk_device(h, K, 2 * K - 1, numconst))
         return rc;
       HIP_CHECK(h, hipMemcpyAsync(h->dSend + mapBytes, h->dCand, payload - mapBytes, hipMemcpyDeviceToDevice, h->stream));
     }
@@ -2718,37 +2814,13 @@ int bioem_hip_merge(bioem_hip_handle *handles, int n, void *pProbMaps_host, int 
   }
   RCCL_CHECK(h0, g_rccl.GroupEnd());
   // fold on the first device, result to the host
-  HIP_CHECK(h0, hipSetDevice(h0->device));
-  if (!h0->dMerged && dev_alloc(h0, h0->dMerged, nMaps))
-    return 1;
-  hipLaunchKernelGGL(k_merge_shards, dim3((nMaps + 127) / 128), dim3(128), 0, h0->stream, h0->dRecv, n, payload, nMaps,
-                     h0->dMerged);
-  HIP_CHECK(h0, hipGetLastError());
-  HIP_CHECK(h0, hipMemcpyAsync(pProbMaps_host, h0->dMerged, mapBytes, hipMemcpyDeviceToHost, h0->stream));
-  std::vector<std::vector<bioem_hip_angle_candidate>> gathered;
-  if (K > 0)
-  {
-    gathered.resize(n);
-    for (int s = 0; s < n; s++)
-    {
-      gathered[s].resize((size_t) nMaps * K);
-      HIP_CHECK(h0, hipMemcpyAsync(gathered[s].data(), h0->dRecv + (size_t) s * payload + mapBytes, payload - mapBytes,
-                                   hipMemcpyDeviceToHost, h0->stream));
-    }
-  }
-  for (int i = 0; i < n; i++)
+  const int rc = merge_gathered(h0, n, K, payload, pProbMaps_host, cand_host);
+  for (int i = 1; i < n; i++)
   {
     HIP_CHECK(handles[i], hipSetDevice(handles[i]->device));
     HIP_CHECK(handles[i], hipStreamSynchronize(handles[i]->stream));
   }
-  if (K > 0)
-  {
-    std::vector<const bioem_hip_angle_candidate *> ptrs(n);
-    for (int s = 0; s < n; s++)
-      ptrs[s] = gathered[s].data();
-    return bioem_hip_merge_topk_host(n, nMaps, K, ptrs.data(), cand_host);
-  }
-  return 0;
+  return rc;
 }
 
 } // extern "C" (closed around the helpers below: Staging::get is a template, as dev_alloc is)
@@ -4815,6 +4887,31 @@ int bioem_hip_debug_orient_sums_own(bioem_hip_handle h, const bioem_hip_prob_ang
     return 2;
   }
   return debug_orient(h, "debug_orient_sums_own", table, nO, nMaps, angles4, offsets, isQuat, nullptr, out);
+}
+
+// k_topk_angles on a table handed in, with the launch shape of topk_device
+int bioem_hip_debug_topk(bioem_hip_handle h, const bioem_hip_prob_angle *table, int nO, int nMaps, int o0, int K, int W,
+                         double numconst, bioem_hip_angle_candidate *out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "debug_topk"};
+  if (!table || !out || nO < 1 || nMaps < 1 || o0 < 0)
+    return refuse("null argument, an empty table or a negative offset");
+  if (K < 1 || (W != K && W != 2 * K - 1))
+    return refuse("K < 1, or a width that is neither K nor 2K - 1");
+  OrientDebugBufs B;
+  bioem_hip_prob_angle *dTab = nullptr;
+  bioem_hip_angle_candidate *dOut = nullptr;
+  const size_t outBytes = sizeof(bioem_hip_angle_candidate) * (size_t) nMaps * W;
+  HIP_CHECK(h, B.get(&dTab, table, sizeof(bioem_hip_prob_angle) * (size_t) nO * nMaps));
+  HIP_CHECK(h, B.get(&dOut, nullptr, outBytes));
+  hipLaunchKernelGGL(k_topk_angles, dim3((nMaps + 63) / 64), dim3(64), 0, h->stream, dTab, nO, nMaps, o0, K, W, numconst, dOut);
+  HIP_CHECK(h, hipGetLastError());
+  HIP_CHECK(h, hipMemcpyAsync(out, dOut, outBytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 // ---- occupancy of every orientation over the particles (orient_kernels.hpp: k_orient_occ) ----

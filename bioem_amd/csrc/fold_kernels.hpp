@@ -438,48 +438,70 @@ __host__ __device__ inline bool cand_less(double la, int ia, double lb, int ib)
   return la < lb || (la == lb && ia < ib);
 }
 
+// the writer's key of a table entry (bioem.cpp:1262): every pass of k_topk_angles forms it here, so that equal table
+// entries give equal bits wherever they are met
+__device__ inline double cand_key(const bioem_hip_prob_angle &pa, double numconst)
+{
+  return log(pa.forAngles) + pa.ConstAngle + numconst;
+}
+
+__device__ inline bioem_hip_angle_candidate cand_make(const bioem_hip_prob_angle &pa, double logp, int orient)
+{
+  bioem_hip_angle_candidate c;
+  c.forAngles = pa.forAngles;
+  c.ConstAngle = pa.ConstAngle;
+  c.logp = logp;
+  c.orient = orient;
+  c.pad = 0;
+  return c;
+}
+
+__device__ inline bioem_hip_angle_candidate cand_unused()
+{
+  bioem_hip_angle_candidate c;
+  c.forAngles = 0.;
+  c.ConstAngle = MIN_PROB;
+  c.logp = -INFINITY;
+  c.orient = -1;
+  c.pad = 0;
+  return c;
+}
+
 // K best orientations per particle among the nO owned ones, by the reference writer's own rule (bioem.cpp:1251-1286):
 // walk the orientations in order; fill a K-entry set; afterwards an entry replaces the set's minimum (by (logp,
 // orientation)) when the minimum's logp is strictly below its own.  One thread per particle: the table is
 // orientation-major, so the 64 particles of a wave read consecutive 16-byte entries of one orientation row.  The set
-// lives in the thread's K output slots; replacements are rare (~K ln(nO/K) per particle), each followed by a scan
-// of the K slots for the new minimum.  Output sorted best first (descending (logp, orientation), the order in which
-// the reference prints after emptying its heap).
-__global__ void k_topk_angles(const bioem_hip_prob_angle *__restrict__ pang, int nO, int nMaps, int o0, int K,
+// lives in the thread's first K output slots; replacements are rare (~K ln(nO/K) per particle), each followed by a scan
+// of the K slots for the new minimum.  Slots 0 ... K-1 sorted best first (descending (logp, orientation), the order in
+// which the reference prints after emptying its heap).
+// A particle owns W >= K slots.  With W > K a second walk adds what a LATER walk over a longer list could still have
+// kept from this block: with t the smallest key of the set, the entries of key t among the first K entries of key >= t
+// that the first walk rejected or evicted (at most K - 1), in ascending orientation from slot K on.  The writer's loop
+// over the shards' lists of width 2K - 1, in orientation order, is the writer's loop over the whole table;
+// K slots are enough only while no equal keys meet a shard's threshold.  Unused slots: (0, MIN_PROB, -inf, -1).
+__global__ void k_topk_angles(const bioem_hip_prob_angle *__restrict__ pang, int nO, int nMaps, int o0, int K, int W,
                               double numconst, bioem_hip_angle_candidate *__restrict__ out)
 {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= nMaps)
     return;
-  bioem_hip_angle_candidate *mine = out + (size_t) p * K;
+  bioem_hip_angle_candidate *mine = out + (size_t) p * W;
   int cnt = 0, minSlot = 0;
   double minLogp = 0.;
   int minIo = 0;
   for (int io = 0; io < nO; io++)
   {
     const bioem_hip_prob_angle pa = pang[(size_t) io * nMaps + p];
-    const double logp = log(pa.forAngles) + pa.ConstAngle + numconst;
+    const double logp = cand_key(pa, numconst);
     bool rescan = false;
     if (cnt < K)
     {
-      bioem_hip_angle_candidate c;
-      c.forAngles = pa.forAngles;
-      c.ConstAngle = pa.ConstAngle;
-      c.logp = logp;
-      c.orient = o0 + io;
-      c.pad = 0;
-      mine[cnt++] = c;
+      mine[cnt++] = cand_make(pa, logp, o0 + io);
       rescan = cnt == K;
     }
     else if (minLogp < logp)
     {
-      bioem_hip_angle_candidate c;
-      c.forAngles = pa.forAngles;
-      c.ConstAngle = pa.ConstAngle;
-      c.logp = logp;
-      c.orient = o0 + io;
-      c.pad = 0;
-      mine[minSlot] = c;
+      mine[minSlot] = cand_make(pa, logp, o0 + io);
       rescan = true;
     }
     if (rescan)
@@ -515,15 +537,32 @@ __global__ void k_topk_angles(const bioem_hip_prob_angle *__restrict__ pang, int
     }
   }
   for (int a = cnt; a < K; a++)
+    mine[a] = cand_unused();
+  if (W == K)
+    return;
+  // second walk: the set is full only when the block holds more than K - 1 entries; minLogp is then its threshold t
+  int extra = K;
+  if (cnt == K && nO > K)
   {
-    bioem_hip_angle_candidate c;
-    c.forAngles = 0.;
-    c.ConstAngle = MIN_PROB;
-    c.logp = -INFINITY;
-    c.orient = -1;
-    c.pad = 0;
-    mine[a] = c;
+    int seen = 0; // entries of key >= t met so far
+    for (int io = 0; io < nO && seen < K && extra < W; io++)
+    {
+      const bioem_hip_prob_angle pa = pang[(size_t) io * nMaps + p];
+      const double logp = cand_key(pa, numconst);
+      if (logp < minLogp)
+        continue;
+      seen++;
+      if (logp != minLogp)
+        continue;
+      bool kept = false;
+      for (int j = 0; j < K; j++)
+        kept = kept || mine[j].orient == o0 + io;
+      if (!kept)
+        mine[extra++] = cand_make(pa, logp, o0 + io);
+    }
   }
+  for (int a = extra; a < W; a++)
+    mine[a] = cand_unused();
 }
 
 // fold of the gathered shards' map entries (bioem.cpp:909-994 restated for one address space): shard s's entries start

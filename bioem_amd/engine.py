@@ -149,6 +149,10 @@ def load_library():
     L.bioem_hip_phase_records.argtypes = [vp, vp, ci, C.POINTER(ci)]
     L.bioem_hip_topk_angles.argtypes = [vp, ci, C.c_double, vp]
     L.bioem_hip_merge_topk_host.argtypes = [ci, ci, ci, C.POINTER(vp), vp]
+    L.bioem_hip_merge_candidates.argtypes = [vp, ci, C.c_double, vp]
+    L.bioem_hip_merge_topk_host_wide.argtypes = [ci, ci, ci, ci, C.POINTER(vp), vp]
+    L.bioem_hip_debug_topk.argtypes = [vp, vp, ci, ci, ci, ci, ci, C.c_double, vp]
+    L.bioem_hip_debug_merge_gathered.argtypes = [vp, vp, ci, ci, vp, vp]
     L.bioem_hip_merge.argtypes = [C.POINTER(vp), ci, vp, ci, C.c_double, vp]
     L.bioem_hip_merge_host.argtypes = [ci, ci, ci, ci, C.POINTER(vp), vp]
     L.bioem_hip_debug_projection.argtypes = [vp, ci, vp]
@@ -175,7 +179,8 @@ def load_library():
 
 EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard", "bioem_hip_destroy",
            "bioem_hip_last_error", "bioem_hip_project_convolve_compare_ctf", "bioem_hip_topk_angles",
-           "bioem_hip_merge_topk_host", "bioem_hip_merge",
+           "bioem_hip_merge_topk_host", "bioem_hip_merge", "bioem_hip_merge_candidates", "bioem_hip_merge_topk_host_wide",
+           "bioem_hip_debug_topk", "bioem_hip_debug_merge_gathered",
            "bioem_hip_upload_particles", "bioem_hip_upload_particle_maps", "bioem_hip_upload_ctf",
            "bioem_hip_upload_model", "bioem_hip_upload_orientations", "bioem_hip_host_alloc",
            "bioem_hip_host_free", "bioem_hip_prob_size", "bioem_hip_start_run", "bioem_hip_compare",
@@ -532,10 +537,44 @@ class Engine:
         self._chk(self.L.bioem_hip_finish_run(self.h, _p(raw)), "finish_run")
 
     def topk_angles(self, K, numconst):
-        """K best orientations per particle among the owned ones, selected on the device: [nMaps, K] CANDIDATE_DTYPE"""
+        """K best orientations per particle among the owned ones, selected on the device: [nMaps, K] CANDIDATE_DTYPE.
+        The writer's result for a handle that owns the whole list.  The merge of shards' K-wide lists reproduces the
+        writer only while no equal keys meet a shard's threshold; merge_candidates gives the lists that always do."""
         out = np.zeros((self.nMaps, K), dtype=CANDIDATE_DTYPE)
         self._chk(self.L.bioem_hip_topk_angles(self.h, K, float(numconst), _p(out)), "topk_angles")
         return out
+
+    def merge_candidates(self, K, numconst):
+        """what a shard contributes to a merge: [nMaps, 2K - 1] CANDIDATE_DTYPE, slots 0 ... K-1 = topk_angles, then in
+        ascending orientation the entries of the K-th best key that the block's own walk rejected or evicted but a walk
+        over the whole list may keep (include/bioem_hip.h); orient = -1 in unused slots.  merge_topk_host(lists, K=K)
+        of such lists is the writer's K best of the whole table for any keys and any cut."""
+        out = np.zeros((self.nMaps, 2 * K - 1), dtype=CANDIDATE_DTYPE)
+        self._chk(self.L.bioem_hip_merge_candidates(self.h, K, float(numconst), _p(out)), "merge_candidates")
+        return out
+
+    def debug_topk(self, table, o0, K, W, numconst):
+        """test hook: the selection kernel of topk_angles / merge_candidates on a table handed in, PROB_ANGLE_DTYPE
+        [nO, nMaps] whose first row is orientation o0; W = K or 2K - 1.  Returns CANDIDATE_DTYPE [nMaps, W]."""
+        table = np.ascontiguousarray(table, dtype=PROB_ANGLE_DTYPE)
+        nO, nMaps = table.shape
+        out = np.zeros((nMaps, W), dtype=CANDIDATE_DTYPE)
+        self._chk(self.L.bioem_hip_debug_topk(self.h, _p(table), nO, nMaps, int(o0), int(K), int(W), float(numconst),
+                                              _p(out)), "debug_topk")
+        return out
+
+    def debug_merge_gathered(self, gathered, nShards, K):
+        """test hook: what bioem_hip_merge does after its all-gather, on `gathered` = nShards payloads (uint8; per
+        payload nMaps map entries, then with K > 0 nMaps lists of 2K - 1 candidates).  Returns (PROB_MAP_DTYPE [nMaps],
+        CANDIDATE_DTYPE [nMaps, K] or None)."""
+        gathered = np.ascontiguousarray(gathered, dtype=np.uint8).reshape(-1)
+        payload = self.nMaps * (PROB_MAP_DTYPE.itemsize + (CANDIDATE_DTYPE.itemsize * (2 * K - 1) if K > 0 else 0))
+        assert gathered.size == nShards * payload
+        pmap = np.zeros(self.nMaps, dtype=PROB_MAP_DTYPE)
+        cand = np.zeros((self.nMaps, K), dtype=CANDIDATE_DTYPE) if K > 0 else None
+        self._chk(self.L.bioem_hip_debug_merge_gathered(self.h, _p(gathered), int(nShards), int(K), _p(pmap), _p(cand)),
+                  "debug_merge_gathered")
+        return pmap, cand
 
     def render_best_maps(self, pmap, p0=0, p1=None, own=False):
         """the calculated image of the best match of particles [p0, p1): float32 [p1 - p0, N, N] with
@@ -1100,15 +1139,20 @@ def r2c(images, device=0):
     return out
 
 
-def merge_topk_host(cands):
-    """K-way merge of per-shard candidate lists ([nMaps, K] each, shards in ascending orientation-block order)."""
+def merge_topk_host(cands, K=None):
+    """Merge of per-shard candidate lists ([nMaps, W] each): the writer's heap rule over their union, [nMaps, K].
+    K = None: K-wide lists (Engine.topk_angles), K = W; they reproduce the writer of the whole table only while no
+    equal keys meet a shard's threshold.  With K given, the lists are Engine.merge_candidates' (W = 2K - 1, or any
+    W >= K), which always reproduce it."""
     L = load_library()
-    nMaps, K = cands[0].shape
+    nMaps, W = cands[0].shape
+    K = W if K is None else int(K)
     cands = [np.ascontiguousarray(c, dtype=CANDIDATE_DTYPE) for c in cands]
+    assert all(c.shape == (nMaps, W) for c in cands)
     out = np.zeros((nMaps, K), dtype=CANDIDATE_DTYPE)
     arr = (C.c_void_p * len(cands))(*[c.ctypes.data for c in cands])
-    if L.bioem_hip_merge_topk_host(len(cands), nMaps, K, arr, _p(out)):
-        raise RuntimeError("bioem_hip_merge_topk_host failed")
+    if L.bioem_hip_merge_topk_host_wide(len(cands), nMaps, K, W, arr, _p(out)):
+        raise RuntimeError("bioem_hip_merge_topk_host_wide failed")
     return out
 
 

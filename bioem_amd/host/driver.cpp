@@ -1312,15 +1312,18 @@ int Driver::run()
       fatal("merge failed");
     if (K)
     {
+      // lists of 2K - 1: the K best and the tie candidates, so that the merge is the writer's walk over the whole table
+      // whatever keys are equal (K-wide lists are not enough then)
+      const int W = 2 * K - 1;
       std::vector<std::vector<bioem_hip_angle_candidate>> lists(nShards);
       std::vector<const bioem_hip_angle_candidate *> ptrs(nShards);
       for (int g = 0; g < nShards; g++)
       {
-        lists[g].resize((size_t) nMaps * K);
-        check(shards[g].h, bioem_hip_topk_angles(shards[g].h, K, numconst, lists[g].data()), "top-K orientations");
+        lists[g].resize((size_t) nMaps * W);
+        check(shards[g].h, bioem_hip_merge_candidates(shards[g].h, K, numconst, lists[g].data()), "top-K orientations");
         ptrs[g] = lists[g].data();
       }
-      if (bioem_hip_merge_topk_host(nShards, nMaps, K, ptrs.data(), cand.data()))
+      if (bioem_hip_merge_topk_host_wide(nShards, nMaps, K, W, ptrs.data(), cand.data()))
         fatal("merge failed");
     }
   }
@@ -1504,8 +1507,8 @@ static void compose_list(const float *b, const std::vector<float> &grid, float *
 }
 
 // Round 2 around SEVERAL orientations per particle (--RefineSeeds M >= 2, --RefineLogWindow W): the seeds of particle p
-// are the first of its M best orientations of round 1 (the ANG_PROB ranking: bioem_hip_topk_angles, or the merged top-K
-// over shards) and those of the others whose log posterior lies within W of the first's, in that order; its list is the
+// are the first of its M best orientations of round 1 (the ANG_PROB ranking: bioem_hip_topk_angles, or over shards the
+// merge of the lists of bioem_hip_merge_candidates, which is that ranking under equal keys too) and those of the others whose log posterior lies within W of the first's, in that order; its list is the
 // concatenation of seed (x) grid over its seeds, no duplicates removed (bioem_amd/refine.py: seed_lists).  The lists
 // differ in length, and the line of particle p carries ITS constant: volu of a list of K_p orientations, what a run on
 // that particle alone with its list through --ReadOrientation prints.

@@ -262,12 +262,38 @@ int bioem_hip_render_best_maps(bioem_hip_handle h, const bioem_hip_prob_map *rec
 /* WRITE_PROB_ANGLES without moving the table: selects on the device the K best orientations of every particle among
  * the orientations this handle owns, with the reference writer's own rule (a K-entry min-heap on (logp, orientation)
  * walked in orientation order, bioem.cpp:1251-1286; numconst as computed at bioem.cpp:1141-1150).  out = [nMaps][K],
- * best first; entries beyond the owned orientation count have orient = -1.  Call after finish_run. */
+ * best first; entries beyond the owned orientation count have orient = -1.  Call after finish_run.
+ * For a handle that owns the whole list this IS the writer's result.  For shards, the K best of the union of such
+ * K-wide lists is the writer's result only while no equal keys meet a shard's threshold: a heap that is full rejects
+ * the newest of equal keys and evicts the oldest, so which of them survive depends on what the earlier blocks held.
+ * Lists for a merge come from bioem_hip_merge_candidates, which always reproduces the writer. */
 int bioem_hip_topk_angles(bioem_hip_handle h, int K, double numconst, bioem_hip_angle_candidate *out);
-/* K-way merge of the shards' candidate lists (shards in ascending orientation-block order): the K best of the union,
- * same heap rule.  cands[s] = [nMaps][K]; out = [nMaps][K], best first. */
+/* The list a shard contributes to a merge: out = [nMaps][2K - 1].  Slots 0 ... K-1 are exactly what
+ * bioem_hip_topk_angles returns.  Slots K ... 2K-2 hold, in ascending orientation, the entries whose key equals the
+ * K-th best key t of the block, that lie among the block's first K entries of key >= t, and that the block's own walk
+ * rejected or evicted (at most K - 1); unused slots are (0, MIN_PROB, -inf, -1).  The writer's loop over the union of
+ * the shards' lists, in orientation order (bioem_hip_merge_topk_host_wide with W = 2K - 1), equals the writer's loop
+ * over the whole table for any keys and any cut into blocks. */
+int bioem_hip_merge_candidates(bioem_hip_handle h, int K, double numconst, bioem_hip_angle_candidate *out);
+/* Merge of the shards' candidate lists (any shard order: the union is sorted by orientation): the writer's heap rule
+ * over the union.  cands[s] = [nMaps][W] with W >= K, slots with orient < 0 are skipped; out = [nMaps][K], best
+ * first, unused slots (0, MIN_PROB, -inf, -1).  W = 2K - 1 with lists of bioem_hip_merge_candidates reproduces the
+ * writer; bioem_hip_merge_topk_host is the same call with W = K, for K-wide lists (see bioem_hip_topk_angles for
+ * what those cannot guarantee).  No device.  Returns 2 for nShards < 1, K < 1, W < K or a null argument. */
+int bioem_hip_merge_topk_host_wide(int nShards, int nMaps, int K, int W, const bioem_hip_angle_candidate *const *cands,
+                                   bioem_hip_angle_candidate *out);
 int bioem_hip_merge_topk_host(int nShards, int nMaps, int K, const bioem_hip_angle_candidate *const *cands,
                               bioem_hip_angle_candidate *out);
+/* test hooks, no RCCL.  bioem_hip_debug_topk: the selection kernel with the launch shape of the two entries above on a
+ * table handed in, table = [nO][nMaps] on the host, o0 the global index of its first row, W = K or 2K - 1,
+ * out = [nMaps][W].  bioem_hip_debug_merge_gathered: the half of bioem_hip_merge that follows the all-gather, on
+ * `gathered` = nShards payloads of nMaps map entries followed (K > 0) by nMaps lists of 2K - 1 candidates, as the
+ * all-gather leaves them, for the handle's nMaps; maps_out = [nMaps] map entries, cand_out = [nMaps][K] (NULL with
+ * K = 0).  Both return 2 with a message for a null argument or a shape they do not serve. */
+int bioem_hip_debug_topk(bioem_hip_handle h, const bioem_hip_prob_angle *table, int nO, int nMaps, int o0, int K, int W,
+                         double numconst, bioem_hip_angle_candidate *out);
+int bioem_hip_debug_merge_gathered(bioem_hip_handle h, const void *gathered, int nShards, int K, void *maps_out,
+                                   bioem_hip_angle_candidate *cand_out);
 
 /* Log-sum-exp merge of orientation shards (replaces the MPI merge of bioem.cpp:909-1044) on the host:
  * shards = nShards probability blocks of identical shape, out = merged block.  Ties on Constoadd go to
@@ -275,8 +301,8 @@ int bioem_hip_merge_topk_host(int nShards, int nMaps, int K, const bioem_hip_ang
 int bioem_hip_merge_host(int nShards, int nMaps, int nAngles, int writeAngles, const void *const *shards, void *out);
 
 /* The path's single exchange step over RCCL / xGMI (replaces the MPI merge of bioem.cpp:909-1044) for n handles on n
- * DIFFERENT GPUs of this process: every device contributes its nMaps map entries -- and, when K > 0, its K best
- * orientations per particle (bioem_hip_topk_angles) -- to ONE ncclAllGather; the device of handles[0] folds the
+ * DIFFERENT GPUs of this process: every device contributes its nMaps map entries -- and, when K > 0, its list of
+ * 2K - 1 candidates per particle (bioem_hip_merge_candidates) -- to ONE ncclAllGather; the device of handles[0] folds the
  * gathered shards (log-sum-exp of Total / Constoadd, arg-max record from the lowest shard holding the maximum =
  * lowest orientation index; candidates by the heap rule) and the result is copied to the host.
  * pProbMaps_host = [nMaps] bioem_hip_prob_map, cand_host = [nMaps][K] or NULL when K == 0.  Call after every handle's

@@ -42,8 +42,8 @@ def main():
     E.start_run(raw)
     E.project_convolve_compare(o0, o1)
     E.finish_run(raw)
-    cands = E.topk_angles(K, orc.logp_constant(S.pd)) if K else None
-    merged = merge_prob_maps(pmap, dev, cands=cands)
+    cands = E.merge_candidates(K, orc.logp_constant(S.pd)) if K else None          # 2K - 1 wide: ties at a rank's threshold
+    merged = merge_prob_maps(pmap, dev, cands=cands, K=K if K else None)
     if K:
         merged, mc = merged
         np.save(os.path.join(outdir, "cands_%d.npy" % rank), mc)

@@ -1,7 +1,6 @@
 """world_size-2 gloo tests (CPU) of the N>1 path: orientation blocks per rank + one all-gather + log-sum-exp merge over
 torch.distributed, against the oracle's unsharded run -- the map entries, the arg-max orientation of ranks that number
 their block from 0 (orient_offset), and with WRITE_PROB_ANGLES the K best orientations per particle."""
-import heapq
 import math
 import os
 import socket
@@ -49,23 +48,24 @@ def _worker(rank, world, port, outdir):
 
 
 def _block_candidates(pang, o0, o1, K, numconst):
-    """What bioem_hip_topk_angles returns for the block [o0, o1): the writer's heap rule (bioem.cpp:1251-1286)."""
+    """What bioem_hip_merge_candidates returns for the block [o0, o1): the K best by the writer's heap rule
+    (bioem.cpp:1251-1286), then the tie candidates, 2K - 1 slots in all (merge_reference.shard_list)."""
     from bioem_amd.engine import CANDIDATE_DTYPE
-    nMaps = pang.shape[1]
-    out = np.zeros((nMaps, K), dtype=CANDIDATE_DTYPE)
+    from merge_reference import shard_list
+    nMaps, W = pang.shape[1], 2 * K - 1
+    out = np.zeros((nMaps, W), dtype=CANDIDATE_DTYPE)
+    out["ConstAngle"] = -999999.0
     out["orient"] = -1
     out["logp"] = -np.inf
     for m in range(nMaps):
-        q = []
+        keys = []
         for io in range(o0, o1):
             pa = pang[io, m]
-            logp = (math.log(pa["forAngles"]) if pa["forAngles"] > 0 else -math.inf) + pa["ConstAngle"] + numconst
-            if len(q) < K:
-                heapq.heappush(q, (logp, io))
-            elif q[0][0] < logp:
-                heapq.heapreplace(q, (logp, io))
-        for k, (lp, io) in enumerate(sorted(q, reverse=True)):
-            out[m, k] = (pang[io, m]["forAngles"], pang[io, m]["ConstAngle"], lp, io, 0)
+            keys.append((math.log(pa["forAngles"]) if pa["forAngles"] > 0 else -math.inf) + pa["ConstAngle"] + numconst)
+        for k, x in enumerate(shard_list(keys, o0, K, W)):
+            if x is not None:
+                lp, io = x
+                out[m, k] = (pang[io, m]["forAngles"], pang[io, m]["ConstAngle"], lp, io, 0)
     return out
 
 
@@ -87,7 +87,7 @@ def _worker_angles(rank, world, port, outdir):
     o0, o1 = rank * nA // world, (rank + 1) * nA // world
     pm, pang = S.run(1, o0, o1)
     cands = _block_candidates(pang, o0, o1, K, orc.logp_constant(S.pd))
-    merged, mc = merge_prob_maps(pm, torch.device("cpu"), cands=cands)
+    merged, mc = merge_prob_maps(pm, torch.device("cpu"), cands=cands, K=K)
     np.save(os.path.join(outdir, "merged_%d.npy" % rank), merged)
     np.save(os.path.join(outdir, "cands_%d.npy" % rank), mc)
     dist.barrier()
@@ -112,8 +112,8 @@ def test_two_rank_merge_matches_unsharded(tmp_path):
 
 
 def test_two_rank_merge_of_the_k_best_orientations(tmp_path):
-    """WRITE_PROB_ANGLES across ranks: every orientation has one owner, so each rank ships its K best per particle and
-    the K best of the union must be the K best of the unsharded table (ANG_PROB of the reference, g4)."""
+    """WRITE_PROB_ANGLES across ranks: every orientation has one owner, so each rank ships its list of 2K - 1 candidates per
+    particle and the writer's walk over the union must be the K best of the unsharded table (ANG_PROB of the reference, g4)."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import oracle as orc
     from golden_util import load_case, oracle_setup

@@ -31,7 +31,6 @@ Strength (scratch copies of k_fold_wave, not committed): the last row of lane 7'
 equal), d (SNR 0.03) and e; `<=` for `<` in the launch-to-launch update fails c (launches and calls) and e; `i2 > idx` in
 the shuffle's tie rule fails c (lanes, every row equal).
 """
-import heapq
 import math
 
 import mpmath
@@ -39,6 +38,7 @@ import numpy as np
 import pytest
 
 from fold_reference import MIN_PROB, PREC, bound, fold, log_entry
+from merge_reference import writer_heap
 
 pytestmark = pytest.mark.gpu
 
@@ -578,18 +578,6 @@ def test_f_own_lists_three_ctf_sets(mode):
 # ------------------------------------------------------------------------------------------------------
 # g. k_topk_angles with equal keys: the reference writer's heap, restated on the host
 # ------------------------------------------------------------------------------------------------------
-def writer_heap(logp, K):
-    """a K-entry min-heap of (logp, orientation) walked in orientation order; a newcomer replaces the minimum only when
-    the minimum's logp is strictly below its own; emptied, the heap reads best first in descending (logp, orientation)"""
-    q = []
-    for io, lp in enumerate(logp):
-        if len(q) < K:
-            heapq.heappush(q, (float(lp), io))
-        elif q[0][0] < lp:
-            heapq.heapreplace(q, (float(lp), io))
-    return sorted(q, reverse=True)
-
-
 def test_g_topk_with_equal_keys(tie_rig):
     plain, pool = tie_rig
     K, T, numconst = 5, 130, -1234.5
