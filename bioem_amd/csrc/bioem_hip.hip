@@ -147,6 +147,7 @@ struct HipErr
 #include "grad_kernels.hpp"
 #include "recon_kernels.hpp"
 #include "slice_kernels.hpp"
+#include "vgrad_kernels.hpp"
 #include "soft_kernels.hpp"
 #include "orient_kernels.hpp"
 
@@ -186,6 +187,18 @@ struct bioem_hip_ctx
   // [PN][PN][PH], PN = volPad N; null with a point model -- a handle holds one kind, an upload replaces the other
   double2 *dVolC = nullptr;
   int volPad = 0;
+  // what the upload was given, for the transpose of its passes (bioem_hip_volume_gradient): the centre, the flag word and
+  // whether the model came as a spectrum
+  double volCentre[3] = {0., 0., 0.};
+  int volFlags = 0;
+  bool volFromSpectrum = false;
+  // bioem_hip_volume_gradient / _debug_volume_backproject / _debug_volume_adjoint (vgrad_kernels.hpp): A beside C (volAPad:
+  // the padding it is sized for), the matrices, view parameters and flags of a launch of the scan, Y and the double slices
+  // of a batch (allocated at the first call)
+  double2 *dVolA = nullptr, *dVgY = nullptr, *dVgSlices = nullptr;
+  int volAPad = 0;
+  double *dVgR = nullptr, *dVgView = nullptr;
+  int *dVgFlag = nullptr;
   // bioem_hip_debug_slices: angles, matrices and slices of a chunk of maxOrientations (allocated at the first call)
   float4 *dSliceAngles = nullptr;
   double *dSliceR = nullptr;
@@ -1791,7 +1804,8 @@ int bioem_hip_upload_model(bioem_hip_handle h, const bioem_hip_model_point *pts,
   { // the points replace a volume model: nothing queued may still read it
     HIP_CHECK(h, hipDeviceSynchronize());
     dev_release(h, h->dVolC);
-    h->volPad = 0;
+    dev_release(h, h->dVolA); // (bioem_hip_volume_gradient's A beside C goes with the volume)
+    h->volPad = h->volAPad = 0;
     void_slot(h->slot[0]); // (what a slot holds staged are slices of the volume)
     void_slot(h->slot[1]);
   }
@@ -5051,7 +5065,8 @@ void centre_table(int PN, double c, double2 *e)
 
 // spec on the device ([PN][PN][PH], un-centred; owned by the caller, not yet a field of the handle) becomes the handle's
 // model: centred, Re C(0) checked, and only then the model it replaces goes.  dSpec is released on every failure.
-int volume_commit(bioem_hip_ctx *h, const Refuse &refuse, double2 *dSpec, int pad, const double *centre, int shiftX, int shiftY)
+int volume_commit(bioem_hip_ctx *h, const Refuse &refuse, double2 *dSpec, int pad, const double *centre, int shiftX, int shiftY,
+                  int flags, bool fromSpectrum)
 {
   const int N = h->N, PN = pad * N, o = (N + 1) / 2;
   std::vector<double2> tab((size_t) 4 * PN);
@@ -5096,6 +5111,11 @@ int volume_commit(bioem_hip_ctx *h, const Refuse &refuse, double2 *dSpec, int pa
     return 1;
   }
   dev_release(h, h->dVolC);
+  if (h->volAPad != pad)
+  { // A beside C is kept for a model of the same size only
+    dev_release(h, h->dVolA);
+    h->volAPad = 0;
+  }
   dev_release(h, h->dPts);
   dev_release(h, h->dStamp);
   h->nPts = 0;
@@ -5103,6 +5123,10 @@ int volume_commit(bioem_hip_ctx *h, const Refuse &refuse, double2 *dSpec, int pa
   h->modelRadius = 0.;
   h->dVolC = dSpec;
   h->volPad = pad;
+  for (int d = 0; d < 3; d++)
+    h->volCentre[d] = centre ? centre[d] : 0.;
+  h->volFlags = flags;
+  h->volFromSpectrum = fromSpectrum;
   h->NormDen = (float) c0.x;
   h->shiftX = shiftX;
   h->shiftY = shiftY;
@@ -5147,7 +5171,7 @@ int bioem_hip_upload_model_spectrum(bioem_hip_handle h, const double *spec, int 
     (void) hipGetLastError();
     return 1;
   }
-  return volume_commit(h, refuse, dSpec, pad, centre, shiftX, shiftY);
+  return volume_commit(h, refuse, dSpec, pad, centre, shiftX, shiftY, 0, true);
 }
 
 int bioem_hip_upload_model_volume(bioem_hip_handle h, const float *vol, int pad, int flags, const double *centre, int shiftX,
@@ -5222,7 +5246,7 @@ int bioem_hip_upload_model_volume(bioem_hip_handle h, const float *vol, int pad,
     dev_release(h, dSpec);
     return 1;
   }
-  return volume_commit(h, refuse, dSpec, pad, centre, shiftX, shiftY);
+  return volume_commit(h, refuse, dSpec, pad, centre, shiftX, shiftY, flags, false);
 }
 
 int bioem_hip_debug_slices(bioem_hip_handle h, const float *angles4, int n, int isQuat, double *out)
@@ -5265,6 +5289,357 @@ int bioem_hip_debug_slices(bioem_hip_handle h, const float *angles4, int n, int 
     HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
   return 0;
+}
+
+} // extern "C" (closed around the helpers of the volume gradient)
+
+// ---- the gradient with respect to the voxels of a volume model (vgrad_kernels.hpp) ----
+namespace
+{
+// the staging of the volume-gradient entries; a failed allocation (return 1) leaves the handle as it was
+int vgrad_staging(bioem_hip_ctx *h)
+{
+  const size_t OB = (size_t) h->OB, M = (size_t) h->M, cap = (size_t) scan_capacity(h);
+  if (!h->dVgY)
+  {
+    Staging st = {h};
+    st.get(h->dVgY, OB * M);
+    st.get(h->dVgSlices, OB * M);
+    st.get(h->dVgR, 9 * cap);
+    st.get(h->dVgView, (size_t) kVgradViewDoubles * cap);
+    st.get(h->dVgFlag, cap);
+    if (st.commit())
+      return 1;
+  }
+  if (h->volAPad != h->volPad)
+  { // A beside C: 16 PN^2 PH bytes
+    const size_t PN = (size_t) h->volPad * h->N;
+    Staging st = {h};
+    st.get(h->dVolA, PN * PN * (PN / 2 + 1));
+    if (st.commit())
+      return 1;
+    h->volAPad = h->volPad;
+  }
+  return 0;
+}
+
+std::string vgrad_flag_reason(int flag)
+{
+  if (flag == 1)
+    return "rows 0 and 1 of the orientation's matrix are rank-deficient or not finite";
+  char buf[128];
+  snprintf(buf, sizeof(buf), "the orientation's matrix shrinks too much: candidate half-width beyond %.1f", kVgradHalfCap);
+  return buf;
+}
+
+// matrices, view parameters and flags of the n orientations angles[0 ... n), left on the device
+int vgrad_views(bioem_hip_ctx *h, const float4 *dAngles, int isQuat, int n)
+{
+  HIP_CHECK(h, bioem_recon_matrices_launch(h->stream, dAngles, nullptr, isQuat ? 1 : 0, n, h->dVgR));
+  HIP_CHECK(h, bioem_vgrad_views_launch(h->stream, h->dVgR, n, h->volPad, h->dVgView, h->dVgFlag));
+  return 0;
+}
+
+// the same, and the flags looked at on the host; first: the first flagged view, or -1
+int vgrad_views_checked(bioem_hip_ctx *h, const float4 *dAngles, int isQuat, int n, int &first, int &flag)
+{
+  std::vector<int> flags((size_t) n);
+  if (vgrad_views(h, dAngles, isQuat, n))
+    return 1;
+  HIP_CHECK(h, hipMemcpyAsync(flags.data(), h->dVgFlag, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  first = -1;
+  flag = 0;
+  for (int i = 0; i < n && first < 0; i++)
+    if (flags[(size_t) i])
+    {
+      first = i;
+      flag = flags[(size_t) i];
+    }
+  return 0;
+}
+
+// gvol [N][N][N] on the host from A on the device (which becomes A_spec): the un-centring, the three passes and the
+// real part, divided by the sinc^2 product where the model was uploaded as a volume with precorrection
+int vgrad_adjoint(bioem_hip_ctx *h, const char *what, double2 *dA, double *vol_out)
+{
+  const size_t N = (size_t) h->N, PN = (size_t) h->volPad * N, PH = PN / 2 + 1, NNN = N * N * N;
+  const int o = (int) ((N + 1) / 2);
+  const int correct = (h->volFlags & BIOEM_HIP_VOLUME_PRECORRECT) && !h->volFromSpectrum;
+  std::vector<double2> tab(4 * PN);
+  for (size_t j = 0; j < PN; j++)
+    tab[j] = twiddle_d((long long) j, (int) PN);
+  for (int d = 0; d < 3; d++)
+    centre_table((int) PN, h->volCentre[d], tab.data() + (size_t) (d + 1) * PN);
+  std::vector<double> sinc2(N, 1.);
+  if (correct)
+    for (size_t x = 0; x < N; x++)
+    { // (the table of bioem_hip_upload_model_volume)
+      const double t = M_PI * ((double) x - (double) ((N + 1) / 2)) / (double) PN;
+      const double s = t == 0. ? 1. : sin(t) / t;
+      sinc2[x] = s * s;
+    }
+  double2 *dT1 = nullptr, *dT2 = nullptr, *dTab = nullptr;
+  double *dG = nullptr, *dSinc = nullptr;
+  // axis 0: [PN][PN][PH] -> [N][PN][PH]; axis 1: -> [N][N][PH]; axis 2: -> [N][N][N] (in the buffer of the first pass)
+  int rc = dev_alloc(h, dT1, std::max(N * PN * PH, NNN)) || dev_alloc(h, dT2, N * N * PH) || dev_alloc(h, dTab, 4 * PN) ||
+           dev_alloc(h, dG, NNN) || dev_alloc(h, dSinc, N);
+  if (!rc)
+  {
+    hipError_t e = hipMemcpyAsync(dTab, tab.data(), sizeof(double2) * 4 * PN, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(dSinc, sinc2.data(), sizeof(double) * N, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess)
+      e = bioem_vgrad_uncentre_launch(h->stream, dA, (int) PN, o, dTab, dTab + PN);
+    if (e == hipSuccess)
+      e = bioem_vgrad_axis_launch(h->stream, dA, 1, (int) PN, (int) N, PN * PH, (int) PN, dTab, dT1);
+    if (e == hipSuccess)
+      e = bioem_vgrad_axis_launch(h->stream, dT1, N, (int) PN, (int) N, PH, (int) PN, dTab, dT2);
+    if (e == hipSuccess)
+      e = bioem_vgrad_axis_launch(h->stream, dT2, N * N, (int) PH, (int) N, 1, (int) PN, dTab, dT1);
+    if (e == hipSuccess)
+      e = bioem_vgrad_finish_launch(h->stream, dT1, (int) N, dSinc, correct, dG);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(vol_out, dG, sizeof(double) * NNN, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess)
+      e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess)
+    {
+      h->err = std::string(what) + " failed: " + hipGetErrorString(e);
+      rc = 1;
+    }
+  }
+  else
+    (void) hipGetLastError();
+  dev_release(h, dT1);
+  dev_release(h, dT2);
+  dev_release(h, dTab);
+  dev_release(h, dG);
+  dev_release(h, dSinc);
+  return rc;
+}
+} // namespace
+
+extern "C" {
+
+int bioem_hip_volume_gradient(bioem_hip_handle h, const bioem_hip_grad_request *req, const double *weights, int n, int ownLists,
+                              double *vol_out, double *spec_out, double *coef_out, bioem_hip_param5 *params_out,
+                              double *stats_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "volume_gradient"};
+  if (!req || n < 1)
+    return refuse("null argument or no requests");
+  if (!vol_out && !spec_out)
+    return refuse("vol_out and spec_out both null");
+  if (const char *why = missing_state(h, NEED_ALL, ownLists))
+    return refuse(why);
+  if (!h->dVolC)
+    return refuse("the model is a point model");
+  const int N = h->N, OB = h->OB, G = h->nCTF, pad = h->volPad;
+  const int cap = scan_capacity(h); // records one launch of the scan serves: whole batches
+  std::vector<BioemWindowRecord> recs((size_t) n);
+  std::vector<BioemScanShift> shifts((size_t) n);
+  std::vector<BioemGradRecord> grecs((size_t) n);
+  std::vector<double> ws((size_t) n, 1.);
+  double sumw = 0.;
+  for (int i = 0; i < n; i++)
+  {
+    const bioem_hip_grad_request &r = req[i];
+    int first, len;
+    const char *why = bad_request(h, r, REQ_CONV | REQ_SHIFT, ownLists, first, len);
+    if (!why && weights && !std::isfinite(weights[i]))
+      why = "weight not finite";
+    if (why)
+      return refuse(request_refusal(h, i, why, r, REQ_CONV | REQ_SHIFT, len));
+    recs[(size_t) i] = {first + r.orient, r.conv, r.particle, 0, {0.f, 0.f}};
+    shifts[(size_t) i] = {r.shiftX, r.shiftY};
+    grecs[(size_t) i] = {r.conv, r.particle, (i % cap) * G + r.conv, 0};
+    if (weights)
+      ws[(size_t) i] = weights[i];
+    sumw += ws[(size_t) i];
+  }
+  if (grad_staging(h, G, 0) || vgrad_staging(h) || begin_analysis(h, true))
+    return 1;
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  const OrientList src = ownLists ? own_list(h) : shared_list(h);
+  const size_t M = (size_t) h->M, PN = (size_t) pad * N, V = PN * PN * (PN / 2 + 1);
+  // every request's matrix is looked at before anything is inserted: a refusal leaves nothing half done
+  for (int g0 = 0; g0 < n; g0 += cap)
+  {
+    const int ng = std::min(cap, n - g0);
+    int bad, flag;
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
+    if (gather_matches(h, src, h->dScanRec, ng, h->dGradAngles) ||
+        vgrad_views_checked(h, h->dGradAngles, src.isQuat, ng, bad, flag))
+      return 1;
+    if (bad >= 0)
+    {
+      int first, len;
+      orient_span(h, ownLists, req[g0 + bad].particle, first, len);
+      return refuse(request_refusal(h, g0 + bad, vgrad_flag_reason(flag).c_str(), req[g0 + bad], REQ_CONV | REQ_SHIFT, len));
+    }
+  }
+  std::vector<double> coef(4 * (size_t) std::min(cap, n));
+  double notFinite = 0.;
+  for (int g0 = 0; g0 < n; g0 += cap) // the requests one launch of the scan serves
+  {
+    const int ng = std::min(cap, n - g0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradRec, grecs.data() + g0, sizeof(BioemGradRecord) * ng, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradW, ws.data() + g0, sizeof(double) * ng, hipMemcpyHostToDevice, h->stream));
+    if (gather_matches(h, src, h->dScanRec, ng, h->dGradAngles) || vgrad_views(h, h->dGradAngles, src.isQuat, ng))
+      return 1;
+    // the front half of bioem_hip_model_gradient, unchanged: per batch the projection and the scan's preparation
+    for (int b0 = 0; b0 < ng; b0 += OB)
+    {
+      const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
+      HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shifts.data() + r0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
+      if (project_matches(h, src, h->dGradAngles, b0, nb, r0))
+        return 1;
+      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, r0, r0 + nb, 0, 0))
+        return 1;
+      if (r0 == 0 && grad_candidates(h)) // (part of the first batch's preparation)
+        return 1;
+      if (unreorder_runs(h, recs.data() + r0, nb, h->dWinRef))
+        return 1;
+      HIP_CHECK(h, bioem_scan_prep_launch(h->stream, s0.specRef, h->dWinRef, h->dScanShift, nb, N, h->dTwD,
+                                          h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0));
+      if (phase_end(h, h->stream))
+        return 1;
+    }
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, g0, g0 + ng, 0, 0))
+      return 1;
+    HIP_CHECK(h, bioem_scan_launch(h->stream, h->dScanPacked, h->dScanCtf, G, h->dScanPw, h->dScanZ, h->dScanRec, h->dSumRef,
+                                   h->dSumsqRef, h->pd, ng, N, h->dScanLogp, h->dScanCc, h->dScanParams));
+    HIP_CHECK(h, bioem_grad_coef_launch(h->stream, h->dGradRec, h->dScanCc, h->dScanParams, h->dSumRef, h->dSumsqRef, ng, N,
+                                        h->dGradCoef, h->dGradParams));
+    if (phase_end(h, h->stream))
+      return 1;
+    for (int b0 = 0; b0 < ng; b0 += OB)
+    {
+      const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
+      // phase 2: the gradient spectrum, Y and <C, A_r> through the adjoint identity, on the double slice of the request
+      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, r0, r0 + nb, 0, 0))
+        return 1;
+      HIP_CHECK(h, bioem_grad_spectrum_launch(h->stream, h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0, h->dCTF,
+                                              h->dGradRec + b0, h->dGradCoef + 4 * (size_t) b0, 0, nb, N, h->dGradSpec));
+      HIP_CHECK(h, bioem_vgrad_prepare_launch(h->stream, h->dGradSpec, h->dGradW + b0, nb, N, h->dTwD, h->shiftX, h->shiftY, 1,
+                                              h->dVgY));
+      HIP_CHECK(h, bioem_slice_project_launch(h->stream, h->dVolC, pad, h->dVgR + 9 * (size_t) b0, nb, N, h->dTwD, h->shiftX,
+                                              h->shiftY, (double) h->NormDen, nullptr, h->dVgSlices, nullptr));
+      HIP_CHECK(h, bioem_vgrad_dot_launch(h->stream, h->dGradSpec, h->dVgSlices, nb, N, h->dGradCoef + 4 * (size_t) b0 + 3, 4));
+      // phase 3: the back-insertion
+      if (phase_end(h, h->stream) || phase_begin(h, h->stream, 3, r0, r0 + nb, 0, 0))
+        return 1;
+      HIP_CHECK(h, bioem_vgrad_insert_launch(h->stream, h->dVgY, h->dVgR + 9 * (size_t) b0,
+                                             h->dVgView + (size_t) kVgradViewDoubles * b0, nb, N, pad, 1, r0 == 0, h->dVolA));
+      if (phase_end(h, h->stream))
+        return 1;
+    }
+    if (params_out)
+      HIP_CHECK(h, hipMemcpyAsync(params_out + g0, h->dGradParams, sizeof(bioem_hip_param5) * ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(coef.data(), h->dGradCoef, sizeof(double) * 4 * ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < ng; i++)
+    {
+      const double *c = coef.data() + 4 * (size_t) i;
+      if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2])))
+        notFinite += 1.;
+    }
+    if (coef_out)
+      memcpy(coef_out + 4 * (size_t) g0, coef.data(), sizeof(double) * 4 * ng);
+  }
+  if (spec_out)
+    HIP_CHECK(h, hipMemcpy(spec_out, h->dVolA, sizeof(double2) * V, hipMemcpyDeviceToHost));
+  if (vol_out)
+  { // one more record of phase 3 with an empty request range [n, n): the transpose of the upload's passes
+    if (phase_begin(h, h->stream, 3, n, n, 0, 0))
+      return 1;
+    if (vgrad_adjoint(h, "volume_gradient", h->dVolA, vol_out))
+    { // (the open record goes; those that closed are delivered)
+      drop_open_phase(h);
+      drain_phases(h);
+      return 1;
+    }
+    if (phase_end(h, h->stream))
+      return 1;
+  }
+  if (stats_out)
+  {
+    stats_out[0] = (double) n;
+    stats_out[1] = sumw;
+    stats_out[2] = notFinite;
+  }
+  drain_phases(h);
+  return 0;
+}
+
+int bioem_hip_debug_volume_backproject(bioem_hip_handle h, const float *angles4, int n, int isQuat, const double *gamma,
+                                       const double *weights, int cull, double *spec_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "debug_volume_backproject"};
+  if (!angles4 || !gamma || !spec_out || n < 1)
+    return refuse("null argument or no views");
+  if (!h->dVolC)
+    return refuse(h->dPts ? "the model is a point model" : "model not uploaded");
+  for (int i = 0; i < n && weights; i++)
+    if (!std::isfinite(weights[i]))
+      return refuse("view " + std::to_string(i) + ": weight not finite");
+  if (grad_staging(h, std::max(1, h->scanCapG), 0) || vgrad_staging(h) || begin_analysis(h, false))
+    return 1;
+  const int N = h->N, OB = h->OB, pad = h->volPad;
+  const size_t M = (size_t) h->M, PN = (size_t) pad * N, V = PN * PN * (PN / 2 + 1);
+  for (int pass = 0; pass < 2; pass++) // every view's matrix first, then the insertion
+  {
+    if (pass)
+      HIP_CHECK(h, hipMemsetAsync(h->dVolA, 0xff, sizeof(double2) * V, h->stream)); // (poisoned: the first launch starts from 0)
+    for (int g0 = 0; g0 < n; g0 += OB)
+    {
+      const int nb = std::min(OB, n - g0);
+      int bad, flag;
+      HIP_CHECK(h, hipMemcpyAsync(h->dGradAngles, angles4 + 4 * (size_t) g0, sizeof(float4) * nb, hipMemcpyHostToDevice, h->stream));
+      if (vgrad_views_checked(h, h->dGradAngles, isQuat, nb, bad, flag))
+        return 1;
+      if (bad >= 0)
+        return refuse("view " + std::to_string(g0 + bad) + ": " + vgrad_flag_reason(flag));
+      if (!pass)
+        continue;
+      HIP_CHECK(h, hipMemcpyAsync(h->dGradSpec, gamma + 2 * M * (size_t) g0, sizeof(double2) * M * nb, hipMemcpyHostToDevice,
+                                  h->stream));
+      if (weights)
+        HIP_CHECK(h, hipMemcpyAsync(h->dGradW, weights + g0, sizeof(double) * nb, hipMemcpyHostToDevice, h->stream));
+      HIP_CHECK(h, bioem_vgrad_prepare_launch(h->stream, h->dGradSpec, weights ? h->dGradW : nullptr, nb, N, h->dTwD, h->shiftX,
+                                              h->shiftY, 0, h->dVgY));
+      HIP_CHECK(h, bioem_vgrad_insert_launch(h->stream, h->dVgY, h->dVgR, h->dVgView, nb, N, pad, cull ? 1 : 0, g0 == 0,
+                                             h->dVolA));
+      HIP_CHECK(h, hipStreamSynchronize(h->stream)); // (the staging is reused by the next chunk)
+    }
+  }
+  HIP_CHECK(h, hipMemcpy(spec_out, h->dVolA, sizeof(double2) * V, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int bioem_hip_debug_volume_adjoint(bioem_hip_handle h, const double *spec_in, double *vol_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "debug_volume_adjoint"};
+  if (!spec_in || !vol_out)
+    return refuse("null argument");
+  if (!h->dVolC)
+    return refuse(h->dPts ? "the model is a point model" : "model not uploaded");
+  if (grad_staging(h, std::max(1, h->scanCapG), 0) || vgrad_staging(h) || begin_analysis(h, false))
+    return 1;
+  const size_t PN = (size_t) h->volPad * h->N, V = PN * PN * (PN / 2 + 1);
+  HIP_CHECK(h, hipMemcpy(h->dVolA, spec_in, sizeof(double2) * V, hipMemcpyHostToDevice));
+  return vgrad_adjoint(h, "debug_volume_adjoint", h->dVolA, vol_out);
 }
 
 int bioem_hip_debug_projection(bioem_hip_handle h, int iOrient, float *spec_out)

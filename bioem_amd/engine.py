@@ -131,6 +131,10 @@ def load_library():
         L.bioem_hip_upload_model_spectrum.argtypes = [vp, vp, ci, vp, ci, ci]
         L.bioem_hip_upload_model_volume.argtypes = [vp, vp, ci, ci, vp, ci, ci]
         L.bioem_hip_debug_slices.argtypes = [vp, vp, ci, ci, vp]
+    if hasattr(L, "bioem_hip_volume_gradient"):
+        L.bioem_hip_volume_gradient.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
+        L.bioem_hip_debug_volume_backproject.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp]
+        L.bioem_hip_debug_volume_adjoint.argtypes = [vp, vp, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -204,7 +208,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_view_sums_soft", "bioem_hip_debug_view_sums_soft", "bioem_hip_reconstruct_soft",
            "bioem_hip_set_compare_variant", "bioem_hip_debug_projection_maps", "bioem_hip_debug_stamps",
            "bioem_hip_debug_convolve_batch",
-           "bioem_hip_upload_model_spectrum", "bioem_hip_upload_model_volume", "bioem_hip_debug_slices"]
+           "bioem_hip_upload_model_spectrum", "bioem_hip_upload_model_volume", "bioem_hip_debug_slices",
+           "bioem_hip_volume_gradient", "bioem_hip_debug_volume_backproject", "bioem_hip_debug_volume_adjoint"]
 
 
 def _p(a):
@@ -395,6 +400,7 @@ class Engine:
         self._chk(self.L.bioem_hip_upload_model(self.h, _p(points), len(points), float(NormDen), float(pixelSize),
                                                 int(shiftX), int(shiftY)), "upload_model")
         self._nPts = len(points)
+        self._volPad = 0
 
     @staticmethod
     def _centre(centre):
@@ -419,6 +425,7 @@ class Engine:
         self._chk(self.L.bioem_hip_upload_model_volume(self.h, _p(vol), int(pad), flags, _p(centre), int(shiftX),
                                                        int(shiftY)), "upload_model_volume")
         self._nPts = 0
+        self._volPad = int(pad)
 
     def upload_model_spectrum(self, spec, pad=1, centre=None, shiftX=0, shiftY=0):
         """the same from the spectrum itself: spec complex128 [PN, PN, PH], PN = pad N, PH = PN // 2 + 1, un-centred, in
@@ -432,6 +439,7 @@ class Engine:
         self._chk(self.L.bioem_hip_upload_model_spectrum(self.h, _p(spec), int(pad), _p(centre), int(shiftX), int(shiftY)),
                   "upload_model_spectrum")
         self._nPts = 0
+        self._volPad = int(pad)
 
     def debug_slices(self, angles, isQuat=True):
         """test hook: the slice kernel alone under the orientations angles float32 [n, 4]; complex128 [n, N, H], the
@@ -935,6 +943,64 @@ class Engine:
         map entries (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
         req = _match_requests(_pmap(pmap, self.nMaps), p0, self.nMaps if p1 is None else p1, GRAD_REQUEST_DTYPE)
         return self.model_gradient(req, weights=weights, own=own, want_grad=want_grad, want_params=want_params)
+
+    def _vol_spec_shape(self):
+        PN = max(1, getattr(self, "_volPad", 0)) * self.N   # (no volume model: the entries refuse)
+        return (PN, PN, PN // 2 + 1)
+
+    def volume_gradient(self, requests, weights=None, own=False, want_vol=True, want_spec=False, want_params=False):
+        """the derivative of the log posterior of the requests (particle, orient, conv, shiftX, shiftY) of
+        GRAD_REQUEST_DTYPE [n] (or an [n, 5] integer array), weighted by weights float64 [n] (None: all 1) and summed in
+        request order, with respect to every voxel of the volume model (include/bioem_hip.h).  Returns a
+        dict: "coef" float64 [n, 4] = (a, b, g, <C, A_r>); "stats" float64 [3] = (n, sum of the weights, requests whose
+        coefficients are not finite); with want_vol "vol" float64 [N, N, N], the gradient with respect to the array
+        handed to upload_model_volume; with want_spec "spec" complex128 [PN, PN, PH], the gradient A with respect to the
+        centred spectrum; with want_params "params" PARAM5_DTYPE [n].  Outside a run; a refusal raises RuntimeError with
+        .rc == 2."""
+        r = _requests(requests, GRAD_REQUEST_DTYPE)
+        n = len(r)
+        w = _vector(weights, n)
+        out = {"coef": np.zeros((n, 4), dtype=np.float64), "stats": np.zeros(3, dtype=np.float64)}
+        if want_vol:
+            out["vol"] = np.zeros((self.N,) * 3, dtype=np.float64)
+        if want_spec:
+            out["spec"] = np.zeros(self._vol_spec_shape(), dtype=np.complex128)
+        if want_params:
+            out["params"] = np.zeros(n, dtype=PARAM5_DTYPE)
+        self._chk(self.L.bioem_hip_volume_gradient(self.h, _p(r) if n else None, _p(w), n, int(bool(own)), _p(out.get("vol")),
+                                                   _p(out.get("spec")), _p(out["coef"]), _p(out.get("params")),
+                                                   _p(out["stats"])), "volume_gradient")
+        return out
+
+    def best_match_volume_gradient(self, pmap, p0=0, p1=None, own=False, weights=None, want_vol=True, want_spec=False,
+                                   want_params=False):
+        """volume_gradient of the best record (orient, conv, cent_x, cent_y) of particles [p0, p1) of a probability block's
+        map entries (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
+        req = _match_requests(_pmap(pmap, self.nMaps), p0, self.nMaps if p1 is None else p1, GRAD_REQUEST_DTYPE)
+        return self.volume_gradient(req, weights=weights, own=own, want_vol=want_vol, want_spec=want_spec,
+                                    want_params=want_params)
+
+    def debug_volume_backproject(self, angles, gamma, weights=None, isQuat=True, cull=True):
+        """test hook: Y and the back-insertion alone, on the spectra gamma complex128 [n, N, H] handed in as Gamma under the
+        orientations angles float32 [n, 4], scaled by weights float64 [n] alone; complex128 [PN, PN, PH] = A"""
+        angles = np.ascontiguousarray(angles, dtype=np.float32).reshape(-1, 4)
+        n = len(angles)
+        gamma = np.ascontiguousarray(gamma, dtype=np.complex128)
+        assert gamma.shape == (n, self.N, self.H), gamma.shape
+        w = _vector(weights, n)
+        out = np.zeros(self._vol_spec_shape(), dtype=np.complex128)
+        self._chk(self.L.bioem_hip_debug_volume_backproject(self.h, _p(angles) if n else None, n, int(bool(isQuat)),
+                                                            _p(gamma) if n else None, _p(w), int(bool(cull)), _p(out)),
+                  "debug_volume_backproject")
+        return out
+
+    def debug_volume_adjoint(self, spec):
+        """test hook: the passes from A complex128 [PN, PN, PH] back to the volume alone; float64 [N, N, N]"""
+        spec = np.ascontiguousarray(spec, dtype=np.complex128)
+        assert spec.shape == self._vol_spec_shape(), spec.shape
+        out = np.zeros((self.N,) * 3, dtype=np.float64)
+        self._chk(self.L.bioem_hip_debug_volume_adjoint(self.h, _p(spec), _p(out)), "debug_volume_adjoint")
+        return out
 
     def debug_grad_image(self, specConv, specRef, kernels, params, sumRef, sumsqRef, shifts):
         """test hook: a, b, g and the gradient image G_P of n records from conv spectra, particle spectra and kernels handed

@@ -187,6 +187,16 @@ std::string write_ctf_scan(const char *file, const double *logp, const float *tr
 // requests whose coefficients were not finite).  17 significant digits.  Returns the empty string, or the error.
 std::string write_model_gradient(const char *file, const bioem_hip_model_point *points, const bioem_hip_grad_point *acc, int nPts,
                                  int nonfinite);
+// --VolumeGradient (volgrad.cpp): the text file beside the gradient volume gvol [N][N][N] of bioem_hip_volume_gradient over
+// the particles' best records, vol the model's density.  After the HEADER:: NOTATION bar, one notation line and the bar
+// again, per shell s (the voxels whose distance from the origin voxel (N + 1) / 2 rounds to s) that holds voxels
+//  SHELL s voxels sum power vol_dot_g
+// (the sums of g, g^2 and vol g over the shell) and one line
+//  DATASET vol_dot_g norm requests sumw nonfinite
+// (sum_x vol g, analytically -sumw; the Euclidean norm of g; the requests, the sum of their weights and how many had
+// coefficients that were not finite).  17 significant digits.  Returns the empty string, or the error.
+std::string write_volume_gradient(const char *file, const double *gvol, const float *vol, int N, int nRequests, double sumw,
+                                  int nonfinite);
 // --OrientStats (orientstats.cpp): the text file of the sums sums[nMaps] of bioem_hip_orientation_sums.  After the
 // HEADER:: NOTATION bar, one notation line (it carries the constant as NumericalConst) and the bar again, per particle
 //  ORIENT p count logZ omax A pTop entropy nEff meanq1 meanq2 meanq3 meanq4 spreadDeg
@@ -357,6 +367,7 @@ public:
   // FILE_Round2); k = 4 is a conventional choice, not a tuned one
   std::string ctfScanFile;
   int ctfScanFactor = 4;
+  std::string volGradFile;     // --VolumeGradient: the density gradient of the best matches per voxel (FILE, FILE.mrc, _Round2)
   std::string modelGradFile;   // --ModelGradient: the density gradient of the best matches per model point (FILE, FILE_Round2)
   std::string orientStatsFile; // --OrientStats: summaries of every particle's orientation posterior (WRITE_PROB_ANGLES)
   std::string orientOccFile;   // --OrientOccupancy: occupancy of every orientation over the data set (WRITE_PROB_ANGLES)
@@ -431,6 +442,10 @@ private:
   // --ModelGradient: the records' gradient per model point from handle h (bioem_hip_model_gradient), written by
   // write_model_gradient
   void writeModelGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
+  // --VolumeGradient: the records' gradient per voxel of the volume model from handle h (bioem_hip_volume_gradient), written
+  // as the MRC volume file + ".mrc" (write_mrc_volume: it overlays the model file voxel for voxel) and the text file
+  // (write_volume_gradient)
+  void writeVolumeGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
   // --OrientStats: the shards' orientation sums (bioem_hip_orientation_sums) merged on the host, written by
   // write_orient_stats; numconst: the constant of ANG_PROB
   void writeOrientStats(const std::string &file, double numconst);

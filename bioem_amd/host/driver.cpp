@@ -126,6 +126,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"CTFScan", required_argument, 0, 0},
                                        {"CTFScanFactor", required_argument, 0, 0},
                                        {"ModelGradient", required_argument, 0, 0},
+                                       {"VolumeGradient", required_argument, 0, 0},
                                        {"OrientStats", required_argument, 0, 0},
                                        {"OrientOccupancy", required_argument, 0, 0},
                                        {"FitOrientPrior", required_argument, 0, 0},
@@ -177,6 +178,8 @@ int Driver::readOptions(int ac, char **av)
     printf("                         also arg_Round2)\n");
     printf("  --CTFScanFactor arg    (Optional) With --CTFScan: every CTF axis with more than one point is refined arg-fold;\n");
     printf("                         1, 2, 4, 8 or 16 (default 4)\n");
+    printf("  --VolumeGradient arg   (Optional) With --ModelVolume: write the gradient of the log posterior of the particles' best\n");
+    printf("                         matches per voxel of the model as arg.mrc, and its shells as text to arg\n");
     printf("  --ModelGradient arg    (Optional) Write per model point the gradient of the log posterior of the particles' best\n");
     printf("                         matches with respect to its density (which part of the model do the data argue against?\n");
     printf("                         with --RefineOrientations also arg_Round2)\n");
@@ -341,6 +344,11 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Writing the density gradient of the best matches per model point to: " << optarg << "\n";
       modelGradFile = optarg;
     }
+    else if (name == "VolumeGradient")
+    {
+      std::cout << "Writing the density gradient of the best matches per voxel of the volume model to: " << optarg << "\n";
+      volGradFile = optarg;
+    }
     else if (name == "OrientStats")
     {
       std::cout << "Writing the summaries of the orientation posteriors to: " << optarg << "\n";
@@ -438,10 +446,16 @@ int Driver::readOptions(int ac, char **av)
     if (model.readModelMRC)
       fatal("--ModelVolume is not valid with --ReadModelMRC (which turns every voxel into a point; choose one)");
     if (!modelGradFile.empty())
-      fatal("--ModelVolume is not valid with --ModelGradient (the gradient is per model point; a volume has none)");
+      fatal("--ModelVolume is not valid with --ModelGradient (the gradient is per model point; a volume has none): the "
+            "gradient per voxel is --VolumeGradient");
     if (!bestParamFile.empty())
       fatal("--ModelVolume is not valid with --PrintBestCalMap (its one-record mode reads the model as points)");
   }
+  if (!volGradFile.empty() && !model.readVolume)
+    fatal("--VolumeGradient needs --ModelVolume (the gradient is per voxel of a volume model; per model point it is "
+          "--ModelGradient)");
+  if (!volGradFile.empty() && !bestParamFile.empty())
+    fatal("--PrintBestCalMap goes without --VolumeGradient");
   if (!bestParamFile.empty())
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
@@ -1082,6 +1096,35 @@ void Driver::writeModelGradient(const std::string &file, bioem_hip_handle h, con
             << " model points written to: " << file << "\n";
 }
 
+// --VolumeGradient: the gradient of the log posterior of every record from handle h with respect to every voxel of the
+// volume model, summed over the particles with weight 1 (bioem_hip_volume_gradient), then the MRC volume and the text file
+void Driver::writeVolumeGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists)
+{
+  const int nMaps = particles.ntot, N = param.N;
+  std::vector<bioem_hip_grad_request> req;
+  for_each_match(pmap, nMaps, "Density gradient of RefMap %d not computed: no run compared it",
+                 [&](int p, const bioem_hip_prob_map &r) {
+                   req.push_back({p, r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y});
+                 });
+  const size_t NNN = (size_t) N * N * N;
+  std::vector<double> gvol(NNN, 0.);
+  double stats[3] = {0., 0., 0.};
+  if (!req.empty())
+    check(h, bioem_hip_volume_gradient(h, req.data(), nullptr, (int) req.size(), ownLists, gvol.data(), nullptr, nullptr, nullptr,
+                                       stats),
+          "volume gradient");
+  std::vector<float> gf(NNN);
+  for (size_t e = 0; e < NNN; e++)
+    gf[e] = (float) gvol[e];
+  std::string err = write_mrc_volume((file + ".mrc").c_str(), gf.data(), N, param.pixelSize);
+  if (err.empty())
+    err = write_volume_gradient(file.c_str(), gvol.data(), model.volume.data(), N, (int) req.size(), stats[1], (int) stats[2]);
+  if (!err.empty())
+    fatal("--VolumeGradient: %s", err.c_str());
+  std::cout << "Density gradient of " << req.size() << " particles' best matches over the " << N << "^3 voxels of the model written "
+            << "to: " << file << " and " << file << ".mrc\n";
+}
+
 // every shard's sums over the orientations it owns under logPrior (bioem_hip_orientation_sums), merged on the host in
 // shard order
 void Driver::shardOrientSums(const double *logPrior, std::vector<bioem_hip_orient_sums> &sums)
@@ -1394,6 +1437,8 @@ int Driver::run()
     writeCtfScan(ctfScanFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0, param.pd);
   if (!modelGradFile.empty())
     writeModelGradient(modelGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
+  if (!volGradFile.empty())
+    writeVolumeGradient(volGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!viewAvgFile.empty())
     writeViewAverages(viewAvgFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
   if (!reconFile.empty())
@@ -1477,6 +1522,8 @@ void Driver::runRound2()
     writeCtfScan(ctfScanFile + "_Round2", h, pm.data(), 1, pd2);
   if (!modelGradFile.empty())
     writeModelGradient(modelGradFile + "_Round2", h, pm.data(), 1);
+  if (!volGradFile.empty())
+    writeVolumeGradient(volGradFile + "_Round2", h, pm.data(), 1);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), (size_t) G);
   bioem_hip_destroy(h);
@@ -1577,6 +1624,8 @@ void Driver::runRound2Seeds()
     writeCtfScan(ctfScanFile + "_Round2", h, pm.data(), 1, pd2, volu.data());
   if (!modelGradFile.empty())
     writeModelGradient(modelGradFile + "_Round2", h, pm.data(), 1);
+  if (!volGradFile.empty())
+    writeVolumeGradient(volGradFile + "_Round2", h, pm.data(), 1);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), 0, offsets.data(),
                  volu.data());

@@ -795,6 +795,47 @@ int bioem_hip_upload_model_volume(bioem_hip_handle h, const float *vol, int pad,
  * slices as they stand before the rounding to float.  Refused with 2: a null argument, n < 1, the model is not a volume. */
 int bioem_hip_debug_slices(bioem_hip_handle h, const float *angles4, int n, int isQuat, double *out);
 
+/* ---- Density gradient of the log posterior per voxel of a volume model (no reference counterpart) ----
+ * For request (p, o, c, X, Y) with weight w_r the derivative of the log posterior of that match with respect to the array
+ * handed to bioem_hip_upload_model_volume, at a fixed centre.  The slice is exactly linear in the stored spectrum C (no
+ * NormDen / tempden factor, no skip rule), so the adjoint is: the front half of bioem_hip_model_gradient up to G^_P, the
+ * transpose of the slice, the transpose of the upload's passes.  Conventions of the volume model above.
+ *   Gamma    = G^_P, but Gamma[a, 0] = (G^_P[a, 0] + conj G^_P[-a, 0]) / 2 in the self-conjugate column;
+ *   Y[a, b]  = ((w_r w_b) / N^2) (Gamma[a, b] conj(tw[e(a, b)])), w_b = 1 for b = 0, else 2, e the slice's twiddle index,
+ *              used only where a^2 + b^2 <= M^2;
+ *   A[s]     = sum wt (neg ? conj Y[a, b] : Y[a, b]) over every request, coefficient and tap of the slice that lands on the
+ *              stored voxel s of [PN][PN][PH], under every drop rule of the slice, wt its ((w0 w1) w2); requests ascending,
+ *              the target +s before -s, coefficients in ascending (a, b).  dL = sum_s Re(conj(A[s]) dC[s]);
+ *   A_spec[k]= A[k] conj(phi[k]), phi the product of the four unit factors that centre the spectrum;
+ *   gv[x]    = sum_{stored k} Re(A_spec[k] twP[(k.x) mod PN]) over the N^3 box, the stored entries as they are;
+ *   gvol[x]  = gv[x] / prod_d sinc^2(pi (x_d - o) / PN) where the model was uploaded as a volume with precorrection.
+ * vol_out [N][N][N] = gvol; spec_out [PN][PN][PH] (re, im) = A, the gradient with respect to C for a model that came in
+ * through bioem_hip_upload_model_spectrum (such a model delivers vol_out without the sinc^2 division); coef_out [n][4] =
+ * {a, b, g, <C, A_r>}, the last through the adjoint identity as sum (w_b / N^2) Re(conj(Gamma_r) slice_r) on the double
+ * slice of the request (w_r left out, as m of the point entry); params_out [n] the linearisation points; stats_out [3] =
+ * {n, sum_r w_r, the requests whose a, b or g is not finite}.  Any output but not both of vol_out and spec_out may be NULL.
+ * A stays on the device across the batches (16 PN^2 PH bytes beside C).  The back-insertion is a gather without atomics: a
+ * voxel's bits depend on the requests in request order alone, the same for any batch size, batch boundary and run.
+ * Calling rules, batches, scan launches and refusals of bioem_hip_model_gradient; also refused with 2, the request named
+ * and the handle usable: the model is a point model, vol_out and spec_out both null, an orientation whose matrix has rows
+ * 0 and 1 rank-deficient, or shrinks so far that the search for the coefficients of a voxel would pass a half-width of 4
+ * (a rotation has sqrt(3) / pad; quaternions of length 0.85 to 1.07 stay below 3.9 at pad 1; the matrix of a quaternion
+ * of length sqrt(1 / 2) is singular).  Phase records as there through phase 2 (here the gradient
+ * spectrum, Y and <C, A_r>); 3 the back-insertion per batch, and one more record of phase 3 with the empty request range
+ * [n, n): the passes back to the volume. */
+int bioem_hip_volume_gradient(bioem_hip_handle h, const bioem_hip_grad_request *req, const double *weights /* [n] or NULL */,
+                              int n, int ownLists, double *vol_out /* [N][N][N] or NULL */,
+                              double *spec_out /* [PN][PN][PH][2] or NULL */, double *coef_out /* [n][4] or NULL */,
+                              bioem_hip_param5 *params_out /* [n] or NULL */, double *stats_out /* [3] or NULL */);
+/* test hook: Y and the back-insertion alone on the spectra gamma [n][N][H] (re, im) handed in as Gamma, under the
+ * orientations angles4 [n][4]: Y = weights[i] (Gamma conj(tw[e])) (NULL: 1), without w_b and 1 / N^2; cull: whether
+ * views are tested against a brick of voxels first (the same bits either way); the views go through in chunks of
+ * maxOrientations into a buffer poisoned with NaNs.  spec_out [PN][PN][PH] (re, im) = A. */
+int bioem_hip_debug_volume_backproject(bioem_hip_handle h, const float *angles4, int n, int isQuat, const double *gamma,
+                                       const double *weights, int cull, double *spec_out);
+/* test hook: the passes from A (spec_in [PN][PN][PH] (re, im)) to gvol (vol_out [N][N][N]) alone */
+int bioem_hip_debug_volume_adjoint(bioem_hip_handle h, const double *spec_in, double *vol_out);
+
 #ifdef __cplusplus
 }
 #endif
