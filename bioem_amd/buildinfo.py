@@ -1,6 +1,7 @@
 """Identity of the device sources a measurement belongs to: git blob hashes (`git hash-object`) of the files that go
 into the translation unit of the measured kernel (round 4: one translation unit per kernel family -- the counters of
-k_compare_fast do not go stale when only k_compare_wide2 changes).  scripts/pmc_summary.py stores them beside the
+k_compare_fast do not go stale when only k_compare_wide2 changes), and of the host files that decide what the kernel is
+launched on: plan, launch shape and the pitch of the comparison layout.  scripts/pmc_summary.py stores them beside the
 counters it summarises; bench.py refuses counters whose hashes differ from the tree it runs from."""
 import hashlib
 import os
@@ -52,6 +53,9 @@ def source_blobs(kernel=None):
     names = include_closure(tu) if tu else {n for n in os.listdir(CSRC) if n.endswith((".hip", ".hpp", ".h", ".inc"))}
     if tu:  # which instantiations exist does not change the code of one of them (bench.py matches the signature itself)
         names.discard("kernel_table.inc")
+        # the host picks the plan, the launch shape and the pitch of the comparison layout: a change there changes what
+        # a kernel's counters mean without touching its translation unit
+        names |= {"bioem_hip.hip", "kernel_select.hpp", "compare_args.hpp"}
     out = {}
     for name in sorted(names | {"Makefile"}):
         out["bioem_amd/csrc/" + name] = git_blob_sha1(os.path.join(CSRC, name))

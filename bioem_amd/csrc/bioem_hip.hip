@@ -158,7 +158,7 @@ struct bioem_hip_ctx
   PD pd;
   int nMaps = 0, nAngles = 0, nCTF = 0, algo = 1;
   int N = 0, H = 0, M = 0;
-  int Hp = 0;    // row-pair pitch of the comparison layout in 16-byte words (H, or H + 15: comparison_pitch)
+  int Hp = 0;    // row-pair pitch of the comparison layout in 16-byte words (H ... H + 15: comparison_pitch)
   size_t Mc = 0; // float2 per image of the comparison layout, N * Hp
   KernelPlan plan; // which comparison kernel runs this shape and how (kernel_select.hpp)
   int pchunk = 128;               // particle chunk of the fast kernel's block order (0 = all particles); measured:
@@ -564,6 +564,27 @@ void launch_nyquist(bioem_hip_ctx *h, const CompareArgs &aw, int WD, int nOC)
     launch_nyquist_rows<1>(h, aw, WD, nOC);
 }
 
+// Row-pair pitch, in 16-byte words, of the shapes the H + 15 rule (comparison_pitch, below) leaves alone: H rounded up to
+// kPitchAlignWords.  A wave's operand request is 64 lanes x 16 B; the L1 takes it as 16 quads of 64 B and processes one
+// access per 128-byte line a quad touches.  At pitch H (16 H bytes: 16-byte aligned, line aligned in every eighth row
+// pair only) most quads straddle two lines, at a pitch that is a multiple of 4 words none does (8 848 against
+// 6 496 modelled accesses per comparison at 224^2).  At most 15 words are added (debug_convolve_batch sizes for H + 15),
+// and never a multiple of 32 words, i.e. 512 B: the channel aliasing the H + 15 rule exists to avoid.
+// Measured, default against BIOEM_NO_PITCH_PAD=1 on one device (profiles/lean_operand_ab.txt): 224^2 -1.4 % launch time
+// (H + 3 = 116 and H + 11 = 124, 64-byte multiples only, -0.8 % and -0.5 %), 240^2 -1.8 %, 200^2 -1.4 %, 160^2 -0.9 %, ten
+// particles at 224^2 -1.5 %; 96^2 (one column block) +0.6 %: the rule starts at 160 pixels, the smallest size that gained.
+constexpr int kPitchAlignWords = 8;
+constexpr int kLinePitchMinN = 160;
+int line_aligned_pitch(int N, int H)
+{
+  if (N < kLinePitchMinN)
+    return H;
+  int Hp = (H + kPitchAlignWords - 1) / kPitchAlignWords * kPitchAlignWords;
+  if (Hp % 32 == 0)
+    Hp += kPitchAlignWords;
+  return Hp;
+}
+
 // k_compare_fast / k_compare_fastm: a last column block of at most 32 columns is shared by the half-waves
 // (with the Nyquist split the blocks hold the H - 1 columns below N / 2: whole ones, or -- 192^2, 320^2, 448^2, which
 // were planned that way -- a last one of 32, and then the split is not optional)
@@ -582,8 +603,9 @@ int last_block_split(const bioem_hip_ctx *h)
 bool lean_launch_ok(const bioem_hip_ctx *h, int nd, int maxD, int split)
 {
   const KernelPlan &P = h->plan;
+  // (N1 halfR = N / 2 >= 6 row pairs: the lean loop's ring re-reads row pairs 0 .. 4 at the end of the last block)
   return h->lean && !h->direct && P.family == KF_FAST && P.fnLean && sym_window_ok(P.winD, 2 * P.halfR, P.nyq, P.gs) &&
-         nd == 2 * P.winD + 1 && maxD / P.gs == P.winD && !split;
+         nd == 2 * P.winD + 1 && maxD / P.gs == P.winD && !split && P.N1 * P.halfR >= 6;
 }
 fast_kernel_t compare_fn(const bioem_hip_ctx *h, const CompareArgs &a)
 {
@@ -1479,14 +1501,17 @@ static int create_impl(bioem_hip_handle *out, int device, const bioem_hip_param_
   // (timing build first: 512^2 8.3 -> 10.1 M/s; the real thing, same box, +-5 / +-10 px: 512^2 +20 %, 384^2 +6.7 %, 448^2
   // +7 / +4 %, 256^2 +3 %, 192^2 and 320^2 +2...3.5 %, +0...6 % on the matrix-core families; the headline shape, whose
   // kernel reads one argument more, 54.74 against 54.68 M/s).  64^2 and 128^2 gain nothing, 128^2 loses 1...3 % on
-  // few-particle jobs: not padded.  k_compare_wide2 (operands once per comparison) gains nothing: its plans, the tiled
-  // ones, odd sizes and the direct kernel keep Hp = H.
+  // few-particle jobs: not padded by this rule.  k_compare_wide2 (operands once per comparison) gains nothing: its plans,
+  // the tiled ones, odd sizes and the direct kernel keep Hp = H.
+  // Every other shape of the three families from 160 pixels on takes the line-aligned pitch (line_aligned_pitch above:
+  // H rounded up to 8 words, for the L1's sake, not the channels'; 224^2: 113 -> 120, profiles/lean_operand_ab.txt).
   // (Other numbers of words: 7 / 15 / 23 / 31 / 47 are within 2 % of each other at 256^2 ... 512^2,
   // profiles/r04_padded_pitch_ab.txt.)
   constexpr int kPitchPadWords = 15;
-  const bool padPitch = (P.family == KF_FAST || P.family == KF_FASTM || P.family == KF_FASTM2) && !P.tileT &&
-                        !h->direct && N % 64 == 0 && N >= 192 && !getenv("BIOEM_NO_PITCH_PAD");
-  h->Hp = padPitch ? h->H + kPitchPadWords : h->H;
+  const bool padFamily = (P.family == KF_FAST || P.family == KF_FASTM || P.family == KF_FASTM2) && !P.tileT &&
+                         !h->direct && !getenv("BIOEM_NO_PITCH_PAD");
+  const bool padPitch = padFamily && N % 64 == 0 && N >= 192;
+  h->Hp = padPitch ? h->H + kPitchPadWords : padFamily ? line_aligned_pitch(N, h->H) : h->H;
   h->Mc = (size_t) N * h->Hp;
 
   // batch sizing: conv buffer <= ~96 MiB, partial buffer <= ~128 MiB

@@ -460,7 +460,7 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
   const int oc_raw = ocFirst + wave;
   const bool oc_valid = oc_raw < ocEnd;
   const int oc = oc_valid ? oc_raw : ocEnd - 1;
-  const int Hp = a.Hp; // row-pair pitch in 16-byte words (H, or H + 15: comparison_pitch in bioem_hip.hip)
+  const int Hp = a.Hp; // row-pair pitch in 16-byte words (H ... H + 15: comparison_pitch in bioem_hip.hip)
   const size_t M = (size_t) N * Hp;
   // buffer descriptors built from wave-uniform values only (blockIdx / readfirstlane'd wave id)
   const auto rsrcF = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<float2 *>(a.ref + (size_t) p * M)), 0,
@@ -541,6 +541,19 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
     const unsigned laneoff = lane_offset(blk);
     const unsigned laneoff_next = lane_offset(min(blk + 1, nblk - 1));
     const bool has_next = blk + 1 < nblk;
+    // LEAN (no split block): a block that has a successor has all 64 lanes live, and the successor's column of a lane
+    // is this lane's 1 024 bytes on -- a wave-uniform distance, which goes into the SCALAR offset of a request, so the
+    // lane offset is `laneoff` for every request of the block.  Requests issued from this block for the next one cover its
+    // first RD row pairs only; a lane whose column there lies beyond H - 1 reads, unclamped, words of the FOLLOWING row
+    // pair of the same image, which it never consumes (the lane sits out the next block, EXEC masked, as ever).  After
+    // the last block the ring's tail requests are still issued (the wait counts include them): rows 0 .. RD - 1 of this
+    // block again, addresses the wave has read before.
+    // No request leaves the image's N Hp 8 bytes: the largest offset is row pair RD - 1, plus 1 024 bytes and lane 63,
+    // i.e. 127 words and the 16 bytes read; a successor means H > 64, so 128 words are less than two row pairs and the
+    // request ends inside row pair RD + 1 <= 6 of the >= 64 a shape with two blocks has.  Without a successor it ends
+    // inside row pair RD - 1 <= 4, and N / 2 = N1 R / 2 >= 6 is part of lean_launch_ok (bioem_hip.hip).  Nothing relies
+    // on the zeros a descriptor returns out of range.
+    const unsigned nextstart = has_next ? 1024u : 0u;
     float Tr[NW], Ti[NW];
 #pragma unroll
     for (int d = 0; d < NW; d++)
@@ -568,6 +581,9 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
 #pragma unroll
       for (int d = 0; d < NW; d++)
         wk[d] = twk[d];
+      // LEAN: scalar offset of the step's last RD requests, chosen once per step -- the next step's rows, or from the
+      // block's last step the first RD rows of what follows (nextstart)
+      const unsigned tailbase = !LEAN ? 0u : k1 + 1 < n1 ? (unsigned) ((k1 + 1) * R2) * rowbytes : nextstart;
 #pragma unroll
       for (int k2p = 0; k2p < R2; k2p++)
       {
@@ -578,16 +594,26 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
         xi[FFT_IN(2 * k2p)] = fmaf(c.y, f.x, -(c.x * f.y));
         xr[FFT_IN(2 * k2p + 1)] = fmaf(c.z, f.z, c.w * f.w);
         xi[FFT_IN(2 * k2p + 1)] = fmaf(c.w, f.z, -(c.z * f.w));
-        int tn = k1 * R2 + k2p + RD;
-        unsigned vo = laneoff;
-        // (only the last RD requests of a k1 step can leave the block: the first test folds at compile time)
-        if (k2p + RD >= R2 && tn >= ttotal)
-        { // last steps of this block: run on into the next block (or re-read the last row at the very end)
-          tn = has_next ? tn - ttotal : ttotal - 1;
-          vo = has_next ? laneoff_next : laneoff;
+        if constexpr (LEAN)
+        { // lane offset constant over the block, everything else in the scalar offset (tailbase above)
+          const unsigned so = k2p + RD < R2 ? (unsigned) (k1 * R2 + k2p + RD) * rowbytes
+                                            : tailbase + (unsigned) (k2p + RD - R2) * rowbytes;
+          rf[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcF, laneoff, so, 0);
+          rc[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcC, laneoff, so, 0);
         }
-        rf[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcF, vo, (unsigned) tn * rowbytes, 0);
-        rc[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcC, vo, (unsigned) tn * rowbytes, 0);
+        else
+        {
+          int tn = k1 * R2 + k2p + RD;
+          unsigned vo = laneoff;
+          // (only the last RD requests of a k1 step can leave the block: the first test folds at compile time)
+          if (k2p + RD >= R2 && tn >= ttotal)
+          { // last steps of this block: run on into the next block (or re-read the last row at the very end)
+            tn = has_next ? tn - ttotal : ttotal - 1;
+            vo = has_next ? laneoff_next : laneoff;
+          }
+          rf[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcF, vo, (unsigned) tn * rowbytes, 0);
+          rc[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcC, vo, (unsigned) tn * rowbytes, 0);
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
       FFT_RUN(xr, xi);

@@ -15,8 +15,9 @@ namespace
 //             of one register FFT arrive as R/2 such loads).  The `fast` argument carries R/2 (0 = generic).
 //   generic: reference layout kx*H + ky
 // Hp >= H is the pitch of a row pair in 16-byte words (comparison_pitch, bioem_hip.hip): H, or H + 15 where the rows
-// of a column block would otherwise all start in the same few L2 channels (N a multiple of 128); an image then
-// takes N * Hp float2.  The reference layout is never padded.
+// of a column block would otherwise all start in the same few L2 channels (N a multiple of 128), or H rounded up to a
+// multiple of 8 words (128-byte lines, line_aligned_pitch); an image then takes N * Hp float2.  The reference layout is
+// never padded.
 // ------------------------------------------------------------------------------------------------
 __host__ __device__ inline size_t layout_index(int fast, int N1, int H, int kx, int ky, int Hp = 0)
 {
