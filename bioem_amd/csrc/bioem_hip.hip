@@ -68,6 +68,9 @@
 //   slice_kernels.hpp    k_slice_axis, k_slice_centre, k_slice_project  a volume as the model: its padded, centred spectrum
 //                          and the central slices that stand in for projection + r2c (kernels_slice.hip; declarations
 //                          only here)
+//   pose_kernels.hpp     k_pose_partials, k_pose_fold  bioem_hip_pose_gradient: the derivative of a request's log posterior
+//                          with respect to the orientation matrix and the model shifts of a volume model (kernels_pose.hip;
+//                          declarations only here)
 //   soft_kernels.hpp     k_soft_cols, k_soft_rows, k_soft_accumulate  bioem_hip_view_sums_soft / _reconstruct_soft: the view
 //                          sums under a table of weighted shifts per (particle, group, CTF set) (kernels_soft.hip;
 //                          declarations only here)
@@ -148,6 +151,7 @@ struct HipErr
 #include "recon_kernels.hpp"
 #include "slice_kernels.hpp"
 #include "vgrad_kernels.hpp"
+#include "pose_kernels.hpp"
 #include "soft_kernels.hpp"
 #include "orient_kernels.hpp"
 
@@ -196,6 +200,7 @@ struct bioem_hip_ctx
   // the padding it is sized for), the matrices, view parameters and flags of a launch of the scan, Y and the double slices
   // of a batch (allocated at the first call)
   double2 *dVolA = nullptr, *dVgY = nullptr, *dVgSlices = nullptr;
+  double *dPosePart = nullptr, *dPoseRows = nullptr; // bioem_hip_pose_gradient (pose_kernels.hpp): a batch's partial sums, a launch's rows
   int volAPad = 0;
   double *dVgR = nullptr, *dVgView = nullptr;
   int *dVgFlag = nullptr;
@@ -4525,6 +4530,81 @@ int grad_candidates(bioem_hip_ctx *h)
   HIP_CHECK(h, hipMemcpyAsync(h->dScanCtf, h->dCtfParam, sizeof(float) * 3 * h->nCTF, hipMemcpyDeviceToDevice, h->stream));
   return 0;
 }
+// the requests of a gradient entry as the front half takes them
+struct GradRequests
+{
+  std::vector<BioemWindowRecord> recs;
+  std::vector<BioemScanShift> shifts;
+  std::vector<BioemGradRecord> grecs;
+  std::vector<double> ws;
+};
+
+// looks at every request (and weight; null: all 1) before anything runs; 0, or the refusal's 2 with the request named
+int grad_requests(bioem_hip_ctx *h, const Refuse &refuse, const bioem_hip_grad_request *req, const double *weights, int n,
+                  int ownLists, GradRequests &q)
+{
+  const int G = h->nCTF, cap = scan_capacity(h); // records one launch of the scan serves: whole batches
+  q.recs.resize((size_t) n);
+  q.shifts.resize((size_t) n);
+  q.grecs.resize((size_t) n);
+  q.ws.assign((size_t) n, 1.);
+  for (int i = 0; i < n; i++)
+  {
+    const bioem_hip_grad_request &r = req[i];
+    int first, len;
+    const char *why = bad_request(h, r, REQ_CONV | REQ_SHIFT, ownLists, first, len);
+    if (!why && weights && !std::isfinite(weights[i]))
+      why = "weight not finite";
+    if (why)
+      return refuse(request_refusal(h, i, why, r, REQ_CONV | REQ_SHIFT, len));
+    q.recs[(size_t) i] = {first + r.orient, r.conv, r.particle, 0, {0.f, 0.f}};
+    q.shifts[(size_t) i] = {r.shiftX, r.shiftY};
+    q.grecs[(size_t) i] = {r.conv, r.particle, (i % cap) * G + r.conv, 0};
+    if (weights)
+      q.ws[(size_t) i] = weights[i];
+  }
+  return 0;
+}
+
+// The front half of the gradient entries for the requests [g0, g0 + ng) that one launch of the scan serves: the records,
+// their orientations gathered into dGradAngles, per batch the projection and the scan's preparation into their places of
+// the launch, then the linearisation point: one scan of the launch's records against the handle's own CTF sets, of which
+// each record takes its own, and a, b, g (dGradCoef, dGradParams).
+int grad_front(bioem_hip_ctx *h, const OrientList &src, const GradRequests &q, int g0, int ng)
+{
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  const int N = h->N, OB = h->OB, G = h->nCTF;
+  const size_t M = (size_t) h->M;
+  HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, q.recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(h, hipMemcpyAsync(h->dGradRec, q.grecs.data() + g0, sizeof(BioemGradRecord) * ng, hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(h, hipMemcpyAsync(h->dGradW, q.ws.data() + g0, sizeof(double) * ng, hipMemcpyHostToDevice, h->stream));
+  if (gather_matches(h, src, h->dScanRec, ng, h->dGradAngles)) // (once per launch of the scan: the back half reads them again)
+    return 1;
+  for (int b0 = 0; b0 < ng; b0 += OB)
+  {
+    const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, q.shifts.data() + r0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
+    if (project_matches(h, src, h->dGradAngles, b0, nb, r0))
+      return 1;
+    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, r0, r0 + nb, 0, 0))
+      return 1;
+    if (r0 == 0 && grad_candidates(h)) // (part of the first batch's preparation)
+      return 1;
+    if (unreorder_runs(h, q.recs.data() + r0, nb, h->dWinRef))
+      return 1;
+    HIP_CHECK(h, bioem_scan_prep_launch(h->stream, s0.specRef, h->dWinRef, h->dScanShift, nb, N, h->dTwD,
+                                        h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0));
+    if (phase_end(h, h->stream))
+      return 1;
+  }
+  if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, g0, g0 + ng, 0, 0))
+    return 1;
+  HIP_CHECK(h, bioem_scan_launch(h->stream, h->dScanPacked, h->dScanCtf, G, h->dScanPw, h->dScanZ, h->dScanRec, h->dSumRef,
+                                 h->dSumsqRef, h->pd, ng, N, h->dScanLogp, h->dScanCc, h->dScanParams));
+  HIP_CHECK(h, bioem_grad_coef_launch(h->stream, h->dGradRec, h->dScanCc, h->dScanParams, h->dSumRef, h->dSumsqRef, ng, N,
+                                      h->dGradCoef, h->dGradParams));
+  return phase_end(h, h->stream);
+}
 } // namespace
 
 int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *req, const double *weights, int n, int ownLists,
@@ -4545,25 +4625,9 @@ int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *r
     return refuse(why);
   const int N = h->N, OB = h->OB, G = h->nCTF, nPts = h->nPts;
   const int cap = scan_capacity(h); // records one launch of the scan serves: whole batches
-  std::vector<BioemWindowRecord> recs((size_t) n);
-  std::vector<BioemScanShift> shifts((size_t) n);
-  std::vector<BioemGradRecord> grecs((size_t) n);
-  std::vector<double> ws((size_t) n, 1.);
-  for (int i = 0; i < n; i++)
-  {
-    const bioem_hip_grad_request &r = req[i];
-    int first, len;
-    const char *why = bad_request(h, r, REQ_CONV | REQ_SHIFT, ownLists, first, len);
-    if (!why && weights && !std::isfinite(weights[i]))
-      why = "weight not finite";
-    if (why)
-      return refuse(request_refusal(h, i, why, r, REQ_CONV | REQ_SHIFT, len));
-    recs[(size_t) i] = {first + r.orient, r.conv, r.particle, 0, {0.f, 0.f}};
-    shifts[(size_t) i] = {r.shiftX, r.shiftY};
-    grecs[(size_t) i] = {r.conv, r.particle, (i % cap) * G + r.conv, 0};
-    if (weights)
-      ws[(size_t) i] = weights[i];
-  }
+  GradRequests q;
+  if (const int rc = grad_requests(h, refuse, req, weights, n, ownLists, q))
+    return rc;
   if (grad_staging(h, G, nPts) || begin_analysis(h, true))
     return 1;
   bioem_hip_ctx::Slot &s0 = h->slot[0];
@@ -4575,38 +4639,7 @@ int bioem_hip_model_gradient(bioem_hip_handle h, const bioem_hip_grad_request *r
   for (int g0 = 0; g0 < n; g0 += cap) // the requests one launch of the scan serves
   {
     const int ng = std::min(cap, n - g0);
-    HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(h, hipMemcpyAsync(h->dGradRec, grecs.data() + g0, sizeof(BioemGradRecord) * ng, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(h, hipMemcpyAsync(h->dGradW, ws.data() + g0, sizeof(double) * ng, hipMemcpyHostToDevice, h->stream));
-    if (gather_matches(h, src, h->dScanRec, ng, h->dGradAngles)) // (once per launch of the scan: phase 3 reads them again)
-      return 1;
-    // per batch: the projection and the scan's preparation of its records, into their places of the launch
-    for (int b0 = 0; b0 < ng; b0 += OB)
-    {
-      const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
-      HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shifts.data() + r0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
-      if (project_matches(h, src, h->dGradAngles, b0, nb, r0))
-        return 1;
-      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, r0, r0 + nb, 0, 0))
-        return 1;
-      if (r0 == 0 && grad_candidates(h)) // (part of the first batch's preparation)
-        return 1;
-      if (unreorder_runs(h, recs.data() + r0, nb, h->dWinRef))
-        return 1;
-      HIP_CHECK(h, bioem_scan_prep_launch(h->stream, s0.specRef, h->dWinRef, h->dScanShift, nb, N, h->dTwD,
-                                          h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0));
-      if (phase_end(h, h->stream))
-        return 1;
-    }
-    // the linearisation point: one scan of the launch's records against the handle's own CTF sets, of which each record
-    // takes its own; then a, b, g
-    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, g0, g0 + ng, 0, 0))
-      return 1;
-    HIP_CHECK(h, bioem_scan_launch(h->stream, h->dScanPacked, h->dScanCtf, G, h->dScanPw, h->dScanZ, h->dScanRec, h->dSumRef,
-                                   h->dSumsqRef, h->pd, ng, N, h->dScanLogp, h->dScanCc, h->dScanParams));
-    HIP_CHECK(h, bioem_grad_coef_launch(h->stream, h->dGradRec, h->dScanCc, h->dScanParams, h->dSumRef, h->dSumsqRef, ng, N,
-                                        h->dGradCoef, h->dGradParams));
-    if (phase_end(h, h->stream))
+    if (grad_front(h, src, q, g0, ng))
       return 1;
     for (int b0 = 0; b0 < ng; b0 += OB)
     {
@@ -5322,7 +5355,7 @@ int bioem_hip_debug_slices(bioem_hip_handle h, const float *angles4, int n, int 
 namespace
 {
 // the staging of the volume-gradient entries; a failed allocation (return 1) leaves the handle as it was
-int vgrad_staging(bioem_hip_ctx *h)
+int vgrad_staging(bioem_hip_ctx *h, bool withA = true)
 {
   const size_t OB = (size_t) h->OB, M = (size_t) h->M, cap = (size_t) scan_capacity(h);
   if (!h->dVgY)
@@ -5336,7 +5369,7 @@ int vgrad_staging(bioem_hip_ctx *h)
     if (st.commit())
       return 1;
   }
-  if (h->volAPad != h->volPad)
+  if (withA && h->volAPad != h->volPad)
   { // A beside C: 16 PN^2 PH bytes
     const size_t PN = (size_t) h->volPad * h->N;
     Staging st = {h};
@@ -5465,30 +5498,14 @@ int bioem_hip_volume_gradient(bioem_hip_handle h, const bioem_hip_grad_request *
     return refuse("the model is a point model");
   const int N = h->N, OB = h->OB, G = h->nCTF, pad = h->volPad;
   const int cap = scan_capacity(h); // records one launch of the scan serves: whole batches
-  std::vector<BioemWindowRecord> recs((size_t) n);
-  std::vector<BioemScanShift> shifts((size_t) n);
-  std::vector<BioemGradRecord> grecs((size_t) n);
-  std::vector<double> ws((size_t) n, 1.);
+  GradRequests q;
+  if (const int rc = grad_requests(h, refuse, req, weights, n, ownLists, q))
+    return rc;
   double sumw = 0.;
   for (int i = 0; i < n; i++)
-  {
-    const bioem_hip_grad_request &r = req[i];
-    int first, len;
-    const char *why = bad_request(h, r, REQ_CONV | REQ_SHIFT, ownLists, first, len);
-    if (!why && weights && !std::isfinite(weights[i]))
-      why = "weight not finite";
-    if (why)
-      return refuse(request_refusal(h, i, why, r, REQ_CONV | REQ_SHIFT, len));
-    recs[(size_t) i] = {first + r.orient, r.conv, r.particle, 0, {0.f, 0.f}};
-    shifts[(size_t) i] = {r.shiftX, r.shiftY};
-    grecs[(size_t) i] = {r.conv, r.particle, (i % cap) * G + r.conv, 0};
-    if (weights)
-      ws[(size_t) i] = weights[i];
-    sumw += ws[(size_t) i];
-  }
+    sumw += q.ws[(size_t) i];
   if (grad_staging(h, G, 0) || vgrad_staging(h) || begin_analysis(h, true))
     return 1;
-  bioem_hip_ctx::Slot &s0 = h->slot[0];
   const OrientList src = ownLists ? own_list(h) : shared_list(h);
   const size_t M = (size_t) h->M, PN = (size_t) pad * N, V = PN * PN * (PN / 2 + 1);
   // every request's matrix is looked at before anything is inserted: a refusal leaves nothing half done
@@ -5496,7 +5513,7 @@ int bioem_hip_volume_gradient(bioem_hip_handle h, const bioem_hip_grad_request *
   {
     const int ng = std::min(cap, n - g0);
     int bad, flag;
-    HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, q.recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
     if (gather_matches(h, src, h->dScanRec, ng, h->dGradAngles) ||
         vgrad_views_checked(h, h->dGradAngles, src.isQuat, ng, bad, flag))
       return 1;
@@ -5512,36 +5529,8 @@ int bioem_hip_volume_gradient(bioem_hip_handle h, const bioem_hip_grad_request *
   for (int g0 = 0; g0 < n; g0 += cap) // the requests one launch of the scan serves
   {
     const int ng = std::min(cap, n - g0);
-    HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(h, hipMemcpyAsync(h->dGradRec, grecs.data() + g0, sizeof(BioemGradRecord) * ng, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(h, hipMemcpyAsync(h->dGradW, ws.data() + g0, sizeof(double) * ng, hipMemcpyHostToDevice, h->stream));
-    if (gather_matches(h, src, h->dScanRec, ng, h->dGradAngles) || vgrad_views(h, h->dGradAngles, src.isQuat, ng))
-      return 1;
-    // the front half of bioem_hip_model_gradient, unchanged: per batch the projection and the scan's preparation
-    for (int b0 = 0; b0 < ng; b0 += OB)
-    {
-      const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
-      HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shifts.data() + r0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
-      if (project_matches(h, src, h->dGradAngles, b0, nb, r0))
-        return 1;
-      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, r0, r0 + nb, 0, 0))
-        return 1;
-      if (r0 == 0 && grad_candidates(h)) // (part of the first batch's preparation)
-        return 1;
-      if (unreorder_runs(h, recs.data() + r0, nb, h->dWinRef))
-        return 1;
-      HIP_CHECK(h, bioem_scan_prep_launch(h->stream, s0.specRef, h->dWinRef, h->dScanShift, nb, N, h->dTwD,
-                                          h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0));
-      if (phase_end(h, h->stream))
-        return 1;
-    }
-    if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_CONVOLUTION, g0, g0 + ng, 0, 0))
-      return 1;
-    HIP_CHECK(h, bioem_scan_launch(h->stream, h->dScanPacked, h->dScanCtf, G, h->dScanPw, h->dScanZ, h->dScanRec, h->dSumRef,
-                                   h->dSumsqRef, h->pd, ng, N, h->dScanLogp, h->dScanCc, h->dScanParams));
-    HIP_CHECK(h, bioem_grad_coef_launch(h->stream, h->dGradRec, h->dScanCc, h->dScanParams, h->dSumRef, h->dSumsqRef, ng, N,
-                                        h->dGradCoef, h->dGradParams));
-    if (phase_end(h, h->stream))
+    // the front half of bioem_hip_model_gradient, then the matrices and view parameters of the launch's orientations
+    if (grad_front(h, src, q, g0, ng) || vgrad_views(h, h->dGradAngles, src.isQuat, ng))
       return 1;
     for (int b0 = 0; b0 < ng; b0 += OB)
     {
@@ -5665,6 +5654,150 @@ int bioem_hip_debug_volume_adjoint(bioem_hip_handle h, const double *spec_in, do
   const size_t PN = (size_t) h->volPad * h->N, V = PN * PN * (PN / 2 + 1);
   HIP_CHECK(h, hipMemcpy(h->dVolA, spec_in, sizeof(double2) * V, hipMemcpyHostToDevice));
   return vgrad_adjoint(h, "debug_volume_adjoint", h->dVolA, vol_out);
+}
+
+// ---- the gradient with respect to the orientation matrix and the model shifts of a volume model (pose_kernels.hpp) ----
+} // extern "C" (closed around the helper of the pose gradient)
+
+namespace
+{
+// the staging of the pose entries beside that of the volume gradient (without A); a failed allocation (return 1) leaves
+// the handle as it was
+int pose_staging(bioem_hip_ctx *h)
+{
+  if (vgrad_staging(h, false))
+    return 1;
+  if (h->dPosePart)
+    return 0;
+  const size_t OB = (size_t) h->OB, cap = (size_t) scan_capacity(h);
+  Staging st = {h};
+  st.get(h->dPosePart, OB * (size_t) bioem_pose_patches(h->N) * kPoseSums);
+  st.get(h->dPoseRows, (size_t) kPoseRow * cap);
+  return st.commit();
+}
+} // namespace
+
+extern "C" {
+
+int bioem_hip_pose_gradient(bioem_hip_handle h, const bioem_hip_grad_request *req, int n, int ownLists, double *pose_out,
+                            double *coef_out, bioem_hip_param5 *params_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "pose_gradient"};
+  if (!req || n < 1)
+    return refuse("null argument or no requests");
+  if (!pose_out)
+    return refuse("pose_out null");
+  if (const char *why = missing_state(h, NEED_ALL, ownLists))
+    return refuse(why);
+  if (!h->dVolC)
+    return refuse("the model is a point model");
+  const int N = h->N, OB = h->OB, G = h->nCTF, pad = h->volPad;
+  const int cap = scan_capacity(h); // records one launch of the scan serves: whole batches
+  GradRequests q;
+  if (const int rc = grad_requests(h, refuse, req, nullptr, n, ownLists, q))
+    return rc;
+  if (grad_staging(h, G, 0) || pose_staging(h) || begin_analysis(h, true))
+    return 1;
+  const OrientList src = ownLists ? own_list(h) : shared_list(h);
+  const size_t M = (size_t) h->M;
+  // every request's matrix is looked at before anything runs
+  std::vector<double> mats(9 * (size_t) std::min(cap, n));
+  for (int g0 = 0; g0 < n; g0 += cap)
+  {
+    const int ng = std::min(cap, n - g0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanRec, q.recs.data() + g0, sizeof(BioemWindowRecord) * ng, hipMemcpyHostToDevice, h->stream));
+    if (gather_matches(h, src, h->dScanRec, ng, h->dGradAngles))
+      return 1;
+    HIP_CHECK(h, bioem_recon_matrices_launch(h->stream, h->dGradAngles, nullptr, src.isQuat ? 1 : 0, ng, h->dVgR));
+    HIP_CHECK(h, hipMemcpyAsync(mats.data(), h->dVgR, sizeof(double) * 9 * ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 9 * ng; i++)
+      if (!std::isfinite(mats[(size_t) i]))
+      {
+        const int bad = g0 + i / 9;
+        int first, len;
+        orient_span(h, ownLists, req[bad].particle, first, len);
+        return refuse(request_refusal(h, bad, "an entry of the orientation's matrix is not finite", req[bad],
+                                      REQ_CONV | REQ_SHIFT, len));
+      }
+  }
+  for (int g0 = 0; g0 < n; g0 += cap) // the requests one launch of the scan serves
+  {
+    const int ng = std::min(cap, n - g0);
+    if (grad_front(h, src, q, g0, ng))
+      return 1;
+    HIP_CHECK(h, bioem_recon_matrices_launch(h->stream, h->dGradAngles, nullptr, src.isQuat ? 1 : 0, ng, h->dVgR));
+    for (int b0 = 0; b0 < ng; b0 += OB)
+    {
+      const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
+      // phase 2: the gradient spectrum and Y; phase 3: the nine sums
+      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, r0, r0 + nb, 0, 0))
+        return 1;
+      HIP_CHECK(h, bioem_grad_spectrum_launch(h->stream, h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0, h->dCTF,
+                                              h->dGradRec + b0, h->dGradCoef + 4 * (size_t) b0, 0, nb, N, h->dGradSpec));
+      HIP_CHECK(h, bioem_vgrad_prepare_launch(h->stream, h->dGradSpec, nullptr, nb, N, h->dTwD, h->shiftX, h->shiftY, 1, h->dVgY));
+      if (phase_end(h, h->stream) || phase_begin(h, h->stream, 3, r0, r0 + nb, 0, 0))
+        return 1;
+      HIP_CHECK(h, bioem_pose_launch(h->stream, h->dVolC, pad, h->dVgR + 9 * (size_t) b0, h->dVgY, nb, N, h->dPosePart,
+                                     h->dPoseRows + (size_t) kPoseRow * b0));
+      if (phase_end(h, h->stream))
+        return 1;
+    }
+    HIP_CHECK(h, hipMemcpyAsync(pose_out + (size_t) kPoseRow * g0, h->dPoseRows, sizeof(double) * kPoseRow * ng,
+                                hipMemcpyDeviceToHost, h->stream));
+    if (params_out)
+      HIP_CHECK(h, hipMemcpyAsync(params_out + g0, h->dGradParams, sizeof(bioem_hip_param5) * ng, hipMemcpyDeviceToHost, h->stream));
+    if (coef_out)
+      HIP_CHECK(h, hipMemcpyAsync(coef_out + 4 * (size_t) g0, h->dGradCoef, sizeof(double) * 4 * ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    if (coef_out)
+      for (int i = 0; i < ng; i++) // (the fourth slot of the device's coefficients is not written by this entry)
+        coef_out[4 * (size_t) (g0 + i) + 3] = pose_out[(size_t) kPoseRow * (g0 + i) + 8];
+  }
+  drain_phases(h);
+  return 0;
+}
+
+int bioem_hip_debug_pose_sums(bioem_hip_handle h, const float *angles4, int n, int isQuat, const double *gamma,
+                              const double *weights, double *pose_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "debug_pose_sums"};
+  if (!angles4 || !gamma || !pose_out || n < 1)
+    return refuse("null argument or no views");
+  if (!h->dVolC)
+    return refuse(h->dPts ? "the model is a point model" : "model not uploaded");
+  for (int i = 0; i < n && weights; i++)
+    if (!std::isfinite(weights[i]))
+      return refuse("view " + std::to_string(i) + ": weight not finite");
+  if (grad_staging(h, std::max(1, h->scanCapG), 0) || pose_staging(h) || begin_analysis(h, false))
+    return 1;
+  const int N = h->N, OB = h->OB;
+  const size_t M = (size_t) h->M;
+  for (int g0 = 0; g0 < n; g0 += OB)
+  {
+    const int nb = std::min(OB, n - g0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradAngles, angles4 + 4 * (size_t) g0, sizeof(float4) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradSpec, gamma + 2 * M * (size_t) g0, sizeof(double2) * M * nb, hipMemcpyHostToDevice,
+                                h->stream));
+    if (weights)
+      HIP_CHECK(h, hipMemcpyAsync(h->dGradW, weights + g0, sizeof(double) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, bioem_recon_matrices_launch(h->stream, h->dGradAngles, nullptr, isQuat ? 1 : 0, nb, h->dVgR));
+    HIP_CHECK(h, bioem_vgrad_prepare_launch(h->stream, h->dGradSpec, weights ? h->dGradW : nullptr, nb, N, h->dTwD, h->shiftX,
+                                            h->shiftY, 0, h->dVgY));
+    // (poisoned: a sum the kernels leave unwritten reads back as a NaN)
+    HIP_CHECK(h, hipMemsetAsync(h->dPoseRows, 0xff, sizeof(double) * kPoseRow * nb, h->stream));
+    HIP_CHECK(h, bioem_pose_launch(h->stream, h->dVolC, h->volPad, h->dVgR, h->dVgY, nb, N, h->dPosePart, h->dPoseRows));
+    HIP_CHECK(h, hipMemcpyAsync(pose_out + (size_t) kPoseRow * g0, h->dPoseRows, sizeof(double) * kPoseRow * nb,
+                                hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream)); // (the staging is reused by the next chunk)
+  }
+  return 0;
 }
 
 int bioem_hip_debug_projection(bioem_hip_handle h, int iOrient, float *spec_out)

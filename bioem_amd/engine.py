@@ -24,6 +24,8 @@ ORIENT_OCC_DTYPE = np.dtype([("occ", "<f8"), ("occ2", "<f8"), ("wmax", "<f8"), (
 WINDOW_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4")])
 SCAN_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("shiftX", "<i4"), ("shiftY", "<i4")])
 GRAD_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4"), ("shiftX", "<i4"), ("shiftY", "<i4")])
+# a row of bioem_hip_pose_gradient: d log P / d R[i][j] (rows 0 and 1), d log P / d (shiftX, shiftY), <C, A_r>, the matrix
+POSE_GRAD_DTYPE = np.dtype([("J", "<f8", (2, 3)), ("T", "<f8", (2,)), ("dot", "<f8"), ("R", "<f8", (3, 3))])
 SOFT_MEMBER_DTYPE = np.dtype([("particle", "<i4"), ("group", "<i4"), ("conv", "<i4"), ("pad", "<i4"), ("s2", "<f8"),
                               ("b", "<f8"), ("mass", "<f8")])
 GRAD_POINT_DTYPE = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("sumw", "<f8"), ("count", "<i8")])
@@ -135,6 +137,9 @@ def load_library():
         L.bioem_hip_volume_gradient.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
         L.bioem_hip_debug_volume_backproject.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp]
         L.bioem_hip_debug_volume_adjoint.argtypes = [vp, vp, vp]
+    if hasattr(L, "bioem_hip_pose_gradient"):
+        L.bioem_hip_pose_gradient.argtypes = [vp, vp, ci, ci, vp, vp, vp]
+        L.bioem_hip_debug_pose_sums.argtypes = [vp, vp, ci, ci, vp, vp, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -209,7 +214,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_set_compare_variant", "bioem_hip_debug_projection_maps", "bioem_hip_debug_stamps",
            "bioem_hip_debug_convolve_batch",
            "bioem_hip_upload_model_spectrum", "bioem_hip_upload_model_volume", "bioem_hip_debug_slices",
-           "bioem_hip_volume_gradient", "bioem_hip_debug_volume_backproject", "bioem_hip_debug_volume_adjoint"]
+           "bioem_hip_volume_gradient", "bioem_hip_debug_volume_backproject", "bioem_hip_debug_volume_adjoint",
+           "bioem_hip_pose_gradient", "bioem_hip_debug_pose_sums"]
 
 
 def _p(a):
@@ -992,6 +998,40 @@ class Engine:
         self._chk(self.L.bioem_hip_debug_volume_backproject(self.h, _p(angles) if n else None, n, int(bool(isQuat)),
                                                             _p(gamma) if n else None, _p(w), int(bool(cull)), _p(out)),
                   "debug_volume_backproject")
+        return out
+
+    def pose_gradient(self, requests, own=False, want_params=False):
+        """the derivative of the log posterior of each request (particle, orient, conv, shiftX, shiftY) of
+        GRAD_REQUEST_DTYPE [n] (or an [n, 5] integer array) with respect to rows 0 and 1 of its orientation matrix and to
+        the handle's model shifts, for a volume model (include/bioem_hip.h).  Returns a dict: "pose"
+        POSE_GRAD_DTYPE [n]; "coef" float64 [n, 4] = (a, b, g, <C, A_r>); with want_params "params" PARAM5_DTYPE [n].
+        Outside a run; a refusal raises RuntimeError with .rc == 2."""
+        r = _requests(requests, GRAD_REQUEST_DTYPE)
+        n = len(r)
+        out = {"pose": np.zeros(n, dtype=POSE_GRAD_DTYPE), "coef": np.zeros((n, 4), dtype=np.float64)}
+        if want_params:
+            out["params"] = np.zeros(n, dtype=PARAM5_DTYPE)
+        self._chk(self.L.bioem_hip_pose_gradient(self.h, _p(r) if n else None, n, int(bool(own)), _p(out["pose"]),
+                                                 _p(out["coef"]), _p(out.get("params"))), "pose_gradient")
+        return out
+
+    def best_match_pose_gradient(self, pmap, p0=0, p1=None, own=False):
+        """pose_gradient of the best record (orient, conv, cent_x, cent_y) of particles [p0, p1) of a probability block's
+        map entries (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
+        req = _match_requests(_pmap(pmap, self.nMaps), p0, self.nMaps if p1 is None else p1, GRAD_REQUEST_DTYPE)
+        return self.pose_gradient(req, own=own)
+
+    def debug_pose_sums(self, angles, gamma, weights=None, isQuat=True):
+        """test hook: Y and the two pose kernels alone, on the spectra gamma complex128 [n, N, H] handed in as Gamma under
+        the orientations angles float32 [n, 4], scaled by weights float64 [n] alone; POSE_GRAD_DTYPE [n]"""
+        angles = np.ascontiguousarray(angles, dtype=np.float32).reshape(-1, 4)
+        n = len(angles)
+        gamma = np.ascontiguousarray(gamma, dtype=np.complex128)
+        assert gamma.shape == (n, self.N, self.H), gamma.shape
+        w = _vector(weights, n)
+        out = np.zeros(n, dtype=POSE_GRAD_DTYPE)
+        self._chk(self.L.bioem_hip_debug_pose_sums(self.h, _p(angles) if n else None, n, int(bool(isQuat)),
+                                                   _p(gamma) if n else None, _p(w), _p(out)), "debug_pose_sums")
         return out
 
     def debug_volume_adjoint(self, spec):

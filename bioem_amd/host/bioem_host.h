@@ -197,6 +197,17 @@ std::string write_model_gradient(const char *file, const bioem_hip_model_point *
 // coefficients that were not finite).  17 significant digits.  Returns the empty string, or the error.
 std::string write_volume_gradient(const char *file, const double *gvol, const float *vol, int N, int nRequests, double sumw,
                                   int nonfinite);
+// --PoseGradient (posegrad.cpp): the text file of the rows rows[n][18] = {J[6], T[2], dot, R[9]} of bioem_hip_pose_gradient
+// over the particles' best records req[n], angles4[n][4] the four numbers of each record's orientation.  After the HEADER::
+// NOTATION bar, one notation line and the bar again, per record
+//  POSE particle orient q0 q1 q2 q3 conv shiftX shiftY gw0 gw1 gw2 gdeg T0 T1 dot
+// (g_w the derivative with respect to a small rotation in the frame of the image, pose_rotation_gradient; gdeg = |g_w| pi /
+// 180, the change of log P per degree along the ascent axis; T the derivative with respect to the model shifts) and one line
+//  DATASET particles rms_gdeg rms_T
+// 17 significant digits.  Returns the empty string, or the error.
+void pose_rotation_gradient(const double *row, double *g);
+std::string write_pose_gradient(const char *file, const double *rows, const bioem_hip_grad_request *req, const float *angles4,
+                                int n);
 // --OrientStats (orientstats.cpp): the text file of the sums sums[nMaps] of bioem_hip_orientation_sums.  After the
 // HEADER:: NOTATION bar, one notation line (it carries the constant as NumericalConst) and the bar again, per particle
 //  ORIENT p count logZ omax A pTop entropy nEff meanq1 meanq2 meanq3 meanq4 spreadDeg
@@ -367,6 +378,7 @@ public:
   // FILE_Round2); k = 4 is a conventional choice, not a tuned one
   std::string ctfScanFile;
   int ctfScanFactor = 4;
+  std::string poseGradFile;    // --PoseGradient: the pose gradient of the best matches on a volume model (FILE, FILE_Round2)
   std::string volGradFile;     // --VolumeGradient: the density gradient of the best matches per voxel (FILE, FILE.mrc, _Round2)
   std::string modelGradFile;   // --ModelGradient: the density gradient of the best matches per model point (FILE, FILE_Round2)
   std::string orientStatsFile; // --OrientStats: summaries of every particle's orientation posterior (WRITE_PROB_ANGLES)
@@ -446,6 +458,11 @@ private:
   // as the MRC volume file + ".mrc" (write_mrc_volume: it overlays the model file voxel for voxel) and the text file
   // (write_volume_gradient)
   void writeVolumeGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
+  // --PoseGradient: the records' gradient with respect to the orientation and the model shifts from handle h
+  // (bioem_hip_pose_gradient), written by write_pose_gradient; angles: the shared list, or with ownLists the particles'
+  // lists (anglesPerMap each, or angleOffsets [nMaps + 1] where they differ in length)
+  void writePoseGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
+                         const float *angles, size_t anglesPerMap, const long long *angleOffsets = nullptr);
   // --OrientStats: the shards' orientation sums (bioem_hip_orientation_sums) merged on the host, written by
   // write_orient_stats; numconst: the constant of ANG_PROB
   void writeOrientStats(const std::string &file, double numconst);

@@ -127,6 +127,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"CTFScanFactor", required_argument, 0, 0},
                                        {"ModelGradient", required_argument, 0, 0},
                                        {"VolumeGradient", required_argument, 0, 0},
+                                       {"PoseGradient", required_argument, 0, 0},
                                        {"OrientStats", required_argument, 0, 0},
                                        {"OrientOccupancy", required_argument, 0, 0},
                                        {"FitOrientPrior", required_argument, 0, 0},
@@ -180,6 +181,9 @@ int Driver::readOptions(int ac, char **av)
     printf("                         1, 2, 4, 8 or 16 (default 4)\n");
     printf("  --VolumeGradient arg   (Optional) With --ModelVolume: write the gradient of the log posterior of the particles' best\n");
     printf("                         matches per voxel of the model as arg.mrc, and its shells as text to arg\n");
+    printf("  --PoseGradient arg     (Optional) With --ModelVolume: write per particle the gradient of the log posterior of its best\n");
+    printf("                         match with respect to a small rotation of the orientation and to the model shifts (with\n");
+    printf("                         --RefineOrientations also arg_Round2)\n");
     printf("  --ModelGradient arg    (Optional) Write per model point the gradient of the log posterior of the particles' best\n");
     printf("                         matches with respect to its density (which part of the model do the data argue against?\n");
     printf("                         with --RefineOrientations also arg_Round2)\n");
@@ -349,6 +353,11 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Writing the density gradient of the best matches per voxel of the volume model to: " << optarg << "\n";
       volGradFile = optarg;
     }
+    else if (name == "PoseGradient")
+    {
+      std::cout << "Writing the pose gradient of the best matches on the volume model to: " << optarg << "\n";
+      poseGradFile = optarg;
+    }
     else if (name == "OrientStats")
     {
       std::cout << "Writing the summaries of the orientation posteriors to: " << optarg << "\n";
@@ -456,6 +465,10 @@ int Driver::readOptions(int ac, char **av)
           "--ModelGradient)");
   if (!volGradFile.empty() && !bestParamFile.empty())
     fatal("--PrintBestCalMap goes without --VolumeGradient");
+  if (!poseGradFile.empty() && !model.readVolume)
+    fatal("--PoseGradient needs --ModelVolume (a point model's projector has no derivative with respect to the orientation)");
+  if (!poseGradFile.empty() && !bestParamFile.empty())
+    fatal("--PrintBestCalMap goes without --PoseGradient");
   if (!bestParamFile.empty())
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
@@ -1125,6 +1138,30 @@ void Driver::writeVolumeGradient(const std::string &file, bioem_hip_handle h, co
             << "to: " << file << " and " << file << ".mrc\n";
 }
 
+// --PoseGradient: the gradient of the log posterior of every record from handle h with respect to rows 0 and 1 of its
+// orientation matrix and to the model shifts (bioem_hip_pose_gradient), then the text file (write_pose_gradient)
+void Driver::writePoseGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
+                               const float *angles, size_t anglesPerMap, const long long *angleOffsets)
+{
+  const int nMaps = particles.ntot;
+  std::vector<bioem_hip_grad_request> req;
+  std::vector<float> quats;
+  for_each_match(pmap, nMaps, "Pose gradient of RefMap %d not computed: no run compared it",
+                 [&](int p, const bioem_hip_prob_map &r) {
+                   req.push_back({p, r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y});
+                   const size_t first = !ownLists ? 0 : angleOffsets ? (size_t) angleOffsets[p] : anglesPerMap * (size_t) p;
+                   const float *q = angles + 4 * (first + (size_t) r.max_prob_orient);
+                   quats.insert(quats.end(), q, q + 4);
+                 });
+  std::vector<double> rows(18 * req.size());
+  if (!req.empty())
+    check(h, bioem_hip_pose_gradient(h, req.data(), (int) req.size(), ownLists, rows.data(), nullptr, nullptr), "pose gradient");
+  const std::string err = write_pose_gradient(file.c_str(), rows.data(), req.data(), quats.data(), (int) req.size());
+  if (!err.empty())
+    fatal("--PoseGradient: %s", err.c_str());
+  std::cout << "Pose gradient of " << req.size() << " particles' best matches written to: " << file << "\n";
+}
+
 // every shard's sums over the orientations it owns under logPrior (bioem_hip_orientation_sums), merged on the host in
 // shard order
 void Driver::shardOrientSums(const double *logPrior, std::vector<bioem_hip_orient_sums> &sums)
@@ -1439,6 +1476,8 @@ int Driver::run()
     writeModelGradient(modelGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!volGradFile.empty())
     writeVolumeGradient(volGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
+  if (!poseGradFile.empty())
+    writePoseGradient(poseGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0, param.angles.data(), 0);
   if (!viewAvgFile.empty())
     writeViewAverages(viewAvgFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
   if (!reconFile.empty())
@@ -1524,6 +1563,8 @@ void Driver::runRound2()
     writeModelGradient(modelGradFile + "_Round2", h, pm.data(), 1);
   if (!volGradFile.empty())
     writeVolumeGradient(volGradFile + "_Round2", h, pm.data(), 1);
+  if (!poseGradFile.empty())
+    writePoseGradient(poseGradFile + "_Round2", h, pm.data(), 1, lists.data(), (size_t) G);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), (size_t) G);
   bioem_hip_destroy(h);
@@ -1626,6 +1667,8 @@ void Driver::runRound2Seeds()
     writeModelGradient(modelGradFile + "_Round2", h, pm.data(), 1);
   if (!volGradFile.empty())
     writeVolumeGradient(volGradFile + "_Round2", h, pm.data(), 1);
+  if (!poseGradFile.empty())
+    writePoseGradient(poseGradFile + "_Round2", h, pm.data(), 1, lists.data(), 0, offsets.data());
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), 0, offsets.data(),
                  volu.data());

@@ -836,6 +836,33 @@ int bioem_hip_debug_volume_backproject(bioem_hip_handle h, const float *angles4,
 /* test hook: the passes from A (spec_in [PN][PN][PH] (re, im)) to gvol (vol_out [N][N][N]) alone */
 int bioem_hip_debug_volume_adjoint(bioem_hip_handle h, const double *spec_in, double *vol_out);
 
+/* ---- Pose gradient of the log posterior for a volume model (no reference counterpart) ----
+ * For request (p, o, c, X, Y) the derivative of the log posterior of that match with respect to the six entries of rows 0
+ * and 1 of the orientation's matrix R (the float matrix widened to double) and to the handle's model shifts shiftX, shiftY
+ * taken as real numbers.  With Y[a, b] of the volume gradient at weight 1, q = P (a R[0,:] + b R[1,:]), the cell c =
+ * floor(q), its weights and the eight taps v_t under every drop rule of the slice, per coefficient of the disc:
+ *   s   = sum_t ((w0 w1) w2) v_t, the slice's tap sum before its twiddle;
+ *   D_0 = sum_t sigma_0(t) (w1 w2) v_t, D_1 with (w0 w2), D_2 with (w0 w1), sigma_d(t) = +1 where tap t has d_d = 1, else
+ *         -1: the gradient of the trilinear interpolant in the cell (at f_d = 0 the right-hand derivative);
+ *   J[i][j] = sum P x_i Re(conj(Y) D_j), x_0 = a, x_1 = b: d log P / d R[i][j];
+ *   T[i]    = sum (2 pi x_i / N) Re(conj(Y) i s): d log P / d shiftX, d shiftY;
+ *   dot     = sum Re(conj(Y) s) = <C, A_r> of the volume gradient (to rounding, not to the bit).
+ * pose_out [n][18] = {J[0][0..2], J[1][0..2], T[0], T[1], dot, R[0..8]}; coef_out [n][4] = {a, b, g, dot}; params_out [n]
+ * the linearisation points; the last two may be NULL.  Double throughout, no atomics: a row's bits depend on its request
+ * alone, the same for any batch, list, position and run.  Calling rules, batches, scan launches and refusals of
+ * bioem_hip_volume_gradient (no cap on the matrix: A and the search of the back-insertion are not needed); also refused
+ * with 2, the request named and the handle usable: the model is a point model, pose_out null, an orientation whose matrix
+ * has an entry that is not finite.  Phase records as there through phase 2 (the gradient spectrum and Y); 3 the nine sums
+ * per batch. */
+int bioem_hip_pose_gradient(bioem_hip_handle h, const bioem_hip_grad_request *req, int n, int ownLists,
+                            double *pose_out /* [n][18] */, double *coef_out /* [n][4] or NULL */,
+                            bioem_hip_param5 *params_out /* [n] or NULL */);
+/* test hook: the two kernels alone on the spectra gamma [n][N][H] (re, im) handed in as Gamma under the orientations
+ * angles4 [n][4]: Y = weights[i] (Gamma conj(tw[e])) (NULL: 1), without w_b and 1 / N^2, 0 outside the disc; the views go
+ * through in chunks of maxOrientations.  pose_out [n][18] as above. */
+int bioem_hip_debug_pose_sums(bioem_hip_handle h, const float *angles4, int n, int isQuat, const double *gamma,
+                              const double *weights, double *pose_out);
+
 #ifdef __cplusplus
 }
 #endif
