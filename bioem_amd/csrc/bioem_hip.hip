@@ -5963,6 +5963,40 @@ int bioem_hip_debug_convolve_batch(bioem_hip_handle h, const float *specP, int n
   return 0;
 }
 
+int bioem_hip_debug_direct_conv(bioem_hip_handle h, const float *specConv, int nRows, double *Z_out, float *real_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "debug_direct_conv"};
+  if (!h->direct)
+    return refuse("the handle was not created under BIOEM_CC_DIRECT");
+  if (!specConv || !real_out)
+    return refuse("null argument");
+  if (nRows < 1 || nRows > h->maxOC)
+    return refuse("between 1 and the " + std::to_string(h->maxOC) + " conv rows of a batch per call");
+  if (begin_analysis(h, true))
+    return 1;
+  const size_t M = (size_t) h->M, NN = (size_t) h->N * h->N;
+  bioem_hip_ctx::Slot &s0 = h->slot[0];
+  OrientDebugBufs B;
+  float2 *stage = nullptr; // the rows in reference layout, as the staging ring of bioem_hip_compare holds them
+  HIP_CHECK(h, B.get(&stage, specConv, sizeof(float2) * M * nRows));
+  hipLaunchKernelGGL(k_reorder, dim3(std::min(2048, 8 * nRows)), dim3(256), 0, h->stream, stage, s0.conv, nRows, h->N, h->H,
+                     h->plan.halfR, h->plan.N1, h->Hp);
+  // the two launches of launch_compare_fold
+  hipLaunchKernelGGL(k_c2r_cols, dim3(h->H, nRows), dim3(128), sizeof(double2) * h->N, h->stream, s0.conv, h->N, h->H,
+                     h->plan.halfR, h->plan.N1, h->dTwD, h->dDirectZ);
+  hipLaunchKernelGGL(k_c2r_rows, dim3(h->N, nRows), dim3(128), sizeof(double2) * h->H, h->stream, h->dDirectZ, h->N,
+                     h->H, h->dTwD, h->dConvReal);
+  HIP_CHECK(h, hipGetLastError());
+  if (Z_out)
+    HIP_CHECK(h, hipMemcpyAsync(Z_out, h->dDirectZ, sizeof(double2) * M * nRows, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipMemcpyAsync(real_out, h->dConvReal, sizeof(float) * NN * nRows, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int bioem_hip_debug_particles(bioem_hip_handle h, float *refFFT_out, float *sum_out, float *sumsq_out)
 {
   HIP_CHECK(h, hipSetDevice(h->device));

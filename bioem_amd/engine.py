@@ -172,6 +172,7 @@ def load_library():
     if hasattr(L, "bioem_hip_debug_convolve_batch"):
         L.bioem_hip_debug_convolve_batch.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp]
     L.bioem_hip_debug_particles.argtypes = [vp, vp, vp, vp]
+    L.bioem_hip_debug_direct_conv.argtypes = [vp, vp, ci, vp, vp]
     L.bioem_hip_kernel_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.bioem_hip_reset_kernel_stats.argtypes = [vp]
     L.bioem_hip_uses_fast_path.argtypes = [vp]
@@ -212,7 +213,7 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_reconstruct", "bioem_hip_debug_reconstruct",
            "bioem_hip_view_sums_soft", "bioem_hip_debug_view_sums_soft", "bioem_hip_reconstruct_soft",
            "bioem_hip_set_compare_variant", "bioem_hip_debug_projection_maps", "bioem_hip_debug_stamps",
-           "bioem_hip_debug_convolve_batch",
+           "bioem_hip_debug_convolve_batch", "bioem_hip_debug_direct_conv",
            "bioem_hip_upload_model_spectrum", "bioem_hip_upload_model_volume", "bioem_hip_debug_slices",
            "bioem_hip_volume_gradient", "bioem_hip_debug_volume_backproject", "bioem_hip_debug_volume_adjoint",
            "bioem_hip_pose_gradient", "bioem_hip_debug_pose_sums"]
@@ -1216,6 +1217,18 @@ class Engine:
         if raw is not None:
             raw = raw.reshape(-1)[:rows * self.N * info["Hp"] * 2].reshape(rows, self.N * info["Hp"], 2).copy()
         return conv, params, raw, info
+
+    def debug_direct_conv(self, specConv, want_Z=True):
+        """the c2r of a BIOEM_CC_DIRECT handle on conv spectra float32 [n, N, H, 2] in reference layout
+        (bioem_hip_debug_direct_conv): (Z float64 [n, N, H, 2] of the column pass or None, the real maps float32 [n, N, N],
+        unnormalised).  Invalid arguments raise with .rc == 2; the handle stays usable."""
+        specConv = _spectra(specConv)
+        assert specConv.ndim == 4 and specConv.shape[1:] == (self.N, self.H, 2), specConv.shape
+        n = len(specConv)
+        Z = np.zeros((n, self.N, self.H, 2), dtype=np.float64) if want_Z else None
+        real = np.zeros((n, self.N, self.N), dtype=np.float32)
+        self._chk(self.L.bioem_hip_debug_direct_conv(self.h, _p(specConv), n, _p(Z), _p(real)), "debug_direct_conv")
+        return Z, real
 
     def debug_particles(self):
         spec = np.empty((self.nMaps, self.N, self.H, 2), dtype=np.float32)

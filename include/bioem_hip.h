@@ -367,6 +367,13 @@ int bioem_hip_debug_convolution(bioem_hip_handle h, int iOrient, int iConv, floa
  * path selected without a buffer for the ordered sums of nO nC rows. */
 int bioem_hip_debug_convolve_batch(bioem_hip_handle h, const float *specP, int nO, int c0, int nC, float *conv_out,
                                    bioem_hip_param5 *params_out, float *raw_out, int *info_out);
+/* The c2r of a BIOEM_CC_DIRECT handle (compare_direct.hpp) on conv spectra the caller hands in, outside a run: specConv
+ * [nRows][N][N/2+1][2] (reference layout) goes into the conv rows of buffer set 0 through the reorder of
+ * bioem_hip_compare, and k_c2r_cols and k_c2r_rows are launched on them with the launch parameters of a run.  Z_out NULL
+ * or [nRows][N][N/2+1] double2, the column pass Z[x][ky]; real_out [nRows][N][N] float, the unnormalised real maps the
+ * comparison kernel reads.  Refused with 2 and a message, the handle usable afterwards: a handle that is not direct, a
+ * null argument (Z_out may be), nRows outside [1, conv rows of a batch]. */
+int bioem_hip_debug_direct_conv(bioem_hip_handle h, const float *specConv, int nRows, double *Z_out, float *real_out);
 /* download device-side particle precompute (reference layout); refFFT_out may be NULL: the sums alone */
 int bioem_hip_debug_particles(bioem_hip_handle h, float *refFFT_out, float *sum_out, float *sumsq_out);
 /* accumulated HIP-event time of the comparison kernel on the engine's stream since the last reset:
