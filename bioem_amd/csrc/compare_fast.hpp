@@ -465,8 +465,13 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
   // buffer descriptors built from wave-uniform values only (blockIdx / readfirstlane'd wave id)
   const auto rsrcF = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<float2 *>(a.ref + (size_t) p * M)), 0,
                                                        (int) (M * sizeof(float2)), 0x00020000);
-  const auto rsrcC = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<float2 *>(a.conv + (size_t) oc * M)), 0,
-                                                       (int) (M * sizeof(float2)), 0x00020000);
+  // STRIP (strip lanes, below; the lean kernels of 16 k points): ONE conv descriptor for the block, based at its first
+  // row and covering its sRows rows
+  constexpr bool STRIP = LEAN && R2 % 8 == 0;
+  const int sRows = STRIP ? min(4, ocEnd - ocFirst) : 1;
+  const auto rsrcC = __builtin_amdgcn_make_buffer_rsrc(
+      uniform_ptr(const_cast<float2 *>(a.conv + (size_t) (STRIP ? ocFirst : oc) * M)), 0,
+      (int) ((STRIP ? (size_t) sRows : (size_t) 1) * M * sizeof(float2)), 0x00020000);
 
   // window lanes (LEAN reads none of the general pass's: G ... rowbase stay unreferenced there)
   const int nd = LEAN ? NW : a.nd;
@@ -517,12 +522,57 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
   const int sHalf = (N1 + 1) >> 1;
   const int hsel = lane >> 5;
   const unsigned halfoff = (unsigned) (hsel * sHalf * R2) * rowbytes;
+  // STRIP, strip lanes: during the column pass a lane is (row sq of the block, column sc of a 16-column strip), and in
+  // column block b wave w takes columns 64 b + 16 w + sc of ALL rows of the block: the same 64 columns x 4 rows per
+  // block, the same k1 steps per wave, and for every (row, column) the arithmetic of the lane = column mapping in its
+  // order (the recombination twiddles are wave-uniform either way).  What changes is who asks for the operands.
+  //   conv      every lane, through the block's descriptor: lane offset = row sqc M 8 + column 16, sqc = sq clamped to
+  //             the block's last row (a ragged last group computes that row again, as a clamped wave does); a request is
+  //             four 256-byte runs, eight 128-byte lines as before.
+  //   particle  ONE request per group of four row pairs: lane (sq, sc) asks for column sc of row pair 4 g + sq, so a
+  //             request is again four 256-byte runs, all of it wanted, a quarter as many requests per wave and per block
+  //             a quarter of the L1 accesses (the four waves no longer ask for the same 1 KiB each).  A landed group goes
+  //             with one ds_write_b128 (lane l at byte 16 l: row pair r of the group at 256 r + 16 sc) into one of two
+  //             1 KiB slots at the head of the wave's OWN T region Tl, idle during the k1 loop, and every lane reads row
+  //             pair t + 2 back at (slot, row pair, sc) -- four lanes per address, an LDS broadcast -- into the registers
+  //             the product of row pair t has just released.
+  // Groups: a step of R2 = 8 row pairs is two groups, so slot and register of a group are compile-time functions of k2p.
+  // In the iteration of row pair t = 4 g group g + 1 (requested eight iterations earlier) is written to slot (g + 1) % 2
+  // -- whose last reader, row pair 4 g - 1, was read back at t - 3 -- and group g + 3 requested into its registers.
+  // No new barrier: Tl of wave w is read by wave w alone (window pass), other waves write it only between the two
+  // barriers of a block, the first of which follows every wave's k1 loop (whose last read-backs are in registers by
+  // then: the barrier waits for them); in between the scratch is written and read by one wave in its program order.
+  const int sq = STRIP ? lane >> 4 : 0, sc = STRIP ? lane & 15 : 0;
   auto lane_offset = [&](int b) -> unsigned { // byte offset of this lane's column (and half) in column block b
     const bool sp = SPLIT_OK && a.split && b == nblk - 1;
-    const int kyb = b * 64 + (sp ? (lane & 31) : lane);
+    const int kyb = b * 64 + (STRIP ? wave * 16 + sc : sp ? (lane & 31) : lane);
     return (unsigned) (kyb < H ? kyb : H - 1) * 16u + (sp ? halfoff : 0u);
   };
-  u32x4 rf[RD], rc[RD];
+  // No conv request leaves the descriptor's sRows N Hp 8 bytes: a request's offset is that of the one-image case (below,
+  // at `nextstart`: it ends inside the image) plus sqc images, sqc <= sRows - 1.
+  const unsigned rowsel = STRIP ? (unsigned) min(sq, sRows - 1) * (unsigned) (M * sizeof(float2)) : 0u;
+  // (the writers' address is formed from `lane`, the readers' from `sc`: two expressions, so that the compiler, which
+  // knows nothing of the other lanes' stores, cannot forward a lane's own store into its read; the wave-scope fences say
+  // the same and emit nothing)
+  unsigned char *scr = STRIP ? reinterpret_cast<unsigned char *>(Tl) + sc * 16 : nullptr;
+  unsigned char *scrw = STRIP ? reinterpret_cast<unsigned char *>(Tl) + lane * 16 : nullptr;
+  const unsigned grow = STRIP ? (unsigned) sq * rowbytes : 0u; // the lane's row pair inside a group
+  u32x4 rf[RD], rc[RD], fr[2], rg[2];
+  if constexpr (STRIP)
+  {
+    const unsigned lo0 = lane_offset(0);
+    const u32x4 g0 = __builtin_amdgcn_raw_buffer_load_b128(rsrcF, lo0 + grow, 0u, 0);
+    rg[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrcF, lo0 + grow, 4u * rowbytes, 0);
+    rg[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrcF, lo0 + grow, 8u * rowbytes, 0);
+#pragma unroll
+    for (int t = 0; t < RD; t++)
+      rc[t] = __builtin_amdgcn_raw_buffer_load_b128(rsrcC, lo0 + rowsel, (unsigned) t * rowbytes, 0);
+    *reinterpret_cast<u32x4 *>(scrw) = g0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    fr[0] = *reinterpret_cast<const u32x4 *>(scr);
+    fr[1] = *reinterpret_cast<const u32x4 *>(scr + 256);
+  }
+  else
   {
     const unsigned lo0 = lane_offset(0);
 #pragma unroll
@@ -537,8 +587,10 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
     const bool split = SPLIT_OK && a.split && blk == nblk - 1;
     const int n1 = split ? sHalf : N1;
     const int ttotal = R2 * n1;
-    const int ky = blk * 64 + (split ? (lane & 31) : lane);
+    const int ky = blk * 64 + (STRIP ? wave * 16 + sc : split ? (lane & 31) : lane);
     const unsigned laneoff = lane_offset(blk);
+    const unsigned laneoffC = STRIP ? laneoff + rowsel : laneoff; // (STRIP: the conv operand of this lane's row,
+    const unsigned laneoffF = STRIP ? laneoff + grow : 0u;        //  the particle operand of its row pair of a group)
     const unsigned laneoff_next = lane_offset(min(blk + 1, nblk - 1));
     const bool has_next = blk + 1 < nblk;
     // LEAN (no split block): a block that has a successor has all 64 lanes live, and the successor's column of a lane
@@ -553,6 +605,14 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
     // request ends inside row pair RD + 1 <= 6 of the >= 64 a shape with two blocks has.  Without a successor it ends
     // inside row pair RD - 1 <= 4, and N / 2 = N1 R / 2 >= 6 is part of lean_launch_ok (bioem_hip.hip).  Nothing relies
     // on the zeros a descriptor returns out of range.
+    // Strip lanes: the columns of a block are the same 64, lane 63's now asked for by lane 15 of wave 3, so the bound
+    // holds for the conv requests as it stands, inside the image sqc of the block's descriptor.  A particle request is a
+    // group: row pairs 4 g .. 4 g + 3 (the lane's sq rowbytes on top of its column), requested up to two steps ahead.
+    // Inside a block the last group asked for is the block's last.  Past it: with a successor, groups 0 .. 2 of the next
+    // block, i.e. up to row pair 11 plus 1 024 bytes and the column, under two row pairs: inside row pair 13 of >= 64;
+    // without one (and in the prologue), groups 0 .. 2 of this block again, row pairs 0 .. 11 of N / 2 = 8 N1 -- inside
+    // the image from N1 = 2 on, and a 21-row window needs N >= 32.  These tail groups are never consumed; should one lie
+    // beyond the image (N1 = 1, which no plan of this window has), the one-image descriptor makes no access for it.
     const unsigned nextstart = has_next ? 1024u : 0u;
     float Tr[NW], Ti[NW];
 #pragma unroll
@@ -584,10 +644,17 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
       // LEAN: scalar offset of the step's last RD requests, chosen once per step -- the next step's rows, or from the
       // block's last step the first RD rows of what follows (nextstart)
       const unsigned tailbase = !LEAN ? 0u : k1 + 1 < n1 ? (unsigned) ((k1 + 1) * R2) * rowbytes : nextstart;
+      // STRIP: base of the row pairs j steps ahead (a group of particle row pairs is requested up to two steps ahead)
+      // (past the block's last step: what follows, `nextstart`, as one wave-uniform correction of the running offset --
+      // a select between two loop invariants, where a select between two products became a branch inside the loop)
+      const unsigned wrapadj = STRIP ? nextstart - (unsigned) ttotal * rowbytes : 0u;
+      auto stepbase = [&](int j) -> unsigned {
+        return (unsigned) ((k1 + j) * R2) * rowbytes + (k1 + j < n1 ? 0u : wrapadj);
+      };
 #pragma unroll
       for (int k2p = 0; k2p < R2; k2p++)
       {
-        const float4 f = as_float4(rf[k2p % RD]);
+        const float4 f = as_float4(STRIP ? fr[k2p % 2] : rf[k2p % RD]);
         const float4 c = as_float4(rc[k2p % RD]);
         // X = conv * conj(ref)   (bioem.cpp:1452-1455)
         xr[FFT_IN(2 * k2p)] = fmaf(c.x, f.x, c.y * f.y);
@@ -598,8 +665,23 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
         { // lane offset constant over the block, everything else in the scalar offset (tailbase above)
           const unsigned so = k2p + RD < R2 ? (unsigned) (k1 * R2 + k2p + RD) * rowbytes
                                             : tailbase + (unsigned) (k2p + RD - R2) * rowbytes;
-          rf[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcF, laneoff, so, 0);
-          rc[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcC, laneoff, so, 0);
+          if constexpr (STRIP)
+          {
+            if (k2p % 4 == 0)
+            { // group k2p / 4 + 1 of this step into its slot, group k2p / 4 + 3 requested: row pairs k2p + 12 .. + 15
+              const int gs = (k2p / 4 + 1) % 2;
+              const int rq = k2p + 12, sj = rq / R2;
+              const unsigned sog = (sj == 1 ? tailbase : stepbase(sj)) + (unsigned) (rq % R2) * rowbytes;
+              *reinterpret_cast<u32x4 *>(scrw + gs * 1024) = rg[gs];
+              rg[gs] = __builtin_amdgcn_raw_buffer_load_b128(rsrcF, laneoffF, sog, 0);
+              __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
+            // row pair k2p + 2 back into the registers `f` has just left
+            fr[k2p % 2] = *reinterpret_cast<const u32x4 *>(scr + (((k2p + 2) / 4) % 2) * 1024 + ((k2p + 2) % 4) * 256);
+          }
+          else
+            rf[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcF, laneoff, so, 0);
+          rc[k2p % RD] = __builtin_amdgcn_raw_buffer_load_b128(rsrcC, laneoffC, so, 0);
         }
         else
         {
@@ -633,6 +715,15 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
         Ti[d + WD] = ti;
       }
     }
+    // STRIP: slot 0 holds the first group of what follows, and the T exchange below overwrites it: its row pairs 2 and 3,
+    // not read back yet, cross the exchange in registers and are put back after this wave's window pass (every lane of a
+    // column writes the same 16 bytes; no other wave touches Tl after the second barrier)
+    u32x4 carry[2];
+    if constexpr (STRIP)
+    {
+      carry[0] = *reinterpret_cast<const u32x4 *>(scr + 512);
+      carry[1] = *reinterpret_cast<const u32x4 *>(scr + 768);
+    }
     if constexpr (SPLIT_OK)
     if (split)
     {
@@ -658,9 +749,20 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
     // T block of THIS wave only, written and read between block barriers (they keep the 4 waves in lock-step)
     {
       __syncthreads(); // previous window reads are done
+      if constexpr (STRIP)
+      { // strip lanes: this lane holds T of row sq at column 16 wave + sc of the block -- into row sq's T region, which
+        // wave sq reads below (a row beyond the block's last is the clamped copy, as a clamped wave's was)
+        float2 *Tq = Tall + (size_t) sq * NW * TS + wave * 16 + sc;
 #pragma unroll
-      for (int d = 0; d < NW; d++)
-        Tl[d * TS + lane] = make_float2(Tr[d] * wgt, Ti[d] * wgt);
+        for (int d = 0; d < NW; d++)
+          Tq[d * TS] = make_float2(Tr[d] * wgt, Ti[d] * wgt);
+      }
+      else
+      {
+#pragma unroll
+        for (int d = 0; d < NW; d++)
+          Tl[d * TS + lane] = make_float2(Tr[d] * wgt, Ti[d] * wgt);
+      }
       if (symw)
       {
 #pragma unroll
@@ -689,6 +791,12 @@ __global__ __launch_bounds__(256, 3) void k_compare_fast(const ARGS a)
         for (int r = 0; r < NR; r++)
           rowoff[r] = row_of(r);
         window_accumulate<NR, false, 32, TS>(Tl, twl, N, step, idx0, rowoff, nr, acc, npairs);
+      }
+      if constexpr (STRIP)
+      {
+        *reinterpret_cast<u32x4 *>(scr + 512) = carry[0];
+        *reinterpret_cast<u32x4 *>(scr + 768) = carry[1];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       }
     }
   }
