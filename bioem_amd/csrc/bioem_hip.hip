@@ -71,6 +71,9 @@
 //   pose_kernels.hpp     k_pose_partials, k_pose_fold  bioem_hip_pose_gradient: the derivative of a request's log posterior
 //                          with respect to the orientation matrix and the model shifts of a volume model (kernels_pose.hip;
 //                          declarations only here)
+//   ctfgrad_kernels.hpp  k_ctfgrad_partials, k_ctfgrad_fold, k_ctfgrad_finish  bioem_hip_ctf_gradient: gradient and curvature
+//                          of a request's log posterior with respect to the CTF triple of its set (kernels_ctfgrad.hip;
+//                          declarations only here)
 //   soft_kernels.hpp     k_soft_cols, k_soft_rows, k_soft_accumulate  bioem_hip_view_sums_soft / _reconstruct_soft: the view
 //                          sums under a table of weighted shifts per (particle, group, CTF set) (kernels_soft.hip;
 //                          declarations only here)
@@ -152,6 +155,7 @@ struct HipErr
 #include "slice_kernels.hpp"
 #include "vgrad_kernels.hpp"
 #include "pose_kernels.hpp"
+#include "ctfgrad_kernels.hpp"
 #include "soft_kernels.hpp"
 #include "orient_kernels.hpp"
 
@@ -201,6 +205,12 @@ struct bioem_hip_ctx
   // of a batch (allocated at the first call)
   double2 *dVolA = nullptr, *dVgY = nullptr, *dVgSlices = nullptr;
   double *dPosePart = nullptr, *dPoseRows = nullptr; // bioem_hip_pose_gradient (pose_kernels.hpp): a batch's partial sums, a launch's rows
+  // bioem_hip_ctf_gradient (ctfgrad_kernels.hpp): a batch's partial sums, a launch's sums and rows; the host's row map and
+  // table of the radial variable for ctfgPixel (0: none yet); a batch's triples and derivatives of the debug entry
+  double *dCtfgPart = nullptr, *dCtfgSums = nullptr, *dCtfgRows = nullptr, *dCtfgDerivs = nullptr;
+  int *dCtfgRowIdx = nullptr;
+  float *dCtfgRadsq = nullptr, *dCtfgTheta = nullptr;
+  float ctfgPixel = 0.f;
   int volAPad = 0;
   double *dVgR = nullptr, *dVgView = nullptr;
   int *dVgFlag = nullptr;
@@ -5794,6 +5804,235 @@ int bioem_hip_debug_pose_sums(bioem_hip_handle h, const float *angles4, int n, i
     HIP_CHECK(h, hipMemsetAsync(h->dPoseRows, 0xff, sizeof(double) * kPoseRow * nb, h->stream));
     HIP_CHECK(h, bioem_pose_launch(h->stream, h->dVolC, h->volPad, h->dVgR, h->dVgY, nb, N, h->dPosePart, h->dPoseRows));
     HIP_CHECK(h, hipMemcpyAsync(pose_out + (size_t) kPoseRow * g0, h->dPoseRows, sizeof(double) * kPoseRow * nb,
+                                hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream)); // (the staging is reused by the next chunk)
+  }
+  return 0;
+}
+
+// ---- gradient and curvature of the log posterior with respect to the CTF triple of a request (ctfgrad_kernels.hpp) ----
+} // extern "C" (closed around the helpers of the CTF gradient)
+
+namespace
+{
+// The host's row map and its table of the radial variable (ctf_kernel_one of the host layer, CTF mode).  The map is what
+// replaying the host's loop leaves behind (index i < H is written to rows i and N - 1 - i, the last write wins); the table
+// holds, per m = i^2 + j^2, the float of the host's own expression, formed here with the same float operations.
+void ctfgrad_tables(int N, float pixelSize, std::vector<int> &rowIdx, std::vector<float> &radsq)
+{
+  const int H = N / 2 + 1;
+  rowIdx.assign((size_t) N, 0);
+  for (int i = 0; i < H; i++)
+  {
+    rowIdx[(size_t) i] = i;
+    rowIdx[(size_t) (N - 1 - i)] = i;
+  }
+  radsq.assign(2 * (size_t) (H - 1) * (H - 1) + 1, 0.f);
+  for (int i = 0; i < H; i++)
+    for (int j = 0; j < H; j++)
+      radsq[(size_t) (i * i + j * j)] = (float) (i * i + j * j) / N / N / pixelSize / pixelSize;
+}
+
+// the staging of the CTF gradient entries beside that of the gradient entries, and the tables for pixelSize (uploaded once
+// per handle and pixel size); a failed allocation (return 1) leaves the handle as it was
+int ctfgrad_staging(bioem_hip_ctx *h, float pixelSize, bool derivs)
+{
+  const size_t OB = (size_t) h->OB, cap = (size_t) scan_capacity(h), Hm = (size_t) h->H - 1;
+  if (!h->dCtfgPart)
+  {
+    Staging st = {h};
+    st.get(h->dCtfgPart, OB * (size_t) bioem_ctfgrad_blocks(h->N) * kCtfgSums);
+    st.get(h->dCtfgSums, cap * kCtfgSums);
+    st.get(h->dCtfgRows, cap * kCtfgRow);
+    st.get(h->dCtfgTheta, 3 * OB);
+    st.get(h->dCtfgRowIdx, (size_t) h->N);
+    st.get(h->dCtfgRadsq, 2 * Hm * Hm + 1);
+    if (st.commit())
+      return 1;
+    h->ctfgPixel = 0.f;
+  }
+  if (derivs && !h->dCtfgDerivs)
+  {
+    Staging st = {h};
+    st.get(h->dCtfgDerivs, OB * (size_t) h->M * kCtfgDerivs);
+    if (st.commit())
+      return 1;
+  }
+  if (h->ctfgPixel != pixelSize)
+  {
+    std::vector<int> rowIdx;
+    std::vector<float> radsq;
+    ctfgrad_tables(h->N, pixelSize, rowIdx, radsq);
+    HIP_CHECK(h, hipMemcpyAsync(h->dCtfgRowIdx, rowIdx.data(), sizeof(int) * rowIdx.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dCtfgRadsq, radsq.data(), sizeof(float) * radsq.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream)); // (the vectors are read by then)
+    h->ctfgPixel = pixelSize;
+  }
+  return 0;
+}
+
+// what the entries refuse about the handle and the pixel size; nullptr: nothing
+const char *ctfgrad_refused(const bioem_hip_ctx *h, float pixelSize)
+{
+  if (h->pd.tousepsf)
+    return "the handle is in PSF mode: its kernels are transforms of a real-space function, not the closed form";
+  if (!(std::isfinite(pixelSize) && pixelSize > 0.f))
+    return "pixelSize not finite or not positive";
+  return nullptr;
+}
+
+// rho = sqrt(1 - amp^2) / amp is singular at both ends (and the host refuses amp < 1e-10)
+bool ctfgrad_amp_outside(float amp) { return !((double) amp > 1e-10 && amp < 1.f); }
+} // namespace
+
+extern "C" {
+
+int bioem_hip_ctf_gradient(bioem_hip_handle h, const bioem_hip_grad_request *req, int n, int ownLists, float pixelSize,
+                           double *rows_out, double *coef_out, bioem_hip_param5 *params_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "ctf_gradient"};
+  if (!req || n < 1)
+    return refuse("null argument or no requests");
+  if (!rows_out)
+    return refuse("rows_out null");
+  if (const char *why = ctfgrad_refused(h, pixelSize))
+    return refuse(why);
+  if (const char *why = missing_state(h, NEED_ALL, ownLists))
+    return refuse(why);
+  const int N = h->N, OB = h->OB, G = h->nCTF;
+  const int cap = scan_capacity(h); // records one launch of the scan serves: whole batches
+  GradRequests q;
+  if (const int rc = grad_requests(h, refuse, req, nullptr, n, ownLists, q))
+    return rc;
+  // every request's amplitude is looked at before anything runs
+  std::vector<float> theta(3 * (size_t) G);
+  HIP_CHECK(h, hipMemcpy(theta.data(), h->dCtfParam, sizeof(float) * theta.size(), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; i++)
+    if (ctfgrad_amp_outside(theta[3 * (size_t) req[i].conv]))
+    {
+      int first, len;
+      orient_span(h, ownLists, req[i].particle, first, len);
+      return refuse(request_refusal(h, i, "amp of the CTF set outside (1e-10, 1)", req[i], REQ_CONV | REQ_SHIFT, len));
+    }
+  if (grad_staging(h, G, 0) || ctfgrad_staging(h, pixelSize, false) || begin_analysis(h, true))
+    return 1;
+  const OrientList src = ownLists ? own_list(h) : shared_list(h);
+  const size_t M = (size_t) h->M;
+  for (int g0 = 0; g0 < n; g0 += cap) // the requests one launch of the scan serves
+  {
+    const int ng = std::min(cap, n - g0);
+    if (grad_front(h, src, q, g0, ng))
+      return 1;
+    for (int b0 = 0; b0 < ng; b0 += OB)
+    {
+      const int nb = std::min(OB, ng - b0), r0 = g0 + b0;
+      // phase 2: the twenty sums; phase 3: the rows
+      if (phase_begin(h, h->stream, BIOEM_HIP_PHASE_COMPARISON, r0, r0 + nb, 0, 0))
+        return 1;
+      HIP_CHECK(h, bioem_ctfgrad_sums_launch(h->stream, h->dScanPw + M * (size_t) b0, h->dScanZ + M * (size_t) b0, h->dGradRec + b0,
+                                             h->dCtfParam, h->dCtfgRowIdx, h->dCtfgRadsq, nb, N, h->dCtfgPart,
+                                             h->dCtfgSums + (size_t) kCtfgSums * b0, nullptr));
+      if (phase_end(h, h->stream) || phase_begin(h, h->stream, 3, r0, r0 + nb, 0, 0))
+        return 1;
+      HIP_CHECK(h, bioem_ctfgrad_finish_launch(h->stream, h->dCtfgSums + (size_t) kCtfgSums * b0, h->dGradRec + b0, h->dScanCc,
+                                               h->dScanParams, h->dSumRef, h->dSumsqRef, h->dGradCoef + 4 * (size_t) b0, h->pd,
+                                               nb, N, h->dCtfgRows + (size_t) kCtfgRow * b0));
+      if (phase_end(h, h->stream))
+        return 1;
+    }
+    HIP_CHECK(h, hipMemcpyAsync(rows_out + (size_t) kCtfgRow * g0, h->dCtfgRows, sizeof(double) * kCtfgRow * ng,
+                                hipMemcpyDeviceToHost, h->stream));
+    if (params_out)
+      HIP_CHECK(h, hipMemcpyAsync(params_out + g0, h->dGradParams, sizeof(bioem_hip_param5) * ng, hipMemcpyDeviceToHost, h->stream));
+    if (coef_out)
+      HIP_CHECK(h, hipMemcpyAsync(coef_out + 4 * (size_t) g0, h->dGradCoef, sizeof(double) * 4 * ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    if (coef_out)
+      for (int i = 0; i < ng; i++) // (the fourth slot of the device's coefficients is not written by this entry)
+        coef_out[4 * (size_t) (g0 + i) + 3] = 0.;
+  }
+  drain_phases(h);
+  return 0;
+}
+
+int bioem_hip_debug_ctf_gradient(bioem_hip_handle h, const float *specP, const float *specRef, const int *shiftXY,
+                                 const float *triples, int n, float pixelSize, double *rows_out, double *derivs_out)
+{
+  if (!h)
+    return 2;
+  HIP_CHECK(h, hipSetDevice(h->device));
+  const Refuse refuse = {h, "debug_ctf_gradient"};
+  if (!specP || !specRef || !shiftXY || !triples || n < 1)
+    return refuse("null argument or no records");
+  if (!rows_out)
+    return refuse("rows_out null");
+  if (const char *why = ctfgrad_refused(h, pixelSize))
+    return refuse(why);
+  if (const int rc = debug_shifts_refused(h, refuse, shiftXY, n))
+    return rc;
+  for (int i = 0; i < n; i++)
+    if (ctfgrad_amp_outside(triples[3 * (size_t) i]))
+      return refuse("record " + std::to_string(i) + ": amp outside (1e-10, 1)");
+  if (grad_staging(h, std::max(1, h->scanCapG), 0) || ctfgrad_staging(h, pixelSize, derivs_out != nullptr) ||
+      begin_analysis(h, false)) // (buffer set 0 is not written)
+    return 1;
+  const int N = h->N, H = h->H, OB = h->OB;
+  const size_t M = (size_t) h->M;
+  const double Nt = (double) N * (double) N;
+  std::vector<BioemGradRecord> grecs((size_t) OB);
+  for (int i = 0; i < OB; i++)
+    grecs[(size_t) i] = {i, i, i, 0};
+  HIP_CHECK(h, hipMemcpyAsync(h->dGradRec, grecs.data(), sizeof(BioemGradRecord) * OB, hipMemcpyHostToDevice, h->stream));
+  std::vector<double> sums((size_t) kCtfgSums * OB);
+  std::vector<bioem_hip_param5> par((size_t) OB);
+  std::vector<float> lin(3 * (size_t) OB); // cc, sumRef, sumsqRef of the batch
+  for (int b0 = 0; b0 < n; b0 += OB)
+  {
+    const int nb = std::min(OB, n - b0);
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanShift, shiftXY + 2 * (size_t) b0, sizeof(BioemScanShift) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinConv, specP + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dWinRef, specRef + 2 * M * (size_t) b0, sizeof(float2) * M * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dCtfgTheta, triples + 3 * (size_t) b0, sizeof(float) * 3 * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, bioem_scan_prep_launch(h->stream, h->dWinConv, h->dWinRef, h->dScanShift, nb, N, h->dTwD, h->dScanPw, h->dScanZ));
+    // (poisoned: a sum or an entry of a row the kernels leave unwritten reads back as a NaN)
+    HIP_CHECK(h, hipMemsetAsync(h->dCtfgSums, 0xff, sizeof(double) * kCtfgSums * nb, h->stream));
+    HIP_CHECK(h, hipMemsetAsync(h->dCtfgRows, 0xff, sizeof(double) * kCtfgRow * nb, h->stream));
+    HIP_CHECK(h, bioem_ctfgrad_sums_launch(h->stream, h->dScanPw, h->dScanZ, h->dGradRec, h->dCtfgTheta, h->dCtfgRowIdx,
+                                           h->dCtfgRadsq, nb, N, h->dCtfgPart, h->dCtfgSums, derivs_out ? h->dCtfgDerivs : nullptr));
+    HIP_CHECK(h, hipMemcpyAsync(sums.data(), h->dCtfgSums, sizeof(double) * kCtfgSums * nb, hipMemcpyDeviceToHost, h->stream));
+    if (derivs_out)
+      HIP_CHECK(h, hipMemcpyAsync(derivs_out + (size_t) kCtfgDerivs * M * b0, h->dCtfgDerivs, sizeof(double) * kCtfgDerivs * M * nb,
+                                  hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    // the linearisation point the spectra imply: sumC the projection's origin (k(0) = 1), sumsquareC and cc the sums ss0
+    // and cc0 over Nt narrowed to float, the particle's sum its origin and its sum of squares by Parseval's identity
+    for (int i = 0; i < nb; i++)
+    {
+      const float *P = specP + 2 * M * (size_t) (b0 + i), *F = specRef + 2 * M * (size_t) (b0 + i);
+      double ssr = 0.;
+      for (int e = 0; e < N * H; e++)
+      {
+        const int j = e % H;
+        const double fr = (double) F[2 * e], fi = (double) F[2 * e + 1];
+        ssr += ((j == 0 || 2 * j == N) ? 1. : 2.) * (fr * fr + fi * fi);
+      }
+      const float *t3 = triples + 3 * (size_t) (b0 + i);
+      par[(size_t) i] = {t3[0], t3[1], t3[2], P[0], (float) (sums[(size_t) kCtfgSums * i] / Nt)};
+      lin[(size_t) i] = (float) (sums[(size_t) kCtfgSums * i + 1] / Nt);
+      lin[(size_t) OB + i] = F[0];
+      lin[2 * (size_t) OB + i] = (float) (ssr / Nt);
+    }
+    HIP_CHECK(h, hipMemcpyAsync(h->dGradParams, par.data(), sizeof(bioem_hip_param5) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanCc, lin.data(), sizeof(float) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, hipMemcpyAsync(h->dScanSums, lin.data() + OB, sizeof(float) * 2 * OB, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(h, bioem_grad_coef_launch(h->stream, h->dGradRec, h->dScanCc, h->dGradParams, h->dScanSums, h->dScanSums + OB, nb,
+                                        N, h->dGradCoef, nullptr));
+    HIP_CHECK(h, bioem_ctfgrad_finish_launch(h->stream, h->dCtfgSums, h->dGradRec, h->dScanCc, h->dGradParams, h->dScanSums,
+                                             h->dScanSums + OB, h->dGradCoef, h->pd, nb, N, h->dCtfgRows));
+    HIP_CHECK(h, hipMemcpyAsync(rows_out + (size_t) kCtfgRow * b0, h->dCtfgRows, sizeof(double) * kCtfgRow * nb,
                                 hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(h, hipStreamSynchronize(h->stream)); // (the staging is reused by the next chunk)
   }

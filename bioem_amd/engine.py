@@ -26,6 +26,11 @@ SCAN_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("shiftX"
 GRAD_REQUEST_DTYPE = np.dtype([("particle", "<i4"), ("orient", "<i4"), ("conv", "<i4"), ("shiftX", "<i4"), ("shiftY", "<i4")])
 # a row of bioem_hip_pose_gradient: d log P / d R[i][j] (rows 0 and 1), d log P / d (shiftX, shiftY), <C, A_r>, the matrix
 POSE_GRAD_DTYPE = np.dtype([("J", "<f8", (2, 3)), ("T", "<f8", (2,)), ("dot", "<f8"), ("R", "<f8", (3, 3))])
+# a row of bioem_hip_ctf_gradient: theta = (amp, pha, env) of the request's CTF set, the twenty sums (ss0, cc0, U[3], V[3],
+# UU[6], VV[6]), gradient and Hessian of log P with respect to theta, the data's part and that of -prior apart; the Hessian's
+# upper triangle in the order aa, ap, ae, pp, pe, ee, the prior's diagonal
+CTF_GRAD_DTYPE = np.dtype([("theta", "<f8", (3,)), ("sums", "<f8", (20,)), ("gData", "<f8", (3,)), ("gPrior", "<f8", (3,)),
+                           ("HData", "<f8", (6,)), ("HPrior", "<f8", (3,))])
 SOFT_MEMBER_DTYPE = np.dtype([("particle", "<i4"), ("group", "<i4"), ("conv", "<i4"), ("pad", "<i4"), ("s2", "<f8"),
                               ("b", "<f8"), ("mass", "<f8")])
 GRAD_POINT_DTYPE = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("sumw", "<f8"), ("count", "<i8")])
@@ -140,6 +145,9 @@ def load_library():
     if hasattr(L, "bioem_hip_pose_gradient"):
         L.bioem_hip_pose_gradient.argtypes = [vp, vp, ci, ci, vp, vp, vp]
         L.bioem_hip_debug_pose_sums.argtypes = [vp, vp, ci, ci, vp, vp, vp]
+    if hasattr(L, "bioem_hip_ctf_gradient"):
+        L.bioem_hip_ctf_gradient.argtypes = [vp, vp, ci, ci, cf, vp, vp, vp]
+        L.bioem_hip_debug_ctf_gradient.argtypes = [vp, vp, vp, vp, vp, ci, cf, vp, vp]
     L.bioem_hip_host_alloc.argtypes = [C.c_size_t]
     L.bioem_hip_host_alloc.restype = vp
     L.bioem_hip_host_free.argtypes = [vp]
@@ -216,7 +224,8 @@ EXPORTS = ["bioem_hip_device_count", "bioem_hip_create", "bioem_hip_create_shard
            "bioem_hip_debug_convolve_batch", "bioem_hip_debug_direct_conv",
            "bioem_hip_upload_model_spectrum", "bioem_hip_upload_model_volume", "bioem_hip_debug_slices",
            "bioem_hip_volume_gradient", "bioem_hip_debug_volume_backproject", "bioem_hip_debug_volume_adjoint",
-           "bioem_hip_pose_gradient", "bioem_hip_debug_pose_sums"]
+           "bioem_hip_pose_gradient", "bioem_hip_debug_pose_sums",
+           "bioem_hip_ctf_gradient", "bioem_hip_debug_ctf_gradient"]
 
 
 def _p(a):
@@ -1034,6 +1043,46 @@ class Engine:
         self._chk(self.L.bioem_hip_debug_pose_sums(self.h, _p(angles) if n else None, n, int(bool(isQuat)),
                                                    _p(gamma) if n else None, _p(w), _p(out)), "debug_pose_sums")
         return out
+
+    def ctf_gradient(self, requests, pixel_size, own=False, want_params=False):
+        """gradient and Hessian of the log posterior of each request (particle, orient, conv, shiftX, shiftY) of
+        GRAD_REQUEST_DTYPE [n] (or an [n, 5] integer array) with respect to the triple (amp, pha, env) of its CTF set, at
+        the pixel size the kernels were made with (include/bioem_hip.h); CTF mode, point and volume models.
+        Returns a dict: "rows" CTF_GRAD_DTYPE [n]; "coef" float64 [n, 4] = (a, b, g, 0); with want_params "params"
+        PARAM5_DTYPE [n].  Outside a run; a refusal raises RuntimeError with .rc == 2."""
+        r = _requests(requests, GRAD_REQUEST_DTYPE)
+        n = len(r)
+        out = {"rows": np.zeros(n, dtype=CTF_GRAD_DTYPE), "coef": np.zeros((n, 4), dtype=np.float64)}
+        if want_params:
+            out["params"] = np.zeros(n, dtype=PARAM5_DTYPE)
+        self._chk(self.L.bioem_hip_ctf_gradient(self.h, _p(r) if n else None, n, int(bool(own)), float(pixel_size),
+                                                _p(out["rows"]), _p(out["coef"]), _p(out.get("params"))), "ctf_gradient")
+        return out
+
+    def best_match_ctf_gradient(self, pmap, pixel_size, p0=0, p1=None, own=False):
+        """ctf_gradient of the best record (orient, conv, cent_x, cent_y) of particles [p0, p1) of a probability block's
+        map entries (PROB_MAP_DTYPE [nMaps]); own as for render_best_maps"""
+        req = _match_requests(_pmap(pmap, self.nMaps), p0, self.nMaps if p1 is None else p1, GRAD_REQUEST_DTYPE)
+        return self.ctf_gradient(req, pixel_size, own=own)
+
+    def debug_ctf_gradient(self, specP, specRef, shifts, triples, pixel_size, want_derivs=False):
+        """test hook: the three kernels of ctf_gradient on n (projection, particle) spectrum pairs handed in, float32
+        [n, N, H, 2] each (or complex64 [n, N, H]), the shifts int [n, 2] and a triple (amp, pha, env) float32 [n, 3] per
+        record; a row is finished at the linearisation point its spectra imply (include/bioem_hip.h).  Needs only the
+        handle's parameters.  Returns CTF_GRAD_DTYPE [n], with want_derivs also float64 [n, N H, 10]: k, its three first
+        and six second derivatives per position of the walk order; a refusal raises with .rc == 2."""
+        specP, specRef = _spectra(specP), _spectra(specRef)
+        n = len(specP)
+        shifts = np.ascontiguousarray(shifts, dtype=np.int32)
+        triples = np.ascontiguousarray(triples, dtype=np.float32)
+        assert specP.shape == (n, self.N, self.H, 2) and specRef.shape == specP.shape
+        assert shifts.shape == (n, 2) and triples.shape == (n, 3)
+        rows = np.zeros(n, dtype=CTF_GRAD_DTYPE)
+        derivs = np.zeros((n, self.N * self.H, 10), dtype=np.float64) if want_derivs else None
+        self._chk(self.L.bioem_hip_debug_ctf_gradient(self.h, _p(specP) if n else None, _p(specRef) if n else None,
+                                                      _p(shifts), _p(triples), n, float(pixel_size), _p(rows), _p(derivs)),
+                  "debug_ctf_gradient")
+        return (rows, derivs) if want_derivs else rows
 
     def debug_volume_adjoint(self, spec):
         """test hook: the passes from A complex128 [PN, PN, PH] back to the volume alone; float64 [N, N, N]"""

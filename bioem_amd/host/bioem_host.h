@@ -208,6 +208,16 @@ std::string write_volume_gradient(const char *file, const double *gvol, const fl
 void pose_rotation_gradient(const double *row, double *g);
 std::string write_pose_gradient(const char *file, const double *rows, const bioem_hip_grad_request *req, const float *angles4,
                                 int n);
+// --CTFGradient (ctfgrad.cpp): the text file of the rows rows[n][38] of bioem_hip_ctf_gradient over the particles' best records
+// req[n].  After the HEADER:: NOTATION bar, one notation line and the bar again, per record
+//  CTFGRAD particle orient conv shiftX shiftY amp defocus env g_amp g_defocus g_env H_aa H_ad H_ae H_dd H_de H_ee
+//          newton_defocus sigma_defocus
+// (the CTF columns as --ProbCTF prints them, defocus = pha / (2 pi 1e4 lambda) in micro-m; gradient and Hessian of the data's
+// part of log P in those units -- the prior's part is left out; the Newton defocus along the defocus axis alone and its Laplace
+// error bar sqrt(-1 / H_dd), nan where H_dd is not negative) and one line
+//  DATASET particles defined rms_g_defocus
+// 17 significant digits.  Returns the empty string, or the error.
+std::string write_ctf_gradient(const char *file, const double *rows, const bioem_hip_grad_request *req, int n, float elecwavel);
 // --OrientStats (orientstats.cpp): the text file of the sums sums[nMaps] of bioem_hip_orientation_sums.  After the
 // HEADER:: NOTATION bar, one notation line (it carries the constant as NumericalConst) and the bar again, per particle
 //  ORIENT p count logZ omax A pTop entropy nEff meanq1 meanq2 meanq3 meanq4 spreadDeg
@@ -378,6 +388,7 @@ public:
   // FILE_Round2); k = 4 is a conventional choice, not a tuned one
   std::string ctfScanFile;
   int ctfScanFactor = 4;
+  std::string ctfGradFile;     // --CTFGradient: gradient and curvature with respect to the CTF triple of the best matches (FILE, FILE_Round2)
   std::string poseGradFile;    // --PoseGradient: the pose gradient of the best matches on a volume model (FILE, FILE_Round2)
   std::string volGradFile;     // --VolumeGradient: the density gradient of the best matches per voxel (FILE, FILE.mrc, _Round2)
   std::string modelGradFile;   // --ModelGradient: the density gradient of the best matches per model point (FILE, FILE_Round2)
@@ -463,6 +474,9 @@ private:
   // lists (anglesPerMap each, or angleOffsets [nMaps + 1] where they differ in length)
   void writePoseGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists,
                          const float *angles, size_t anglesPerMap, const long long *angleOffsets = nullptr);
+  // --CTFGradient: the records' gradient and curvature with respect to the triple of their CTF set from handle h
+  // (bioem_hip_ctf_gradient), written by write_ctf_gradient
+  void writeCtfGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists);
   // --OrientStats: the shards' orientation sums (bioem_hip_orientation_sums) merged on the host, written by
   // write_orient_stats; numconst: the constant of ANG_PROB
   void writeOrientStats(const std::string &file, double numconst);

@@ -128,6 +128,7 @@ int Driver::readOptions(int ac, char **av)
                                        {"ModelGradient", required_argument, 0, 0},
                                        {"VolumeGradient", required_argument, 0, 0},
                                        {"PoseGradient", required_argument, 0, 0},
+                                       {"CTFGradient", required_argument, 0, 0},
                                        {"OrientStats", required_argument, 0, 0},
                                        {"OrientOccupancy", required_argument, 0, 0},
                                        {"FitOrientPrior", required_argument, 0, 0},
@@ -184,6 +185,9 @@ int Driver::readOptions(int ac, char **av)
     printf("  --PoseGradient arg     (Optional) With --ModelVolume: write per particle the gradient of the log posterior of its best\n");
     printf("                         match with respect to a small rotation of the orientation and to the model shifts (with\n");
     printf("                         --RefineOrientations also arg_Round2)\n");
+    printf("  --CTFGradient arg      (Optional) Write per particle the gradient and the curvature of the log posterior of its best\n");
+    printf("                         match with respect to the CTF amplitude, defocus and B-envelope, the Newton defocus and its\n");
+    printf("                         error bar (CTF parameters only; with --RefineOrientations also arg_Round2)\n");
     printf("  --ModelGradient arg    (Optional) Write per model point the gradient of the log posterior of the particles' best\n");
     printf("                         matches with respect to its density (which part of the model do the data argue against?\n");
     printf("                         with --RefineOrientations also arg_Round2)\n");
@@ -358,6 +362,11 @@ int Driver::readOptions(int ac, char **av)
       std::cout << "Writing the pose gradient of the best matches on the volume model to: " << optarg << "\n";
       poseGradFile = optarg;
     }
+    else if (name == "CTFGradient")
+    {
+      std::cout << "Writing the CTF gradient and curvature of the best matches to: " << optarg << "\n";
+      ctfGradFile = optarg;
+    }
     else if (name == "OrientStats")
     {
       std::cout << "Writing the summaries of the orientation posteriors to: " << optarg << "\n";
@@ -469,6 +478,8 @@ int Driver::readOptions(int ac, char **av)
     fatal("--PoseGradient needs --ModelVolume (a point model's projector has no derivative with respect to the orientation)");
   if (!poseGradFile.empty() && !bestParamFile.empty())
     fatal("--PrintBestCalMap goes without --PoseGradient");
+  if (!ctfGradFile.empty() && !bestParamFile.empty())
+    fatal("--PrintBestCalMap goes without --CTFGradient");
   if (!bestParamFile.empty())
   { // the reference's one-record mode (bioem.cpp:386-433): the BEST_* file stands for the parameter file, one orientation,
     // one CTF / PSF kernel, no particles, no grids
@@ -507,6 +518,9 @@ int Driver::readOptions(int ac, char **av)
   if (scanOptions && ctfScanFile.empty())
     fatal("--CTFScanFactor goes with --CTFScan");
   param.readParameters(infile.c_str());
+  if (!ctfGradFile.empty() && param.usepsf)
+    fatal("--CTFGradient is not valid with PSF parameters (a PSF kernel is the transform of a real-space function, not the "
+          "closed form of the CTF that is differentiated)");
   if (refineFile.empty() && (refineSeeds != 1 || refineLogWindow >= 0.))
     fatal("--RefineSeeds / --RefineLogWindow go with --RefineOrientations");
   if (!orientStatsFile.empty())
@@ -1162,6 +1176,26 @@ void Driver::writePoseGradient(const std::string &file, bioem_hip_handle h, cons
   std::cout << "Pose gradient of " << req.size() << " particles' best matches written to: " << file << "\n";
 }
 
+// --CTFGradient: gradient and curvature of the log posterior of every record from handle h with respect to the triple of its
+// CTF set (bioem_hip_ctf_gradient), then the text file (write_ctf_gradient)
+void Driver::writeCtfGradient(const std::string &file, bioem_hip_handle h, const bioem_hip_prob_map *pmap, int ownLists)
+{
+  const int nMaps = particles.ntot;
+  std::vector<bioem_hip_grad_request> req;
+  for_each_match(pmap, nMaps, "CTF gradient of RefMap %d not computed: no run compared it",
+                 [&](int p, const bioem_hip_prob_map &r) {
+                   req.push_back({p, r.max_prob_orient, r.max_prob_conv, r.max_prob_cent_x, r.max_prob_cent_y});
+                 });
+  std::vector<double> rows(38 * req.size());
+  if (!req.empty())
+    check(h, bioem_hip_ctf_gradient(h, req.data(), (int) req.size(), ownLists, param.pixelSize, rows.data(), nullptr, nullptr),
+          "CTF gradient");
+  const std::string err = write_ctf_gradient(file.c_str(), rows.data(), req.data(), (int) req.size(), param.elecwavel);
+  if (!err.empty())
+    fatal("--CTFGradient: %s", err.c_str());
+  std::cout << "CTF gradient of " << req.size() << " particles' best matches written to: " << file << "\n";
+}
+
 // every shard's sums over the orientations it owns under logPrior (bioem_hip_orientation_sums), merged on the host in
 // shard order
 void Driver::shardOrientSums(const double *logPrior, std::vector<bioem_hip_orient_sums> &sums)
@@ -1478,6 +1512,8 @@ int Driver::run()
     writeVolumeGradient(volGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!poseGradFile.empty())
     writePoseGradient(poseGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0, param.angles.data(), 0);
+  if (!ctfGradFile.empty())
+    writeCtfGradient(ctfGradFile, shards[0].h, (const bioem_hip_prob_map *) prob.data(), 0);
   if (!viewAvgFile.empty())
     writeViewAverages(viewAvgFile, shards[0].h, (const bioem_hip_prob_map *) prob.data());
   if (!reconFile.empty())
@@ -1565,6 +1601,8 @@ void Driver::runRound2()
     writeVolumeGradient(volGradFile + "_Round2", h, pm.data(), 1);
   if (!poseGradFile.empty())
     writePoseGradient(poseGradFile + "_Round2", h, pm.data(), 1, lists.data(), (size_t) G);
+  if (!ctfGradFile.empty())
+    writeCtfGradient(ctfGradFile + "_Round2", h, pm.data(), 1);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), (size_t) G);
   bioem_hip_destroy(h);
@@ -1669,6 +1707,8 @@ void Driver::runRound2Seeds()
     writeVolumeGradient(volGradFile + "_Round2", h, pm.data(), 1);
   if (!poseGradFile.empty())
     writePoseGradient(poseGradFile + "_Round2", h, pm.data(), 1, lists.data(), 0, offsets.data());
+  if (!ctfGradFile.empty())
+    writeCtfGradient(ctfGradFile + "_Round2", h, pm.data(), 1);
   if (!probCtfFile.empty())
     writeCtfProb(probCtfFile + "_Round2", std::vector<bioem_hip_handle>(1, h), pd2, lists.data(), 0, offsets.data(),
                  volu.data());

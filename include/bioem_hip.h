@@ -870,6 +870,43 @@ int bioem_hip_pose_gradient(bioem_hip_handle h, const bioem_hip_grad_request *re
 int bioem_hip_debug_pose_sums(bioem_hip_handle h, const float *angles4, int n, int isQuat, const double *gamma,
                               const double *weights, double *pose_out);
 
+/* ---- CTF gradient and curvature of the log posterior per match (no reference counterpart) ----
+ * For request (p, o, c, X, Y) the first and second derivatives of the log posterior of that match with respect to the
+ * triple theta = (amp, pha, env) of CTF set c, CTF mode only.  The host's kernel is then the closed form
+ *   k(s; theta) = exp(-env s / 2) (cos(pha s / 2) + rho sin(pha s / 2)),  rho = sqrt(1 - amp^2) / amp,  k(0) = 1,
+ * of the radial variable s of a stored element: the float of the host's own expression at pixelSize (a table made on the
+ * host, uploaded once per handle and pixel size), widened to double.  With P the projection's spectrum, Z = w conj(F) tw,
+ * D_t = dk / dtheta_t, D_tu the second derivatives and Nt = N N, twenty sums over the stored elements, in double:
+ *   ss0 = sum w |P|^2 k^2, cc0 = sum Re(P Z) k, U_t = sum w |P|^2 k D_t, V_t = sum Re(P Z) D_t,
+ *   UU_tu = sum w |P|^2 (D_t D_u + k D_tu), VV_tu = sum Re(P Z) D_tu        (tu = aa, ap, ae, pp, pe, ee)
+ * and, with ss_t = 2 U_t / Nt, cc_t = V_t / Nt, ss_tu = 2 UU_tu / Nt, cc_tu = VV_tu / Nt, b and g of the other gradient
+ * entries (bit for bit) and L_bb, L_bg, L_gg the second derivatives of the same closed form with respect to (sumsquareC, cc)
+ * at the device's float linearisation point:
+ *   gData_t  = b ss_t + g cc_t
+ *   HData_tu = L_bb ss_t ss_u + L_bg (ss_t cc_u + ss_u cc_t) + L_gg cc_t cc_u + b ss_tu + g cc_tu.
+ * sumC does not depend on theta (k(0) = 1).  The prior's part is reported apart, the derivatives of -prior with the signs
+ * of the reference's expression: gPrior = ((amp - c_a) / s_a^2, (pha - c_d) / s_d^2, -env / s_b^2), HPrior = (1 / s_a^2,
+ * 1 / s_d^2, -1 / s_b^2) -- a caller may leave them out.
+ * rows_out [n][38] = {theta[3], the sums in the order above [20], gData[3], gPrior[3], HData[6] (aa, ap, ae, pp, pe, ee),
+ * HPrior[3] (its diagonal)}; coef_out [n][4] = {a, b, g, 0}; params_out [n] the linearisation points; the last two may be
+ * NULL.  No atomics: a row's bits depend on its request alone, the same for any batch, list, position and run.  Point and
+ * volume models alike.  Calling rules, batches, scan launches and request refusals of bioem_hip_model_gradient; also refused
+ * with 2, the request named where there is one and the handle usable: a handle in PSF mode, pixelSize not finite or not
+ * positive, rows_out null, a request whose set has amp <= 1e-10 or amp >= 1.  Phase records as there through phase 1; 2 the
+ * sums of a batch; 3 its rows. */
+int bioem_hip_ctf_gradient(bioem_hip_handle h, const bioem_hip_grad_request *req, int n, int ownLists, float pixelSize,
+                           double *rows_out /* [n][38] */, double *coef_out /* [n][4] or NULL */,
+                           bioem_hip_param5 *params_out /* [n] or NULL */);
+/* test hook: the three kernels alone on n pairs of spectra handed in (specP, specRef [n][N][H] (re, im)), the shifts
+ * shiftXY [n][2] and a triple per record, triples [n][3].  A record's row is finished at the linearisation point its
+ * spectra imply: sumC = Re specP[0][0], sumsquareC = (float) (ss0 / Nt), cc = (float) (cc0 / Nt), the particle's sum
+ * Re specRef[0][0] and its sum of squares (float) (sum w |specRef|^2 / Nt).  rows_out [n][38] as above; derivs_out
+ * [n][N H][10] or NULL: k, D_a, D_p, D_e, D_aa, D_ap, D_ae, D_pp, D_pe, D_ee per position of the walk order (rows; inside
+ * a row the columns 1 ... , then 0, then N / 2 for even N), the device's own values.  Records go through in chunks of
+ * maxOrientations. */
+int bioem_hip_debug_ctf_gradient(bioem_hip_handle h, const float *specP, const float *specRef, const int *shiftXY,
+                                 const float *triples, int n, float pixelSize, double *rows_out, double *derivs_out);
+
 #ifdef __cplusplus
 }
 #endif
